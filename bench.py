@@ -2,7 +2,7 @@
 """Throughput benchmark of the SimT training iteration on MI355X (BASELINE.json metric: training images/sec at
 768x768, DeepLabv2-R101+SimT).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without a torch.distributed environment: this process spawns `python -m torch.distributed.run --nproc-per-node N ...
 bench.py` BEFORE touching the GPU and passes the child's output through (one rank per GPU over RCCL).  Launched by
@@ -88,12 +88,65 @@ def parse():
                          "NOT the headline configuration: the default computes everything the reference's iteration computes")
     ap.add_argument("--shapes", action="store_true", help="print a per-shape conv timing table to stderr")
     ap.add_argument("--cpu-iters", type=int, default=3, help="timed CPU-baseline iterations per point (after one warm-up)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (losses, NTM matrices, a fixed "
+                         "sample of the trained parameters) as DIR/<name>.npy (rank 0), to compare two builds output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     dflt = {"v2": (4, [768, 768], 3), "v3": (4, [512, 1024], 6), "vgg": (8, [512, 512], 3)}[a.model]
     a.batch = a.batch if a.batch is not None else dflt[0]
     a.size = a.size if a.size is not None else dflt[1]
     a.open_classes = a.open_classes if a.open_classes is not None else dflt[2]
     return a
+
+
+DUMP_SAMPLE_PER_TENSOR = 16384        # parameter values kept per tensor: at most ~320 tensors x 64 KB, far below the 64 MB budget
+
+
+def dump_outputs(tr, out_dir):
+    """What the last step handed its caller, as finite float32 .npy files: the ten loss slots of `lout` that losses() reports (total, loss_p1,
+    loss_p2, loss_y1, loss_y2, place, convex, volume, anchor, vol_ok), the NTM matrices after Adam and the parameters after SGD.
+    A loss that is a mean over zero pixels is NaN, as in the reference (CrossEntropy2d over an empty mask; csrc/head_loss.hip): it is written
+    as 0 with loss_defined = 0 beside it, so that two builds compare value for value and definedness for definedness.  Parameters larger than
+    DUMP_SAMPLE_PER_TENSOR elements are represented by a fixed, seeded sample of their elements (the same positions for the same shapes),
+    concatenated over the sorted parameter names.  Any other non-finite value is an error, never written."""
+    import numpy as np
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:      # a directory this run made holds outputs, never sources
+            f.write("*\n")
+    lo = tr.lout[:10].detach().float().cpu()
+    ok = torch.isfinite(lo)
+    arrs = {"losses": torch.where(ok, lo, torch.zeros_like(lo)), "loss_defined": ok.float()}
+    ntm = tr.ntm if isinstance(tr.ntm, (list, tuple)) else [tr.ntm]
+    for i, m in enumerate(ntm):
+        arrs[f"ntm{i + 1}"] = m
+    names, parts, offs = [], [], [0]
+    for k in sorted(tr.params):
+        v = tr.params[k]
+        if not v.is_floating_point():
+            continue
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+            rng = np.random.default_rng([len(names), flat.numel()])
+            idx = torch.from_numpy(np.sort(rng.choice(flat.numel(), DUMP_SAMPLE_PER_TENSOR, replace=False))).to(flat.device)
+            flat = flat[idx]
+        names.append(k)
+        parts.append(flat)
+        offs.append(offs[-1] + flat.numel())
+    arrs["params_sample"] = torch.cat(parts)
+    arrs = {n: t.detach().float().cpu().numpy() for n, t in arrs.items()}
+    for n, x in arrs.items():
+        if not np.isfinite(x).all():
+            raise SystemExit(f"bench.py --dump-outputs: {n} of the last timed step holds {int((~np.isfinite(x)).sum())} non-finite value(s)")
+    files = {}
+    for n, x in arrs.items():
+        np.save(os.path.join(out_dir, n + ".npy"), x)
+        files[n] = list(x.shape)
+    with open(os.path.join(out_dir, "params_sample_index.json"), "w") as f:
+        json.dump({"names": names, "offsets": offs, "sample_per_tensor": DUMP_SAMPLE_PER_TENSOR}, f)
+    return {"dir": out_dir, "arrays": files}
 
 
 def spawn_ranks(n):
@@ -342,6 +395,7 @@ def main():
     # a fused BatchNorm launch that gave up polling leaves the sticky error word set and every optimiser launch skipped: never report such a run
     if getattr(tr, "plan", None) is not None and tr.plan.fbn_error():
         raise SystemExit("bench.py: a fused BatchNorm launch timed out (TrunkPlan.fbn_error): the timed steps did not train; rerun with SIMT_BN_GRID=0")
+    dumped = dump_outputs(tr, a.dump_outputs) if a.dump_outputs and rank == 0 else None       # after the timed region, before anything reruns the step
     comm = None
     if red is not None:
         comm = red.report()              # the exchange of the timed steps (plus warm-up): bytes, buckets, exposed wait
@@ -550,6 +604,8 @@ def main():
         if pw.report() is not None:
             line["power_clock"] = pw.report()
         line.update(extra)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line))
     if dp_job:
         import torch.distributed as dist

@@ -82,3 +82,31 @@ def test_bench_dp_job_over_a_real_one_rank_rccl_group(dev):
     assert line["n_gpus"] == 1 and "RCCL" in line["config"]["workload"] and c["op"] == "AVG" and c["world"] == 1
     assert c["steps_measured"] >= 3 and c["exposed_wait_ms_median"] >= 0.0 and all(r >= 0 for r in c["bucket_released_launch"])
     assert line["value"] > 0
+
+
+def test_bench_steps_and_dump_outputs(dev, tmp_path):
+    """--steps sets the number of timed steps, the line carries ms_per_step, and --dump-outputs writes the last timed step's outputs as
+    finite float32 arrays, under 64 MB in all."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1",
+                        "--size", "129", "129", "--no-cpu-baseline", "--no-roofline", "--no-extra-passes", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=1500)
+    assert p.returncode == 0, (p.stdout[-3000:], p.stderr[-3000:])
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-3000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1 * 1000.0 / line["ms_per_step"]) / line["value"] < 0.01
+    arrays = line["dump_outputs"]["arrays"]
+    assert set(arrays) == {"losses", "loss_defined", "ntm1", "ntm2", "params_sample"}
+    total = 0
+    for n, shape in arrays.items():
+        x = np.load(out / (n + ".npy"))
+        assert x.dtype == np.float32 and list(x.shape) == shape and np.isfinite(x).all(), n
+        total += os.path.getsize(out / (n + ".npy"))
+    assert total < 64 << 20
+    lo, ok = np.load(out / "losses.npy"), np.load(out / "loss_defined.npy")
+    assert lo.shape == ok.shape == (10,) and set(ok.tolist()) <= {0.0, 1.0} and (lo[ok == 0] == 0).all()
+    assert (ok[1:5] == 1).all() and (lo[1:5] != 0).all()          # loss_p1, loss_p2, loss_y1, loss_y2 of the last timed step

@@ -271,3 +271,38 @@ def test_measurement_tools_compile():
     with tempfile.TemporaryDirectory() as td:
         for f in files:
             py_compile.compile(f, cfile=os.path.join(td, "x.pyc"), doraise=True)
+
+
+def test_bench_dump_outputs_layout_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: finite float32 .npy per output of the last step; a loss over zero pixels (NaN, as in the reference) written as 0
+    with loss_defined = 0; parameters above the per-tensor cap reduced to a seeded sample that picks the same positions on every call (two
+    builds must be comparable output for output), integer buffers left out; any other non-finite output refused before anything is written."""
+    import json
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    cap = bench.DUMP_SAMPLE_PER_TENSOR
+    g = torch.Generator().manual_seed(0)
+    params = {"a.weight": torch.arange(cap * 3 + 7, dtype=torch.float32), "b.bias": torch.randn(5, generator=g),
+              "bn.num_batches_tracked": torch.zeros((), dtype=torch.long)}
+    lout = torch.arange(16, dtype=torch.float32)
+    lout[0] = lout[5] = float("nan")                 # total and place when no pixel carries a confidence label
+    tr = types.SimpleNamespace(lout=lout, hout=torch.full((40,), float("nan")), params=params,
+                               ntm=[torch.randn(22, 19, generator=g), torch.randn(22, 19, generator=g)])
+    rep = [bench.dump_outputs(tr, str(tmp_path / d)) for d in ("x", "y")]
+    assert set(rep[0]["arrays"]) == {"losses", "loss_defined", "ntm1", "ntm2", "params_sample"}
+    for n in rep[0]["arrays"]:
+        x, y = np.load(tmp_path / "x" / (n + ".npy")), np.load(tmp_path / "y" / (n + ".npy"))
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y)
+    np.testing.assert_array_equal(np.load(tmp_path / "x" / "losses.npy"), [0, 1, 2, 3, 4, 0, 6, 7, 8, 9])
+    np.testing.assert_array_equal(np.load(tmp_path / "x" / "loss_defined.npy"), [0, 1, 1, 1, 1, 0, 1, 1, 1, 1])
+    ps = np.load(tmp_path / "x" / "params_sample.npy")
+    idx = json.load(open(tmp_path / "x" / "params_sample_index.json"))
+    assert idx["names"] == ["a.weight", "b.bias"] and idx["offsets"] == [0, cap, cap + 5] and ps.shape == (cap + 5,)
+    assert (np.diff(ps[:cap]) > 0).all() and ps[0] >= 0 and ps[cap - 1] < cap * 3 + 7 and (ps[:cap] % 1 == 0).all()  # distinct elements, in order
+    np.testing.assert_array_equal(ps[cap:], params["b.bias"].numpy())
+    assert sum(os.path.getsize(os.path.join(tmp_path, "x", f)) for f in os.listdir(tmp_path / "x")) < 64 << 20
+    tr.ntm[1][3, 4] = float("inf")
+    with pytest.raises(SystemExit, match="ntm2"):
+        bench.dump_outputs(tr, str(tmp_path / "z"))
+    assert not [f for f in os.listdir(tmp_path / "z") if f.endswith(".npy")]
