@@ -423,6 +423,13 @@ int simt_entropy2d(const float* x, int n, int c, int h, int w, void* ws, float* 
 int simt_upsample_sum_argmax(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H,
                              int W, int C, int32_t* pred, simt_stream_t stream);
 int simt_confusion_hist(const int64_t* gt, const int32_t* pred, long P, int n, int64_t* hist, simt_stream_t stream);
+/* pseudo-label export (the save lines of evaluate_simt :150-156 / evaluate_warmup :214-219; trainV2_simt.py:353-359):
+ * mode 0: out[b][y][x] = the label simt_upsample_sum_argmax writes (bit for bit), as uint8;
+ * mode 1: la holds low-res PROBABILITIES (simt_softmax_rows of the logits), lb must be NULL: out = argmax_c up(la)[c] where
+ *         max_c up(la)[c] > threshold (strictly), 255 elsewhere.
+ * out: uint8 [B][H][W], 4-byte aligned.  counts: int64 [C+1] accumulated across calls (classes 0..C-1, then the 255s).  C <= 255. */
+int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H, int W, int C,
+                         int mode, float threshold, uint8_t* out, int64_t* counts, simt_stream_t stream);
 /* F.interpolate(bilinear) of an NHWC fp32 map [B][h][w][lds] (first C channels) to NCHW fp32 [B][C][H][W] and its adjoint
  * (model/deeplabv3.py:137 upsamples inside the model with align_corners=False; align_corners=1 = interp_target) */
 int simt_upsample_nchw(const float* src, int B, int h, int w, int lds, int C, int H, int W, int align_corners, float* dst,

@@ -77,6 +77,122 @@ extern "C" int simt_upsample_sum_argmax(const float* la, int ha, int wa, int lda
   return SIMT_OK;
 }
 
+// ---- pseudo-label export (the commented-out save lines of evaluate_simt :150-156 / evaluate_warmup :214-219; the confidence rule of
+// trainV2_simt.py:353-359 with the high threshold only).  Same gather as upsample_sum_argmax_kernel, written as uint8 (a quarter of the
+// int32 bytes) together with the class counts of compute_ClassDistribution.py (bins 0..C-1, then the 255s).
+struct PseudoArgs {
+  const float* la;     // [B][ha][wa][lda] logits (mode 0) or probabilities (mode 1), first C channels used
+  const float* lb;     // [B][hb][wb][ldb] logits, scale B, or NULL (mode 1: always NULL)
+  unsigned char* out;  // [B][H][W] labels, 4-byte aligned
+  unsigned long long* counts;   // [C+1], accumulated
+  int B, ha, wa, lda, hb, wb, ldb, H, W, C;
+  float sya, sxa, syb, sxb, threshold;
+};
+
+// MODE 0: arg-max of up(la) + up(lb) -- the arithmetic of upsample_sum_argmax_kernel, statement for statement, so the labels are its
+// labels bit for bit.  MODE 1: max / arg-max of up(la); the arg-max where max > threshold, 255 elsewhere.
+template <int MODE>
+__device__ __forceinline__ int pseudo_pixel(const PseudoArgs& a, int b, int y, int x) {
+  int a00, a01, a10, a11, b00 = 0, b01 = 0, b10 = 0, b11 = 0;
+  float ay0, ay1, ax0, ax1, by0 = 0, by1 = 0, bx0 = 0, bx1 = 0;
+  bil_taps(y, x, a.ha, a.wa, a.sya, a.sxa, a00, a01, a10, a11, ay0, ay1, ax0, ax1);
+  const float* pa = a.la + (long)b * a.ha * a.wa * a.lda;
+  const float* pb = nullptr;
+  if (MODE == 0 && a.lb) {
+    bil_taps(y, x, a.hb, a.wb, a.syb, a.sxb, b00, b01, b10, b11, by0, by1, bx0, bx1);
+    pb = a.lb + (long)b * a.hb * a.wb * a.ldb;
+  }
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c = 0; c < a.C; ++c) {
+    float v = ay0 * (ax0 * pa[(long)a00 * a.lda + c] + ax1 * pa[(long)a01 * a.lda + c]) +
+              ay1 * (ax0 * pa[(long)a10 * a.lda + c] + ax1 * pa[(long)a11 * a.lda + c]);
+    if (MODE == 0 && pb) {
+      const float u = by0 * (bx0 * pb[(long)b00 * a.ldb + c] + bx1 * pb[(long)b01 * a.ldb + c]) +
+                      by1 * (bx0 * pb[(long)b10 * a.ldb + c] + bx1 * pb[(long)b11 * a.ldb + c]);
+      v = v + u;
+    }
+    if (v > best) { best = v; arg = c; }     // first index on ties
+  }
+  if (MODE == 1) return best > a.threshold ? arg : 255;   // strictly greater (:359)
+  return arg;
+}
+
+// One pixel per lane, so that neighbouring lanes gather neighbouring taps exactly as upsample_sum_argmax_kernel does (a version in which
+// each thread labelled 4 consecutive pixels itself touched ~4x the cache lines per load instruction and ran 2.3-3.3x slower than that
+// kernel).  Each quad of lanes = 4 consecutive pixels of the flattened [B][H][W] map (consecutive x; the quad runs on into the next row
+// when W % 4 != 0): two lane shuffles pack the 4 labels into the quad leader, which writes one 32-bit store (byte stores for the last
+// P % 4 pixels).  Counts: LDS histogram per block (the leader adds runs of equal labels once), one global atomic per non-zero bin --
+// exact and order independent, like hist2d_u8_kernel.  The flush is what this kernel adds to the gather: with 256-thread blocks and up to
+// 2048 of them (41 k 64-bit atomics on 20 words) it cost 7-13 us at 1 x 1024 x 2048; 1024-thread blocks, at most 512 of them (the
+// same 32 waves per CU), cut it to ~3 us (launch-shape sweep on MI355X, 138.6 us against 143.5 us of upsample_sum_argmax_kernel).
+constexpr int PL_BLOCK = 1024, PL_MAX_GRID = 512;
+template <int MODE>
+__global__ __launch_bounds__(PL_BLOCK) void pseudo_label_u8_kernel(PseudoArgs a) {
+  __shared__ unsigned int sh[256];
+  const int nbins = a.C + 1;
+  for (int i = threadIdx.x; i < nbins; i += PL_BLOCK) sh[i] = 0u;
+  __syncthreads();
+  const long P = (long)a.B * a.H * a.W;
+  const bool leader = (threadIdx.x & 3) == 0;
+  // the loop bound is uniform over the block: every lane of a wave reaches the shuffles together
+  for (long base = (long)blockIdx.x * PL_BLOCK; base < P; base += (long)gridDim.x * PL_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      lab = (unsigned int)pseudo_pixel<MODE>(a, (int)(t / a.H), (int)(t % a.H), x);
+    }
+    unsigned int word = lab | (__shfl_down(lab, 1, 4) << 8);
+    word |= __shfl_down(word, 2, 4) << 16;
+    if (leader && p < P) {
+      const int n = P - p < 4 ? (int)(P - p) : 4;
+      if (n == 4) {
+        *reinterpret_cast<unsigned int*>(a.out + p) = word;
+      } else {
+        for (int i = 0; i < n; ++i) a.out[p + i] = (unsigned char)(word >> (8 * i));
+      }
+      int run_bin = 0, run_n = 0;
+      for (int i = 0; i < n; ++i) {
+        const unsigned int l = (word >> (8 * i)) & 255u;
+        const int bin = l == 255u ? a.C : (int)l;
+        if (bin != run_bin && run_n) { atomicAdd(&sh[run_bin], (unsigned int)run_n); run_n = 0; }
+        run_bin = bin;
+        ++run_n;
+      }
+      atomicAdd(&sh[run_bin], (unsigned int)run_n);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbins; i += PL_BLOCK)
+    if (sh[i]) atomicAdd(&a.counts[i], (unsigned long long)sh[i]);
+}
+
+extern "C" int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H,
+                                    int W, int C, int mode, float threshold, uint8_t* out, int64_t* counts, simt_stream_t stream) {
+  SIMT_CHECK(la && out && counts && B > 0 && H > 0 && W > 0 && ha > 0 && wa > 0 && C > 0 && C <= 255 && C <= lda);
+  SIMT_CHECK((mode == 0 && (!lb || (C <= ldb && hb > 0 && wb > 0))) || (mode == 1 && !lb));
+  SIMT_CHECK(((uintptr_t)out & 3) == 0);
+  PseudoArgs a;
+  a.la = la; a.lb = lb; a.out = out; a.counts = (unsigned long long*)counts;
+  a.B = B; a.ha = ha; a.wa = wa; a.lda = lda; a.hb = hb; a.wb = wb; a.ldb = ldb; a.H = H; a.W = W; a.C = C;
+  a.sya = H > 1 ? (float)(ha - 1) / (float)(H - 1) : 0.f;
+  a.sxa = W > 1 ? (float)(wa - 1) / (float)(W - 1) : 0.f;
+  a.syb = (lb && H > 1) ? (float)(hb - 1) / (float)(H - 1) : 0.f;
+  a.sxb = (lb && W > 1) ? (float)(wb - 1) / (float)(W - 1) : 0.f;
+  a.threshold = threshold;
+  const long P = (long)B * H * W;
+  long grid = (P + PL_BLOCK - 1) / PL_BLOCK;
+  if (grid > PL_MAX_GRID) grid = PL_MAX_GRID;
+  if (mode == 0)
+    hipLaunchKernelGGL(pseudo_label_u8_kernel<0>, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(pseudo_label_u8_kernel<1>, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
 // hist[n*gt + pred] += 1 for 0 <= gt < n   (fast_hist: labels outside [0, n) -- the 255 "ignore" id -- are skipped)
 __global__ __launch_bounds__(256) void confusion_hist_kernel(const int64_t* gt, const int32_t* pred, long P, int n,
                                                              unsigned long long* hist) {

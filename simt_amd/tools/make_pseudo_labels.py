@@ -1,0 +1,313 @@
+#!/usr/bin/env python3
+"""Pseudo-label export on MI355X: a source ("black-box") checkpoint -> the label PNGs, the `.lst` file `cityscapesPseudo` reads and the
+`ClassDist_<name>.npy` prior `sig_NTM` multiplies into T -- everything the SimT stage (tools/trainV2_simt.py) takes as input.
+
+The reference made its lists from its evaluation loop: the commented-out save lines of tools/evaluate_cityscapes.py:150-156
+(evaluate_simt: main head at two input scales, upsampled to 1024 x 2048 with align_corners=True, summed, arg-maxed) and :214-219
+(evaluate_warmup: one scale), and compute_ClassDistribution.py:66-92 for the prior.  `--threshold T` instead applies the SimT confidence
+rule of trainV2_simt.py:353-359 (high threshold only): softmax at low resolution, upsampled, arg-max where max > T, 255 elsewhere.
+
+    python -m simt_amd.tools.make_pseudo_labels --restore-from src.pth --arch single --data-dir $CS --data-list train.txt \
+        --out-name pseudo_mine --list-out pseudo_mine.lst [--threshold 0.8] [--save-color --devkit-dir dataset/cityscapes_list]
+
+Device: both eval-mode forwards (engine.TrunkPlan, BN folded), the resizes (data.pipeline.InputPrep, Pillow-exact) and one fused
+upsample + arg-max kernel (simt_pseudo_label_u8) that writes the uint8 label map and the class counts.  Host: PNG decoding on a bounded
+thread pool, pinned copies of the label maps (guarded by events), PNG encoding on a writer pool, atomic file writes."""
+import argparse
+import json
+import os
+import os.path as osp
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from simt_amd import _lib as L
+from simt_amd import ops
+from simt_amd.engine import TrunkPlan, multi_heads, single_head
+
+MAX_WORKERS = 16
+DEFAULT_SCALES = ((512, 1024), (640, 1280))          # (h, w): the crop sizes (1024, 512) and (1280, 640) of evaluate_simt :103-106
+
+
+class PseudoLabeller:
+    """Eval-mode plans of a DeepLab-v2 ResNet at each input scale + the fused label kernel.
+
+    arch "multi": DeeplabMulti(C, K, K > 0), head x2, first C channels (evaluate_simt :128, :133).  arch "single": Res_Deeplab(C)
+    (model/deeplab.py), head x.  mode "argmax": up(logits) summed over the scales, arg-max (one scale = evaluate_warmup).
+    mode "confidence": first scale only, softmax -> up -> arg-max where max > threshold, else 255.
+    label(*images) -> uint8 [B, H, W] on the device; `counts` accumulates int64 [C+1] (classes, then the 255s)."""
+
+    def __init__(self, state, *, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
+                 mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, batch=1):
+        if arch not in ("multi", "single"):
+            raise ValueError(f"arch must be 'multi' or 'single', not {arch!r}")
+        if mode not in ("argmax", "confidence"):
+            raise ValueError(f"mode must be 'argmax' or 'confidence', not {mode!r}")
+        if arch == "single" and open_classes:
+            raise ValueError("the single-head model has no open-set classes")
+        if not 0 < num_classes <= 255:
+            raise ValueError("uint8 labels hold at most 255 classes (255 = ignore)")
+        self.dev = torch.device(device)
+        self.C, self.mode, self.threshold, self.dtype = num_classes, mode, float(threshold), dtype
+        scales = tuple(tuple(s) for s in scales)
+        if mode == "confidence":
+            scales = scales[:1]
+        if arch == "multi":
+            heads, self.head = multi_heads(num_classes, open_classes, open_classes > 0), "x2"
+        else:
+            heads, self.head = single_head(num_classes), "x"
+        params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
+        kw = {"layers": layers} if layers is not None else {}
+        self.plans = [TrunkPlan(params, batch, h, w, heads, dtype=dtype, train=False, **kw) for (h, w) in scales]
+        self.scales = scales
+        self.B, (self.H, self.W) = batch, tuple(label_hw)
+        self.labels = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.uint8)
+        self.counts = torch.zeros(num_classes + 1, device=self.dev, dtype=torch.int64)
+        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode == "confidence" else None
+
+    def label(self, *images):
+        """images: one [B,3,h,w] fp32 tensor (BGR - mean) per scale.  Returns the label map uint8 [B,H,W] (device, reused by the next
+        call) and adds its class counts to `counts`."""
+        if len(images) != len(self.plans):
+            raise ValueError(f"{len(self.plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+        outs = [plan.forward(img.to(self.dev))[self.head] for plan, img in zip(self.plans, images)]
+        if self.mode == "confidence":
+            o = outs[0]
+            B, h, w, ld = o.shape
+            ops.softmax_rows(o, ld, self.prob, ld, B * h * w, self.C)
+            outs, mode = [self.prob], 1
+        else:
+            mode = 0
+        la = outs[0]
+        lb = outs[1] if len(outs) > 1 else None
+        hb, wb, ldb = (lb.shape[1], lb.shape[2], lb.shape[3]) if lb is not None else (0, 0, 0)
+        L.call("simt_pseudo_label_u8", ops._p(la), la.shape[1], la.shape[2], la.shape[3], ops._p(lb), hb, wb, ldb,
+               self.B, self.H, self.W, self.C, mode, self.threshold, ops._p(self.labels), ops._p(self.counts), ops.stream_ptr())
+        return self.labels
+
+
+# ---- host side: names, files, palette, prior ----------------------------------------------------------------------------------------
+
+def label_basename(name):
+    """'aachen/aachen_000000_000019_leftImg8bit.png' -> 'aachen_000000_000019_leftImg8bit' (evaluate_simt :152, :156)."""
+    return osp.splitext(name.split("/")[-1])[0]
+
+
+def list_line(set_name, name, out_name):
+    """One line of a pseudo-label list in the layout of pseudo_bapa.lst: '<set>/<name>\\t<out_name>/<basename>.png'."""
+    return f"{set_name}/{name}\t{out_name}/{label_basename(name)}.png"
+
+
+def output_paths(data_dir, out_name, name):
+    """-> (label PNG, colour PNG) under <data_dir>/<out_name>/."""
+    base = osp.join(data_dir, out_name, label_basename(name))
+    return base + ".png", base + "_color.png"
+
+
+def read_palette(devkit_dir):
+    """The colour palette of <devkit_dir>/info.json ('palette': [[r, g, b], ...] or flat), zero-padded to 256 entries."""
+    with open(osp.join(devkit_dir, "info.json"), "r") as fp:
+        info = json.load(fp)
+    if "palette" not in info:
+        raise ValueError(f"{osp.join(devkit_dir, 'info.json')} has no 'palette' entry (needed by --save-color)")
+    flat = [int(v) for v in np.asarray(info["palette"]).reshape(-1)]
+    if len(flat) > 768:
+        raise ValueError("palette has more than 256 colours")
+    return flat + [0] * (768 - len(flat))
+
+
+def colorize(label, palette):
+    """uint8 label map -> mode 'P' image with the palette (colorize_mask of the reference's evaluation script)."""
+    from PIL import Image
+    img = Image.fromarray(np.asarray(label, dtype=np.uint8)).convert("P")
+    img.putpalette(palette)
+    return img
+
+
+def class_dist(counts, num_classes):
+    """Normalised prior of compute_ClassDistribution.py:92: counts[:C] / (sum + 10e-10), float64 [C]; 255s do not count."""
+    c = np.asarray(counts, dtype=np.float64)[:num_classes]
+    return c / (np.sum(c) + 10e-10)
+
+
+def save_png_atomic(img, path):
+    """Encode to a temporary name in the target directory, then os.replace: a reader never sees a partial file."""
+    tmp = f"{path}.{os.getpid()}.tmp"
+    try:
+        img.save(tmp, format="PNG")
+        os.replace(tmp, path)
+    finally:
+        if osp.exists(tmp):
+            os.remove(tmp)
+
+
+def save_npy_atomic(arr, path):
+    tmp = f"{path}.{os.getpid()}.tmp"
+    with open(tmp, "wb") as f:
+        np.save(f, arr)
+    os.replace(tmp, path)
+
+
+def _bounded_map(pool, fn, items, depth):
+    """pool.map(fn, items) in order, with at most `depth` results pending (pool.map would decode the whole list ahead of the GPU)."""
+    pending = deque()
+    it = iter(items)
+    for x in it:
+        pending.append(pool.submit(fn, x))
+        if len(pending) >= depth:
+            break
+    while pending:
+        fut = pending.popleft()
+        for x in it:
+            pending.append(pool.submit(fn, x))
+            break
+        yield fut.result()
+
+
+def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", save_color=False, devkit_dir=None, workers=8,
+           class_dist_out=None, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
+           mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, labeller=None, verbose=True):
+    """Label every frame of cityscapesDataSet(data_dir, data_list, set=set_name) and write
+    <data_dir>/<out_name>/<basename>.png (8-bit trainIds, 255 = ignore; with save_color also <basename>_color.png), the list file
+    `list_out` and the prior `class_dist_out` (default: ClassDist_<out_name>.npy beside the list).  Returns the int64 counts [C+1]."""
+    from PIL import Image
+
+    from simt_amd.data.pipeline import IMG_MEAN, InputPrep
+    from simt_amd.dataset.cityscapes_dataset import cityscapesDataSet
+    workers = min(max(1, int(workers)), MAX_WORKERS)
+    palette = None
+    if save_color:
+        if not devkit_dir:
+            raise ValueError("save_color needs devkit_dir (the palette of info.json)")
+        palette = read_palette(devkit_dir)
+    if class_dist_out is None:
+        class_dist_out = osp.join(osp.dirname(osp.abspath(list_out)), f"ClassDist_{out_name}.npy")
+    dev = torch.device(device)
+    lab = labeller or PseudoLabeller(state, num_classes=num_classes, open_classes=open_classes, arch=arch, scales=scales,
+                                     label_hw=label_hw, mode=mode, threshold=threshold, dtype=dtype, device=dev, layers=layers)
+    if lab.B != 1:
+        raise ValueError("export labels one frame at a time (batch 1)")
+    C = lab.C
+    ds = cityscapesDataSet(data_dir, data_list, crop_size=(lab.scales[0][1], lab.scales[0][0]), mean=IMG_MEAN, scale=False, mirror=False,
+                           set=set_name)
+    os.makedirs(osp.join(data_dir, out_name), exist_ok=True)
+    lab.counts.zero_()
+
+    def write(slot, name):
+        slot["ready"].synchronize()                     # the D2H copy into this pinned buffer has landed
+        m = slot["host"][0].numpy()
+        png, color = output_paths(data_dir, out_name, name)
+        save_png_atomic(Image.fromarray(m), png)
+        if palette is not None:
+            save_png_atomic(colorize(m, palette), color)
+
+    # pinned staging buffers, one per label map in flight: the GPU labels frame i+1 while the writers encode frame i
+    slots = [{"host": torch.empty(1, lab.H, lab.W, dtype=torch.uint8).pin_memory(), "ready": torch.cuda.Event(), "job": None}
+             for _ in range(workers + 2)]
+    preps, xs = {}, None
+    lines = []
+    with ThreadPoolExecutor(workers) as readers, ThreadPoolExecutor(workers) as writers:
+        for i, (rgb, _, name) in enumerate(_bounded_map(readers, ds.decode, range(len(ds)), 2 * workers)):
+            key = rgb.shape[:2]
+            if key not in preps:
+                preps[key] = [InputPrep(1, key, (w, h), dev, with_label=False) for (h, w) in lab.scales]
+                xs = [torch.empty(1, 3, h, w, device=dev) for (h, w) in lab.scales]
+            rgb_d = torch.from_numpy(rgb[None]).to(dev)
+            for prep, x in zip(preps[key], xs):
+                prep.run(rgb_d, x)
+            out = lab.label(*xs)
+            slot = slots[i % len(slots)]
+            if slot["job"] is not None:
+                slot["job"].result()                    # the writer is done with this buffer (and re-raises its error, if any)
+            slot["host"].copy_(out, non_blocking=True)
+            slot["ready"].record()
+            slot["job"] = writers.submit(write, slot, name)
+            lines.append(list_line(set_name, name, out_name))
+        for slot in slots:
+            if slot["job"] is not None:
+                slot["job"].result()
+    counts = lab.counts.cpu().numpy()
+    tmp = f"{list_out}.{os.getpid()}.tmp"
+    with open(tmp, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
+    os.replace(tmp, list_out)
+    save_npy_atomic(class_dist(counts, C), class_dist_out)
+    if verbose:
+        total = max(int(counts.sum()), 1)
+        share = counts[:C] / max(int(counts[:C].sum()), 1)
+        print(f"{len(lines)} label maps -> {osp.join(data_dir, out_name)}; list {list_out}; prior {class_dist_out}")
+        for c in range(C):
+            print(f"class {c:3d}: {100 * share[c]:6.2f} %")
+        print(f"ignored (255): {100 * counts[C] / total:.2f} % of the pixels")
+    return counts
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------------
+
+def _wh(s):
+    try:
+        w, h = (int(v) for v in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected W,H, got {s!r}")
+    if w <= 0 or h <= 0:
+        raise argparse.ArgumentTypeError(f"expected positive W,H, got {s!r}")
+    return w, h
+
+
+def get_arguments(argv=None):
+    p = argparse.ArgumentParser(description="Export pseudo labels (PNG + list + class prior) from a DeepLab-v2 checkpoint on MI355X")
+    p.add_argument("--restore-from", type=str, required=True, help="source checkpoint (the same key forms as the training tools)")
+    p.add_argument("--arch", choices=["multi", "single"], default="multi",
+                   help="multi: DeeplabMulti (head layer6, first C channels); single: Res_Deeplab of model/deeplab.py")
+    p.add_argument("--num-classes", type=int, default=19)
+    p.add_argument("--open-classes", type=int, default=0, help="open-set classes of a SimT (multi) checkpoint; 0 for a source model")
+    p.add_argument("--data-dir", type=str, default="")
+    p.add_argument("--data-list", type=str, default="../dataset/cityscapes_list/train.txt")
+    p.add_argument("--set", type=str, default="train")
+    p.add_argument("--input-size", type=_wh, action="append", default=None,
+                   help="W,H of an input scale; repeat for several (default 1024,512 and 1280,640; --threshold uses the first)")
+    p.add_argument("--label-size", type=_wh, default=(2048, 1024), help="W,H of the label maps")
+    p.add_argument("--out-name", type=str, default="pseudo_labels", help="label directory under --data-dir, and the list's label prefix")
+    p.add_argument("--list-out", type=str, default=None, help="list file to write (default <out-name>.lst)")
+    p.add_argument("--class-dist-out", type=str, default=None, help="class prior .npy (default ClassDist_<out-name>.npy beside the list)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="confidence mode: softmax arg-max where max > T, 255 elsewhere (trainV2_simt.py:353-359); default: plain arg-max")
+    p.add_argument("--save-color", action="store_true", help="also write <name>_color.png with the palette of <devkit-dir>/info.json")
+    p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
+    p.add_argument("--eval-dtype", choices=["f32", "bf16"], default="f32",
+                   help="arithmetic of the forwards: fp32 like the reference; bf16 is a labelled opt-in")
+    p.add_argument("--num-workers", type=int, default=8, help=f"decode / encode threads each (capped at {MAX_WORKERS})")
+    p.add_argument("--gpu", type=int, default=0)
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = get_arguments(argv)
+    from simt_amd import model_spec as ms
+    from simt_amd.tools.trainV2_simt import restore
+    if not torch.cuda.is_available():
+        raise SystemExit("make_pseudo_labels needs a GPU: the forward and the label kernel have no CPU fallback")
+    dev = torch.device("cuda", args.gpu)
+    torch.cuda.set_device(dev)
+    C, K = args.num_classes, args.open_classes
+    single = args.arch == "single"
+    shapes = ms.state_shapes(C, single_head=True) if single else ms.state_shapes(C, K, K > 0)
+    state = ms.reference_init(shapes)
+    n = restore(state, args.restore_from, strip_prefix=6, required=True)
+    sizes = args.input_size or [(1024, 512), (1280, 640)]
+    dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
+    list_out = args.list_out or f"{args.out_name}.lst"
+    mode = "argmax" if args.threshold is None else "confidence"
+    print(f"restored {n} tensors from {args.restore_from}; arch {args.arch}, {mode}"
+          + (f" (threshold {args.threshold})" if args.threshold is not None else "")
+          + ("" if dtype == torch.float32 else "   (bf16 plans: not the reference's fp32 arithmetic)"))
+    export(state, args.data_dir, args.data_list, args.out_name, list_out, set_name=args.set, save_color=args.save_color,
+           devkit_dir=args.devkit_dir, workers=args.num_workers, class_dist_out=args.class_dist_out, num_classes=C, open_classes=K,
+           arch=args.arch, scales=[(h, w) for (w, h) in sizes], label_hw=(args.label_size[1], args.label_size[0]), mode=mode,
+           threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev)
+
+
+if __name__ == "__main__":
+    main()

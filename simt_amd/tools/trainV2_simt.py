@@ -14,13 +14,14 @@ without --synthetic is an error (a run that silently trains on noise would still
 Every --save-pred-every iterations: evaluate_simt on the validation set (--data-dir-val ...) and the best-mIoU snapshot rotation of
 trainV2_simt.py:452-464.  Additions over the reference (all optional): --synthetic, --compute-dtype, --eval-dtype (fp32 like the
 reference unless bf16 is asked for), --print-every, --data-dir-val,
---data-list-val, --gt-dir-val, --devkit-dir.
+--data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels).
 """
 import argparse
 import os
 import os.path as osp
 import time
 
+import numpy as np
 import torch
 
 from simt_amd import model_spec as ms
@@ -79,7 +80,25 @@ def get_arguments(argv=None):
     p.add_argument("--gt-dir-val", type=str, default="", help="directory of *_gtFine_labelIds.png (evaluate_cityscapes.py:140)")
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     p.add_argument("--from-scratch", action="store_true", help="allow training from the constructor init (no --restore-from)")
+    p.add_argument("--class-dist", type=str, default=None,
+                   help="class prior .npy of the pseudo labels (make_pseudo_labels writes it); default: ClassDist_bapa.npy")
     return p.parse_args(argv)
+
+
+def load_class_dist_arg(path, num_classes):
+    """--class-dist: the prior sig_NTM multiplies into T (model/deeplab_multi.py:255), checked before any training starts: a missing
+    or malformed file (shape other than [num_classes], sum not 1 within 1e-6) is a SystemExit naming the file."""
+    if not osp.isfile(path):
+        raise SystemExit(f"--class-dist {path!r} does not exist")
+    try:
+        cd = ms.load_class_dist(path=path)
+    except Exception as e:
+        raise SystemExit(f"--class-dist {path!r} is not a readable .npy file: {e}")
+    if cd.shape != (num_classes,) or not np.issubdtype(cd.dtype, np.floating):
+        raise SystemExit(f"--class-dist {path!r}: expected a float vector of shape ({num_classes},), got {cd.dtype} {cd.shape}")
+    if not np.all(np.isfinite(cd)) or abs(float(cd.sum()) - 1.0) > 1e-6:
+        raise SystemExit(f"--class-dist {path!r}: the prior must sum to 1 (within 1e-6), sums to {float(cd.sum())!r}")
+    return cd
 
 
 def restore(state, path, not_restore_last=False, strip_prefix=0, required=False):
@@ -161,6 +180,7 @@ def batches(args, B, H, W, cd, rank, world, dev):
 
 def main(argv=None):
     args = get_arguments(argv)
+    class_dist = load_class_dist_arg(args.class_dist, args.num_classes) if args.class_dist else None
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -182,7 +202,7 @@ def main(argv=None):
     fixed = ms.reference_init(ms.state_shapes(C, 0, False), seed=args.random_seed)
     n1 = restore(state, args.restore_from, args.not_restore_last, required=not (args.synthetic or args.from_scratch))
     n2 = restore(fixed, args.restore_from, required=not (args.synthetic or args.from_scratch))
-    cd = ms.load_class_dist("bapa")
+    cd = class_dist if class_dist is not None else ms.load_class_dist("bapa")
     hp = Hyper(num_classes=C, open_classes=K, th_high=args.Threshold_high, th_low=args.Threshold_low,
                lambda_seg=args.lambda_seg, lambda_place=args.lambda_Place, lambda_convex=args.lambda_Convex,
                lambda_volume=args.lambda_Volume, lambda_anchor=args.lambda_Anchor, iter_size=args.iter_size,
