@@ -1,0 +1,392 @@
+"""The two other benchmarked models, launch by launch, against float64 (bench.py --model v3 / --model vgg, bf16).
+
+DeepLabv3 (B=4, 512x1024, layers (3, 4, 6), Q = 19 + 6) and DeepLab-VGG16 (B=8, 512x512, Q = 19 + 3): the trainable plan (pack list,
+forward, backward) and the frozen plan (pack list, forward) at the sizes bench.py times, Kaiming weights.  Every launch of those lists is
+replayed ONE AT A TIME on one stream (SIMT_SINGLE_STREAM=1; SIMT_BN_GRID=0: the two-pass BatchNorm, whose fused forms
+tests/test_gpu_bn_fused.py ties bit for bit to these), its inputs snapshotted and its outputs poisoned before it runs, and checked right
+after by the descriptor-driven float64 oracle of tests/_launch_oracle.py; the chain then continues on the kernel's own result.
+
+Coverage is enforced: a launch that no handler checks and whose tag is not in NOT_HERE fails the test by name.  Each conv launch's weight
+operand is traced to the parameter(s) the pack jobs wrote into that buffer, and the launch's geometry (Cin, Cout, stride, taps, H / W) must
+be that layer's as v3_block_specs / ASSP_BRANCHES / VGG_LAYERS describe it; every layer must be launched in each direction.  With the
+packing check (packed operand == bf16 of the parameter) this ties every conv's weight operand to its own parameter.  The activation
+operand is not traced: it is whatever the previous launch of the chain wrote, checked there.
+"""
+import time
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _launch_oracle as lo
+from oracle import simt_oracle as so
+from simt_amd import _lib as L
+from simt_amd import model_spec as ms
+from simt_amd import ops
+
+pytestmark = pytest.mark.gpu
+BF = torch.bfloat16
+CD = so.load_class_dist()
+
+# tag -> the test that holds launches of that tag instead.  Empty: with SIMT_BN_GRID=0 the plans carry no fused-BatchNorm launch (the only
+# form this oracle refuses), and every other entry point has a handler.
+NOT_HERE = {}
+
+
+def _key(d):
+    return (d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.stride, tuple(lo.conv_taps_of(d)))
+
+
+def _k(Bn, Hi, Wi, Cin, Ho, Wo, Cout, stride, taps):
+    return (Bn, Hi, Wi, Cin, Ho, Wo, Cout, stride, tuple(taps))
+
+
+def _neg(taps):
+    return [(-a, -b) for (a, b) in taps]
+
+
+def v3_layers(B, H, W, layers, Q, width=64, ac=256):
+    """{parameter prefix: {"fwd": geometry, "bwd": geometry or None}} of DeepLabv3, restated from the layer specs (model/deeplabv3.py via
+    engine_v3's tables): the conv launch whose weight operand was packed from that parameter must have exactly this geometry."""
+    from simt_amd.engine_v3 import ASSP_BRANCHES, R50, v3_block_specs, v3_geometry
+    (H0, W0), (Hp, Wp) = v3_geometry(H, W)
+    one = [(0, 0)]
+    out = {R50 + "conv1": {"fwd": _k(1, 1, B * H0 * W0, 192, 1, B * H0 * W0, width, 1, one), "bwd": None}}
+    Hc, Wc = Hp, Wp
+    t3 = ops.conv_taps(3, 3, 1, 1)
+    for (n, inpl, p, s, down) in v3_block_specs(layers, width):
+        Ho, Wo, c4 = (Hc - 1) // s + 1, (Wc - 1) // s + 1, 4 * p
+        out[n + ".conv1"] = {"fwd": _k(B, Hc, Wc, inpl, Hc, Wc, p, 1, one), "bwd": _k(B, Hc, Wc, p, Hc, Wc, inpl, 1, one)}
+        out[n + ".conv2"] = {"fwd": _k(B, Hc, Wc, p, Ho, Wo, p, s, t3), "bwd": _k(B, Hc, Wc, p, Hc, Wc, p, 1, _neg(t3))}
+        out[n + ".conv3"] = {"fwd": _k(B, Ho, Wo, p, Ho, Wo, c4, 1, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, p, 1, one)}
+        if down:
+            out[n + ".downsample.0"] = {"fwd": _k(B, Hc, Wc, inpl, Ho, Wo, c4, s, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, inpl, 1, one)}
+        Hc, Wc, cin = Ho, Wo, c4
+    h, w = Hc, Wc
+    for (i, k, dil) in ASSP_BRANCHES:
+        taps = ops.conv_taps(3, 3, dil, dil) if k == 3 else one
+        out[f"assp.conv{i}"] = {"fwd": _k(B, h, w, cin, h, w, ac, 1, taps), "bwd": _k(B, h, w, ac, h, w, cin, 1, _neg(taps))}
+    # convf: 5 taps stepping one plane over the virtual concat; its dgrad plane by plane
+    out["assp.convf"] = {"fwd": _k(1, 5 * B * h, w, ac, B * h, w, ac, 1, [(t * B * h, 0) for t in range(5)]), "bwd": _k(B, h, w, ac, h, w, ac, 1, one)}
+    for pre in (("conv", "conv_1") if Q > 19 else ("conv",)):                    # classifier(s): fp32 logits, K-padded dgrad
+        out[pre] = {"fwd": _k(B, h, w, ac, h, w, Q, 1, one), "bwd": _k(B, h, w, ops.round_up(Q, 64), h, w, ac, 1, one)}
+    return out
+
+
+def vgg_layers(B, H, W, Q, kq=64):
+    from simt_amd.engine_vgg import VGG_LAYERS
+    one = [(0, 0)]
+    out = {}
+    Hc, Wc = H, W
+    for li, (idx, cin, cout, dil, pool) in enumerate(VGG_LAYERS):
+        M = B * Hc * Wc
+        if li == 0:                                                              # im2col matrix, K = 27 padded to 64
+            out[f"features.{idx}"] = {"fwd": _k(1, 1, M, kq, 1, M, cout, 1, one), "bwd": None}
+        else:
+            t3 = ops.conv_taps(3, 3, dil, dil)
+            out[f"features.{idx}"] = {"fwd": _k(B, Hc, Wc, cin, Hc, Wc, cout, 1, t3), "bwd": _k(B, Hc, Wc, cout, Hc, Wc, cin, 1, _neg(t3))}
+        if pool:
+            Hc, Wc = Hc // 2, Wc // 2
+    nt, QP, c = 18, ops.round_up(Q, 8), VGG_LAYERS[-1][2]
+    for i in range(2):                                                           # the two live branches, one tap-expanded GEMM
+        out[f"classifier.conv2d_list.{i}"] = {"fwd": _k(B, Hc, Wc, c, Hc, Wc, nt * QP, 1, one),
+                                              "bwd": _k(B, Hc, Wc, ops.round_up(nt * QP, kq), Hc, Wc, c, 1, one)}
+    return out
+
+
+def match_layers(plan, run, layers, train):
+    """Each recorded conv launch -> the parameter(s) packed into the buffer its weight operand points into (the plan's pack jobs), in the packing
+    direction (mode 1 = dgrad operand); its geometry must be that layer's.  Records which (layer, direction) pairs were launched."""
+    mem = _mem(plan)
+    names = {t.data_ptr(): n[:-len(".weight")] for n, t in plan.p.items() if n.endswith(".weight")}
+    packs = {}
+    for it in plan._pack_items_raw:
+        if lo.fn_name(it) != "simt_pack_weight":
+            continue
+        w, dst, mode = it.args[0], it.args[1], it.args[9]
+        packs.setdefault(mem.span_of(dst)[0], set()).add((names[w], "bwd" if (mode & 0xFF) == 1 else "fwd"))
+    for (where, dirn, key, wptr) in run.convs:
+        owners = packs.get(mem.span_of(wptr)[0])
+        if not owners:
+            run.layer_bad.append(f"{where}: weight operand not packed from any parameter")
+            continue
+        for (pname, pdir) in sorted(owners):
+            want = layers.get(pname, {}).get(pdir)
+            if pdir != dirn or want != key:
+                run.layer_bad.append(f"{where}: operand packed from {pname} ({pdir}) expects {want}, launch has {key} ({dirn})")
+            else:
+                run.layer_seen.add((pname, pdir))
+    want_all = {(n, dd) for n, g in layers.items() for dd in (("fwd", "bwd") if train else ("fwd",)) if g[dd] is not None}
+    run.layer_missing = sorted(want_all - run.layer_seen)
+
+
+def _mem(plan):
+    ts = list(plan._keep) + list(plan._bufs.values()) + list(plan.p.values())
+    if getattr(plan, "flat_grad", None) is not None:
+        ts.append(plan.flat_grad)
+    for lst in (plan.pack_list, plan.fwd_list, plan.bwd_list):
+        for it in lst.items:
+            if isinstance(it.keep, tuple):
+                ts += [t for t in it.keep if isinstance(t, torch.Tensor)]
+    return lo.Mem(ts)
+
+
+class Run:
+    def __init__(self):
+        self.worst = {}          # (tag, shape) -> worst error / bound
+        self.fail, self.uncovered = [], []
+        self.convs = []          # (where, "fwd" | "bwd", geometry, weight operand pointer) of every conv launch
+        self.layer_bad, self.layer_seen, self.layer_missing = [], set(), []
+        self.secs, self.tflop = 0.0, 0.0
+        self.red = {}            # what -> list of perturbations the checker caught
+        self.n = 0
+
+
+def replay(plan, lists, run, red=None, seed=0):
+    """Replay the lists item by item under the oracle.  red(lname, it, chk, got): optional hook called after a green check."""
+    mem = _mem(plan)
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx = {"seed": seed, "dst_sizes": lambda ptr, dt: (sum(mem.span_of(ptr)) - ptr) // torch.empty((), dtype=dt).element_size()}
+    for lname, lst in lists:
+        for i, it in enumerate(lst.items):
+            if it.fn is None:
+                continue
+            name = lo.fn_name(it)
+            where = f"{lname}[{i}] {name} <{it.tag}> {it.shape or ''}"
+            if name == "simt_conv_fprop":
+                assert not it.keep.fbn, f"{where}: fused BatchNorm launch although SIMT_BN_GRID=0"
+                run.convs.append((where, "bwd" if lname.endswith("bwd") else "fwd", _key(it.keep), it.keep.w))
+            try:
+                chk = lo.prepare(it, mem, ctx)
+            except (AssertionError, KeyError, NotImplementedError) as e:
+                run.fail.append(f"{where}: cannot prepare: {e}")
+                chk = None
+            if chk is None and lo.HANDLERS.get(name) is None and it.tag not in NOT_HERE:
+                run.uncovered.append(where)
+            rc = it.fn(*it.args, stream)
+            if rc != 0:
+                L.check(rc)
+            if chk is None:
+                continue
+            torch.cuda.synchronize()
+            got = chk.outputs()
+            try:
+                for (tag, shape, r) in chk.check(got):
+                    key = (tag, shape)
+                    run.worst[key] = max(run.worst.get(key, 0.0), r)
+                if red is not None:
+                    red(lname, it, chk, got)
+            except (AssertionError, NotImplementedError, RuntimeError) as e:
+                run.fail.append(f"{where}: {e}")
+            chk.finish()
+            run.n += 1
+            del chk, got
+
+
+def _env(mp):
+    mp.setenv("SIMT_SINGLE_STREAM", "1")
+    mp.setenv("SIMT_BN_GRID", "0")
+    import simt_amd.engine as eng
+    eng._SIDE_STREAMS.clear()
+
+
+def _seed_and_backward(plan, lists_bwd, run, red, B, Q, dev, v3):
+    g = torch.Generator().manual_seed(8)
+    if v3:
+        plan.dout_full.copy_((torch.randn(plan.dout_full.shape, generator=g) / (plan.H * plan.W)).to(dev))
+    else:
+        for dl in plan.dlogits.values():
+            hd = plan.heads[0]
+            dl.zero_()
+            dl[:, :Q] = (torch.randn(dl.shape[0], Q, generator=g) / (hd.h * hd.w)).to(BF).to(dev)
+    replay(plan, lists_bwd, run, red)
+
+
+def _perturb(chk, got, what, cases):
+    """Each case: (name, mutate(copy of got)) -> the checker must raise AssertionError."""
+    caught = []
+    for name, mut in cases:
+        g2 = {k: v.clone() for k, v in got.items()}
+        mut(g2)
+        try:
+            chk.check(g2)
+        except AssertionError:
+            caught.append(name)
+    return caught
+
+
+def _two_ulps(t, idx):
+    v = t[idx].double()
+    t[idx] = (v + 2.5 * lo.ulp_bf16(v.abs(), 1e-30) * (1 if v >= 0 else -1)).to(t.dtype)
+
+
+def _red_hook(run):
+    def hook(lname, it, chk, got):
+        name = lo.fn_name(it)
+        if "conv" not in run.red and name == "simt_conv_fprop" and it.keep.stats and it.keep.ntaps == 9 and it.keep.stride == 1 \
+                and it.keep.B * it.keep.Ho * it.keep.Wo == 8192:
+            y = got["y"]
+            col = int(y[0].float().abs().argmax())
+            border = 10                                           # pixel (b 0, row 0, col 10): its top taps read outside the image
+            cases = [("2 ulps", lambda g: _two_ulps(g["y"], (0, col))),
+                     ("columns swapped", lambda g: g["y"].copy_(g["y"][:, [1, 0] + list(range(2, g["y"].shape[1]))])),
+                     ("border row zeroed", lambda g: g["y"][border].zero_()),
+                     ("stats slot 1e-3", lambda g: g["stats"][3].mul_(1.0 + 1e-3))]
+            run.red["conv"] = (f"{it.tag} {it.shape}", [c[0] for c in cases], _perturb(chk, got, "conv", cases))
+        if "wgrad" not in run.red and name == "simt_conv_wgrad" and it.keep.ntaps == 9 and int(it.keep.dy_[0]) == -18:
+            s = got["slab0"]
+            flat = int(s[0].abs().argmax())
+            co, kk = flat // s.shape[2], flat % s.shape[2]
+            cases = [("2 ulps", lambda g: _two_ulps(g["slab0"], (0, co, kk))),
+                     ("columns swapped", lambda g: g["slab0"].copy_(g["slab0"][:, :, [1, 0] + list(range(2, s.shape[2]))])),
+                     ("edge-tap row zeroed", lambda g: g["slab0"][:, 0, :it.keep.Cin].zero_())]
+            run.red["wgrad"] = (f"{it.tag} {it.shape}", [c[0] for c in cases], _perturb(chk, got, "wgrad", cases))
+        if "maxpool2_bwd" not in run.red and name == "simt_maxpool2_bwd":
+            da = got["da"]
+            nz = (da[0, 0] != 0).nonzero()
+            assert nz.shape[0] > 0
+            e = (0, 0) + tuple(int(v) for v in nz[0])
+            cases = [("2 ulps", lambda g: _two_ulps(g["da"], e)),
+                     ("columns swapped", lambda g: g["da"].copy_(g["da"][..., [1, 0] + list(range(2, da.shape[-1]))])),
+                     ("border row zeroed", lambda g: g["da"][0, 0].zero_())]
+            run.red["maxpool2_bwd"] = (f"{it.tag} {it.args[4:8]}", [c[0] for c in cases], _perturb(chk, got, "maxpool2_bwd", cases))
+    return hook
+
+
+@pytest.fixture(scope="module")
+def runs(dev):
+    """Both models replayed once (the red cases are taken on the way); every test below reads its part."""
+    from simt_amd.engine_v3 import V3Plan, v3_state_shapes
+    from simt_amd.engine_vgg import VggPlan, vgg_state_shapes
+    out = {}
+    with pytest.MonkeyPatch.context() as mp:
+        _env(mp)
+        # ---- DeepLabv3, bench.py --model v3: B=4, 512x1024, layers (3, 4, 6), Q = 19 + 6
+        t0, f0 = time.time(), lo.GEMM_FLOPS[0]
+        K, B, H, W, lay = 6, 4, 512, 1024, (3, 4, 6)
+        run = Run()
+        hook = _red_hook(run)
+        img, _ = ms.synthetic_batch(B, H, W, CD.numpy(), seed=7, device=dev)
+        st = ms.kaiming_init(v3_state_shapes(19, K, True, layers=lay), seed=1234)
+        p = {k: v.to(dev) for k, v in st.items()}
+        tr = V3Plan(p, B, H, W, 19, K, True, dtype=BF, train=True, layers=lay)
+        tr.x_in.copy_(img)
+        replay(tr, [("v3.pack", tr.pack_list), ("v3.fwd", tr.fwd_list)], run, hook)
+        _seed_and_backward(tr, [("v3.bwd", tr.bwd_list)], run, hook, B, 19 + K, dev, True)
+        match_layers(tr, run, v3_layers(B, H, W, lay, 19 + K), True)
+        del tr, p
+        torch.cuda.empty_cache()
+        fst = ms.kaiming_init(v3_state_shapes(19, 0, False, layers=lay), seed=1234)
+        fp = {k: v.to(dev) for k, v in fst.items()}
+        fr = V3Plan(fp, B, H, W, 19, 0, False, dtype=BF, train=False, layers=lay)
+        fr.x_in.copy_(img)
+        run_f = Run()
+        replay(fr, [("v3f.pack", fr.pack_list), ("v3f.fwd", fr.fwd_list)], run_f)
+        match_layers(fr, run_f, v3_layers(B, H, W, lay, 19), False)
+        del fr, fp
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        out["v3"] = (run, run_f, time.time() - t0, lo.GEMM_FLOPS[0] - f0)
+        # ---- DeepLab-VGG16, bench.py --model vgg: B=8, 512x512, Q = 19 + 3
+        t0, f0 = time.time(), lo.GEMM_FLOPS[0]
+        K, B, H, W = 3, 8, 512, 512
+        run = Run()
+        hook = _red_hook(run)
+        img, _ = ms.synthetic_batch(B, H, W, CD.numpy(), seed=7, device=dev)
+        st = ms.kaiming_init(vgg_state_shapes(19 + K), seed=1234)
+        p = {k: v.to(dev) for k, v in st.items()}
+        tr = VggPlan(p, B, H, W, 19 + K, dtype=BF, train=True)
+        tr.x_in.copy_(img)
+        replay(tr, [("vgg.pack", tr.pack_list), ("vgg.fwd", tr.fwd_list)], run, hook)
+        _seed_and_backward(tr, [("vgg.bwd", tr.bwd_list)], run, hook, B, 19 + K, dev, False)
+        match_layers(tr, run, vgg_layers(B, H, W, 19 + K), True)
+        del tr, p
+        torch.cuda.empty_cache()
+        fst = ms.kaiming_init(vgg_state_shapes(19), seed=1234)
+        fp = {k: v.to(dev) for k, v in fst.items()}
+        fr = VggPlan(fp, B, H, W, 19, dtype=BF, train=False)
+        fr.x_in.copy_(img)
+        run_f = Run()
+        replay(fr, [("vggf.pack", fr.pack_list), ("vggf.fwd", fr.fwd_list)], run_f)
+        match_layers(fr, run_f, vgg_layers(B, H, W, 19), False)
+        del fr, fp
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        out["vgg"] = (run, run_f, time.time() - t0, lo.GEMM_FLOPS[0] - f0)
+    import simt_amd.engine as eng
+    eng._SIDE_STREAMS.clear()
+    return out
+
+
+def _assert_model(name, runs):
+    run, run_f, secs, flops = runs[name]
+    worst = dict(run.worst)
+    for k, v in run_f.worst.items():
+        worst[k] = max(worst.get(k, 0.0), v)
+    print(f"\n{name}: {run.n + run_f.n} launches checked in {secs:.1f} s wall (plans built, replayed and checked; "
+          f"{flops / 1e12:.2f} TFLOP of float64 GEMM in the oracle); {len(worst)} distinct (tag, shape), worst error / bound:")
+    for (tag, shape), r in sorted(worst.items()):
+        print(f"  {r:6.3f}  {tag}  {shape}")
+    fails = run.fail + run_f.fail
+    assert not fails, f"{name}: {len(fails)} launch(es) outside their float64 bar:\n  " + "\n  ".join(fails[:40])
+    unc = run.uncovered + run_f.uncovered
+    assert not unc, f"{name}: {len(unc)} launch(es) neither checked by a handler nor listed in NOT_HERE:\n  " + "\n  ".join(unc[:40])
+    # every conv launch has the geometry of the layer whose parameter was packed into its weight operand, and every layer is launched
+    bad = run.layer_bad + run_f.layer_bad
+    assert not bad, f"{name}: {len(bad)} conv launch(es) not matching their layer:\n  " + "\n  ".join(bad[:20])
+    for what, r in (("trainable", run), ("frozen", run_f)):
+        assert not r.layer_missing, f"{name} {what} plan: layers never launched {r.layer_missing[:6]}"
+    assert all(r <= 1.0 for r in worst.values())
+
+
+def test_v3_plan_launches_hold_float64_b4_512x1024(runs):
+    """DeepLabv3 + SimT(K=6) bf16 at bench.py's size: every launch of the trainable (pack, forward, backward) and frozen (pack, forward)
+    plans within its float64 bar; each conv launch has the geometry of its layer (v3_block_specs / ASSP_BRANCHES)."""
+    _assert_model("v3", runs)
+
+
+def test_vgg_plan_launches_hold_float64_b8_512x512(runs):
+    """DeepLab-VGG16 + SimT(K=3) bf16 at bench.py's size (M = 2 097 152 in layer 0): every launch within its float64 bar; each conv launch has
+    the geometry of its layer (VGG_LAYERS, the tap-expanded head)."""
+    _assert_model("vgg", runs)
+
+
+def test_launch_oracle_is_red_on_perturbed_results(runs):
+    """The checker must fail on a copy of a real launch's stored result with one element moved by 2 bf16 ulps, two output columns swapped, one
+    border row zeroed and (conv) one statistics slot off by 1e-3 relative: a conv launch at M = 8192 (3x3, statistics), the dilation-18 ASSP
+    weight gradient and a VGG max-pool backward.  Stored data only is perturbed; the descriptors are untouched."""
+    red = {}
+    for name in ("v3", "vgg"):
+        red.update(runs[name][0].red)
+    assert set(red) == {"conv", "wgrad", "maxpool2_bwd"}, f"red cases found: {sorted(red)}"
+    for what, (launch, cases, caught) in red.items():
+        print(f"{what}: {launch}: caught {caught}")
+        assert caught == cases, f"{what} ({launch}): the checker missed {sorted(set(cases) - set(caught))}"
+
+
+def test_maxpool2_ties_follow_torch(dev):
+    """simt_maxpool2 on bf16 with planted ties (equal values in 2x2 windows, all-zero windows, a negative-zero tie) against CPU
+    torch.max_pool2d(return_indices=True), which keeps the FIRST maximum in scan order; and the oracle's restatement of that rule
+    (_launch_oracle.maxpool2_expect) against the same."""
+    B, H, W, Cn = 2, 64, 96, 64
+    g = torch.Generator().manual_seed(5)
+    y = torch.randn(B, H, W, Cn, generator=g).round().to(BF)          # integers in about [-4, 4]: many exact ties
+    y[:, 0:8] = 0.0                                                   # all-zero windows
+    y[0, 8, 0, :] = 3.0
+    y[0, 9, 1, :] = 3.0                                               # tie between (0, 0) and (1, 1)
+    y[1, 10, 2, :] = -0.0
+    y[1, 10, 3, :] = 0.0
+    y[1, 11, 2:4, :] = -1.0                                           # +0 / -0 tie
+    yd = y.to(dev)
+    Hp, Wp = H // 2, W // 2
+    p = torch.empty(B, Hp, Wp, Cn, device=dev, dtype=BF)
+    idx = torch.empty(B, Hp, Wp, Cn, device=dev, dtype=torch.uint8)
+    L.call("simt_maxpool2", yd.data_ptr(), p.data_ptr(), idx.data_ptr(), B, H, W, Cn, L.SIMT_BF16, ops.stream_ptr())
+    torch.cuda.synchronize()
+    rv, ri = F.max_pool2d(y.permute(0, 3, 1, 2), 2, 2, return_indices=True)
+    ri = ri.permute(0, 2, 3, 1)                                       # flat index iy * W + ix in the plane
+    r_idx = ((ri // W) % 2) * 2 + (ri % W) % 2
+    assert torch.equal(p.cpu(), rv.permute(0, 2, 3, 1))
+    assert torch.equal(idx.cpu().long(), r_idx), "arg-max index differs from torch's first maximum"
+    best, bi = lo.maxpool2_expect(y)
+    assert torch.equal(best, rv.permute(0, 2, 3, 1)) and torch.equal(bi.long(), r_idx)

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _launch_oracle import tight_bf16 as _tight_bf16
+from _launch_oracle import ulp_bf16 as _ulp_bf16
 from oracle import ops_ref
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
@@ -38,14 +40,9 @@ def _rel(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
 
 
-# ---- the bf16 per-op bar, tied to the STORAGE FORMAT (round 5) -------------------------------------------------------------
-# `_rel < 1e-2 of max|ref|` is 10-50x looser than one bf16 ulp of a typical element: round 4's stale-dword store bug passed it.  Here every
-# element is compared with the float64 result of the same op on the same bf16 operands (shifted float64 matmuls on the device: test
-# infrastructure, the product never calls a vendor GEMM):
-#     |got - ref| <= 1 ulp_bf16(ref) + 16 * sqrt(K) * 2^-24 * rms(ref)        (one rounding of an fp32 sum of K products)
-# for EVERY element, and got == bf16(ref) exactly for at least `exact_min` of them (what is left are round-to-nearest ties decided by the
-# last bits of the fp32 sum).  ulp_bf16(v) = 2^(floor(log2 |v|) - 7), floored at the ulp of rms * 2^-6 so that near-zero results are held to
-# the accumulation slack, not to a vanishing ulp.
+# ---- the bf16 per-op bar, tied to the STORAGE FORMAT (round 5): tests/_launch_oracle.py tight_bf16 (its comment derives the bound).  Every element
+# is compared with the float64 result of the same op on the same bf16 operands (shifted float64 matmuls on the device: test infrastructure, the
+# product never calls a vendor GEMM).
 def _conv64(x_nhwc, w_oihw, stride, pad, dil):
     """float64 conv of NHWC x (any float dtype, on the device) with OIHW weights -> [B, Ho, Wo, Cout] float64, as k*k shifted matmuls."""
     B, H, W, Cin = x_nhwc.shape
@@ -59,33 +56,6 @@ def _conv64(x_nhwc, w_oihw, stride, pad, dil):
             xs = xp[:, r * dil:r * dil + (Ho - 1) * stride + 1:stride, c * dil:c * dil + (Wo - 1) * stride + 1:stride, :]
             out += xs.reshape(-1, Cin) @ wd[:, :, r, c].t()
     return out.view(B, Ho, Wo, Cout)
-
-
-def _ulp_bf16(ref64, floor_at):
-    mag = ref64.abs().clamp_min(floor_at)
-    return torch.exp2(torch.floor(torch.log2(mag)) - 7.0)
-
-
-def _tight_bf16(got_bf16, ref64, K, what, exact_min=0.995, inner64=None):
-    """got: bf16 tensor as stored by the kernel; ref64: float64 result before the final rounding (same shape, same device).
-    inner64: for the epilogues that ROUND TWICE -- the conv kernels park the accumulators as a bf16 tile in LDS and apply bias / residual /
-    ReLU to the parked values on the way out (what unfused bf16 PyTorch ops do: the conv's output tensor is bf16 before `+= residual`) -- the
-    float64 conv result before that FIRST rounding; ref64 is then computed by the caller from bf16(inner64).  Where the fp32 sum and the
-    float64 sum round to different bf16 neighbours (rare: decided by the last bits of the sum) the output moves by one ulp OF THE CONV RESULT,
-    which after a cancelling residual can be many ulps of the output: one such ulp is added to the bound."""
-    assert got_bf16.dtype == BF and ref64.dtype == torch.float64 and got_bf16.shape == ref64.shape
-    g = got_bf16.double()
-    rms = ref64.pow(2).mean().sqrt().item()
-    tol = _ulp_bf16(ref64, rms * 2.0 ** -6) + 16.0 * (K ** 0.5) * 2.0 ** -24 * rms
-    if inner64 is not None:
-        tol = tol + _ulp_bf16(inner64, inner64.pow(2).mean().sqrt().item() * 2.0 ** -6)
-    bad = (g - ref64).abs() > tol
-    nbad = int(bad.sum().item())
-    exact = (got_bf16 == ref64.float().to(BF)).double().mean().item()
-    assert nbad == 0, (f"{what}: {nbad} of {bad.numel()} elements off by more than 1 bf16 ulp + fp32 accumulation slack (worst "
-                       f"{((g - ref64).abs() / tol).max().item():.1f} x the bound; first at {bad.nonzero()[0].tolist()})")
-    assert exact >= exact_min, f"{what}: only {exact:.5f} of the elements equal the float64 result rounded to bf16 (bar {exact_min})"
-    return exact
 
 
 def _variant(d):
