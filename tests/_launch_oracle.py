@@ -15,7 +15,8 @@ The bars:
   * fp32 outputs and per-slot fp32 partial sums: `fp32_sum_bound`, the form of test_wgrad_production_shapes_bf16's bound;
   * data movement (pools, scatters, im2col, packing, slab reduces): bit-exact against a restatement of the same arithmetic.
 
-Conv outputs are checked on a sampled set of pixel rows (`conv_rows`); statistics and BatchNorm sums on whole columns.
+Conv outputs are checked on a sampled set of pixel rows (`conv_rows`); statistics and BatchNorm sums on whole columns (the direct stem's
+statistics slot by slot: each is one 8 x 32 output tile).
 Launches that carry a fused BatchNorm (simt_conv_desc.fbn) are refused: run the plans with SIMT_BN_GRID=0.
 """
 import ctypes as C
@@ -164,11 +165,14 @@ class Mem:
             if key not in spans or spans[key][1] < base.nbytes():
                 spans[key] = (key, base.nbytes(), t)
         self.spans = sorted(spans.values(), key=lambda s: s[0])
+        self.log = None          # while a handler prepares a launch (see prepare): every (address, bytes) it views
 
     def view(self, ptr, n, dtype):
         """Flat [n] view of dtype at device address ptr."""
         assert ptr, "NULL operand"
         esz = torch.empty((), dtype=dtype).element_size()
+        if self.log is not None:
+            self.log.append((ptr, n * esz))
         for start, nbytes, t in self.spans:
             if start <= ptr and ptr + n * esz <= start + nbytes:
                 raw = torch.empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage(), 0, (nbytes,))
@@ -188,11 +192,29 @@ def _overlap(a, b):
     return a[0] < b[0] + b[1] and b[0] < a[0] + a[1]
 
 
-class Check:
-    """One prepared launch: `outs` = {name: (view, poison)} written by the kernel; `fn(got) -> [(tag, shape, ratio)]`."""
+def extent(v):
+    """(address, bytes) a written view covers: whole rows of a pitched [rows, cols] view (its pitch columns included), else the view."""
+    esz = v.element_size()
+    if v.dim() == 2 and v.stride(1) == 1 and v.stride(0) >= v.shape[1]:
+        return v.data_ptr(), v.shape[0] * v.stride(0) * esz
+    assert v.is_contiguous(), "written view is neither contiguous nor row-pitched"
+    return v.data_ptr(), v.numel() * esz
 
-    def __init__(self, outs, fn, restore=()):
+
+class Check:
+    """One prepared launch: `outs` = {name: (view, poison)} written by the kernel; `fn(got) -> [(tag, shape, ratio)]`.
+
+    For the last-writer trace (tests/_plan_trace.py): `reads` = [(operand name, address, bytes)] -- the activation operands by name (conv
+    x / res, weight-gradient dy{i} / x{i}, BatchNorm-backward dz / y), every other range the handler viewed as in{k} (filled by prepare);
+    writes() = the extents of `outs`.  `problems` = [(dy name, x name, output name)] of a weight-gradient launch; `jobs` = [(slab read name,
+    destination output name)] of a slab reduce."""
+
+    def __init__(self, outs, fn, restore=(), reads=(), problems=(), jobs=()):
         self.outs, self.fn, self.restore = outs, fn, list(restore)
+        self.reads, self.problems, self.jobs = list(reads), list(problems), list(jobs)
+
+    def writes(self):
+        return [(k,) + extent(v) for k, (v, _p) in self.outs.items()]
 
     def outputs(self):
         return {k: v.clone() for k, (v, _p) in self.outs.items()}
@@ -295,28 +317,34 @@ def prepare_conv(it, mem, seed=0):
     w = mem.view(d.w, d.Npad * K, tin).view(d.Npad, K)
     ins = [(d.x, B * H * W * Cin * x.element_size()), (d.w, d.Npad * K * w.element_size())]
     snap = {"x": x, "w": w}                                                   # views; cloned below where an output may alias them
+    reads = [("x", d.x, ins[0][1]), ("w", d.w, ins[1][1])]
     if d.bias:
         snap["bias"] = mem.view(d.bias, Cout, torch.float32).clone()
     if d.res:
         r = mem.view(d.res, M * d.ldr, tin).view(M, d.ldr)
         snap["res"] = r[:, :Nst].clone()
         ins.append((d.res, M * d.ldr * r.element_size()))
+        reads.append(("res", d.res, M * d.ldr * r.element_size()))
     if d.res_bits:
         snap["res_bits"] = unpack_bits(mem.view(d.res_bits, M * d.ldr // 8, torch.uint8), M, d.ldr)[:, :Nst].clone()
+        reads.append(("res_bits", d.res_bits, M * d.ldr // 8))
     if d.mask:
         mk = mem.view(d.mask, M * d.ldm, tin).view(M, d.ldm)
         snap["mask"] = mk[:, :Nst].clone()
         ins.append((d.mask, M * d.ldm * mk.element_size()))
+        reads.append(("mask", d.mask, M * d.ldm * mk.element_size()))
     if d.in_scale:
         snap["in_scale"] = mem.view(d.in_scale, Cin, torch.float32).clone()
         snap["in_shift"] = mem.view(d.in_shift, Cin, torch.float32).clone()
     if d.bnr_mode:
         snap["bnr_y"] = mem.view(d.bnr_y, M * d.bnr_ld, tin).view(M, d.bnr_ld)[:, :Cout].clone()
+        reads.append(("bnr_y", d.bnr_y, M * d.bnr_ld * snap["bnr_y"].element_size()))
         snap["bnr_mean"], snap["bnr_rstd"] = (mem.view(p, Cout, torch.float32).clone() for p in (d.bnr_mean, d.bnr_rstd))
         if d.bnr_mode == 2:
             snap["bnr_scale"], snap["bnr_shift"] = (mem.view(p, Cout, torch.float32).clone() for p in (d.bnr_scale, d.bnr_shift))
         else:
             snap["bnr_bits"] = unpack_bits(mem.view(d.bnr_bits, M * Cout // 8, torch.uint8), M, Cout).clone()
+            reads.append(("bnr_bits", d.bnr_bits, M * Cout // 8))
     yfull = mem.view(d.y, M * ldy, tout).view(M, ldy)
     outs = {"y": (yfull[:, :Nst], True)}
     restore = []
@@ -406,7 +434,7 @@ def prepare_conv(it, mem, seed=0):
             recs.append((it.tag + " [bnr S1/S2]", shape, fp32_bar(got_s[:2], ref, tol, what + " bnr S1/S2")))
             assert bool((got["bnr"][:, 2] == 0).all()), f"{what}: third bnr row not zero"
         return recs
-    return Check(outs, fn, restore)
+    return Check(outs, fn, restore, reads=reads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -441,11 +469,13 @@ def _wgrad_views(d, mem):
 
 def prepare_wgrad_descs(it, descs, mem):
     parts = []
-    outs = {}
+    outs, reads, problems = {}, [], []
     for i, d in enumerate(descs):
         dyv, x, slab, dd, M, Kt, ns = _wgrad_views(d, mem)
         parts.append((dyv, x, dd, M, Kt, ns))                # (views: a weight-gradient launch writes its slab only)
         outs[f"slab{i}"] = (slab, True)
+        reads += [(f"dy{i}", d.dy, M * d.ldd * dyv.element_size()), (f"x{i}", d.x, x.numel() * x.element_size())]
+        problems.append((f"dy{i}", f"x{i}", f"slab{i}"))
     _poison(outs, [])
     shape = it.shape
 
@@ -459,7 +489,7 @@ def prepare_wgrad_descs(it, descs, mem):
             recs.append((it.tag, f"{shape} [problem {i}: Cd{dyv.shape[1]} K{Kt}]" if len(parts) > 1 else shape,
                          fp32_bar(s, r64, tol, f"{it.tag} {shape} problem {i}: slab sum vs float64 dY^T x")))
         return recs
-    return Check(outs, fn)
+    return Check(outs, fn, reads=reads, problems=problems)
 
 
 def _seq_sum(slab_rows):
@@ -479,8 +509,9 @@ def reduce_expect(slab, nsplit, Cd, Ktot, Cin, co_off, tap_off, Cout, RS):
 
 def prepare_wgrad_reduce(it, mem, jobs):
     """jobs: [(slab ptr, dst ptr, nsplit, Cd, Ktot, Cin, co_off, tap_off, Cout, RS, accumulate)]"""
-    outs, exp_in = {}, []
+    outs, exp_in, reads = {}, [], []
     for i, (sp, dp, ns, Cd, Kt, Cin, co, to, Co, RS, acc) in enumerate(jobs):
+        reads.append((f"slab{i}", sp, ns * Cd * Kt * 4))
         slab = mem.view(sp, ns * Cd * Kt, torch.float32).clone()
         dst = mem.view(dp, Co * Cin * RS, torch.float32).view(Co, Cin, RS)
         exp_in.append((slab, ns, Cd, Kt, Cin, co, to, Co, RS, dst.clone() if acc else None))
@@ -494,7 +525,7 @@ def prepare_wgrad_reduce(it, mem, jobs):
                 e = prev + e
             exact_bar(got[f"dst{i}"], e, f"{it.tag} job {i} (co_off {co}, tap_off {to}, Cout {Co}, RS {RS})")
         return [(it.tag, f"{len(jobs)} job(s)", 0.0)]
-    return Check(outs, fn)
+    return Check(outs, fn, reads=reads, jobs=[(f"slab{i}", f"dst{i}") for i in range(len(jobs))])
 
 
 def prepare_wgrad_reduce_exp(it, mem):
@@ -509,7 +540,7 @@ def prepare_wgrad_reduce_exp(it, mem):
         s = _seq_sum(slab[:, rows.reshape(-1)].view(ns, RS, Cout, Cin))          # [RS][Cout][Cin]
         exact_bar(got["dst"], s.permute(1, 2, 0).contiguous(), f"{it.tag} (row_off {row_off}, tap_off {tap_off})")
         return [(it.tag, f"Cd{Cd} Cin{Cin} Cout{Cout} RS{RS}", 0.0)]
-    return Check(outs, fn)
+    return Check(outs, fn, reads=[("slab0", slab_p, ns * Cd * Cin * 4)], jobs=[("slab0", "dst")])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -687,6 +718,11 @@ def prepare_bn_bwd(it, mem):
         if p:
             outs[k] = (mem.view(p, n, t).view(M, Cn), True) if k in ("dy2", "gout") else (mem.view(p, Cn, torch.float32), True)
     ins = [(getattr(d, k), n * s["dz"].element_size()) for k in ("dz", "y") if getattr(d, k)]
+    reads = [(k, getattr(d, k), n * s["dz"].element_size()) for k in ("dz", "y", "y2") if getattr(d, k)]
+    if mm in (1, 3):
+        reads.append(("z", d.z, n * s["dz"].element_size() if mm == 1 else n // 8))
+    if not own:
+        reads.append(("part", d.part, nblk * 3 * Cn * 4))
     _poison(outs, ins)
     shape = f"M{M} C{Cn} mask{mm}{' +downsample' if d.y2 else ''}{' (reduce in the conv)' if not own else ''}"
 
@@ -744,7 +780,7 @@ def prepare_bn_bwd(it, mem):
         if "gout" in got:
             exact_bar(got["gout"], gm.to(t), what + " gout")
         return recs
-    return Check(outs, fn)
+    return Check(outs, fn, reads=reads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -1089,14 +1125,196 @@ def prepare_tap_scatter(it, mem):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
+# direct 7x7 / stride-2 / pad-3 stem (csrc/stem7.hip): packing, forward with up to two weight sets, weight gradient from the image
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+STEM_TILE = (8, 32)            # output pixels of one statistics slot (simt_stem7_tiles: one slot per 8 x 32 tile)
+
+
+class _StemGeom:
+    """The stem as a conv geometry for conv_rows / conv_gather / wgrad_ref: 49 taps (r - 3, s - 3), stride 2, K = 49 x 3 tap-major."""
+
+    def __init__(self, B, H, W, Ho, Wo):
+        self.B, self.H, self.W, self.Ho, self.Wo, self.stride, self.ntaps = B, H, W, Ho, Wo, 2, 49
+        self.dy = [r - 3 for r in range(7) for s in range(7)]
+        self.dx = [s - 3 for r in range(7) for s in range(7)]
+
+
+def stem_operand(x_nchw):
+    """The image as the stem kernels stage it: each fp32 value rounded once to bf16 (f2bf, round to nearest even), NHWC."""
+    return x_nchw.to(BF).permute(0, 2, 3, 1).contiguous()
+
+
+def stem_tile_sums(v, tiles_shape):
+    """v: [B, Ho, Wo, C] float64 -> [tiles, C] sums over each 8 x 32 tile, slot t = (b * tiles_y + ty) * tiles_x + tx (zero-padded edges)."""
+    B, Ho, Wo, Cn = v.shape
+    ty, tx = tiles_shape
+    vp = v.new_zeros(B, ty * STEM_TILE[0], tx * STEM_TILE[1], Cn)
+    vp[:, :Ho, :Wo] = v
+    return vp.view(B, ty, STEM_TILE[0], tx, STEM_TILE[1], Cn).sum((2, 4)).reshape(B * ty * tx, Cn)
+
+
+def prepare_stem7_pack(it, mem):
+    """dst[o][r][s * 3 + c] = bf16(fp32(w[o][c][r][s] * cscale[o])) (one fp32 product, then f2bf), or bf16(w) without a scale; columns 21..31
+    zero.  Bit-exact."""
+    w_p, cs_p, dst_p = it.args
+    w = mem.view(w_p, 64 * 147, torch.float32).view(64, 3, 7, 7).clone()
+    cs = mem.view(cs_p, 64, torch.float32).clone() if cs_p else None
+    outs = {"dst": (mem.view(dst_p, 64 * 7 * 32, BF).view(64, 7, 32), True)}
+    _poison(outs, [])
+
+    def fn(got):
+        v = w.permute(0, 2, 3, 1)                                               # [o][r][s][c]
+        if cs is not None:
+            v = v * cs.view(64, 1, 1, 1)                                         # fp32 product, rounded once
+        e = torch.zeros(64, 7, 32, dtype=BF, device=w.device)
+        e[:, :, :21] = v.reshape(64, 7, 21).to(BF)
+        exact_bar(got["dst"], e, f"{it.tag}{' (folded scale)' if cs is not None else ''}")
+        return [(it.tag, "64 x 7 x 32" + (" (folded scale)" if cs is not None else ""), 0.0)]
+    return Check(outs, fn)
+
+
+def prepare_stem7_fwd(it, mem, seed=0):
+    """Every weight set of the launch against float64 on the bf16-rounded image, on conv_rows' sample (every row whose 7x7 window leaves the
+    image included).  A set with statistics stores bf16(conv) (one rounding, K = 147 storage bar) and its [tiles][2][64] slots are each held to
+    the fp32 blocked-summation bound over the tile's STORED values; a set with bias + ReLU stores bf16(relu(conv + bias)), rounded once."""
+    d = it.keep
+    B, H, W, Ho, Wo, ns = d.B, d.H, d.W, d.Ho, d.Wo, d.nsets
+    M = B * Ho * Wo
+    lib = L.load()
+    tiles = lib.simt_stem7_tiles(B, Ho, Wo)
+    ts = (-(-Ho // STEM_TILE[0]), -(-Wo // STEM_TILE[1]))
+    assert tiles == B * ts[0] * ts[1]
+    xb = stem_operand(mem.view(d.x, B * 3 * H * W, torch.float32).view(B, 3, H, W))
+    reads = [("x", d.x, B * 3 * H * W * 4)]
+    outs, sets = {}, []
+    for i in range(ns):
+        w = mem.view(d.w[i], 64 * 7 * 32, BF).view(64, 7, 32).clone()
+        reads.append((f"w{i}", d.w[i], 64 * 7 * 32 * 2))
+        bias = mem.view(d.bias[i], 64, torch.float32).clone() if d.bias[i] else None
+        outs[f"y{i}"] = (mem.view(d.y[i], M * 64, BF).view(M, 64), True)
+        if d.stats[i]:
+            outs[f"stats{i}"] = (mem.view(d.stats[i], tiles * 2 * 64, torch.float32).view(tiles, 2, 64), True)
+        sets.append((i, w[:, :, :21].reshape(64, 147), bias, int(d.relu[i]), bool(d.stats[i])))   # (order r, s, c = conv_gather's tap-major K)
+    _poison(outs, [r[1:] for r in reads])
+    g = _StemGeom(B, H, W, Ho, Wo)
+    rows = conv_rows(g, xb.device, seed=seed)
+    shape = f"M{M} N64 K147 direct 7x7 s2, {ns} set(s)"
+
+    def fn(got):
+        recs = []
+        inner_all = conv_ref(xb, torch.cat([s_[1] for s_ in sets]), g, rows)            # [S, 64 * nsets]
+        for (i, _w, bias, relu, stats) in sets:
+            inner = inner_all[:, 64 * i:64 * (i + 1)]
+            v = inner + bias.double() if bias is not None else inner
+            if relu:
+                v = torch.relu(v)
+            what = f"{it.tag} set {i}"
+            _e, r = tight_bf16_ratio(got[f"y{i}"][rows], v, 147, what)
+            recs.append((it.tag + f" [set {i}{' +bias' if bias is not None else ''}{' relu' if relu else ''}]", shape, r))
+            if stats:
+                yv = got[f"y{i}"].double().view(B, Ho, Wo, 64)
+                s1, s2 = stem_tile_sums(yv, ts), stem_tile_sums(yv * yv, ts)
+                a1 = stem_tile_sums(yv.abs(), ts)
+                R = STEM_TILE[0] * STEM_TILE[1]
+                st = got[f"stats{i}"].double()
+                rr = max(fp32_bar(st[:, 0], s1, 16.0 * U * R ** 0.5 * a1 + 2.0 ** -22 * s1.abs(), what + " statistics slots (sum)"),
+                         fp32_bar(st[:, 1], s2, 16.0 * U * R ** 0.5 * s2 + 2.0 ** -22 * s2, what + " statistics slots (sum of squares)"))
+                recs.append((it.tag + f" [set {i} stats, {tiles} slots]", shape, rr))
+        return recs
+    return Check(outs, fn, reads=reads)
+
+
+def stem7_wgrad_reduce_expect(part):
+    """dW from the workgroups' partials [nwg][64][7][32] in the documented fixed order (csrc/stem7.hip stem7_wgrad_reduce_kernel): row q of 16
+    adds partials q, q + 16, ... in order, then the 16 row sums are added in order -- fp32 adds, bit for bit -- mapped k' = s * 3 + c to OIHW."""
+    nwg = part.shape[0]
+    p2 = part.reshape(nwg, -1)
+    rows = []
+    for q in range(16):
+        t = torch.zeros_like(p2[0])
+        for g_ in range(q, nwg, 16):
+            t = t + p2[g_]
+        rows.append(t)
+    v = rows[0]
+    for q in range(1, 16):
+        v = v + rows[q]
+    return v.view(64, 7, 32)[:, :, :21].reshape(64, 7, 7, 3).permute(0, 3, 1, 2).contiguous()
+
+
+def prepare_stem7_wgrad(it, mem):
+    """dw [64][3][7][7] against float64 conv2d_weight(bf16(image), dy) with the fp32 blocked-summation bound of the weight-gradient bar's form
+    (blocks = the persistent workgroups' pixel sets, then <= 256 partials added in fp32); the workspace `part` is poisoned too and must be
+    written whole, and dw must be its fixed-order sum (stem7_wgrad_reduce_expect) bit for bit."""
+    x_p, dy_p, part_p, dw_p, B, H, W, Ho, Wo = it.args[:9]
+    lib = L.load()
+    nwg = lib.simt_stem7_wgrad_workgroups(B, Ho, Wo)
+    M = B * Ho * Wo
+    xb = stem_operand(mem.view(x_p, B * 3 * H * W, torch.float32).view(B, 3, H, W))
+    dy = mem.view(dy_p, M * 64, BF).view(M, 64).clone()
+    reads = [("x", x_p, B * 3 * H * W * 4), ("dy", dy_p, M * 64 * 2)]
+    outs = {"part": (mem.view(part_p, nwg * 64 * 7 * 32, torch.float32).view(nwg, 64, 7, 32), True),
+            "dw": (mem.view(dw_p, 64 * 147, torch.float32).view(64, 3, 7, 7), True)}
+    _poison(outs, [r[1:] for r in reads])
+    g = _StemGeom(B, H, W, Ho, Wo)
+    shape = f"M{M} direct, {nwg} workgroups"
+
+    def fn(got):
+        # float64 reference and the per-workgroup absolute sums: tile t = (b * tiles_y + ty) * tiles_x + tx goes to workgroup t % nwg
+        dev = dy.device
+        m = torch.arange(M, device=dev)
+        ty_n, tx_n = -(-Ho // STEM_TILE[0]), -(-Wo // STEM_TILE[1])
+        t = ((m // (Ho * Wo)) * ty_n + ((m // Wo) % Ho) // STEM_TILE[0]) * tx_n + (m % Wo) // STEM_TILE[1]
+        wg = t % nwg
+        order = torch.argsort(wg, stable=True)
+        counts = torch.bincount(wg, minlength=nwg).tolist()
+        ref = torch.zeros(64, 147, dtype=F64, device=dev)
+        a2 = torch.zeros(64, 147, dtype=F64, device=dev)
+        GEMM_FLOPS[0] += 4.0 * M * 64 * 147
+        off, step = 0, 16
+        for g0 in range(0, nwg, step):
+            n = sum(counts[g0:g0 + step])
+            rows = order[off:off + n]
+            X = conv_gather(xb, g, rows)                                       # [n, 147] float64, (r, s, c)
+            D = dy[rows].double()
+            o2 = 0
+            for c in counts[g0:g0 + step]:
+                Dg, Xg = D[o2:o2 + c], X[o2:o2 + c]
+                ref += Dg.t() @ Xg
+                a2 += (Dg.abs().t() @ Xg.abs()).pow(2)
+                o2 += c
+            off += n
+        R = max(counts)
+        ref4 = ref.view(64, 7, 7, 3).permute(0, 3, 1, 2)
+        tol = (16.0 * U * (R ** 0.5 + nwg ** 0.5) * a2.sqrt()).view(64, 7, 7, 3).permute(0, 3, 1, 2) + 2.0 ** -22 * ref4.abs()
+        r = fp32_bar(got["dw"], ref4, tol, f"{it.tag} dw vs float64")
+        assert not bool(torch.isnan(got["part"]).any()), f"{it.tag}: workspace partials not written whole"
+        exact_bar(got["dw"], stem7_wgrad_reduce_expect(got["part"]), f"{it.tag}: dw vs the fixed-order sum of the partials")
+        return [(it.tag, shape, r)]
+    return Check(outs, fn, reads=reads, problems=[("dy", "x", "dw")])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
 def fn_name(it):
     return getattr(it.fn, "__name__", None)
 
 
 def prepare(it, mem, ctx):
-    """Check for launch `it`, or None if no handler covers its C entry point.  ctx: dict(pack_jobs=[...], dst_sizes=callable) for the packs."""
+    """Check for launch `it`, or None if no handler covers its C entry point.  ctx: dict(pack_jobs=[...], dst_sizes=callable) for the packs.
+    Every range the handler viewed that is neither an output nor a named read is added to chk.reads as in{k}."""
     h = HANDLERS.get(fn_name(it))
-    return None if h is None else h(it, mem, ctx)
+    if h is None:
+        return None
+    mem.log = []
+    try:
+        chk = h(it, mem, ctx)
+    finally:
+        log, mem.log = mem.log, None
+    known = {extent(v) for (v, _p) in chk.outs.values()} | {(p, n) for (_k, p, n) in chk.reads}
+    for (p, n) in log:
+        if (p, n) not in known:
+            chk.reads.append((f"in{len(chk.reads)}", p, n))
+            known.add((p, n))
+    return chk
 
 
 def _pack_multi(it, mem, ctx):
@@ -1153,4 +1371,7 @@ HANDLERS = {
     "simt_upsample_nchw_bwd": lambda it, mem, ctx: prepare_upsample_bwd(it, mem),
     "simt_tap_gather_sum": lambda it, mem, ctx: prepare_tap_gather_sum(it, mem),
     "simt_tap_scatter": lambda it, mem, ctx: prepare_tap_scatter(it, mem),
+    "simt_stem7_pack": lambda it, mem, ctx: prepare_stem7_pack(it, mem),
+    "simt_stem7_fwd": lambda it, mem, ctx: prepare_stem7_fwd(it, mem, seed=ctx.get("seed", 0)),
+    "simt_stem7_wgrad": lambda it, mem, ctx: prepare_stem7_wgrad(it, mem),
 }

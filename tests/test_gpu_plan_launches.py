@@ -3,14 +3,16 @@
 DeepLabv3 (B=4, 512x1024, layers (3, 4, 6), Q = 19 + 6) and DeepLab-VGG16 (B=8, 512x512, Q = 19 + 3): the trainable plan (pack list,
 forward, backward) and the frozen plan (pack list, forward) at the sizes bench.py times, Kaiming weights.  Every launch of those lists is
 replayed ONE AT A TIME on one stream (SIMT_SINGLE_STREAM=1; SIMT_BN_GRID=0: the two-pass BatchNorm, whose fused forms
-tests/test_gpu_bn_fused.py ties bit for bit to these), its inputs snapshotted and its outputs poisoned before it runs, and checked right
-after by the descriptor-driven float64 oracle of tests/_launch_oracle.py; the chain then continues on the kernel's own result.
+tests/test_gpu_bn_fused.py ties bit for bit to these; the replay is tests/_plan_replay.py), its inputs snapshotted and its outputs poisoned
+before it runs, and checked right after by the descriptor-driven float64 oracle of tests/_launch_oracle.py; the chain then continues on the
+kernel's own result.
 
 Coverage is enforced: a launch that no handler checks and whose tag is not in NOT_HERE fails the test by name.  Each conv launch's weight
 operand is traced to the parameter(s) the pack jobs wrote into that buffer, and the launch's geometry (Cin, Cout, stride, taps, H / W) must
 be that layer's as v3_block_specs / ASSP_BRANCHES / VGG_LAYERS describe it; every layer must be launched in each direction.  With the
 packing check (packed operand == bf16 of the parameter) this ties every conv's weight operand to its own parameter.  The activation
-operand is not traced: it is whatever the previous launch of the chain wrote, checked there.
+operand is not traced here: it is whatever the previous launch of the chain wrote, checked there (tests/test_gpu_plan_launches_v2.py
+traces DeepLab-v2's to their last writer).
 """
 import time
 
@@ -19,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 import _launch_oracle as lo
+from _plan_replay import Run, _env, _k, _neg, _perturb, _two_ulps, match_layers, replay
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
 from simt_amd import model_spec as ms
@@ -31,18 +34,6 @@ CD = so.load_class_dist()
 # tag -> the test that holds launches of that tag instead.  Empty: with SIMT_BN_GRID=0 the plans carry no fused-BatchNorm launch (the only
 # form this oracle refuses), and every other entry point has a handler.
 NOT_HERE = {}
-
-
-def _key(d):
-    return (d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.stride, tuple(lo.conv_taps_of(d)))
-
-
-def _k(Bn, Hi, Wi, Cin, Ho, Wo, Cout, stride, taps):
-    return (Bn, Hi, Wi, Cin, Ho, Wo, Cout, stride, tuple(taps))
-
-
-def _neg(taps):
-    return [(-a, -b) for (a, b) in taps]
 
 
 def v3_layers(B, H, W, layers, Q, width=64, ac=256):
@@ -94,102 +85,6 @@ def vgg_layers(B, H, W, Q, kq=64):
     return out
 
 
-def match_layers(plan, run, layers, train):
-    """Each recorded conv launch -> the parameter(s) packed into the buffer its weight operand points into (the plan's pack jobs), in the packing
-    direction (mode 1 = dgrad operand); its geometry must be that layer's.  Records which (layer, direction) pairs were launched."""
-    mem = _mem(plan)
-    names = {t.data_ptr(): n[:-len(".weight")] for n, t in plan.p.items() if n.endswith(".weight")}
-    packs = {}
-    for it in plan._pack_items_raw:
-        if lo.fn_name(it) != "simt_pack_weight":
-            continue
-        w, dst, mode = it.args[0], it.args[1], it.args[9]
-        packs.setdefault(mem.span_of(dst)[0], set()).add((names[w], "bwd" if (mode & 0xFF) == 1 else "fwd"))
-    for (where, dirn, key, wptr) in run.convs:
-        owners = packs.get(mem.span_of(wptr)[0])
-        if not owners:
-            run.layer_bad.append(f"{where}: weight operand not packed from any parameter")
-            continue
-        for (pname, pdir) in sorted(owners):
-            want = layers.get(pname, {}).get(pdir)
-            if pdir != dirn or want != key:
-                run.layer_bad.append(f"{where}: operand packed from {pname} ({pdir}) expects {want}, launch has {key} ({dirn})")
-            else:
-                run.layer_seen.add((pname, pdir))
-    want_all = {(n, dd) for n, g in layers.items() for dd in (("fwd", "bwd") if train else ("fwd",)) if g[dd] is not None}
-    run.layer_missing = sorted(want_all - run.layer_seen)
-
-
-def _mem(plan):
-    ts = list(plan._keep) + list(plan._bufs.values()) + list(plan.p.values())
-    if getattr(plan, "flat_grad", None) is not None:
-        ts.append(plan.flat_grad)
-    for lst in (plan.pack_list, plan.fwd_list, plan.bwd_list):
-        for it in lst.items:
-            if isinstance(it.keep, tuple):
-                ts += [t for t in it.keep if isinstance(t, torch.Tensor)]
-    return lo.Mem(ts)
-
-
-class Run:
-    def __init__(self):
-        self.worst = {}          # (tag, shape) -> worst error / bound
-        self.fail, self.uncovered = [], []
-        self.convs = []          # (where, "fwd" | "bwd", geometry, weight operand pointer) of every conv launch
-        self.layer_bad, self.layer_seen, self.layer_missing = [], set(), []
-        self.secs, self.tflop = 0.0, 0.0
-        self.red = {}            # what -> list of perturbations the checker caught
-        self.n = 0
-
-
-def replay(plan, lists, run, red=None, seed=0):
-    """Replay the lists item by item under the oracle.  red(lname, it, chk, got): optional hook called after a green check."""
-    mem = _mem(plan)
-    stream = torch.cuda.current_stream().cuda_stream
-    ctx = {"seed": seed, "dst_sizes": lambda ptr, dt: (sum(mem.span_of(ptr)) - ptr) // torch.empty((), dtype=dt).element_size()}
-    for lname, lst in lists:
-        for i, it in enumerate(lst.items):
-            if it.fn is None:
-                continue
-            name = lo.fn_name(it)
-            where = f"{lname}[{i}] {name} <{it.tag}> {it.shape or ''}"
-            if name == "simt_conv_fprop":
-                assert not it.keep.fbn, f"{where}: fused BatchNorm launch although SIMT_BN_GRID=0"
-                run.convs.append((where, "bwd" if lname.endswith("bwd") else "fwd", _key(it.keep), it.keep.w))
-            try:
-                chk = lo.prepare(it, mem, ctx)
-            except (AssertionError, KeyError, NotImplementedError) as e:
-                run.fail.append(f"{where}: cannot prepare: {e}")
-                chk = None
-            if chk is None and lo.HANDLERS.get(name) is None and it.tag not in NOT_HERE:
-                run.uncovered.append(where)
-            rc = it.fn(*it.args, stream)
-            if rc != 0:
-                L.check(rc)
-            if chk is None:
-                continue
-            torch.cuda.synchronize()
-            got = chk.outputs()
-            try:
-                for (tag, shape, r) in chk.check(got):
-                    key = (tag, shape)
-                    run.worst[key] = max(run.worst.get(key, 0.0), r)
-                if red is not None:
-                    red(lname, it, chk, got)
-            except (AssertionError, NotImplementedError, RuntimeError) as e:
-                run.fail.append(f"{where}: {e}")
-            chk.finish()
-            run.n += 1
-            del chk, got
-
-
-def _env(mp):
-    mp.setenv("SIMT_SINGLE_STREAM", "1")
-    mp.setenv("SIMT_BN_GRID", "0")
-    import simt_amd.engine as eng
-    eng._SIDE_STREAMS.clear()
-
-
 def _seed_and_backward(plan, lists_bwd, run, red, B, Q, dev, v3):
     g = torch.Generator().manual_seed(8)
     if v3:
@@ -199,25 +94,7 @@ def _seed_and_backward(plan, lists_bwd, run, red, B, Q, dev, v3):
             hd = plan.heads[0]
             dl.zero_()
             dl[:, :Q] = (torch.randn(dl.shape[0], Q, generator=g) / (hd.h * hd.w)).to(BF).to(dev)
-    replay(plan, lists_bwd, run, red)
-
-
-def _perturb(chk, got, what, cases):
-    """Each case: (name, mutate(copy of got)) -> the checker must raise AssertionError."""
-    caught = []
-    for name, mut in cases:
-        g2 = {k: v.clone() for k, v in got.items()}
-        mut(g2)
-        try:
-            chk.check(g2)
-        except AssertionError:
-            caught.append(name)
-    return caught
-
-
-def _two_ulps(t, idx):
-    v = t[idx].double()
-    t[idx] = (v + 2.5 * lo.ulp_bf16(v.abs(), 1e-30) * (1 if v >= 0 else -1)).to(t.dtype)
+    replay(plan, lists_bwd, run, red, not_here=NOT_HERE)
 
 
 def _red_hook(run):
@@ -271,7 +148,7 @@ def runs(dev):
         p = {k: v.to(dev) for k, v in st.items()}
         tr = V3Plan(p, B, H, W, 19, K, True, dtype=BF, train=True, layers=lay)
         tr.x_in.copy_(img)
-        replay(tr, [("v3.pack", tr.pack_list), ("v3.fwd", tr.fwd_list)], run, hook)
+        replay(tr, [("v3.pack", tr.pack_list), ("v3.fwd", tr.fwd_list)], run, hook, not_here=NOT_HERE)
         _seed_and_backward(tr, [("v3.bwd", tr.bwd_list)], run, hook, B, 19 + K, dev, True)
         match_layers(tr, run, v3_layers(B, H, W, lay, 19 + K), True)
         del tr, p
@@ -281,7 +158,7 @@ def runs(dev):
         fr = V3Plan(fp, B, H, W, 19, 0, False, dtype=BF, train=False, layers=lay)
         fr.x_in.copy_(img)
         run_f = Run()
-        replay(fr, [("v3f.pack", fr.pack_list), ("v3f.fwd", fr.fwd_list)], run_f)
+        replay(fr, [("v3f.pack", fr.pack_list), ("v3f.fwd", fr.fwd_list)], run_f, not_here=NOT_HERE)
         match_layers(fr, run_f, v3_layers(B, H, W, lay, 19), False)
         del fr, fp
         torch.cuda.empty_cache()
@@ -297,7 +174,7 @@ def runs(dev):
         p = {k: v.to(dev) for k, v in st.items()}
         tr = VggPlan(p, B, H, W, 19 + K, dtype=BF, train=True)
         tr.x_in.copy_(img)
-        replay(tr, [("vgg.pack", tr.pack_list), ("vgg.fwd", tr.fwd_list)], run, hook)
+        replay(tr, [("vgg.pack", tr.pack_list), ("vgg.fwd", tr.fwd_list)], run, hook, not_here=NOT_HERE)
         _seed_and_backward(tr, [("vgg.bwd", tr.bwd_list)], run, hook, B, 19 + K, dev, False)
         match_layers(tr, run, vgg_layers(B, H, W, 19 + K), True)
         del tr, p
@@ -307,7 +184,7 @@ def runs(dev):
         fr = VggPlan(fp, B, H, W, 19, dtype=BF, train=False)
         fr.x_in.copy_(img)
         run_f = Run()
-        replay(fr, [("vggf.pack", fr.pack_list), ("vggf.fwd", fr.fwd_list)], run_f)
+        replay(fr, [("vggf.pack", fr.pack_list), ("vggf.fwd", fr.fwd_list)], run_f, not_here=NOT_HERE)
         match_layers(fr, run_f, vgg_layers(B, H, W, 19), False)
         del fr, fp
         torch.cuda.empty_cache()
