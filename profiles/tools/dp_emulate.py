@@ -1,6 +1,6 @@
 """The RCCL footprint of the data-parallel step, emulated on ONE GPU.  MEASUREMENT ONLY.
 
-    for p in default first; do python profiles/tools/dp_emulate.py --plan $p; done > profiles/r06_dp_emulation.txt
+    python profiles/tools/dp_emulate.py > profiles/r06_dp_emulation.txt
 
 What it runs: the production data-parallel trainer (SimTTrainer with a REAL one-rank RCCL process group, SIMT_DP_FORCE=1: bucketed exchange on
 the reducer's comm stream, released by the backward replay where `bucket_released_launch` says, early optimiser step waiting for it) at BASELINE
@@ -11,9 +11,8 @@ GB/s per GPU (168.7 MB per step at 150-300 GB/s = 0.6-1.1 ms of all-reduce per s
 would for the wire.
 
 What it varies: occupier count N in {0, 8, 16, 32} x the assumed rate x the occupier's LDS (0: its waves can share a CU with a conv workgroup;
-64 KB: they cannot -- a conv workgroup holds 156 of the CU's 160 KB), for ONE tile plan per process (--plan default: 236 tiles of 160 rows, the
-round-6 default on every GPU count; --plan first: SIMT_PICK_ROWS_FIRST=1, rounds 1-5's 255 tiles of 148 rows; --bn-grid 0: two-pass
-BatchNorm).  One trainer per process ON PURPOSE: the first version of this tool kept three trainers (three comm streams) alive in one process
+64 KB: they cannot -- a conv workgroup holds 156 of the CU's 160 KB), for the production tile plan (236 tiles of 160 rows, the round-6 default
+on every GPU count; rounds 1-5's 255 tiles of 148 rows were measured and removed; --bn-grid 0: two-pass BatchNorm).  One trainer per process ON PURPOSE: the first version of this tool kept three trainers (three comm streams) alive in one process
 and every number in it was 2.7 ms too high -- HIP maps streams onto 4 hardware queues, and the fifth stream shared a queue with the main stream
 (a sleeping occupier on it serialised with the step: +0.9 x the all-reduce time).  The production job has main, side, comm and RCCL's own stream."""
 import argparse
@@ -33,7 +32,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=12)
-    ap.add_argument("--plan", default="default", choices=["default", "first"])
     ap.add_argument("--bn-grid", default=None)
     ap.add_argument("--pg-first", action="store_true", help="create the process group before the plan's streams (rounds 1-5's order)")
     ap.add_argument("--occ", type=int, nargs="+", default=[0, 8, 16, 32])
@@ -63,8 +61,6 @@ def main():
     cd = ms.load_class_dist("bapa")
     hp = Hyper(open_classes=K, lr=6e-4, lr_T=6e-3)
     cfg = {"n": 0, "rate": 300.0, "lds": 0}
-    if a.plan == "first":
-        os.environ["SIMT_PICK_ROWS_FIRST"] = "1"                # read by engine.TrunkPlan at construction (cu_budget = -1)
     if a.bn_grid is not None:
         os.environ["SIMT_BN_GRID"] = a.bn_grid
     tr = SimTTrainer(ms.reference_init(ms.state_shapes(19, K, True), seed=1234), ms.reference_init(ms.state_shapes(19, 0, False), seed=1234),
@@ -89,7 +85,7 @@ def main():
         if cfg["n"] > 0:
             torch.cuda.current_stream().wait_stream(occ_stream)             # the optimiser step waits for the "wire" like handle.wait() does
     red.finish = finish
-    label = f"plan {a.plan}" + (f", SIMT_BN_GRID={a.bn_grid}" if a.bn_grid is not None else "")
+    label = "plan default" + (f", SIMT_BN_GRID={a.bn_grid}" if a.bn_grid is not None else "")
     trainers = {label: tr}
     a.budgets = [label]
     img, lab = ms.synthetic_batch(B, H, W, cd, seed=1234, device=dev)

@@ -2,7 +2,7 @@
 
 A plan is built once for a fixed (B, H, W, dtype): every activation / gradient / workspace buffer is allocated up
 front in HBM (NHWC), every kernel launch is pre-described (ctypes descriptors of include/simt_hip.h), and a step is a
-replay of that launch list on the current HIP stream -- no allocation, no host sync, capturable in a hipGraph.
+replay of that launch list on the current HIP stream -- no allocation, no host sync.
 
 Mirrors (reference, read-only): model/deeplab_multi.py:57-101 Bottleneck, :104-119 Classifier_Module (two live
 branches), :122-192 ResNetMulti; model/deeplab.py:101-177 (single 4-branch head).  BatchNorm runs in train mode with
@@ -22,6 +22,8 @@ from . import ops
 LAYERS = (3, 4, 23, 3)
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+DY_BUFFERS_GROUPED, DY_BUFFERS = 6, 4      # dY buffer sets of the backward with / without grouped weight gradients (TrunkPlan._build_backward)
+WGRAD_BLOCKS = 3                           # Bottlenecks per grouped weight-gradient launch, at most DY_BUFFERS_GROUPED - 3
 
 
 def block_specs(layers=LAYERS):
@@ -87,8 +89,7 @@ def side_stream(device=None):
     if os.environ.get("SIMT_SINGLE_STREAM") == "1":     # profiling aid: serial schedule, per-kernel durations without CU sharing
         return torch.cuda.current_stream(dev)
     if dev not in _SIDE_STREAMS:
-        prio = int(os.environ.get("SIMT_SIDE_PRIORITY", "0"))
-        _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev, priority=prio)
+        _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
     return _SIDE_STREAMS[dev]
 
 
@@ -102,7 +103,7 @@ def reserve_streams(device=None):
     found the plan's side stream (weight gradients, frozen forward) on the MAIN stream's queue: 26.18 ms per step instead of 24.06, the whole
     two-stream overlap gone.  Call this before torch.distributed.init_process_group / before creating other streams (bench.py and the tools do);
     TrunkPlan calls it too, which is early enough in a single-GPU process.  Idempotent."""
-    if not torch.cuda.is_available() or os.environ.get("SIMT_NO_RESERVE_STREAMS") == "1":      # (the switch: A/B only)
+    if not torch.cuda.is_available():
         return
     dev = torch.cuda.current_device() if device is None else torch.device(device).index
     if dev in _RESERVED:
@@ -128,9 +129,7 @@ class DeviceEvent:
 
     def __init__(self):
         h = C.c_void_p()
-        # SIMT_EVENT_SCOPE: 0 (default) hipEventReleaseToDevice, the documented device-scope release; 2 = no release at the marker
-        # (hipEventDisableSystemFence: round 5's form, opt-in); 1 = system scope
-        L.call("simt_event_create", C.byref(h), int(os.environ.get("SIMT_EVENT_SCOPE", "0")))
+        L.call("simt_event_create", C.byref(h), 0)         # scope 0: hipEventReleaseToDevice, the documented device-scope release
         self.h = h
 
     def record(self, stream):
@@ -148,8 +147,8 @@ class DeviceEvent:
 
 
 def _new_event():
-    """SIMT_LIGHT_EVENTS=0: torch.cuda.Event (system-scope release), the A/B switch."""
-    if os.environ.get("SIMT_LIGHT_EVENTS", "1") != "0" and torch.cuda.is_available():
+    """The launch lists' event: a DeviceEvent (torch.cuda.Event where torch sees no GPU)."""
+    if torch.cuda.is_available():
         return DeviceEvent()
     return torch.cuda.Event()
 
@@ -171,22 +170,6 @@ class LaunchList:
 
     def __init__(self):
         self.items = []
-        self.graph = None
-
-    def capture(self, warm=True):
-        """Capture the whole list (both streams, with its fork/join events) into one hipGraph: run() then costs one graph
-        launch instead of len(self) host calls -- what the launch-bound plans (DeepLabv3 at 512x1024: ~450 launches of
-        ~15 us) need.  Every buffer and descriptor is preallocated, so the captured kernel arguments stay valid; the list
-        is replayed once eagerly first so that lazily created workspaces exist before capture."""
-        self.graph = None
-        if warm:
-            self.run()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.run()
-        self.graph = g
-        return g
 
     def add(self, name, *args, keep=None, tag=None, flops=0.0, nbytes=0.0, shape=None, stream=0):
         fn = getattr(L.load(), name)
@@ -235,9 +218,6 @@ class LaunchList:
                 b[3] += 1
 
     def run(self, single_stream=False):
-        if self.graph is not None and not single_stream:
-            self.graph.replay()
-            return
         main = torch.cuda.current_stream()
         if single_stream or not any(it.stream for it in self.items):
             st = main.cuda_stream
@@ -374,9 +354,7 @@ class TrunkPlan:
         # process group exists; at most 20 are given up): any budget >= 236 leaves the plan as it is, so the budget costs nothing; a smaller one
         # re-plans the tile lists (profiles/r06_dp_emulation.txt).  SIMT_CU_BUDGET=n sets it explicitly (0: the whole device).
         cb = os.environ.get("SIMT_CU_BUDGET")
-        if os.environ.get("SIMT_PICK_ROWS_FIRST") == "1":
-            self.cu_budget = -1                        # A/B only: rounds 1-5's tile plan (255 tiles of 148 rows at M = 37 636)
-        elif cb is not None:
+        if cb is not None:
             self.cu_budget = int(cb)
         elif data_parallel:
             self.cu_budget = 256 - max(0, min(20, int(os.environ.get("NCCL_MAX_NCHANNELS", "16"))))
@@ -509,7 +487,7 @@ class TrunkPlan:
         # Few pixels (DeepLabv3's stride-16 maps: M = 8 192 at 512 x 1024): 128-row x 256-column tiles are 64 workgroups on 256 CUs, each
         # streaming the whole weight panel through its LDS.  Narrower column tiles fill the chip and cut the staged bytes per workgroup
         # (same packed operand: Npad is a multiple of every tile width).
-        if x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and os.environ.get("SIMT_SMALL_M_TILES", "1") != "0":
+        if x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16:
             while tile > 64 and ((Bn * Ho * Wo + 127) // 128) * (npad // tile) < 256 and npad % (tile // 2) == 0:
                 tile //= 2
         d = ops.make_conv_desc(x, wp, y, B=Bn, H=Hi, W=Wi, Cin=Cin, Ho=Ho, Wo=Wo, Cout=Cout, taps=taps, stride=stride,
@@ -660,11 +638,9 @@ class TrunkPlan:
                 f.add("simt_bn_relu_maxpool", y0.data_ptr(), one.data_ptr(), zero.data_ptr(), pool.data_ptr(),
                       pidx.data_ptr(), B, H0, W0, 64, Hp, Wp, ops.dt_code(dt))
         elif self.stem_from is not None:
-            # stem_from = plan, or (plan, i, n): this plan convolves images [i * B, (i + 1) * B) of the partner's n * B (the frozen forward split
-            # into n half-batch chains, step.py SIMT_FROZEN_SPLIT): its rows of the partner's im2col matrix
-            o, part, nparts = self.stem_from if isinstance(self.stem_from, tuple) else (self.stem_from, 0, 1)
-            assert (o.B, o.H, o.W, o.dtype) == (B * nparts, self.H, self.W, dt) and not o.direct_stem
-            self.x_in, A = o.x_in, o.saved["stem.A"][part * M0:(part + 1) * M0]
+            o = self.stem_from
+            assert (o.B, o.H, o.W, o.dtype) == (B, self.H, self.W, dt) and not o.direct_stem
+            self.x_in, A = o.x_in, o.saved["stem.A"]
             self.saved["stem.A"] = A
         else:
             self.x_in = self.new(B, 3, self.H, self.W, dtype=torch.float32)
@@ -1070,32 +1046,29 @@ class TrunkPlan:
         # Two-stream schedule: the dgrad / BN-backward chain is the critical path (stream 0); every weight-gradient GEMM
         # (+ slab reduce, bias column sums) runs on the side stream (1) behind an event recorded after the kernel that
         # produced its dY.  dY buffers rotate over the blocks; stream 0 waits for the side stream's work of
-        # the block SIMT_DY_BUFFERS (default 4; memory is not the constraint) steps back before it overwrites them.
+        # the block DY_BUFFERS steps back before it overwrites them (memory is not the constraint).
         e0 = b.record(0)
         b.wait(e0, 1)
-        npar = max(2, int(os.environ.get("SIMT_DY_BUFFERS", "6" if self._wgrad_grouped() else "4")))      # dY buffer sets: the dgrad chain may run this many blocks ahead of the weight gradients
+        npar = DY_BUFFERS_GROUPED if self._wgrad_grouped() else DY_BUFFERS      # dY buffer sets: the dgrad chain may run this many blocks ahead of the weight gradients
         last_side = {i: None for i in range(npar)}
-        # Grouped weight gradients: the jobs of up to SIMT_WGRAD_BLOCKS (default 3) consecutive Bottlenecks over the same pixels (and the
-        # same tile rule) go into one launch (SIMT_WGRAD_PAIR=0: one Bottleneck per launch): 34 tiles of 256 x 256 fill the chip with 7
-        # pixel splits where one block's 17 need 15 -- half the slab bytes again; 51 tiles with 5.  Measured per step: 26.03 ms one block per
-        # launch, 25.88 two, 25.80 three, 25.80 four (the weight gradients of a group start when its LAST block's dY is there: the dY
-        # buffer sets, SIMT_DY_BUFFERS, must outnumber the blocks of a group by three).
+        # Grouped weight gradients: the jobs of up to WGRAD_BLOCKS consecutive Bottlenecks over the same pixels (and the same tile rule) go
+        # into one launch (SIMT_WGRAD_PAIR=0: one Bottleneck per launch): 34 tiles of 256 x 256 fill the chip with 7 pixel splits where one
+        # block's 17 need 15 -- half the slab bytes again; 51 tiles with 5.  Measured per step: 26.03 ms one block per launch, 25.88 two,
+        # 25.80 three, 25.80 four (the weight gradients of a group start when its LAST block's dY is there: the dY buffer sets must outnumber
+        # the blocks of a group by three).
         pair_ok = os.environ.get("SIMT_WGRAD_PAIR", "1") != "0"
-        nblk_group = max(1, min(npar - 3, int(os.environ.get("SIMT_WGRAD_BLOCKS", "3")))) if pair_ok else 1
+        nblk_group = max(1, min(npar - 3, WGRAD_BLOCKS)) if pair_ok else 1
         pend = {"jobs": [], "pars": [], "M": None, "tco": None, "blocks": 0}
-
-        per_block_events = os.environ.get("SIMT_WGRAD_EVENT_PER_BLOCK") == "1"      # A/B switch: round 4's one event per Bottleneck
         waited_main = set()
 
         def flush_wgrads():
             if not pend["jobs"]:
                 return
             # ONE main -> side edge per weight-gradient GROUP (round 5), recorded here: everything the group reads (the dY / dy buffers of up
-            # to three Bottlenecks) is already enqueued on the main stream.  Until round 4 every block recorded its own event although its jobs
-            # only left with the group's launch: a record idles the recording queue for ~6.5 us (profiles/r05_conv_attribution.txt section 6),
-            # 22 of them per step on the critical dgrad / BatchNorm chain.
-            if not per_block_events:
-                b.wait(b.record(0), 1)
+            # to three Bottlenecks) is already enqueued on the main stream.  One event per Bottleneck (round 4) measured 0.04-0.09 ms slower: a record
+            # idles the recording queue for ~6.5 us (profiles/r05_conv_attribution.txt section 6), 22 of them per step on the critical dgrad /
+            # BatchNorm chain.
+            b.wait(b.record(0), 1)
             self._wgrad_group(b, pend["jobs"])
             ev = b.record(1)
             for q in pend["pars"]:
@@ -1122,7 +1095,7 @@ class TrunkPlan:
             assert dz is not None, "no gradient reaches the last block (a head must sit on the last layer)"
             blk_start = len(b)
             par = bi % npar
-            if last_side[par] is not None and (per_block_events or id(last_side[par]) not in waited_main):
+            if last_side[par] is not None and id(last_side[par]) not in waited_main:
                 # (one wait per side-stream event: the three Bottlenecks of a weight-gradient group share the event behind their group's launch)
                 b.wait(last_side[par], 0)
                 waited_main.add(id(last_side[par]))
@@ -1176,7 +1149,7 @@ class TrunkPlan:
                 self._bn_bwd(b, dz=da1, y=rec["y1"], bname=f"{name}.bn1", dy=dy1, M=Mo, Cn=p, mask_mode=2,
                              reduce_done_nblk=self._fused_nblk(dsc, bnr))
             # conv1 (+ downsample) wgrads
-            if not grouped or per_block_events:
+            if not grouped:
                 b.wait(b.record(0), 1)
             wjobs.append(dict(dy=dy1, x=rec["x"], Bn=B, Hi=Hi, Wi=Wi, Cin=inpl, Ho=Ho, Wo=Wo, Cd=p, ldd=p, taps=[(0, 0)], stride=stride,
                               parts=[(f"{name}.conv1.weight", 0, 0, p, 1, inpl)]))
@@ -1252,21 +1225,18 @@ class TrunkPlan:
         dy0 = self.buf("g.dy0", M0, 64)
         self._bn_bwd(b, dz=da0, y=self.saved["stem.y"], bname="bn1", dy=dy0, M=M0, Cn=64, mask_mode=2)
         # the very last weight gradient runs on the main stream (which has nothing else left) beside the side stream's backlog of
-        # layer1 weight gradients instead of behind it
-        stem_stream = 0 if os.environ.get("SIMT_STEM_WGRAD_MAIN", "1") != "0" else 1
-        if stem_stream == 1:
-            b.wait(b.record(0), 1)
+        # layer1 weight gradients instead of behind it (-0.03 ms per step)
         if self.direct_stem_wgrad:
             nwg = L.load().simt_stem7_wgrad_workgroups(B, H0, W0)
-            part = self.buf("wgrad.slab" if stem_stream == 1 else "wgrad.slab.main", self._slab_cap, dtype=torch.float32)
+            part = self.buf("wgrad.slab.main", self._slab_cap, dtype=torch.float32)
             assert nwg * 64 * 7 * 32 <= self._slab_cap
             b.add("simt_stem7_wgrad", self.x_in.data_ptr(), dy0.data_ptr(), part.data_ptr(), self.grads["conv1.weight"].data_ptr(), B, self.H,
-                  self.W, H0, W0, stream=stem_stream, flops=2.0 * M0 * 64 * 147,
+                  self.W, H0, W0, stream=0, flops=2.0 * M0 * 64 * 147,
                   nbytes=float(M0 * 64 * self.esz + B * 3 * self.H * self.W * 4 + 2 * nwg * 64 * 7 * 32 * 4), shape=f"M{M0} direct")
             self.grad_ready["conv1.weight"] = len(b)
         else:
             self._wgrad(b, dy0, self.saved["stem.A"], None, Bn=1, Hi=1, Wi=M0, Cin=192, Ho=1, Wo=M0, Cd=64, ldd=64,
-                        taps=[(0, 0)], stride=1, parts=[("conv1.weight", 0, 0, 64, 1, 147)], stream=stem_stream)
+                        taps=[(0, 0)], stride=1, parts=[("conv1.weight", 0, 0, 64, 1, 147)], stream=0)
         b.wait(b.record(1), 0)        # join: the optimiser (stream 0) sees every gradient
 
     def _build_head_bwd(self, hd, dz_prev, Mo, c4, bi, bnr=None):
@@ -1329,12 +1299,9 @@ class TrunkPlan:
         b.add_desc("simt_tap_scatter", td)
         b.wait(b.record(0), 1)
         # (the heads' weight gradients are the FIRST ones of the backward: nothing of the dgrad / BatchNorm chain runs beside them yet, so they
-        # keep the whole-chip split plan; SIMT_HEAD_WGRAD_HALF=1: planned like the trunk's, for half the chip -- A/B)
-        if os.environ.get("SIMT_HEAD_WGRAD_HALF") == "1":
+        # keep the whole-chip split plan)
+        with ops.wgrad_plan(256, 6):
             nsplit = ops.wgrad_nsplit(Mh, nexp, hd.cin, self.dtype)
-        else:
-            with ops.wgrad_plan(256, 6):
-                nsplit = ops.wgrad_nsplit(Mh, nexp, hd.cin, self.dtype)
         assert nsplit * nexp * hd.cin <= self._slab_cap
         slab = self.buf("wgrad.slab", self._slab_cap, dtype=torch.float32)
         wd = ops.make_wgrad_desc(G, hd.feat, slab, B=B, H=hd.h, W=hd.w, Cin=hd.cin, Ho=hd.h, Wo=hd.w, Cd=nexp, taps=[(0, 0)],
@@ -1367,12 +1334,6 @@ class TrunkPlan:
         return dfeat
 
     # ------------------------------------------------------------------ run
-    def capture_graphs(self):
-        """hipGraphs of the forward and (train plans) backward launch lists; repack() stays eager."""
-        self.fwd_list.capture()
-        if self.train:
-            self.bwd_list.capture()
-
     def forward(self, x_nchw=None):
         """x: [B,3,H,W] fp32 CUDA (BGR, mean-subtracted).  Returns {head name: logits [B,h,w,ldp] fp32 (NHWC)}."""
         if x_nchw is not None:

@@ -133,7 +133,7 @@ _WGRAD_PLAN = {"cus": 128, "epi": 10}      # split-count cost model of the weigh
 class wgrad_plan:
     """with ops.wgrad_plan(cus, epi): ... -- the cost-model constants for the plans built inside (engine_vgg: the BatchNorm-free VGG trunk has no
     long dgrad / BatchNorm chain for the weight gradients to hide behind; its step is 6 % FASTER with the whole-chip plan (256, 6): 661 vs 620
-    images/s, profiles/r06_wgrad_split.txt).  SIMT_WGRAD_CUS / SIMT_WGRAD_EPI_STAGES override everything."""
+    images/s, profiles/r06_wgrad_split.txt)."""
 
     def __init__(self, cus, epi):
         self.new = {"cus": cus, "epi": epi}
@@ -147,27 +147,19 @@ class wgrad_plan:
 
 
 def _wgrad_cus():
-    """CUs the weight-gradient launches plan their rounds for (SIMT_WGRAD_CUS at plan construction).  Round 6: 128, not the 256 the device has --
+    """CUs the weight-gradient launches plan their rounds for.  Round 6: 128, not the 256 the device has --
     the weight gradients run on the side stream BESIDE the dgrad / BatchNorm chain, which is the critical path of the backward (13.5 ms of chain
     against ~4 ms of weight-gradient work): split counts planned for half the chip give the minor launches (layer 4's group, layer3.0's, the
     heads', layer 1-2's, the stem's) about half the workgroups and half the fp32 slab traffic; they take longer alone (layer3.0's group 178 ->
     329 us) and the step is 0.25-0.3 ms SHORTER (profiles/r06_wgrad_split.txt: same-box A/B on three boxes).  The seven 255-workgroup launches
     of layer 3 keep their plan (5 splits of 51 tiles) under either setting; forcing THEM small costs +1.2 ms."""
-    import os
-    return int(os.environ.get("SIMT_WGRAD_CUS", _WGRAD_PLAN["cus"]))
+    return _WGRAD_PLAN["cus"]
 
 
 def _wgrad_epi():
     """Per-workgroup fixed cost of a weight-gradient launch in 64-pixel stages (prologue + the fp32 tile written to its slab + its share of the
-    reduce pass): the constant of the split-count cost model (SIMT_WGRAD_EPI_STAGES at plan construction)."""
-    import os
-    return int(os.environ.get("SIMT_WGRAD_EPI_STAGES", _WGRAD_PLAN["epi"]))
-
-
-def _wgrad_max_wg():
-    """Upper bound on the workgroups of ONE weight-gradient launch (SIMT_WGRAD_MAX_WG at plan construction; 0 = none)."""
-    import os
-    return int(os.environ.get("SIMT_WGRAD_MAX_WG", "0"))
+    reduce pass): the constant of the split-count cost model (round 6: 10; rounds 1-5: 6)."""
+    return _WGRAD_PLAN["epi"]
 
 
 def wgrad_nsplit(M, Cd, Ktot, dtype, target_wg=768):
@@ -178,8 +170,6 @@ def wgrad_nsplit(M, Cd, Ktot, dtype, target_wg=768):
         max_split = max(1, M // (64 * 8))
         best, best_cost = 1, None
         for ns in range(1, min(max_split, 256) + 1):     # one-tile problems (layer1, stem) need up to 256 splits to fill the chip
-            if _wgrad_max_wg() and ns > 1 and tiles * ns > _wgrad_max_wg():
-                break
             rounds = -(-tiles * ns // _wgrad_cus())
             stages = -(-M // (ns * 64))
             cost = rounds * (stages + _wgrad_epi())            # + epilogue/prologue per workgroup
@@ -198,8 +188,6 @@ def wgrad_group_nsplit(M, tiles, max_cap=256):
     max_split = max(1, M // (64 * 8))
     best, best_cost = 1, None
     for ns in range(1, min(max_split, max_cap) + 1):
-        if _wgrad_max_wg() and ns > 1 and tiles * ns > _wgrad_max_wg():
-            break
         rounds = -(-tiles * ns // _wgrad_cus())
         stages = -(-M // (ns * 64))
         cost = rounds * (stages + _wgrad_epi())

@@ -16,6 +16,7 @@ All state lives on the device; scalars are read back only when the caller asks (
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -81,42 +82,11 @@ class SimTTrainer:
         # the frozen model sees the same image: it reuses the trainable plan's stem im2col matrix (one im2col per micro-batch)
         self.fixed = TrunkPlan(self.fixed_params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=False,
                                stem_from=self.plan, data_parallel=process_group is not None, **kw)      # (same CU budget = same tile lists as the trainable plan)
-        # SIMT_FROZEN_SPLIT=n (round 6 experiment): the frozen forward as n chains of B / n images each on n side streams.  The frozen net runs in
-        # eval mode with folded BatchNorm: every image is independent, so the split changes nothing but the launch geometry -- B / n images are
-        # 236 / n one-per-CU workgroups per wide conv, and n such launches FIT the chip side by side (two full-batch launches do not: 2 x 236 > 256),
-        # so one chain's prologue / epilogue can overlap the other's K loop.  Measured +0.65 / +1.65 ms; needs SIMT_DIRECT_STEM=0 (the parts take their
-        # rows of the trainable plan's im2col matrix), ignored otherwise
-        self._fixed_parts, self._side2 = None, []
-        import os
-        nsp = int(os.environ.get("SIMT_FROZEN_SPLIT", "1"))
-        if nsp > 1 and B % nsp == 0 and dtype == torch.bfloat16 and not self.plan.direct_stem:
-            self._fixed_parts = [TrunkPlan(self.fixed_params, B // nsp, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=False,
-                                           stem_from=(self.plan, i, nsp), data_parallel=process_group is not None, **kw) for i in range(nsp)]
-            self._side2 = [torch.cuda.Stream(device=dev) for _ in range(nsp - 1)]
         # item 0 of the trainable forward feeds BOTH nets: the direct stem launch with the frozen net as its second weight set (bf16), or the im2col
         assert self.plan.fwd_list.items[0].tag in ("simt_stem7_fwd", "simt_im2col_stem")
         assert self.plan.fwd_list.items[0].tag == "simt_im2col_stem" or self.plan.stem_desc.nsets == 2
-        import os
-        # hipGraphs of the three launch lists (frozen forward, trainable forward, backward with its two streams): the host spends
-        # ~18 us per eager launch (ctypes + Python), ~1 000 launches per step -- most of a 28 ms step, and the ORDER in which the two
-        # streams' launches reach the GPU was the host's, not the plan's.  SIMT_GRAPHS=0 keeps eager launches (needed by nothing;
-        # the data-parallel backward with its per-bucket hooks stays eager by construction).
-        self._fixed_graph = False
-        # SIMT_GRAPHS: -1 (default) eager launches; 0 frozen forward as a hipGraph, 1 + trainable forward, 2 + backward (measured: 27.6 /
-        # 27.7 / 27.7 / 29.9 ms per step -- the graph executor runs the two-stream backward worse than the eager streams do)
-        self._graph_level = int(os.environ.get("SIMT_GRAPHS", "-1"))
-        self._graphs = self._graph_level >= 0 and torch.device(dev).type == "cuda"
-        self._steps_run = 0
-        self._main_hi = os.environ.get("SIMT_MAIN_PRIORITY", "0") == "1"
-        # host enqueue order of the two forwards (both reach the GPU within ~2 ms; the hardware then favours the queue that was fed
-        # first): "main" = trainable first (default), "side" = frozen first, "interleave" = one list alternating 1:1
-        self._fwd_order = os.environ.get("SIMT_FWD_ORDER", "main")      # "pair" (round 5): one launch per layer for both networks, main stream only (measured +1.3 ms: it gives up the two-stream overlap)
-        self._hi_stream = None
-        fa = os.environ.get("SIMT_FROZEN_AFTER")
-        self._frozen_after = next((r["fwd_start"] for r in self.plan.block_io if r["name"] == fa), None) if fa else None
         self._fwd_rest = LaunchList()
         self._fwd_rest.items = self.plan.fwd_list.items[1:]
-        self._fwd_both = None                      # built on first use (needs self.fixp): both forwards interleaved, see _micro_batch
         h, w = self.plan.heads[1].h, self.plan.heads[1].w
         self.h, self.w = h, w
         Q = self.Q
@@ -196,7 +166,6 @@ class SimTTrainer:
         # updated weights run on the side stream from that point on instead of after the backward (0.7 ms of exclusive tail).
         applied = [n for n in self.sgd_names if self.plan.grad_ready.get(n, 0) > 0]
         self._ev_post = None
-        self._post_side = os.environ.get("SIMT_POST_SIDE", "1") != "0"
         self._early_cut = max(self.plan.grad_ready[n] for n in applied) if applied else None
         if self._early_cut is not None:
             # The block that produced the last applied weight gradient lists its wgrads BEFORE its input-gradient convs
@@ -216,8 +185,7 @@ class SimTTrainer:
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
             order, sizes, end = self.exchange_table()
-            import os as _os
-            be = int(float(_os.environ.get("SIMT_DP_BUCKET_MB", "0")) * (1 << 18)) or self.BUCKET_ELEMS      # (MB of fp32 per all-reduce; default 32)
+            be = int(float(os.environ.get("SIMT_DP_BUCKET_MB", "0")) * (1 << 18)) or self.BUCKET_ELEMS      # (MB of fp32 per all-reduce; default 32)
             buckets = make_buckets(order, sizes, self.plan.grad_ready, bucket_elems=be)
             # the bad-label count (lout[12], accumulated by simt_ntm_post) rides in the same exchange: after the mean every rank holds
             # total / world, so losses() needs no collective of its own and every rank raises in the same call
@@ -276,91 +244,28 @@ class SimTTrainer:
         rc = head.fn(*head.args, st)
         if rc != 0:
             L.check(rc)
-        # 2. frozen model -> low-res posterior, on the side stream: its eval-mode convs share the CUs with the HBM-bound
-        #    BatchNorm passes of the trainable forward (3.) instead of running before it.  The host enqueues ~350 launches per forward
-        #    at ~5 us each, so the ORDER of the two enqueue loops matters: the trainable forward (critical path) goes first -- enqueued
-        #    second, its first conv reached the GPU 3.6 ms into the step (rocprofv3 kernel trace) -- and the frozen forward is one
-        #    hipGraph launch when SIMT_FIXED_GRAPH != 0.
-        order = self._fwd_order
-        if order == "pair" and not self._fixed_graph:
-            if self._fwd_both is None:
-                self._fwd_both = self._paired_forwards()
-            with trace.range("forward + frozen-forward (one launch per layer for both networks)"):
-                self._fwd_both.run()
-        elif order == "paced" and not self._fixed_graph:
-            if self._fwd_both is None:
-                self._fwd_both = self._paced_forwards()
-            with trace.range("forward + frozen-forward (frozen 3x3 convs paced behind the trainable conv3s)"):
-                self._fwd_both.run()
-        elif order in ("bnside", "bnside2") and not self._fixed_graph:
-            if self._fwd_both is None:
-                self._fwd_both = self._bn_side_forwards()
-            with trace.range("forward + frozen-forward (convs on the main stream, BatchNorm passes on the side stream)"):
-                self._fwd_both.run()
-        elif self._fixed_graph or order != "interleave":
-            main = torch.cuda.current_stream()
-            side = side_stream(self.dev)
-            ev_in = torch.cuda.Event()
-            ev_in.record(main)
-
-            def frozen():
-                if self._fixed_parts is not None:
-                    Mp = (self.B // len(self._fixed_parts)) * self.h * self.w
-                    evs = []
-                    for i, part in enumerate(self._fixed_parts):
-                        stq = side if i == 0 else self._side2[i - 1]
-                        with torch.cuda.stream(stq), trace.range("frozen-forward part"):
-                            stq.wait_event(ev_in)
-                            part.forward()
-                            ops.softmax_rows(part.out["x2"], self.ldf, self.fixp[i * Mp:(i + 1) * Mp], self.ldf, Mp, self.C)
-                            if i:
-                                e = torch.cuda.Event()
-                                e.record(stq)
-                                evs.append(e)
-                    with torch.cuda.stream(side):
-                        for e in evs:
-                            side.wait_event(e)
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                    return ev
-                with torch.cuda.stream(side), trace.range("frozen-forward"):
-                    side.wait_event(ev_in)
-                    self.fixed.forward()
-                    ops.softmax_rows(self.fixed.out["x2"], self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                return ev
-            if self._fixed_graph or order == "side":
-                ev_fix = frozen()
-                with trace.range("forward"):
-                    self._fwd_rest.run()           # 3. trainable forward (its im2col already ran above)
-            elif self._frozen_after is not None:
-                # experiment (SIMT_FROZEN_AFTER=<block name>): the frozen forward is released when the trainable forward reaches that block
-                cut = self._frozen_after - 1       # (_fwd_rest starts behind the im2col)
-                a_, b_ = LaunchList(), LaunchList()
-                a_.items, b_.items = self._fwd_rest.items[:cut], self._fwd_rest.items[cut:]
-                with trace.range("forward"):
-                    a_.run()
-                    ev_in.record(main)
-                    ev_fix = frozen()
-                    b_.run()
-            else:
-                with trace.range("forward"):
-                    self._fwd_rest.run()
-                ev_fix = frozen()
-            main.wait_event(ev_fix)
-        else:
-            # ONE list with the launches of the two forwards interleaved 1:1
-            if self._fwd_both is None:
-                self._fwd_both = self._interleaved_forwards()
-            with trace.range("forward + frozen-forward (interleaved)"):
-                self._fwd_both.run()
+        # 2. frozen model -> low-res posterior, on the side stream: its eval-mode convs share the CUs with the HBM-bound BatchNorm passes of the
+        #    trainable forward (3.) instead of running before it.  The host enqueues ~350 launches per forward at ~5 us each: the trainable
+        #    forward (critical path) goes first -- enqueued second, its first conv reached the GPU 3.6 ms into the step (rocprofv3 kernel trace).
+        #    Measured, bit-identical and removed: other enqueue orders of the two forwards (neutral to +1.9 ms), one launch per layer for both
+        #    networks (+1.3 ms: it gives up the two-stream overlap), hipGraphs of the forwards and stream priorities (neutral).
+        main = torch.cuda.current_stream()
+        side = side_stream(self.dev)
+        ev_in = torch.cuda.Event()
+        ev_in.record(main)
+        with trace.range("forward"):
+            self._fwd_rest.run()               # 3. trainable forward (its stem launch already ran above)
+        with torch.cuda.stream(side), trace.range("frozen-forward"):
+            side.wait_event(ev_in)
+            self.fixed.forward()
+            ops.softmax_rows(self.fixed.out["x2"], self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
+            ev_fix = torch.cuda.Event()
+            ev_fix.record(side)
+        main.wait_event(ev_fix)
         # 4. fused head + NTM regularisers + gradients of the low-res logits (every term scaled by 1 / iter_size, :427;
         #    the NTM gradients accumulate on top of the inner loop's leak and of earlier micro-batches)
         #    The regularisers only feed the Adam step and the loss read-out: they run on the side stream (idle between the frozen forward
         #    and the first weight gradients) beside the head's gradient pass instead of in front of it (a 100 us single-block kernel).
-        main = torch.cuda.current_stream()
-        side = side_stream(self.dev) if self._post_side else main
         if self._ev_post is not None:
             main.wait_event(self._ev_post)     # an earlier micro-batch's regularisers still read the head's outputs
         with trace.range("head"):
@@ -374,283 +279,11 @@ class SimTTrainer:
                 self._ev_post.record(side)
             L.call("simt_head_grad", C.byref(self.head_desc), st)
 
-    def _interleaved_forwards(self):
-        """fwd_rest (main stream) and the frozen forward + its soft-max (side stream) as one launch list, alternating."""
-        from .engine import _Launch
-        lib = L.load()
-        both = LaunchList()
-        ev_in = both.record(0)
-        both.wait(ev_in, 1)
-        a = list(self._fwd_rest.items)
-        b = []
-        for it in self.fixed.fwd_list.items:
-            assert it.stream == 0 and it.fn is not None
-            b.append(_Launch(it.fn, it.args, it.keep, it.tag, it.flops, it.bytes, it.shape, stream=1))
-        b.append(_Launch(lib.simt_softmax_rows, (ops._p(self.fixed.out["x2"]), self.ldf, ops._p(self.fixp), self.ldf, self.B * self.h * self.w,
-                                                 self.C), (self.fixed.out["x2"], self.fixp), "simt_softmax_rows", stream=1))
-        assert all(it.stream == 0 for it in a)
-        # paced: the launches of each stream in chunks of `pace`; chunk c of one stream waits for chunk c - 2 of the other, so neither
-        # queue can run more than two chunks ahead (left alone, the GPU serves one queue exclusively for milliseconds: the two forwards
-        # then run one after the other and fill none of each other's tails)
-        import os
-        pace = int(os.environ.get("SIMT_FWD_PACE", "8"))
-        ca = [a[k:k + pace] for k in range(0, len(a), pace)]
-        cb = [b[k:k + pace] for k in range(0, len(b), pace)]
-        # proportional pairing: both streams finish their last chunk together
-        n = max(len(ca), len(cb))
-        ia = [min(len(ca), (k + 1) * len(ca) // n) for k in range(n)]
-        ib = [min(len(cb), (k + 1) * len(cb) // n) for k in range(n)]
-        ev_a, ev_b = [], []
-        pa = pb = 0
-        for k in range(n):
-            if pace > 0 and k >= 2:
-                if ev_b[k - 2] is not None: both.wait(ev_b[k - 2], 0)
-                if ev_a[k - 2] is not None: both.wait(ev_a[k - 2], 1)
-            for c in cb[pb:ib[k]]: both.items.extend(c)
-            for c in ca[pa:ia[k]]: both.items.extend(c)
-            ev_b.append(both.record(1) if ib[k] > pb else None)
-            ev_a.append(both.record(0) if ia[k] > pa else None)
-            pa, pb = ia[k], ib[k]
-        ev_fix = both.record(1)
-        both.wait(ev_fix, 0)
-        return both
-
-    def _paired_forwards(self):
-        """Both forwards as ONE launch list on the main stream with ONE launch per layer for both networks (round 5; OPT-IN,
-        SIMT_FWD_ORDER=pair: measured +1.3 ms per step, the default stays "main"): the trainable and the frozen ResNetMulti run the same conv shapes on the same image
-        (tools/trainV2_simt.py:351-353 and :370 -> model/deeplab_multi.py:172-192), so conv k of one and conv k of the other go into one
-        simt_conv_fprop_pair launch (510 workgroups: the second 255 start as the first drain), each half with its own compile-time epilogue
-        (BatchNorm statistics | folded bias + ReLU [+ residual]).  The two lists are aligned by a longest-common-subsequence match on the
-        conv geometries (their orders differ around the downsample convs: conv3 needs the frozen net's downsample output as its residual),
-        each list's own order is kept, everything that has no partner is launched as before.  The two-stream schedule this replaces ran the
-        forwards one after the other anyway (the GPU serves one conv queue at a time: profiles/r02_step_timeline.txt); what the pairing removes
-        is one launch ramp / drain per layer: 11 us per 3x3 pair, 12 us per conv3 pair, 2.5 us per 1x1 1024 -> 256 pair
-        (profiles/r05_conv_attribution.txt section 5).  Outputs are bit-identical to the separate launches (tests/test_gpu_iteration.py)."""
-        from .engine import _Launch
-        lib = L.load()
-        conv_fn = lib.simt_conv_fprop
-        t_items = list(self._fwd_rest.items)
-        f_items = list(self.fixed.fwd_list.items)
-        f_items.append(_Launch(lib.simt_softmax_rows, (ops._p(self.fixed.out["x2"]), self.ldf, ops._p(self.fixp), self.ldf, self.B * self.h * self.w,
-                                                       self.C), (self.fixed.out["x2"], self.fixp), "simt_softmax_rows"))
-        assert all(it.fn is not None and it.stream == 0 for it in t_items + f_items)
-
-        def segments(items):
-            """[(conv item or None, [the launches that follow it up to the next conv])]; the first segment's conv is None (leading launches)"""
-            segs = [(None, [])]
-            for it in items:
-                if it.fn is conv_fn:
-                    segs.append((it, []))
-                else:
-                    segs[-1][1].append(it)
-            return segs
-        ts, fs = segments(t_items), segments(f_items)
-        tc, fc = ts[1:], fs[1:]
-        fused = [[bool(lib.simt_conv_pair_fused(C.byref(a[0].keep), C.byref(b[0].keep))) for b in fc] for a in tc]
-        # longest common subsequence over the fusable pairs (104 x 104)
-        n, m = len(tc), len(fc)
-        dp = [[0] * (m + 1) for _ in range(n + 1)]
-        for i in range(n - 1, -1, -1):
-            for j in range(m - 1, -1, -1):
-                dp[i][j] = max(dp[i + 1][j], dp[i][j + 1], (1 + dp[i + 1][j + 1]) if fused[i][j] else 0)
-        both = LaunchList()
-        both.items += ts[0][1] + fs[0][1]
-        i = j = 0
-        self.fwd_pairs = 0
-
-        def single(seg):
-            both.items.append(seg[0])
-            both.items.extend(seg[1])
-        while i < n or j < m:
-            if i < n and j < m and fused[i][j] and dp[i][j] == 1 + dp[i + 1][j + 1]:
-                a, b = tc[i][0], fc[j][0]
-                if a.tag.startswith("conv_igemm2_kernel<") and b.tag.startswith("conv_igemm2_kernel<"):
-                    tag = ", ".join(a.tag.split(", ")[:4]) + f", {a.tag.split(', ')[4].rstrip('>')}+{b.tag.split(', ')[4].rstrip('>')}>"
-                else:
-                    tag = a.tag + " (pair)"
-                both.items.append(_Launch(lib.simt_conv_fprop_pair, (C.byref(a.keep), C.byref(b.keep)), (a.keep, b.keep), tag,
-                                          a.flops + b.flops, a.bytes + b.bytes, a.shape + " x2 (trainable + frozen)"))
-                both.items.extend(tc[i][1])
-                both.items.extend(fc[j][1])
-                self.fwd_pairs += 1
-                i, j = i + 1, j + 1
-            elif j < m and (i >= n or dp[i][j] == dp[i][j + 1]):
-                single(fc[j])
-                j += 1
-            else:
-                single(tc[i])
-                i += 1
-        assert len(both.items) == len(t_items) + len(f_items) - self.fwd_pairs
-        return both
-
-    def _bn_side_forwards(self):
-        """Both forwards as ONE launch list (round 5, SIMT_FWD_ORDER=bnside): EVERY conv -- the trainable net's and the frozen net's, alternating
-        layer by layer -- on the main stream, and only the trainable net's BatchNorm launches (finalize, apply, the stem's BN + max-pool) on
-        the side stream, released by an event behind the conv that feeds them and awaited by the trainable net's next conv.  While the
-        statistics are finalised and the HBM-bound apply pass streams (53 VGPRs, no LDS: it shares a CU with a conv workgroup), the main
-        queue runs the FROZEN net's conv of the same layer, which depends on nothing of it.  The two queues never hold two convs at once
-        (each conv workgroup takes a whole CU's LDS, so two conv queues only take turns: profiles/r02_step_timeline.txt), which is what the
-        alternating-convs experiments of round 4 (SIMT_FWD_ORDER=interleave) paid for; this is the backward's pattern (weight gradients
-        released by events) applied to the forward."""
-        from .engine import _Launch
-        lib = L.load()
-        both = LaunchList()
-        conv_fns = (lib.simt_conv_fprop,)
-        t_items = list(self._fwd_rest.items)
-        f_items = list(self.fixed.fwd_list.items)
-        f_items.append(_Launch(lib.simt_softmax_rows, (ops._p(self.fixed.out["x2"]), self.ldf, ops._p(self.fixp), self.ldf, self.B * self.h * self.w,
-                                                       self.C), (self.fixed.out["x2"], self.fixp), "simt_softmax_rows"))
-        assert all(it.fn is not None and it.stream == 0 for it in t_items + f_items)
-        fi = 0
-
-        def frozen_upto_next_conv():
-            """the frozen net's next conv and whatever non-conv launches follow it (main stream)"""
-            nonlocal fi
-            if fi >= len(f_items):
-                return
-            both.items.append(f_items[fi])
-            fi += 1
-            while fi < len(f_items) and f_items[fi].fn not in conv_fns:
-                both.items.append(f_items[fi])
-                fi += 1
-        # the frozen net may start with non-conv launches (none today): flush them
-        while fi < len(f_items) and f_items[fi].fn not in conv_fns:
-            both.items.append(f_items[fi])
-            fi += 1
-        ev_bn = None
-        i = 0
-        while i < len(t_items):
-            it = t_items[i]
-            if it.fn in conv_fns:
-                if ev_bn is not None:
-                    both.wait(ev_bn, 0)
-                    ev_bn = None
-                both.items.append(it)
-                j = i + 1
-                while j < len(t_items) and t_items[j].fn not in conv_fns:
-                    j += 1
-                group = t_items[i + 1:j]
-                # "bnside2": the (tiny, LDS-using) finalize stays on the main stream right behind its conv; only the streaming pass moves
-                if self._fwd_order == "bnside2":
-                    while group and group[0].fn is lib.simt_bn_finalize:
-                        both.items.append(group.pop(0))
-                if group:
-                    ev_conv = both.record(0)
-                    both.wait(ev_conv, 1)
-                    for g in group:
-                        both.items.append(_Launch(g.fn, g.args, g.keep, g.tag, g.flops, g.bytes, g.shape, stream=1))
-                    ev_bn = both.record(1)
-                frozen_upto_next_conv()
-                i = j
-            else:                                   # (a non-conv launch before the first conv: main stream)
-                both.items.append(it)
-                i += 1
-        while fi < len(f_items):
-            frozen_upto_next_conv()
-        if ev_bn is not None:
-            both.wait(ev_bn, 0)
-        return both
-
-    def _paced_forwards(self):
-        """Both forwards as ONE launch list on the two streams (round 6, SIMT_FWD_ORDER=paced): the trainable net on the main stream exactly as in
-        the default order, the frozen net on the side stream -- but its k-th 3x3 conv waits for an event recorded behind the trainable net's k-th
-        conv3.  What follows that conv3 on the main stream is the finalize and the wide bn3 + residual + ReLU pass (231 MB, HBM-bound, no LDS, 53
-        VGPRs: it shares a CU with a conv workgroup), and a BatchNorm pass hides half of itself under a 3x3 conv and nothing under the K = 1024
-        1x1 conv (profiles/r06_corun.txt).  In the default order the host enqueues the frozen forward behind the trainable one and it runs after
-        it, alone (profiles/tools/queue_gaps.py: 4.1 ms), so that pairing never happens.  ONE cross-queue edge per Bottleneck, on the queue that
-        has the slack (the frozen chain is ~100 us per Bottleneck against ~170 us): the main stream never waits for the side stream before the end
-        of the forward (model/deeplab_multi.py:81-101; tools/trainV2_simt.py:351-353,370)."""
-        import re
-        from .engine import _Launch
-        lib = L.load()
-        both = LaunchList()
-        conv = lib.simt_conv_fprop
-        t_items = list(self._fwd_rest.items)
-        f_items = [_Launch(g.fn, g.args, g.keep, g.tag, g.flops, g.bytes, g.shape, stream=1) for g in self.fixed.fwd_list.items]
-        f_items.append(_Launch(lib.simt_softmax_rows, (ops._p(self.fixed.out["x2"]), self.ldf, ops._p(self.fixp), self.ldf, self.B * self.h * self.w,
-                                                       self.C), (self.fixed.out["x2"], self.fixp), "simt_softmax_rows", stream=1))
-        assert all(it.fn is not None and it.stream == 0 for it in t_items)
-
-        def is_conv2(it):
-            return it.fn is conv and " taps9 " in f" {it.shape or ''} " and "tap-expanded" not in (it.shape or "")
-
-        def is_conv3(it):
-            m = re.search(r"N(\d+) K(\d+) taps1 ", f"{it.shape or ''} ") if it.fn is conv else None
-            return bool(m) and int(m.group(1)) == 4 * int(m.group(2))
-        # (layer1.0's downsample conv has conv3's shape: a Bottleneck's conv3 is the first such conv BEHIND its 3x3 conv)
-        marks, armed = set(), False
-        for i, it in enumerate(t_items):
-            if is_conv2(it):
-                armed = True
-            elif armed and is_conv3(it):
-                marks.add(i)
-                armed = False
-        n2 = sum(1 for it in f_items if is_conv2(it))
-        assert n2 == len(marks) and n2 > 0, (n2, len(marks))
-        fi = 0
-
-        def frozen_until_next_conv2(ev):
-            """the frozen net's launches up to (not including) its next 3x3 conv; the first of them -- a 3x3 conv -- behind `ev`"""
-            nonlocal fi
-            if fi < len(f_items) and ev is not None:
-                both.wait(ev, 1)
-            first = True
-            while fi < len(f_items) and (first or not is_conv2(f_items[fi])):
-                both.items.append(f_items[fi])
-                fi += 1
-                first = False
-        # the frozen net's head of list (stem pool, conv1 of the first Bottleneck): free-running beside the trainable stem
-        while fi < len(f_items) and not is_conv2(f_items[fi]):
-            both.items.append(f_items[fi])
-            fi += 1
-        for i, it in enumerate(t_items):
-            both.items.append(it)
-            if i in marks:
-                frozen_until_next_conv2(both.record(0))
-        while fi < len(f_items):
-            both.items.append(f_items[fi])
-            fi += 1
-        both.wait(both.record(1), 0)                 # the head needs the frozen posterior
-        return both
-
-    def _capture_graphs(self):
-        """Record (not run) the three launch lists into hipGraphs, once, after the first eager step created every workspace."""
-        self._graphs = False
-        try:
-            torch.cuda.synchronize()
-            with torch.cuda.stream(side_stream(self.dev)):
-                self.fixed.fwd_list.capture(warm=False)
-            if self._graph_level >= 1:
-                self._fwd_rest.capture(warm=False)
-            if self.reducer is None and self._graph_level >= 2:
-                self.plan.bwd_list.capture(warm=False)
-            self._fixed_graph = True
-        except Exception as e:                     # capture is an optimisation of the host side only
-            self.fixed.fwd_list.graph = self._fwd_rest.graph = self.plan.bwd_list.graph = None
-            self._fixed_graph = False
-            print(f"[simt] hipGraph capture failed ({e}); eager launches", flush=True)
-
     def step(self, image, label, it=None):
-        """Runs _step (below); with SIMT_MAIN_PRIORITY=1 on a high-priority HIP stream ordered after / before the caller's stream."""
-        if not self._main_hi:
-            return self._step(image, label, it)
-        caller = torch.cuda.current_stream()
-        if self._hi_stream is None:
-            self._hi_stream = torch.cuda.Stream(device=self.dev, priority=-1)
-        self._hi_stream.wait_stream(caller)
-        with torch.cuda.stream(self._hi_stream):
-            out = self._step(image, label, it)
-        caller.wait_stream(self._hi_stream)
-        return out
-
-    def _step(self, image, label, it=None):
         """image [B,3,H,W] fp32 (device or host), label [B,H,W] int64 -- or, with hp.iter_size > 1 (gradient accumulation,
         trainV2_simt.py:341-432), sequences of iter_size micro-batches.  Returns the device tensor `lout`
         (total, loss_p1, loss_p2, loss_y1, loss_y2, Place, Convex, Volume, Anchor, vol_ok, ...) of the last micro-batch."""
         hp = self.hp
-        if self._graphs and self._steps_run >= 1:
-            self._capture_graphs()
-        self._steps_run += 1
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         lr_T = lr_poly(hp.lr_T, it, hp.num_steps, hp.power)
@@ -760,14 +393,7 @@ class SimTTrainer:
         return sd
 
     def timed_lists(self):
-        """The launch lists of one iteration for per-kernel timing (bench.py): the forwards as the step launches them (paired: the stem im2col +
-        one list for both networks; otherwise frozen forward, trainable forward), then the backward."""
-        if self._fwd_order == "pair" and not self._fixed_graph:
-            if self._fwd_both is None:
-                self._fwd_both = self._paired_forwards()
-            head = LaunchList()
-            head.items = [self.plan.fwd_list.items[0]]
-            return [head, self._fwd_both, self.plan.bwd_list]
+        """The launch lists of one iteration for per-kernel timing (bench.py): frozen forward, trainable forward, backward."""
         return [self.fixed.fwd_list, self.plan.fwd_list, self.plan.bwd_list]
 
     def losses(self):
