@@ -2,7 +2,7 @@
 """Throughput benchmark of the SimT training iteration on MI355X (BASELINE.json metric: training images/sec at
 768x768, DeepLabv2-R101+SimT).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a torch.distributed environment: this process spawns `python -m torch.distributed.run --nproc-per-node N ...
 bench.py` BEFORE touching the GPU and passes the child's output through (one rank per GPU over RCCL).  Launched by
@@ -13,14 +13,18 @@ A step = one full SimT iteration (tools/trainV2_simt.py:308-436 of the reference
 wgrad of all 104 trunk convs and the heads), gradient all-reduce (N>1), SGD with duplicate listings + Adam on NTM,
 weight re-packing.  `value`: inputs resident in HBM when the timed region starts (the contract of this benchmark); the
 PCIe-inclusive rate (uint8 frames uploaded from pinned host memory every step, converted on the device) is reported beside it
-as "h2d_inclusive".  Rank 0 prints ONE JSON line.
+as "h2d_inclusive" (--full).  Rank 0 prints ONE JSON line.
 
-Extra objects: "roofline" (dominant kernel class = the implicit-GEMM conv, algorithmic FLOPs / HIP-event time measured
-live in a separate, untimed replay), "cpu_baseline" (the CPU oracle -- a port of the reference -- timed on the host cores on a
-bounded sample; rank 0, N=1 only), "trained_like_pass" (same workload with checkpoint-like weights so that both confidence
-thresholds are live), "h2d_inclusive".
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line ("roofline" and
+"cpu_baseline" are null in it).  --full adds everything else, each after the timed steps except the power sampler: "roofline" (dominant
+kernel class = the implicit-GEMM conv, algorithmic FLOPs / HIP-event time measured live in a separate, untimed replay; "aspp_t_step"
+beside it for v2), "cpu_baseline" (the CPU oracle -- a port of the reference -- timed on the host cores on a bounded sample; rank 0,
+N=1 only), and for v2 the passes "h2d_inclusive", "trained_like_pass" (same workload with checkpoint-like weights so that both
+confidence thresholds are live), "skip_unapplied_grads_pass", "f32_parity_mode_pass"; "power_clock" is sampled during the timed steps.
+The --no-* switches trim a --full run.
 """
 import argparse
+import contextlib
 import json
 import os
 import subprocess
@@ -80,20 +84,25 @@ def parse():
                     help="--model v3: Bottlenecks of layer1..3.  3 4 6 = model/deeplabv3.py as written (a torchvision ResNet-50 cut after layer3); "
                          "3 4 23 = the ResNet-101 depth BASELINE.json's configs[3] NAMES ('DeepLabv3-ResNet101')")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra-passes", action="store_true", help="skip the trained-like and PCIe-inclusive passes")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: power / clock during the timed steps, then the roofline replay, the PCIe-inclusive, trained-like, "
+                         "skip-unapplied-gradients and fp32 passes (v2) and the CPU baseline; off: only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline replay")
+    ap.add_argument("--no-extra-passes", action="store_true", help="with --full: skip the PCIe-inclusive, trained-like, skip and fp32 passes")
     ap.add_argument("--skip-unapplied-grads", action="store_true",
                     help="stop the backward at layer3 (the gradients of conv1/layer1/layer2 are never applied by the SimT stage); "
                          "NOT the headline configuration: the default computes everything the reference's iteration computes")
-    ap.add_argument("--shapes", action="store_true", help="print a per-shape conv timing table to stderr")
-    ap.add_argument("--cpu-iters", type=int, default=3, help="timed CPU-baseline iterations per point (after one warm-up)")
+    ap.add_argument("--shapes", action="store_true", help="with --full: print a per-shape conv timing table of the roofline replay to stderr")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="with --full: timed CPU-baseline iterations per point (after one warm-up)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (losses, NTM matrices, a fixed "
                          "sample of the trained parameters) as DIR/<name>.npy (rank 0), to compare two builds output for output")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.shapes and not a.full:
+        ap.error("--shapes prints the roofline replay of a --full run")
     dflt = {"v2": (4, [768, 768], 3), "v3": (4, [512, 1024], 6), "vgg": (8, [512, 512], 3)}[a.model]
     a.batch = a.batch if a.batch is not None else dflt[0]
     a.size = a.size if a.size is not None else dflt[1]
@@ -390,7 +399,8 @@ def main():
     red = getattr(tr, "reducer", None)
     if red is not None:
         red.measure = True
-    with PowerWatch(local) as pw:
+    pw = PowerWatch(local) if a.full else None
+    with pw if pw is not None else contextlib.nullcontext():
         dt, med = timed(tr, resident(1234 + rank), a.steps, a.warmup)
     # a fused BatchNorm launch that gave up polling leaves the sticky error word set and every optimiser launch skipped: never report such a run
     if getattr(tr, "plan", None) is not None and tr.plan.fbn_error():
@@ -411,7 +421,7 @@ def main():
     value = a.batch * world * a.steps / dt
 
     roof, aspp = None, None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         acc, shp = {}, {}
         for _ in range(2):
             acc.clear()
@@ -489,7 +499,7 @@ def main():
                                 "n": v[3]} for k, v in sorted(acc.items(), key=lambda kv: -kv[1][0])[:16]}}
 
     extra = {}
-    if not a.no_extra_passes and a.model == "v2":
+    if a.full and not a.no_extra_passes and a.model == "v2":
         # ---- PCIe-inclusive: decoded uint8 frames in pinned host memory -> upload + device conversion every step, one batch ahead
         from simt_amd.data.pipeline import DevicePrefetcher, InputPrep
         rgb, lab8 = ms.synthetic_batch_u8(a.batch, H, W, cd, seed=1234 + rank)
@@ -572,7 +582,7 @@ def main():
                                              "what": "NOT the headline: the same iteration in the fp32 parity mode (fp32 storage, fp32 MFMA with a k-ordered "
                                                      "fmaf chain; the kernels that carry 'loss within 1e-4'): what the parity mode costs"}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(K, a.cpu_iters)
     if rank == 0:
         if a.model == "v2":
@@ -593,7 +603,7 @@ def main():
                                        f"{H}x{W}, {a.dtype}, {world}xMI355X" + (" DP RCCL all-reduce" if dp_job else "")
                                        + (" [backward stops at layer3: unapplied gradients skipped]" if a.skip_unapplied_grads else ""),
                            "global_batch": a.batch * world, "baseline_config": cfg,
-                           "numerics": mode, "inputs": "resident in HBM (see h2d_inclusive for the PCIe-inclusive rate)",
+                           "numerics": mode, "inputs": "resident in HBM (see h2d_inclusive of a --full run for the PCIe-inclusive rate)",
                            "step_tflops_conv_algorithmic": round(value * flop_img / 1e12, 1),
                            "frac_of_conv_roofline": round(value * flop_img / 1e12 / (world * MFMA_PEAK_TFLOPS[a.dtype]), 4)},
                 "roofline": roof, "cpu_baseline": cpu}
@@ -601,7 +611,7 @@ def main():
             line["aspp_t_step"] = aspp
         if comm is not None:
             line["comm"] = comm
-        if pw.report() is not None:
+        if pw is not None and pw.report() is not None:
             line["power_clock"] = pw.report()
         line.update(extra)
         if dumped is not None:

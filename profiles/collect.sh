@@ -2,7 +2,7 @@
 # Round profile collection on the GPU box (run through gpurun from the repo root):   bash profiles/collect.sh r03
 # Four rocprofv3 passes of the SAME bench command (kernel trace + stats on the production two-stream schedule, the same on the
 # serial schedule that bench.py's roofline leg measures under, and the two PMC passes -- counters in their own runs, with
-# --kernel-trace only, as MI355X_MICROARCH.md prescribes), then the default bench line.  Summaries land in gpurun_out/<tag>/;
+# --kernel-trace only, as MI355X_MICROARCH.md prescribes), then the bench line with --full.  Summaries land in $OUT (below);
 # copy the *_kernel_stats.csv / *_pmc_traffic.json / *_bench_n1.json you want judged into profiles/.
 set -u
 TAG=${1:-r03}
@@ -24,5 +24,5 @@ python3 profiles/pmc_mfma.py $OUT/mfma > $OUT/pmc_mfma.json 2> $OUT/pmc_mfma.err
 for d in prod serial; do f=$(find $OUT/$d -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${d}_kernel_stats.csv; f=$(find $OUT/$d -name "*domain_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${d}_domain_stats.csv; done
 # keep the merged output small: the raw traces are large
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*counter_collection.csv" -delete; find $OUT -name "*agent_info.csv" -delete
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 head -5 $OUT/prod_kernel_stats.csv; head -c 300 $OUT/bench.json

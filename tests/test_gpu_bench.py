@@ -1,4 +1,4 @@
-"""bench.py as the driver runs it: `--gpus N` must produce an N-rank job and ONE JSON line with n_gpus == N carrying the
+"""bench.py as the driver runs it: `--gpus N` must produce an N-rank job and ONE JSON line with n_gpus == N carrying (with --full) the
 roofline object.  With >= 2 GPUs the ranks talk RCCL; on a 1-GPU box the same launcher path is exercised with two ranks sharing
 the device over gloo (SIMT_DIST_BACKEND=gloo: functional check of spawn + DP step + max-over-ranks timing, not a measurement)."""
 import json
@@ -24,7 +24,7 @@ def _run(extra_env, args):
 
 
 def test_bench_gpus2_spawns_two_ranks(dev):
-    small = ["--steps", "2", "--warmup", "1", "--batch", "1", "--size", "129", "129", "--no-cpu-baseline", "--no-extra-passes"]
+    small = ["--steps", "2", "--warmup", "1", "--batch", "1", "--size", "129", "129", "--full", "--no-cpu-baseline", "--no-extra-passes"]
     if torch.cuda.device_count() >= 2:
         line = _run({}, ["--gpus", "2"] + small)
         assert "RCCL" in line["config"]["workload"]
@@ -47,7 +47,7 @@ def test_bench_gpus2_spawns_two_ranks(dev):
 
 
 def test_bench_single_gpu_line_has_every_contract_field(dev):
-    line = _run({}, ["--steps", "3", "--warmup", "1", "--batch", "1", "--size", "257", "257", "--cpu-iters", "1"])
+    line = _run({}, ["--steps", "3", "--warmup", "1", "--batch", "1", "--size", "257", "257", "--full", "--cpu-iters", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline", "h2d_inclusive", "trained_like_pass", "ms_per_step_median"):
         assert k in line, k
@@ -57,6 +57,19 @@ def test_bench_single_gpu_line_has_every_contract_field(dev):
     pc = line.get("power_clock")
     if pc is not None:
         assert pc["samples"] >= 1 and (pc["sclk_mhz_avg"] is None or 50 <= pc["sclk_mhz_avg"] <= 3000)
+
+
+def test_bench_plain_run_carries_the_headline_only(dev):
+    """Without --full the run sets up, warms up, times its steps and prints the contract fields; nothing that takes a run, a replay or a
+    sampler of its own (roofline, CPU baseline, the other passes, power / clock)."""
+    line = _run({}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--size", "129", "129"])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_median", "higher_is_better", "dtype", "config"):
+        assert k in line, k
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "bf16" and line["higher_is_better"] is True
+    assert line["value"] > 0 and abs(line["value"] - 1 * 1000.0 / line["ms_per_step"]) / line["value"] < 0.01
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    for k in ("aspp_t_step", "power_clock", "h2d_inclusive", "trained_like_pass", "skip_unapplied_grads_pass", "f32_parity_mode_pass", "dump_outputs"):
+        assert k not in line, k
 
 
 def test_bench_dp_job_over_a_real_one_rank_rccl_group(dev):

@@ -116,6 +116,21 @@ def test_bench_gpus_flag_spawns_n_ranks_and_fails_loudly_without_gpu():
     assert "local_rank: 0" in err and "local_rank: 1" in err, err[-2000:]
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain bench.py run measures the headline only; everything else is asked for with --full, and --shapes (a table of the --full
+    roofline replay) is refused without it rather than ignored."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and (a.steps, a.warmup, a.batch, a.size) == (4, 2, 4, [768, 768])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--shapes"])
+    assert bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--shapes"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_bench_rejects_world_size_mismatch():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="3", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)
