@@ -423,6 +423,11 @@ int simt_entropy2d(const float* x, int n, int c, int h, int w, void* ws, float* 
 int simt_upsample_sum_argmax(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H,
                              int W, int C, int32_t* pred, simt_stream_t stream);
 int simt_confusion_hist(const int64_t* gt, const int32_t* pred, long P, int n, int64_t* hist, simt_stream_t stream);
+/* the same for a model that upsamples inside (model/deeplabv3.py:137): scale s is first resampled from its NHWC logits [B][h_s][w_s][ld_s]
+ * to a VIRTUAL map [hi_s][wi_s] (align_corners=False, half-pixel, clamped at 0), that map to (H, W) (align_corners=True); pred = the
+ * first-index arg-max of the sum over the scales.  lb may be NULL (single scale).  Nothing is written but pred. */
+int simt_upsample2_sum_argmax(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb, int ldb,
+                              int hib, int wib, int B, int H, int W, int C, int32_t* pred, simt_stream_t stream);
 /* pseudo-label export (the save lines of evaluate_simt :150-156 / evaluate_warmup :214-219; trainV2_simt.py:353-359):
  * mode 0: out[b][y][x] = the label simt_upsample_sum_argmax writes (bit for bit), as uint8;
  * mode 1: la holds low-res PROBABILITIES (simt_softmax_rows of the logits), lb must be NULL: out = argmax_c up(la)[c] where

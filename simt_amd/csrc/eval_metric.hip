@@ -348,6 +348,135 @@ extern "C" int simt_upsample_nchw_bwd(const float* ddst, int B, int h, int w, in
   return SIMT_OK;
 }
 
+// ---- evaluation of a model that upsamples INSIDE (DeepLabv3, model/deeplabv3.py:137): the reference resamples its full-resolution
+// output a second time (evaluate_cityscapes.py:108-133).  Per label pixel and scale: the align_corners=True taps of the label grid over a
+// VIRTUAL [Hi][Wi] map (bil_taps' arithmetic), each of whose 4 samples is the align_corners=False value of the NHWC logits (up_taps, align
+// = 0) -- 16 gathers per channel, nothing stored in between (the map would be 52 + 82 MB per frame at Q = 25).  Both scales summed, then
+// the first-index arg-max, like upsample_sum_argmax_kernel.  V = 4: float4 gathers of 4 consecutive channels (ld % 4 == 0, 16-byte
+// aligned maps; channels C..round_up(C, 4)-1 are read, lie inside ld, and are ignored).
+struct Up2Scale {
+  const float* l;      // [B][h][w][ld] logits, first C channels used
+  int h, w, ld, hi, wi;
+  float osy, osx;      // outer: (hi-1)/(H-1), (wi-1)/(W-1)
+  float isy, isx;      // inner: h/hi, w/wi
+};
+struct Up2Args {
+  Up2Scale s[2];
+  int nscales;
+  int* pred;
+  int B, H, W, C;
+};
+
+struct Up2Taps {
+  int off[4][4];       // [virtual sample yi*2+xi][logit tap yj*2+xj] element offsets (B*h*w*ld < 2^31, checked on the host)
+  float ly[2][2], lx[2][2];   // inner weights [virtual row / column][tap]
+  float oy[2], ox[2];         // outer weights
+};
+
+__device__ __forceinline__ void up2_taps(const Up2Scale& s, int b, int y, int x, Up2Taps& t) {
+  int vy[2], vx[2], iy[2][2], ix[2][2];
+  up_taps(y, s.hi, s.osy, 1, vy[0], vy[1], t.oy[0], t.oy[1]);
+  up_taps(x, s.wi, s.osx, 1, vx[0], vx[1], t.ox[0], t.ox[1]);
+  for (int i = 0; i < 2; ++i) {
+    up_taps(vy[i], s.h, s.isy, 0, iy[i][0], iy[i][1], t.ly[i][0], t.ly[i][1]);
+    up_taps(vx[i], s.w, s.isx, 0, ix[i][0], ix[i][1], t.lx[i][0], t.lx[i][1]);
+  }
+  const int base = b * s.h * s.w;
+  for (int yi = 0; yi < 2; ++yi)
+    for (int xi = 0; xi < 2; ++xi)
+      for (int yj = 0; yj < 2; ++yj)
+        for (int xj = 0; xj < 2; ++xj)
+          t.off[yi * 2 + xi][yj * 2 + xj] = (base + iy[yi][yj] * s.w + ix[xi][xj]) * s.ld;
+}
+
+template <int V> struct VecF;
+template <> struct VecF<1> {
+  float v[1];
+  __device__ __forceinline__ void load(const float* p) { v[0] = *p; }
+};
+template <> struct VecF<4> {
+  float v[4];
+  __device__ __forceinline__ void load(const float* p) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  }
+};
+
+// up(up(l))[c0 .. c0+V-1] at one pixel, in ATen's association at both levels: h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
+template <int V>
+__device__ __forceinline__ void up2_value(const float* l, const Up2Taps& t, int c0, float (&out)[V]) {
+  float vs[4][V];
+  for (int yi = 0; yi < 2; ++yi)
+    for (int xi = 0; xi < 2; ++xi) {
+      const int s = yi * 2 + xi;
+      VecF<V> p00, p01, p10, p11;
+      p00.load(l + t.off[s][0] + c0); p01.load(l + t.off[s][1] + c0);
+      p10.load(l + t.off[s][2] + c0); p11.load(l + t.off[s][3] + c0);
+      const float h0 = t.ly[yi][0], h1 = t.ly[yi][1], w0 = t.lx[xi][0], w1 = t.lx[xi][1];
+      for (int k = 0; k < V; ++k) vs[s][k] = h0 * (w0 * p00.v[k] + w1 * p01.v[k]) + h1 * (w0 * p10.v[k] + w1 * p11.v[k]);
+    }
+  for (int k = 0; k < V; ++k)
+    out[k] = t.oy[0] * (t.ox[0] * vs[0][k] + t.ox[1] * vs[1][k]) + t.oy[1] * (t.ox[0] * vs[2][k] + t.ox[1] * vs[3][k]);
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void upsample2_sum_argmax_kernel(Up2Args a) {
+  const long P = (long)a.B * a.H * a.W;
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(p % a.W);
+    const long t = p / a.W;
+    const int y = (int)(t % a.H);
+    const int b = (int)(t / a.H);
+    Up2Taps ta, tb;
+    up2_taps(a.s[0], b, y, x, ta);
+    const bool two = a.nscales > 1;
+    if (two) up2_taps(a.s[1], b, y, x, tb);
+    float best = -INFINITY;
+    int arg = 0;
+    for (int c0 = 0; c0 < a.C; c0 += V) {
+      float va[V], vb[V];
+      up2_value<V>(a.s[0].l, ta, c0, va);
+      if (two) up2_value<V>(a.s[1].l, tb, c0, vb);
+      for (int k = 0; k < V; ++k) {
+        if (c0 + k >= a.C) break;
+        const float v = two ? va[k] + vb[k] : va[k];
+        if (v > best) { best = v; arg = c0 + k; }     // first index on ties, like np.argmax
+      }
+    }
+    a.pred[p] = arg;
+  }
+}
+
+static void fill_up2(Up2Scale& s, const float* l, int h, int w, int ld, int hi, int wi, int H, int W) {
+  s.l = l; s.h = h; s.w = w; s.ld = ld; s.hi = hi; s.wi = wi;
+  s.osy = H > 1 ? (float)(hi - 1) / (float)(H - 1) : 0.f;
+  s.osx = W > 1 ? (float)(wi - 1) / (float)(W - 1) : 0.f;
+  s.isy = (float)h / (float)hi;
+  s.isx = (float)w / (float)wi;
+}
+
+extern "C" int simt_upsample2_sum_argmax(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb,
+                                         int ldb, int hib, int wib, int B, int H, int W, int C, int32_t* pred, simt_stream_t stream) {
+  SIMT_CHECK(la && pred && B > 0 && H > 0 && W > 0 && C > 0 && C <= lda && ha > 0 && wa > 0 && hia > 0 && wia > 0);
+  SIMT_CHECK(!lb || (C <= ldb && hb > 0 && wb > 0 && hib > 0 && wib > 0));
+  SIMT_CHECK((long)B * ha * wa * lda < 2147483647L && (!lb || (long)B * hb * wb * ldb < 2147483647L));
+  Up2Args a;
+  a.nscales = lb ? 2 : 1;
+  fill_up2(a.s[0], la, ha, wa, lda, hia, wia, H, W);
+  fill_up2(a.s[1], lb ? lb : la, lb ? hb : ha, lb ? wb : wa, lb ? ldb : lda, lb ? hib : hia, lb ? wib : wia, H, W);
+  a.pred = pred; a.B = B; a.H = H; a.W = W; a.C = C;
+  const bool vec = lda % 4 == 0 && ((uintptr_t)la & 15) == 0 && (!lb || (ldb % 4 == 0 && ((uintptr_t)lb & 15) == 0));
+  long P = (long)B * H * W;
+  long grid = (P + 255) / 256;
+  if (grid > 256 * 16) grid = 256 * 16;
+  if (vec)
+    hipLaunchKernelGGL(upsample2_sum_argmax_kernel<4>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(upsample2_sum_argmax_kernel<1>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
 // ---- offline NTM utilities (tools/compute_ClassDistribution.py:49-51,66-86; tools/compute_ConfusionMatrix.py:54-56,68-98) ----------
 // hist[na_idx * nb + b] += 1 over uint8 label images: a = row class (optional 256-entry LUT = label_mapping; NULL a -> row 0, i.e. the
 // 1-D class histogram of compute_CD), b = column class.  Entries with a (after the LUT) >= na or b >= nb are skipped: 255 = ignore.

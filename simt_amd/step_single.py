@@ -225,6 +225,20 @@ class SimTSingleTrainer:
         self.it_done += 1
         return self.lout
 
+    def state_dict(self):
+        """Host copy of the trainable model's state, the counterpart of SimTTrainer.state_dict: every key the trainer was given, fp32 (int64
+        for `num_batches_tracked`).  Trained tensors and running statistics are the current ones; keys the plan never touches (DeepLabv3's
+        layer4 / fc, DeeplabVGG's classifier branches 2 and 3) come back as given.  `num_batches_tracked` grows by the number of steps
+        taken for the BatchNorms that run (nn.BatchNorm2d bumps it once per train-mode forward; DeepLabv3._dead_bns: not layer4's)."""
+        live = set(self.plan.bn) if self.model == "v3" else set()
+        sd = {}
+        for k, v in self.params.items():
+            if k.endswith(".num_batches_tracked"):
+                sd[k] = torch.tensor(int(v.item()) + (self.it_done if k[:-len(".num_batches_tracked")] in live else 0), dtype=torch.long)
+            else:
+                sd[k] = v.detach().cpu()
+        return sd
+
     def timed_lists(self):
         return [self._fix_fwd, self._fwd, self._bwd]
 

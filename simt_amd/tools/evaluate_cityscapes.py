@@ -8,7 +8,12 @@
 
 Two eval-mode plans (BN folded) produce the main head's logits at both scales; one fused kernel upsamples both to the
 label resolution (align_corners=True), sums, arg-maxes; the confusion histogram is accumulated on the device with
-integer atomics.  Dataset IO (PIL decoding, file lists) stays outside: `add` takes tensors."""
+integer atomics.  Dataset IO (PIL decoding, file lists) stays outside: `add` takes tensors.
+
+model: "v2" DeepLab-v2 (DeeplabMulti, the reference's), "v3" DeepLabv3(nc, openc, openset=True), "vgg" DeeplabVGG(nc + openc).
+DeepLabv3 upsamples inside the model (model/deeplabv3.py:137, align_corners=False, to the input size); its plans stop at the
+low-res logits and simt_upsample2_sum_argmax applies both resamples per label pixel without storing the input-size map.
+DeeplabVGG returns low-res logits like DeepLab-v2: the same kernel as v2 over its first nc channels."""
 import numpy as np
 import torch
 
@@ -35,18 +40,44 @@ def label_mapping(inp, mapping):
 
 
 class Evaluator:
+    MODELS = ("v2", "v3", "vgg")
+
     def __init__(self, state, *, num_classes=19, open_classes=0, openset=None, batch=1, label_hw=(1024, 2048),
-                 scales=((512, 1024), (640, 1280)), dtype=torch.float32, device="cuda:0", layers=None):
+                 scales=((512, 1024), (640, 1280)), dtype=torch.float32, device="cuda:0", layers=None, model="v2"):
         # dtype: fp32 by default -- the reference evaluates in fp32 (evaluate_cityscapes.py:96-162) and the metric is defined "argmax bit-exact";
         # bf16 plans are an explicit, labelled opt-in (tools: --eval-dtype bf16; < 0.2 % of the arg-max positions differ)
+        # layers: trunk depth of the plans -- v2: ResNet layers (4 entries), v3: layer1..layer3 of the ResNet, vgg: the VGG_LAYERS list
+        if model not in self.MODELS:
+            raise ValueError(f"model must be one of {self.MODELS}, got {model!r}")
+        self.model = model
         self.dev = torch.device(device)
         self.dtype = dtype
         self.C = num_classes
         openset = (open_classes > 0) if openset is None else openset
         params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
-        kw = {"layers": layers} if layers is not None else {}
-        self.plans = [TrunkPlan(params, batch, h, w, multi_heads(num_classes, open_classes, openset), dtype=dtype, train=False, **kw)
-                      for (h, w) in scales]
+        self.scales = [tuple(s) for s in scales]
+        if model == "v2":
+            kw = {"layers": layers} if layers is not None else {}
+            self.plans = [TrunkPlan(params, batch, h, w, multi_heads(num_classes, open_classes, openset), dtype=dtype, train=False, **kw)
+                          for (h, w) in scales]
+        elif model == "v3":
+            from simt_amd.engine import LaunchList
+            from simt_amd.engine_v3 import V3Plan
+            kw = {"layers": tuple(layers)} if layers is not None else {}
+            self.plans = [V3Plan(params, batch, h, w, num_classes, open_classes, openset, dtype=dtype, train=False, **kw) for (h, w) in scales]
+            # the in-model upsample to the input size (the last forward launch) is folded into simt_upsample2_sum_argmax: the plans stop at
+            # the low-res logits, trimmed as step_single.SimTSingleTrainer trims its forward
+            self._fwd = []
+            for plan in self.plans:
+                assert plan.fwd_list.items[-1].tag == "simt_upsample_nchw"
+                lst = LaunchList()
+                lst.items = plan.fwd_list.items[:-1]
+                self._fwd.append(lst)
+        else:
+            from simt_amd.engine_vgg import VggPlan
+            kw = {"vgg_layers": list(layers)} if layers is not None else {}
+            self.plans = [VggPlan(params, batch, h, w, num_classes + (open_classes if openset else 0), dtype=dtype, train=False, **kw)
+                          for (h, w) in scales]
         self.B, (self.H, self.W) = batch, label_hw
         self.pred = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.int32)
         self.hist = torch.zeros(num_classes * num_classes, device=self.dev, dtype=torch.int64)
@@ -64,9 +95,21 @@ class Evaluator:
 
     def predict(self, *images):
         """images: one [B,3,h,w] fp32 tensor per scale.  Returns the arg-max label map [B,H,W] int32 (device)."""
+        if self.model == "v3":
+            outs = []
+            for plan, lst, img, (hi, wi) in zip(self.plans, self._fwd, images, self.scales):
+                plan.x_in.copy_(img.to(self.dev))
+                lst.run()
+                (h, w) = plan.feat_hw
+                outs.append((plan.logits, h, w, plan.ldq, hi, wi))
+            (la, ha, wa, lda, hia, wia) = outs[0]
+            lb, hb, wb, ldb, hib, wib = (outs[1] if len(outs) > 1 else (None, 0, 0, 0, 0, 0))
+            L.call("simt_upsample2_sum_argmax", ops._p(la), ha, wa, lda, hia, wia, ops._p(lb), hb, wb, ldb, hib, wib, self.B, self.H, self.W,
+                   self.C, ops._p(self.pred), ops.stream_ptr())
+            return self.pred
         outs = []
         for plan, img in zip(self.plans, images):
-            o = plan.forward(img.to(self.dev))["x2"]
+            o = plan.forward(img.to(self.dev))["x2" if self.model == "v2" else "x"]
             outs.append((o, o.shape[1], o.shape[2], o.shape[3]))
         (la, ha, wa, lda) = outs[0]
         lb, hb, wb, ldb = (outs[1] if len(outs) > 1 else (None, 0, 0, 0))
@@ -87,13 +130,15 @@ class Evaluator:
 
 
 def evaluate_simt(state, data_dir, data_list, gt_dir, devkit_dir="../dataset/cityscapes_list", *, num_classes=19, open_classes=0, set_name="val",
-                  device="cuda:0", dtype=torch.float32, evaluator=None, rank=0, world=1, process_group=None, verbose=True, workers=4):
+                  device="cuda:0", dtype=torch.float32, evaluator=None, rank=0, world=1, process_group=None, verbose=True, workers=4,
+                  model="v2", layers=None):
     """File-based evaluation loop of the reference (evaluate_cityscapes.py:96-162): every validation frame at crop sizes (1024, 512) and
     (1280, 640) -> logits[:, :num_classes] of the main head, upsampled to 1024 x 2048, summed, arg-maxed -> fast_hist against the
     ground-truth label ids mapped with info.json's label2train -> mIoU (round(nanmean * 100, 2)).
     dtype: fp32 like the reference; torch.bfloat16 is an opt-in whose mIoU is printed with a "(bf16 plans)" label.
     Host: file lists, PNG decoding (threads), the label LUT.  Device: both resizes (Pillow-exact), BGR - mean, both forwards, the fused
-    upsample + sum + arg-max, the histogram.  Data parallel: ranks take strided shards of the list and the histogram is all-reduced."""
+    upsample + sum + arg-max, the histogram.  Data parallel: ranks take strided shards of the list and the histogram is all-reduced.
+    model / layers: see Evaluator ("v2", "v3" or "vgg"; the plans' trunk depth)."""
     import json
     from concurrent.futures import ThreadPoolExecutor
     from os.path import join
@@ -107,7 +152,7 @@ def evaluate_simt(state, data_dir, data_list, gt_dir, devkit_dir="../dataset/cit
     name_classes = info.get("label", [str(i) for i in range(num_classes)])
     lut = mapping_lut(np.array(info["label2train"]))
     ds = cityscapesDataSet(data_dir, data_list, crop_size=(1024, 512), mean=IMG_MEAN, scale=False, mirror=False, set=set_name)
-    ev = evaluator or Evaluator(state, num_classes=num_classes, open_classes=open_classes, dtype=dtype, device=dev)
+    ev = evaluator or Evaluator(state, num_classes=num_classes, open_classes=open_classes, dtype=dtype, device=dev, model=model, layers=layers)
     if evaluator is not None:
         ev.load(state)
     from PIL import Image

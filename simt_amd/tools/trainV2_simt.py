@@ -15,6 +15,11 @@ Every --save-pred-every iterations: evaluate_simt on the validation set (--data-
 trainV2_simt.py:452-464.  Additions over the reference (all optional): --synthetic, --compute-dtype, --eval-dtype (fp32 like the
 reference unless bf16 is asked for), --print-every, --data-dir-val,
 --data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels).
+
+--model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
+DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
+auxiliary head removed, and are evaluated and checkpointed like the first (their state dicts load into the nn.Modules of
+simt_amd.model).  --iter-size > 1 is implemented for DeepLab only.
 """
 import argparse
 import os
@@ -30,7 +35,7 @@ from simt_amd.step import Hyper, SimTTrainer, lr_poly
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser(description="SimT (DeepLab-ResNet) on MI355X")
-    p.add_argument("--model", type=str, default="DeepLab")
+    p.add_argument("--model", type=str, default="DeepLab", help="DeepLab | DeepLabv3 | DeepLabVGG")
     p.add_argument("--target", type=str, default="cityscapes")
     p.add_argument("--batch-size", type=int, default=1)
     p.add_argument("--iter-size", type=int, default=1)
@@ -82,7 +87,50 @@ def get_arguments(argv=None):
     p.add_argument("--from-scratch", action="store_true", help="allow training from the constructor init (no --restore-from)")
     p.add_argument("--class-dist", type=str, default=None,
                    help="class prior .npy of the pseudo labels (make_pseudo_labels writes it); default: ClassDist_bapa.npy")
+    add_v3_layers(p)
     return p.parse_args(argv)
+
+
+MODELS = ("DeepLab", "DeepLabv3", "DeepLabVGG")
+ENGINE_MODEL = {"DeepLab": "v2", "DeepLabv3": "v3", "DeepLabVGG": "vgg"}      # --model -> Evaluator / SimTSingleTrainer model name
+RESTORE_LAST = {"DeepLab": ("layer5", "layer6"), "DeepLabv3": ("conv.", "conv_1."), "DeepLabVGG": ("classifier.",)}   # --not-restore-last
+
+
+def add_v3_layers(p):
+    p.add_argument("--v3-layers", type=int, nargs=3, default=[3, 4, 6], metavar=("L1", "L2", "L3"),
+                   help="DeepLabv3 trunk: Bottlenecks of layer1..layer3 (3 4 6: model/deeplabv3.py as written, ResNet-50; "
+                        "3 4 23: the ResNet-101 depth)")
+
+
+def check_model_args(args):
+    """--model names one of MODELS (checked here rather than by argparse: the reference's scripts accept any string); --iter-size > 1
+    needs the DeepLab trainer."""
+    if args.model not in MODELS:
+        raise SystemExit(f"--model {args.model!r}: expected one of {', '.join(MODELS)}")
+    if args.model != "DeepLab" and args.iter_size > 1:
+        raise SystemExit(f"--iter-size {args.iter_size}: gradient accumulation is implemented for --model DeepLab only "
+                         f"(SimTSingleTrainer, which trains {args.model}, runs --iter-size 1)")
+
+
+def single_model_states(model, num_classes, open_classes, v3_layers=(3, 4, 6), seed=1234):
+    """(trainable, frozen) state dicts of the nn.Modules of a one-output model at their constructor init: DeepLabv3(nc, openc, openset=True) /
+    DeepLabv3(nc), or DeeplabVGG(nc + openc) / DeeplabVGG(nc).  A DeepLabv3 trunk deeper than the file's is the same module with
+    layer1..layer3 rebuilt at v3_layers (layer4 and fc, which never run, keep the ResNet-50 shapes)."""
+    torch.manual_seed(seed)
+    if model == "DeepLabv3":
+        from simt_amd.model.deeplabv3 import DeepLabv3, _ResNet50Params
+
+        def make(*a, **kw):
+            m = DeepLabv3(*a, **kw)
+            if tuple(v3_layers) != (3, 4, 6):
+                m.resnet.resnet_50 = _ResNet50Params(layers=tuple(v3_layers) + (3,))
+            return {k: v.detach().clone() for k, v in m.state_dict().items()}
+        return make(num_classes, open_classes, openset=True), make(num_classes)
+    if model == "DeepLabVGG":
+        from simt_amd.model.deeplab_vgg import DeeplabVGG
+        return ({k: v.detach().clone() for k, v in DeeplabVGG(num_classes + open_classes).state_dict().items()},
+                {k: v.detach().clone() for k, v in DeeplabVGG(num_classes).state_dict().items()})
+    raise ValueError(model)
 
 
 def load_class_dist_arg(path, num_classes):
@@ -101,9 +149,10 @@ def load_class_dist_arg(path, num_classes):
     return cd
 
 
-def restore(state, path, not_restore_last=False, strip_prefix=0, required=False):
+def restore(state, path, not_restore_last=False, strip_prefix=0, required=False, last=("layer5", "layer6")):
     """Filter-by-key load of an AdaptSegNet-style checkpoint into a fresh state (trainV2_simt.py:248-255).  strip_prefix=6: the warm-up
     stage's `k[6:]` (trainV1_warmup.py:177, checkpoints saved from a wrapped module) -- a key is accepted with or without the prefix.
+    last: the key prefixes not_restore_last skips (the classifiers; RESTORE_LAST per --model).
     required: a missing file or zero matching tensors is an error (the reference crashes in torch.load; silently training from the
     constructor init would still produce checkpoints that look like results)."""
     if not path or not osp.exists(path):
@@ -114,7 +163,7 @@ def restore(state, path, not_restore_last=False, strip_prefix=0, required=False)
     n = 0
     for k, v in saved.items():
         for cand in ((k, k[strip_prefix:]) if strip_prefix else (k,)):
-            if cand in state and (not not_restore_last or not cand.startswith(("layer5", "layer6"))) and state[cand].shape == v.shape:
+            if cand in state and (not not_restore_last or not cand.startswith(tuple(last))) and state[cand].shape == v.shape:
                 state[cand] = v.clone()
                 n += 1
                 break
@@ -180,6 +229,9 @@ def batches(args, B, H, W, cd, rank, world, dev):
 
 def main(argv=None):
     args = get_arguments(argv)
+    check_model_args(args)
+    if args.model != "DeepLab":
+        return main_single(args)
     class_dist = load_class_dist_arg(args.class_dist, args.num_classes) if args.class_dist else None
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
@@ -251,6 +303,85 @@ def main(argv=None):
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             # no validation set given (the reference hard-codes one, :452-464): without an evaluation there is no best-mIoU snapshot,
             # so keep a rolling periodic one -- a crash must not lose the run
+            keeper.rolling(tr.state_dict(), i_iter)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def main_single(args):
+    """--model DeepLabv3 | DeepLabVGG: the same outer loop as main() over SimTSingleTrainer."""
+    from simt_amd.step_single import SimTSingleTrainer
+    class_dist = load_class_dist_arg(args.class_dist, args.num_classes) if args.class_dist else None
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if not torch.cuda.is_available():
+        raise SystemExit("trainV2_simt needs a GPU: the SimT hot path has no CPU fallback")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    pg = None
+    if world > 1:
+        import torch.distributed as dist
+        from simt_amd.engine import reserve_streams
+        reserve_streams(dev)
+        os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")
+        dist.init_process_group("nccl", device_id=dev)
+        pg = dist.group.WORLD
+    w, h = map(int, args.input_size_target.split(","))
+    C, K = args.num_classes, args.open_classes
+    model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
+    state, fixed = single_model_states(args.model, C, K, layers, seed=args.random_seed)
+    required = not (args.synthetic or args.from_scratch)
+    n1 = restore(state, args.restore_from, args.not_restore_last, required=required, last=RESTORE_LAST[args.model])
+    n2 = restore(fixed, args.restore_from, required=required)
+    cd = class_dist if class_dist is not None else ms.load_class_dist("bapa")
+    hp = Hyper(num_classes=C, open_classes=K, th_high=args.Threshold_high, th_low=args.Threshold_low,
+               lambda_seg=args.lambda_seg, lambda_place=args.lambda_Place, lambda_convex=args.lambda_Convex,
+               lambda_volume=args.lambda_Volume, lambda_anchor=args.lambda_Anchor, iter_size=args.iter_size,
+               lr=args.learning_rate, lr_T=args.learning_rate_T, momentum=args.momentum,
+               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
+    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
+    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
+    arch = {"layers": layers} if model == "v3" else None
+    eval_layers = layers if model == "v3" else None
+    tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
+                           device=dev, process_group=pg, arch=arch)
+    if rank == 0:
+        print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
+              f"{h}x{w}, {args.compute_dtype}, K={K}")
+        os.makedirs(args.snapshot_dir, exist_ok=True)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
+    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
+    t0 = time.time()
+    for i_iter in range(args.num_steps):
+        img, lab = next(data)
+        tr.step(img, lab, i_iter)
+        if i_iter % args.print_every == 0:
+            l = tr.losses()
+            if rank == 0:
+                print("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
+                      "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
+                          i_iter, args.num_steps, l["loss_p"], l["loss_y"], l["convex"], l["volume"], l["anchor"], l["place"],
+                          lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                          args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))
+        if i_iter >= args.num_steps_stop - 1:
+            if rank == 0:
+                print("save model ...")
+                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            break
+        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
+            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
+            if evaluator is None:
+                evaluator = Evaluator(tr.params, num_classes=C, open_classes=K, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
+            if rank == 0:
+                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
+            mIoU = evaluate_simt(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
+            if rank == 0:
+                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
+                keeper.best(tr.state_dict(), i_iter, mIoU)
+        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
     if world > 1:
         import torch.distributed as dist
