@@ -335,7 +335,9 @@ typedef struct {
   int32_t mode;         /* 0: SimT loss block.  1: warm-up stage (tools/trainV1_warmup.py:217-224): CE of both heads against
                          * `label` (ignore 255); fixp/T1/T2 unused (may be NULL); hout[0],[1] = loss_seg1/2, hout[14] = total */
   int32_t single;       /* 1: one-output model (model/deeplabv3.py, model/deeplab_vgg.py return ONE tensor): pred1 / T1 / dpred1_* are
-                         * unused (may be NULL) and every auxiliary-head term is dropped; pred2 / T2 / dpred2_* carry the model's head */
+                         * unused (may be NULL) and every auxiliary-head term is dropped; pred2 / T2 / dpred2_* carry the model's head.
+                         * With mode 1 (the warm-up stage of such a model): hout[1] = hout[14] = CE of that head against `label`, g1's
+                         * head-1 rows are not written, fixp / T1 / T2 may be NULL */
   int32_t up_half_pixel; /* 0: interp_target = nn.Upsample(bilinear, align_corners=True) (tools/trainV2_simt.py:301);
                           * 1: F.interpolate(bilinear), align_corners=False, the in-model upsample of model/deeplabv3.py:137 fused here */
   int32_t fix_logits;   /* 1: fixp holds the frozen model's low-res LOGITS; posterior = softmax(upsample(logits)) -- what

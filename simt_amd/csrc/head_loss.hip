@@ -286,8 +286,12 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
 #ifndef SIMT_HEAD_P1_WAVES
 #define SIMT_HEAD_P1_WAVES 2      // 3 waves per SIMD need 21 spilled VGPRs (335-348 us); 2 waves, no scratch: 352-375 us (profiles/tools/ab_head.py)
 #endif
-template <int QM, int QT, int CT>
+// ONE_: empty for every SimT / DeepLab-v2 warm-up flavour (names and code as before the flag existed); {true} for the warm-up stage of a
+// one-output model (single = 1, mode = 1): one head per pixel and only its cross-entropy against the label, run-time channel counts.
+template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head_pass1_kernel(HeadArgs a) {
+  constexpr bool ONE = (false || ... || ONE_);
+  static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time");
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C;
   constexpr int CM = CT ? (CT + 3) / 4 * 4 : QM;
@@ -327,6 +331,27 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head
       b = (int)(t / g.H);
     }
     Taps tp = make_taps(g, b, y, x);
+    if constexpr (ONE) {
+      // warm-up stage of a one-output model: CrossEntropyLoss(ignore_index=255) of its one head against the label (hout[1]); the
+      // out-of-range count as in the other modes.  No frozen posterior, T, placeholder or anchor term.
+      float v2[QM];
+      interp_vec<QM>(a.pred2, g.ldp, Q, tp, v2);
+      HeadEval e2;
+      eval_head<QM>(v2, Q, C, a.th_high, e2);
+      const long long lab = live ? a.label[p] : 255;
+      const bool lab_ok = live && lab >= 0 && lab != 255 && lab < C;
+      if (live && !lab_ok && lab != 255) acc[12] += 1.f;
+      if (lab_ok) {
+        float l2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < QM; ++j)
+          if (j == (int)lab) l2 = e2.lse - v2[j];
+        acc[1] += l2; acc[8] += 1.f;
+      }
+      if (live && a.conf_out) a.conf_out[p] = lab_ok ? (unsigned char)lab : (unsigned char)255;
+      if (live && a.label_ws) a.label_ws[p] = 255;
+      continue;
+    }
     // ---- fixed-model posterior -> confidence label (reference :354-361)
     float fm = 0.f;
     int fa = 0;
@@ -632,8 +657,12 @@ __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL
 // scratch: round 1's "256 MB of HBM traffic per launch" against ~30 MB algorithmic); the compile-time-count builds come out at ~160
 // VGPRs without spills.  At 4 x 768 x 768 on cold operands, pass 2 + y-reduction: 1 016 us (round 1) -> 826 (no spill) -> 680 (compile-time
 // counts, one-instruction exp) -> 432 (run-based x-reduction).  Pass 1 keeps 3 waves per SIMD with a small spill (faster than 2 without).
-template <int QM, int QT, int CT>
+// ONE_: as in head_pass1_kernel.  The one-head flavour evaluates the model's head once per pixel and fills, reduces and writes only the
+// head-2 rows of sG / sAcc / g1 (head_yreduce_kernel skips head 1 of a single-head descriptor).
+template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
+  constexpr bool ONE = (false || ... || ONE_);
+  static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time (rows = 1)");
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C, QP = a.QP;
   constexpr int CM = CT ? (CT + 3) / 4 * 4 : QM;
@@ -668,7 +697,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
   const float gy1 = gs * a.lambda_seg / Ny, gy2 = gs / Ny;
   for (int rr = 0; rr < R; ++rr) {
   const int y = y0 + rr;
-  for (int i = tid; i < 2 * g.w * Q; i += 256) sAcc[i] = 0.f;
+  for (int i = tid + (ONE ? g.w * Q : 0); i < 2 * g.w * Q; i += 256) sAcc[i] = 0.f;     // (ONE: the head-2 half only)
   __syncthreads();
 
   for (int x0 = 0; x0 < g.W; x0 += 256) {
@@ -698,6 +727,29 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
       // instead of the frozen posterior's 4 x C gathers + arg-max and the 8-byte label), else decided again
       const bool from_p1 = a.conf_out != nullptr && a.label_ws != nullptr;
       const long pix = ((long)b * g.H + y) * g.W + x;
+      if constexpr (ONE) {
+        // warm-up stage of a one-output model: gscale * (softmax - onehot(label)) / N_valid of the one head, staged in the head-2 rows
+        float v2[QM];
+        interp_vec<QM>(a.pred2, g.ldp, Q, tp, v2);
+        HeadEval e2;
+        eval_head<QM>(v2, Q, C, a.th_high, e2);
+        int conf = 255;
+        if (from_p1) {
+          conf = live ? (int)a.conf_out[pix] : 255;
+        } else {
+          const long long lab = live ? a.label[pix] : 255;
+          conf = (live && lab >= 0 && lab != 255 && lab < C) ? (int)lab : 255;
+        }
+        const float inv2 = 1.0f / e2.sum;
+#pragma unroll
+        for (int j = 0; j < QM; ++j)
+          if (j < Q) {
+            const float q2 = exp_le0(v2[j] - e2.vmax) * inv2;
+            float G2 = 0.f;
+            if (live && conf != 255) G2 += gp2 * (q2 - ((j == conf) ? 1.f : 0.f));
+            sG[(1 * 256 + tid) * GP + j] = G2;
+          }
+      } else {
       float fm = 0.f;
       int fa = 0;
       if (a.mode == 0 && !from_p1) fixed_posterior<CM>(g, C, a.fixp, tp, fm, fa);
@@ -775,6 +827,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
           sG[(1 * 256 + tid) * GP + j] = G2;
           } else { asm volatile("" :: "v"(G1), "v"(G2)); }
         }
+      }
     }
     __syncthreads();
     // x-reduction: out[hd][xl][j] += sum_x wgt(x, xl) * G[hd][x][j]  -- only the low-res columns this 256-pixel chunk
@@ -798,7 +851,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
         const bool edge = xl == g.w - 1;          // the right tap of the last column is the column itself
         const int rlen = max(a0 - b0, a1 - a0);
         const int rb = rlen <= 8 ? 2 : rlen <= 12 ? 3 : 0;     // runs of at most 4 * rb pixels: every term requested at once (0: looped)
-        for (int L = ln; L < 2 * Q; L += 64) {
+        for (int L = ln + (ONE ? Q : 0); L < 2 * Q; L += 64) {
           const int hd = L >= Q ? 1 : 0, j = L - hd * Q;
           const float* G = sG + hd * 256 * GP + j;
           float s = 0.f;
@@ -812,7 +865,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
         }
       }
     } else
-    for (int idx = tid; idx < 2 * nxl * Q; idx += 256) {
+    for (int idx = tid + (ONE ? nxl * Q : 0); idx < 2 * nxl * Q; idx += 256) {
       int hd = idx / (nxl * Q);
       int r = idx - hd * nxl * Q;
       int xr = r / Q, j = r - xr * Q;
@@ -834,8 +887,8 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
     __syncthreads();
   }
   if (!GROUPED || R == 1) {
-    // write g1[hd][b][y][xl][0..QP)
-    for (int idx = tid; idx < 2 * g.w * QP; idx += 256) {
+    // write g1[hd][b][y][xl][0..QP)  (ONE: no head-1 rows)
+    for (int idx = tid + (ONE ? g.w * QP : 0); idx < 2 * g.w * QP; idx += 256) {
       int hd = idx / (g.w * QP);
       int r = idx - hd * g.w * QP;
       int xl = r / QP, j = r - xl * QP;
@@ -944,7 +997,7 @@ static int head_rows_per_block(const simt_head_desc* d, float sy) {
 
 static int fill_args(const simt_head_desc* d, HeadArgs& a) {
   SIMT_CHECK(d && d->pred2 && d->label && d->part && d->keys && d->hout);
-  SIMT_CHECK(d->single ? (d->mode == 0) : (d->pred1 != nullptr));
+  SIMT_CHECK(d->single || d->pred1 != nullptr);
   SIMT_CHECK(d->mode == 1 || (d->fixp && d->T2 && (d->single || d->T1)));
   SIMT_CHECK(d->Q <= QMAX && d->C < d->Q + 1 && d->C >= 1 && d->Q <= 64);
   SIMT_CHECK(d->ldp % 4 == 0 && d->ldf % 4 == 0 && d->ldp >= ((d->Q + 3) / 4) * 4 && d->ldf >= ((d->C + 3) / 4) * 4);
@@ -964,7 +1017,7 @@ static int fill_args(const simt_head_desc* d, HeadArgs& a) {
   a.th_high = d->th_high; a.th_low = d->th_low; a.lambda_seg = d->lambda_seg; a.lambda_place = d->lambda_place;
   a.part = d->part; a.keys = (unsigned long long*)d->keys; a.hout = d->hout; a.g1 = d->g1; a.QP = d->QP;
   a.gscale = d->gscale;
-  a.rows = head_rows_per_block(d, a.g.sy);
+  a.rows = (d->single && d->mode == 1) ? 1 : head_rows_per_block(d, a.g.sy);     // (the one-head warm-up flavour: run-time counts)
   a.mode = d->mode;
   a.conf_out = d->conf_out;
   a.label_ws = d->label_ws;
@@ -996,12 +1049,15 @@ extern "C" int simt_head_loss(const simt_head_desc* d, simt_stream_t stream) {
   SIMT_CHECK(lds1 <= 160 * 1024);
   static SimtLdsAttrCache lds1_cache;
   if (simt_lds_attr_needed(&lds1_cache, lds1)) {
-#define P1ATTR(QM, QT, CT) (void)hipFuncSetAttribute((const void*)head_pass1_kernel<QM, QT, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)
-    P1ATTR(24, 22, 19); P1ATTR(28, 25, 19); P1ATTR(24, 0, 0); P1ATTR(QMAX, 0, 0);
+#define P1ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass1_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)
+    P1ATTR(24, 22, 19); P1ATTR(28, 25, 19); P1ATTR(24, 0, 0); P1ATTR(QMAX, 0, 0); P1ATTR(24, 0, 0, true); P1ATTR(QMAX, 0, 0, true);
 #undef P1ATTR
   }
-#define P1(QM, QT, CT) hipLaunchKernelGGL((head_pass1_kernel<QM, QT, CT>), dim3(nblk), dim3(256), lds1, st, a)
-  if (d->Q == 22 && d->C == 19) P1(24, 22, 19);          // Cityscapes, K = 3 open classes (BASELINE configs[0..2], [4])
+#define P1(...) hipLaunchKernelGGL((head_pass1_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), lds1, st, a)
+  const bool one = d->single && d->mode == 1;            // warm-up stage of a one-output model: one head, plain CE
+  if (one && d->Q <= 24) P1(24, 0, 0, true);
+  else if (one) P1(QMAX, 0, 0, true);
+  else if (d->Q == 22 && d->C == 19) P1(24, 22, 19);     // Cityscapes, K = 3 open classes (BASELINE configs[0..2], [4])
   else if (d->Q == 25 && d->C == 19) P1(28, 25, 19);     // K = 6 (configs[3])
   else if (d->Q <= 24) P1(24, 0, 0);
   else P1(QMAX, 0, 0);
@@ -1029,12 +1085,15 @@ extern "C" int simt_head_grad(const simt_head_desc* d, simt_stream_t stream) {
   SIMT_CHECK(lds2 <= 160 * 1024);
   static SimtLdsAttrCache lds2_cache;
   if (simt_lds_attr_needed(&lds2_cache, lds2)) {
-#define P2ATTR(QM, QT, CT) (void)hipFuncSetAttribute((const void*)head_pass2_kernel<QM, QT, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)
-    P2ATTR(24, 22, 19); P2ATTR(28, 25, 19); P2ATTR(24, 0, 0); P2ATTR(QMAX, 0, 0);
+#define P2ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass2_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)
+    P2ATTR(24, 22, 19); P2ATTR(28, 25, 19); P2ATTR(24, 0, 0); P2ATTR(QMAX, 0, 0); P2ATTR(24, 0, 0, true); P2ATTR(QMAX, 0, 0, true);
 #undef P2ATTR
   }
-#define P2(QM, QT, CT) hipLaunchKernelGGL((head_pass2_kernel<QM, QT, CT>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
-  if (d->Q == 22 && d->C == 19) P2(24, 22, 19);
+#define P2(...) hipLaunchKernelGGL((head_pass2_kernel<__VA_ARGS__>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
+  const bool one = d->single && d->mode == 1;            // (fill_args: a.rows = 1)
+  if (one && d->Q <= 24) P2(24, 0, 0, true);
+  else if (one) P2(QMAX, 0, 0, true);
+  else if (d->Q == 22 && d->C == 19) P2(24, 22, 19);
   else if (d->Q == 25 && d->C == 19) P2(28, 25, 19);
   else if (d->Q <= 24) P2(24, 0, 0);
   else P2(QMAX, 0, 0);

@@ -253,3 +253,152 @@ class SimTSingleTrainer:
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         return {"total": v[0], "loss_p": v[2], "loss_y": v[4], "place": v[5], "convex": v[6], "volume": v[7], "anchor": v[8],
                 "vol_ok": v[9]}
+
+
+class WarmupSingleTrainer:
+    """The warm-up stage (tools/trainV1_warmup.py:156-256) over a ONE-OUTPUT model: DeepLabv3(nc) or DeeplabVGG(nc), trained by cross-entropy
+    on the pseudo labels, loss = CE(interp_target(model(x)), label) with ignore_index 255 (:212-231 without the auxiliary head; for
+    DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
+    micro-batches and one SGD step.  The checkpoint it writes is what the SimT stage restores (trainV2_simt --model DeepLabv3 | DeepLabVGG).
+    Engine: the plans of SimTSingleTrainer, the fused head kernels in their one-head warm-up flavour (simt_head_desc single = 1, mode = 1),
+    the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
+
+    def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None):
+        """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
+        keyword arguments, as for SimTSingleTrainer."""
+        assert model in ("v3", "vgg")
+        self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
+        dev = self.dev = torch.device(device)
+        self.pg = process_group
+        Cn = self.C = hp.num_classes
+        f32 = torch.float32
+        self.params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
+        arch = dict(arch or {})
+        dp = process_group is not None
+        if model == "v3":
+            from .engine_v3 import V3Plan
+            self.plan = V3Plan(self.params, B, H, W, Cn, 0, False, dtype=dtype, train=True, data_parallel=dp, **arch)
+            # the in-model upsample and its adjoint are fused into the head kernel, as in SimTSingleTrainer
+            assert self.plan.fwd_list.items[-1].tag == "simt_upsample_nchw"
+            self._fwd, self._bwd = LaunchList(), LaunchList()
+            self._fwd.items = self.plan.fwd_list.items[:-1]
+            i0 = next(i for i, it in enumerate(self.plan.bwd_list.items) if it.tag == "simt_upsample_nchw_bwd")
+            self._bwd.items = self.plan.bwd_list.items[:i0] + self.plan.bwd_list.items[i0 + 1:]
+            h, w = self.plan.feat_hw
+            self.pred, self.ldp = self.plan.logits, self.plan.ldq
+            half = 1
+        else:
+            from .engine_vgg import VggPlan
+            self.plan = VggPlan(self.params, B, H, W, Cn, dtype=dtype, train=True, data_parallel=dp, **arch)
+            self._fwd, self._bwd = self.plan.fwd_list, self.plan.bwd_list
+            h, w = self.plan.heads[0].h, self.plan.heads[0].w
+            self.pred, self.ldp = self.plan.out["x"], self.plan.ldp["x"]
+            half = 0
+        self.h, self.w = h, w
+        dl = self.plan.dlogits["x"]
+        lib = L.load()
+        self.part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Cn, Cn), device=dev)
+        self.keys = torch.zeros(lib.simt_head_keys_count(), device=dev, dtype=torch.int64)
+        self.hout = torch.zeros(lib.simt_head_hout_floats(Cn, Cn), device=dev)
+        # labels outside [0, C) other than 255, accumulated over every micro-batch of every step (hout[15] is per launch; see WarmupTrainer)
+        self.bad_labels = torch.zeros(1, device=dev)
+        self._bad_reported = 0
+        self.QP = ops.round_up(Cn, 8)
+        self.g1 = torch.zeros(2, B, H, w, self.QP, device=dev)          # the head-1 half is never written (single = 1)
+        self.label = torch.zeros(B, H, W, device=dev, dtype=torch.int64)
+        hd = L.HeadDesc()
+        hd.pred1, hd.pred2, hd.fixp, hd.label = None, self.pred.data_ptr(), None, self.label.data_ptr()
+        hd.T1, hd.T2 = None, None
+        hd.part, hd.keys, hd.hout, hd.g1 = self.part.data_ptr(), self.keys.data_ptr(), self.hout.data_ptr(), self.g1.data_ptr()
+        hd.dpred1_f32, hd.dpred2_f32, hd.dpred1_t, hd.dpred2_t = None, None, None, dl.data_ptr()
+        hd.B, hd.h, hd.w, hd.H, hd.W, hd.C, hd.Q = B, h, w, H, W, Cn, Cn
+        hd.ldp, hd.ldf, hd.QP, hd.ld_f32, hd.ld_t = self.ldp, self.ldp, self.QP, 0, dl.shape[1]
+        hd.grad_dtype = ops.dt_code(dtype)
+        hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 2.0, -1.0, 0.0, 0.0, 1.0 / hp.iter_size
+        hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 1, 1, half, 0
+        self.head_desc = hd
+        SimTSingleTrainer._build_sgd(self)
+        self.it_done = 0
+        self.reducer = None
+        if self.pg is not None:
+            from .dp import BucketReducer, make_buckets
+            sizes = {n: k for n, (_o, k) in self.plan.grad_offsets.items()}
+            buckets = make_buckets(self.plan.grad_order, sizes, self.plan.grad_ready, bucket_elems=8 << 20)
+            self.reducer = BucketReducer(self.plan.flat_grad, buckets, group=self.pg, extra=[self.bad_labels])
+        self._grad_acc = None
+
+    optim_groups = SimTSingleTrainer.optim_groups
+
+    def step(self, image, label, it=None):
+        """One micro-batch, or sequences of hp.iter_size micro-batches (trainV1_warmup.py:212-231: loss / iter_size, gradients accumulated,
+        one optimiser step; under data parallelism one exchange of the accumulated gradient)."""
+        hp = self.hp
+        it = self.it_done if it is None else it
+        lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
+        st = ops.stream_ptr()
+        images = list(image) if isinstance(image, (list, tuple)) else [image]
+        labels = list(label) if isinstance(label, (list, tuple)) else [label]
+        if len(images) != hp.iter_size or len(labels) != hp.iter_size:
+            raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
+        flat = self.plan.flat_grad
+        for mi, (img, lab) in enumerate(zip(images, labels)):
+            self.plan.x_in.copy_(img, non_blocking=True)
+            self.label.copy_(lab, non_blocking=True)
+            self._fwd.run()
+            L.call("simt_head_loss", C.byref(self.head_desc), st)
+            L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
+            L.call("simt_head_grad", C.byref(self.head_desc), st)
+            if self.reducer is not None and hp.iter_size == 1:
+                self.reducer.start()
+                self._bwd.run()
+                self.reducer.finish()
+                continue
+            self._bwd.run()
+            if hp.iter_size > 1:
+                if self._grad_acc is None:
+                    self._grad_acc = torch.zeros_like(flat)
+                if mi == 0:
+                    self._grad_acc.copy_(flat)
+                elif mi < hp.iter_size - 1:
+                    L.call("simt_vec_acc", self._grad_acc.data_ptr(), flat.data_ptr(), flat.numel(), 1, st)
+                else:
+                    L.call("simt_vec_acc", flat.data_ptr(), self._grad_acc.data_ptr(), flat.numel(), 1, st)
+                    if self.reducer is not None:
+                        self.reducer.start()
+                        self.reducer.finish()
+        d = self.sgd_desc
+        d.lr[0], d.lr[1] = lr, lr * 10.0
+        d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay
+        d.first_step = 1 if self.it_done == 0 else 0
+        L.call("simt_sgd_multi", C.byref(d), st)
+        self.plan.repack()
+        self.it_done += 1
+        return self.hout
+
+    def state_dict(self):
+        """Every key the trainer was given, fp32 (int64 for `num_batches_tracked`); loads strict=True into DeepLabv3(nc) / DeeplabVGG(nc).
+        `num_batches_tracked` grows by steps x iter_size for the BatchNorms that run (see SimTSingleTrainer.state_dict)."""
+        live = set(self.plan.bn) if self.model == "v3" else set()
+        n = self.it_done * self.hp.iter_size
+        sd = {}
+        for k, v in self.params.items():
+            if k.endswith(".num_batches_tracked"):
+                sd[k] = torch.tensor(int(v.item()) + (n if k[:-len(".num_batches_tracked")] in live else 0), dtype=torch.long)
+            else:
+                sd[k] = v.detach().cpu()
+        return sd
+
+    def timed_lists(self):
+        return [self._fwd, self._bwd]
+
+    def losses(self):
+        """Host copy of the last micro-batch's loss; local (see SimTTrainer.losses).  Raises ValueError for labels outside [0, C) other than
+        255 seen in any micro-batch (on any rank) since the last call, RuntimeError if a fused BatchNorm launch gave up (TrunkPlan.fbn_error)."""
+        v = torch.cat([self.hout[:16], self.bad_labels]).cpu().tolist()
+        self.plan.raise_on_fbn_error()
+        bad = int(round(v[16] * (self.reducer.world if self.reducer is not None else 1))) - self._bad_reported      # cumulative, never reset on the device
+        self._bad_reported += max(bad, 0)
+        if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
+            raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
+        # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like WarmupTrainer's
+        return {"total": v[14] / self.hp.iter_size, "loss_seg": v[1]}

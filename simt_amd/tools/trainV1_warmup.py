@@ -5,7 +5,13 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
 
+--model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
+(model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
+write the checkpoint `trainV2_simt --model DeepLabv3 | DeepLabVGG --restore-from` starts from.  Their --restore-from also takes the
+torchvision ImageNet files the reference builds them from (resnet50 / resnet101, vgg16: simt_amd/pretrained.py).
+
     python -m simt_amd.tools.trainV1_warmup --learning-rate 2.5e-4 --input-size-target 1024,512 --num-steps-stop 40000
+    python -m simt_amd.tools.trainV1_warmup --model DeepLabv3 --restore-from resnet50-imagenet.pth --snapshot-dir ../snapshots/v3/
 """
 import argparse
 import os
@@ -16,13 +22,13 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
-from simt_amd.tools.trainV2_simt import SnapshotKeeper, batches, restore, save_atomic
+from simt_amd.tools.trainV2_simt import ENGINE_MODEL, MODELS, SnapshotKeeper, add_v3_layers, batches, restore, save_atomic
 
 
 def get_arguments(argv=None):
     """Every flag of the reference (trainV1_warmup.py:60-150), same names / types / defaults; the ones the reference parses and never
-    reads (--model, --target, --data-dir, --data-list, --ignore-label, --input-size, --is-training, --learning-rate-T,
-    --not-restore-last, --open-classes, --random-scale, --set, --log-dir) are parsed and ignored here too."""
+    reads (--target, --data-dir, --data-list, --ignore-label, --input-size, --is-training, --learning-rate-T, --not-restore-last,
+    --open-classes, --random-scale, --set, --log-dir) are parsed and ignored here too.  --model picks the network (check_model)."""
     p = argparse.ArgumentParser(description="DeepLab-ResNet warm-up on MI355X")
     p.add_argument("--model", type=str, default="DeepLab")
     p.add_argument("--target", type=str, default="cityscapes")
@@ -68,11 +74,18 @@ def get_arguments(argv=None):
     p.add_argument("--data-list-val", type=str, default="../dataset/cityscapes_list/val.txt")
     p.add_argument("--gt-dir-val", type=str, default="", help="directory of *_gtFine_labelIds.png (evaluate_cityscapes.py:140)")
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
+    add_v3_layers(p)
     return p.parse_args(argv)
 
 
-def main(argv=None):
-    args = get_arguments(argv)
+def check_model(args):
+    """--model names one of trainV2_simt.MODELS (as trainV2_simt.check_model_args checks it); --iter-size works for all three."""
+    if args.model not in MODELS:
+        raise SystemExit(f"--model {args.model!r}: expected one of {', '.join(MODELS)}")
+
+
+def setup_devices(args):
+    """-> (rank, world, device, process group or None): this rank's GPU and, under torchrun (WORLD_SIZE > 1), the RCCL group."""
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -88,6 +101,15 @@ def main(argv=None):
         os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")      # the conv tile lists leave 20 CUs to the collective's kernels (engine.TrunkPlan.cu_budget)
         dist.init_process_group("nccl", device_id=dev)
         pg = dist.group.WORLD
+    return rank, world, dev, pg
+
+
+def main(argv=None):
+    args = get_arguments(argv)
+    check_model(args)
+    if args.model != "DeepLab":
+        return main_single(args)
+    rank, world, dev, pg = setup_devices(args)
     if rank == 0:
         print("Start: " + time.asctime(time.localtime(time.time())))                       # :158
     w, h = map(int, args.input_size_target.split(","))
@@ -136,6 +158,81 @@ def main(argv=None):
                 keeper.best(tr.state_dict(), i_iter, mIoU)
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             # no validation set given (the reference hard-codes one, evaluate_cityscapes.py:26-28): a rolling periodic snapshot instead
+            keeper.rolling(tr.state_dict(), i_iter)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def restore_single(state, path, model, required):
+    """--restore-from of the one-output warm-up: a checkpoint in the module's keys, or a torchvision ImageNet file mapped onto them
+    (simt_amd.pretrained.checkpoint_layout); then the key / shape filter of trainV2_simt.restore.  -> (tensors loaded, layout name)."""
+    from simt_amd.pretrained import checkpoint_layout
+    seen = []
+
+    def remap(saved):
+        layout, mapped = checkpoint_layout(saved, model)
+        seen.append(layout)
+        return mapped
+    n = restore(state, path, required=required, remap=remap)
+    return n, (seen[0] if seen else "no file")
+
+
+def main_single(args):
+    """--model DeepLabv3 | DeepLabVGG: the same outer loop as main() over WarmupSingleTrainer."""
+    from simt_amd.step_single import WarmupSingleTrainer
+    from simt_amd.tools.trainV2_simt import single_model_state
+    rank, world, dev, pg = setup_devices(args)
+    if rank == 0:
+        print("Start: " + time.asctime(time.localtime(time.time())))
+    w, h = map(int, args.input_size_target.split(","))
+    C = args.num_classes
+    model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
+    state = single_model_state(args.model, C, layers, seed=args.random_seed)
+    n, layout = restore_single(state, args.restore_from, model, required=not (args.synthetic or args.from_scratch))
+    hp = Hyper(num_classes=C, open_classes=0, lr=args.learning_rate, iter_size=args.iter_size, momentum=args.momentum,
+               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
+    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
+    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
+    arch = {"layers": layers} if model == "v3" else None
+    eval_layers = layers if model == "v3" else None
+    tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch)
+    cd = ms.load_class_dist("bapa")
+    if rank == 0:
+        print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
+              f"{h}x{w}, {args.compute_dtype}")
+        os.makedirs(args.snapshot_dir, exist_ok=True)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
+    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
+    t0 = time.time()
+    for i_iter in range(args.num_steps):
+        mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
+        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
+        tr.step(img, lab, i_iter)
+        if i_iter % args.print_every == 0:
+            l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
+            if rank == 0:
+                print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}  lr = {3:.2e}  ({4:.1f} img/s)".format(
+                    i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                    args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))
+        if i_iter >= args.num_steps_stop - 1:
+            if rank == 0:
+                print("save model ...")
+                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            break
+        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
+            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
+            if evaluator is None:
+                evaluator = Evaluator(tr.params, num_classes=C, open_classes=0, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
+            if rank == 0:
+                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
+            mIoU = evaluate_simt(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                 open_classes=0, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg,
+                                 model=model, layers=eval_layers)
+            if rank == 0:
+                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
+                keeper.best(tr.state_dict(), i_iter, mIoU)
+        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
     if world > 1:
         import torch.distributed as dist

@@ -118,19 +118,31 @@ def single_model_states(model, num_classes, open_classes, v3_layers=(3, 4, 6), s
     layer1..layer3 rebuilt at v3_layers (layer4 and fc, which never run, keep the ResNet-50 shapes)."""
     torch.manual_seed(seed)
     if model == "DeepLabv3":
-        from simt_amd.model.deeplabv3 import DeepLabv3, _ResNet50Params
-
-        def make(*a, **kw):
-            m = DeepLabv3(*a, **kw)
-            if tuple(v3_layers) != (3, 4, 6):
-                m.resnet.resnet_50 = _ResNet50Params(layers=tuple(v3_layers) + (3,))
-            return {k: v.detach().clone() for k, v in m.state_dict().items()}
-        return make(num_classes, open_classes, openset=True), make(num_classes)
+        return _module_state(model, v3_layers, num_classes, open_classes, openset=True), _module_state(model, v3_layers, num_classes)
     if model == "DeepLabVGG":
-        from simt_amd.model.deeplab_vgg import DeeplabVGG
-        return ({k: v.detach().clone() for k, v in DeeplabVGG(num_classes + open_classes).state_dict().items()},
-                {k: v.detach().clone() for k, v in DeeplabVGG(num_classes).state_dict().items()})
+        return _module_state(model, v3_layers, num_classes + open_classes), _module_state(model, v3_layers, num_classes)
     raise ValueError(model)
+
+
+def single_model_state(model, num_classes, v3_layers=(3, 4, 6), seed=1234):
+    """State dict of DeepLabv3(num_classes) / DeeplabVGG(num_classes) at its constructor init: the model the warm-up stage trains
+    (trainV1_warmup --model DeepLabv3 | DeepLabVGG) and the SimT stage freezes."""
+    if model not in ("DeepLabv3", "DeepLabVGG"):
+        raise ValueError(model)
+    torch.manual_seed(seed)
+    return _module_state(model, v3_layers, num_classes)
+
+
+def _module_state(model, v3_layers, *a, **kw):
+    if model == "DeepLabv3":
+        from simt_amd.model.deeplabv3 import DeepLabv3, _ResNet50Params
+        m = DeepLabv3(*a, **kw)
+        if tuple(v3_layers) != (3, 4, 6):
+            m.resnet.resnet_50 = _ResNet50Params(layers=tuple(v3_layers) + (3,))
+    else:
+        from simt_amd.model.deeplab_vgg import DeeplabVGG
+        m = DeeplabVGG(*a, **kw)
+    return {k: v.detach().clone() for k, v in m.state_dict().items()}
 
 
 def load_class_dist_arg(path, num_classes):
@@ -149,10 +161,11 @@ def load_class_dist_arg(path, num_classes):
     return cd
 
 
-def restore(state, path, not_restore_last=False, strip_prefix=0, required=False, last=("layer5", "layer6")):
+def restore(state, path, not_restore_last=False, strip_prefix=0, required=False, last=("layer5", "layer6"), remap=None):
     """Filter-by-key load of an AdaptSegNet-style checkpoint into a fresh state (trainV2_simt.py:248-255).  strip_prefix=6: the warm-up
     stage's `k[6:]` (trainV1_warmup.py:177, checkpoints saved from a wrapped module) -- a key is accepted with or without the prefix.
     last: the key prefixes not_restore_last skips (the classifiers; RESTORE_LAST per --model).
+    remap: optional callable applied to the loaded dict before the filter (the one-output warm-up: simt_amd.pretrained.checkpoint_layout).
     required: a missing file or zero matching tensors is an error (the reference crashes in torch.load; silently training from the
     constructor init would still produce checkpoints that look like results)."""
     if not path or not osp.exists(path):
@@ -160,6 +173,8 @@ def restore(state, path, not_restore_last=False, strip_prefix=0, required=False,
             raise FileNotFoundError(f"--restore-from {path!r} does not exist (pass --from-scratch to train from the constructor init)")
         return 0
     saved = torch.load(path, map_location="cpu")
+    if remap is not None:
+        saved = remap(saved)
     n = 0
     for k, v in saved.items():
         for cand in ((k, k[strip_prefix:]) if strip_prefix else (k,)):
