@@ -437,6 +437,15 @@ int simt_upsample2_sum_argmax(const float* la, int ha, int wa, int lda, int hia,
  * out: uint8 [B][H][W], 4-byte aligned.  counts: int64 [C+1] accumulated across calls (classes 0..C-1, then the 255s).  C <= 255. */
 int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H, int W, int C,
                          int mode, float threshold, uint8_t* out, int64_t* counts, simt_stream_t stream);
+/* the same for a model that upsamples inside (DeepLabv3), over the geometry of simt_upsample2_sum_argmax:
+ * mode 0: out = the label simt_upsample2_sum_argmax writes (bit for bit), as uint8;
+ * mode 1: la holds LOGITS, lb must be NULL: softmax over the first C channels at each virtual [hia][wia] sample (align_corners=False
+ *         from la), the probabilities resampled to (H, W) (align_corners=True); out = their arg-max where max > threshold (strictly),
+ *         255 elsewhere.
+ * out / counts / C: as simt_pseudo_label_u8.  B*h*w*ld < 2^31 per scale. */
+int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb, int ldb,
+                          int hib, int wib, int B, int H, int W, int C, int mode, float threshold, uint8_t* out, int64_t* counts,
+                          simt_stream_t stream);
 /* F.interpolate(bilinear) of an NHWC fp32 map [B][h][w][lds] (first C channels) to NCHW fp32 [B][C][H][W] and its adjoint
  * (model/deeplabv3.py:137 upsamples inside the model with align_corners=False; align_corners=1 = interp_target) */
 int simt_upsample_nchw(const float* src, int B, int h, int w, int lds, int C, int H, int W, int align_corners, float* dst,

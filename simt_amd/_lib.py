@@ -175,6 +175,7 @@ SIGNATURES = {
     "simt_confusion_hist": (_I, [c_p, c_p, _L, _I, c_p, c_p]),
     "simt_upsample2_sum_argmax": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_pseudo_label_u8": (_I, [c_p, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
+    "simt_pseudo_label2_u8": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),
     "simt_loss_ws_bytes": (_I, []),

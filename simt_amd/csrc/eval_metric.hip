@@ -127,15 +127,48 @@ __device__ __forceinline__ int pseudo_pixel(const PseudoArgs& a, int b, int y, i
 // 2048 of them (41 k 64-bit atomics on 20 words) it cost 7-13 us at 1 x 1024 x 2048; 1024-thread blocks, at most 512 of them (the
 // same 32 waves per CU), cut it to ~3 us (launch-shape sweep on MI355X, 138.6 us against 143.5 us of upsample_sum_argmax_kernel).
 constexpr int PL_BLOCK = 1024, PL_MAX_GRID = 512;
+
+// The output side of the pseudo-label kernels.  Every lane of the block calls pl_store once per grid-stride step (the loop bound is
+// uniform over the block: every lane of a wave reaches the shuffles together) with the label of pixel p (anything for p >= P).
+template <int BLOCK>
+__device__ __forceinline__ void pl_hist_init(unsigned int* sh, int nbins) {
+  for (int i = threadIdx.x; i < nbins; i += BLOCK) sh[i] = 0u;
+  __syncthreads();
+}
+__device__ __forceinline__ void pl_store(unsigned int lab, long p, long P, int C, unsigned char* out, unsigned int* sh) {
+  const bool leader = (threadIdx.x & 3) == 0;
+  unsigned int word = lab | (__shfl_down(lab, 1, 4) << 8);
+  word |= __shfl_down(word, 2, 4) << 16;
+  if (leader && p < P) {
+    const int n = P - p < 4 ? (int)(P - p) : 4;
+    if (n == 4) {
+      *reinterpret_cast<unsigned int*>(out + p) = word;
+    } else {
+      for (int i = 0; i < n; ++i) out[p + i] = (unsigned char)(word >> (8 * i));
+    }
+    int run_bin = 0, run_n = 0;
+    for (int i = 0; i < n; ++i) {
+      const unsigned int l = (word >> (8 * i)) & 255u;
+      const int bin = l == 255u ? C : (int)l;
+      if (bin != run_bin && run_n) { atomicAdd(&sh[run_bin], (unsigned int)run_n); run_n = 0; }
+      run_bin = bin;
+      ++run_n;
+    }
+    atomicAdd(&sh[run_bin], (unsigned int)run_n);
+  }
+}
+template <int BLOCK>
+__device__ __forceinline__ void pl_hist_flush(const unsigned int* sh, int nbins, unsigned long long* counts) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbins; i += BLOCK)
+    if (sh[i]) atomicAdd(&counts[i], (unsigned long long)sh[i]);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(PL_BLOCK) void pseudo_label_u8_kernel(PseudoArgs a) {
   __shared__ unsigned int sh[256];
-  const int nbins = a.C + 1;
-  for (int i = threadIdx.x; i < nbins; i += PL_BLOCK) sh[i] = 0u;
-  __syncthreads();
+  pl_hist_init<PL_BLOCK>(sh, a.C + 1);
   const long P = (long)a.B * a.H * a.W;
-  const bool leader = (threadIdx.x & 3) == 0;
-  // the loop bound is uniform over the block: every lane of a wave reaches the shuffles together
   for (long base = (long)blockIdx.x * PL_BLOCK; base < P; base += (long)gridDim.x * PL_BLOCK) {
     const long p = base + threadIdx.x;
     unsigned int lab = 0u;
@@ -144,29 +177,9 @@ __global__ __launch_bounds__(PL_BLOCK) void pseudo_label_u8_kernel(PseudoArgs a)
       const long t = p / a.W;
       lab = (unsigned int)pseudo_pixel<MODE>(a, (int)(t / a.H), (int)(t % a.H), x);
     }
-    unsigned int word = lab | (__shfl_down(lab, 1, 4) << 8);
-    word |= __shfl_down(word, 2, 4) << 16;
-    if (leader && p < P) {
-      const int n = P - p < 4 ? (int)(P - p) : 4;
-      if (n == 4) {
-        *reinterpret_cast<unsigned int*>(a.out + p) = word;
-      } else {
-        for (int i = 0; i < n; ++i) a.out[p + i] = (unsigned char)(word >> (8 * i));
-      }
-      int run_bin = 0, run_n = 0;
-      for (int i = 0; i < n; ++i) {
-        const unsigned int l = (word >> (8 * i)) & 255u;
-        const int bin = l == 255u ? a.C : (int)l;
-        if (bin != run_bin && run_n) { atomicAdd(&sh[run_bin], (unsigned int)run_n); run_n = 0; }
-        run_bin = bin;
-        ++run_n;
-      }
-      atomicAdd(&sh[run_bin], (unsigned int)run_n);
-    }
+    pl_store(lab, p, P, a.C, a.out, sh);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nbins; i += PL_BLOCK)
-    if (sh[i]) atomicAdd(&a.counts[i], (unsigned long long)sh[i]);
+  pl_hist_flush<PL_BLOCK>(sh, a.C + 1, a.counts);
 }
 
 extern "C" int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb, int B, int H,
@@ -402,10 +415,10 @@ template <> struct VecF<4> {
   }
 };
 
-// up(up(l))[c0 .. c0+V-1] at one pixel, in ATen's association at both levels: h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
+// the 4 virtual samples [yi*2+xi] of up(l)[c0 .. c0+V-1] (the inner, align_corners=False level), in ATen's association:
+// h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
 template <int V>
-__device__ __forceinline__ void up2_value(const float* l, const Up2Taps& t, int c0, float (&out)[V]) {
-  float vs[4][V];
+__device__ __forceinline__ void up2_samples(const float* l, const Up2Taps& t, int c0, float (&vs)[4][V]) {
   for (int yi = 0; yi < 2; ++yi)
     for (int xi = 0; xi < 2; ++xi) {
       const int s = yi * 2 + xi;
@@ -415,8 +428,38 @@ __device__ __forceinline__ void up2_value(const float* l, const Up2Taps& t, int 
       const float h0 = t.ly[yi][0], h1 = t.ly[yi][1], w0 = t.lx[xi][0], w1 = t.lx[xi][1];
       for (int k = 0; k < V; ++k) vs[s][k] = h0 * (w0 * p00.v[k] + w1 * p01.v[k]) + h1 * (w0 * p10.v[k] + w1 * p11.v[k]);
     }
+}
+
+// up(up(l))[c0 .. c0+V-1] at one pixel, in ATen's association at both levels
+template <int V>
+__device__ __forceinline__ void up2_value(const float* l, const Up2Taps& t, int c0, float (&out)[V]) {
+  float vs[4][V];
+  up2_samples<V>(l, t, c0, vs);
   for (int k = 0; k < V; ++k)
     out[k] = t.oy[0] * (t.ox[0] * vs[0][k] + t.ox[1] * vs[1][k]) + t.oy[1] * (t.ox[0] * vs[2][k] + t.ox[1] * vs[3][k]);
+}
+
+// the first-index arg-max of up(up(s[0])) (+ up(up(s[1])) with two scales) at one pixel: the evaluator's label, and mode 0 of the
+// pseudo-label export (one function, so the two agree bit for bit)
+template <int V>
+__device__ __forceinline__ int up2_argmax(const Up2Scale (&s)[2], int nscales, int C, int b, int y, int x) {
+  Up2Taps ta, tb;
+  up2_taps(s[0], b, y, x, ta);
+  const bool two = nscales > 1;
+  if (two) up2_taps(s[1], b, y, x, tb);
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c0 = 0; c0 < C; c0 += V) {
+    float va[V], vb[V];
+    up2_value<V>(s[0].l, ta, c0, va);
+    if (two) up2_value<V>(s[1].l, tb, c0, vb);
+    for (int k = 0; k < V; ++k) {
+      if (c0 + k >= C) break;
+      const float v = two ? va[k] + vb[k] : va[k];
+      if (v > best) { best = v; arg = c0 + k; }     // first index on ties, like np.argmax
+    }
+  }
+  return arg;
 }
 
 template <int V>
@@ -427,23 +470,7 @@ __global__ __launch_bounds__(256) void upsample2_sum_argmax_kernel(Up2Args a) {
     const long t = p / a.W;
     const int y = (int)(t % a.H);
     const int b = (int)(t / a.H);
-    Up2Taps ta, tb;
-    up2_taps(a.s[0], b, y, x, ta);
-    const bool two = a.nscales > 1;
-    if (two) up2_taps(a.s[1], b, y, x, tb);
-    float best = -INFINITY;
-    int arg = 0;
-    for (int c0 = 0; c0 < a.C; c0 += V) {
-      float va[V], vb[V];
-      up2_value<V>(a.s[0].l, ta, c0, va);
-      if (two) up2_value<V>(a.s[1].l, tb, c0, vb);
-      for (int k = 0; k < V; ++k) {
-        if (c0 + k >= a.C) break;
-        const float v = two ? va[k] + vb[k] : va[k];
-        if (v > best) { best = v; arg = c0 + k; }     // first index on ties, like np.argmax
-      }
-    }
-    a.pred[p] = arg;
+    a.pred[p] = up2_argmax<V>(a.s, a.nscales, a.C, b, y, x);
   }
 }
 
@@ -473,6 +500,108 @@ extern "C" int simt_upsample2_sum_argmax(const float* la, int ha, int wa, int ld
     hipLaunchKernelGGL(upsample2_sum_argmax_kernel<4>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(upsample2_sum_argmax_kernel<1>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+// ---- pseudo-label export of a model that upsamples inside (DeepLabv3): the gather of upsample2_sum_argmax_kernel with the output side of
+// pseudo_label_u8_kernel.  MODE 0: up2_argmax, as uint8.  MODE 1 (one scale): the confidence rule on the model's OUTPUT -- softmax at
+// each of the 4 virtual samples (the input-size map), the probabilities resampled to the label pixel, arg-max where max > threshold.  The
+// softmax is not separable from the inner resample, so the 4 samples' logits are re-gathered in three channel sweeps (max, sum of
+// exps, probabilities + arg-max) instead of holding 4 x C values per lane; expf / fmaxf / 1/s as in softmax_rows_kernel.
+struct Pseudo2Args {
+  Up2Scale s[2];
+  int nscales;
+  unsigned char* out;           // [B][H][W], 4-byte aligned
+  unsigned long long* counts;   // [C+1], accumulated
+  int B, H, W, C;
+  float threshold;
+};
+
+template <int V>
+__device__ __forceinline__ int up2_confident(const Up2Scale& s, int C, float threshold, int b, int y, int x) {
+  Up2Taps t;
+  up2_taps(s, b, y, x, t);
+  float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, inv[4] = {0.f, 0.f, 0.f, 0.f};
+  float vs[4][V];
+  for (int c0 = 0; c0 < C; c0 += V) {
+    up2_samples<V>(s.l, t, c0, vs);
+    for (int k = 0; k < V; ++k) {
+      if (c0 + k >= C) break;
+      for (int i = 0; i < 4; ++i) mx[i] = fmaxf(mx[i], vs[i][k]);
+    }
+  }
+  for (int c0 = 0; c0 < C; c0 += V) {
+    up2_samples<V>(s.l, t, c0, vs);
+    for (int k = 0; k < V; ++k) {
+      if (c0 + k >= C) break;
+      for (int i = 0; i < 4; ++i) inv[i] += expf(vs[i][k] - mx[i]);
+    }
+  }
+  for (int i = 0; i < 4; ++i) inv[i] = 1.0f / inv[i];
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c0 = 0; c0 < C; c0 += V) {
+    up2_samples<V>(s.l, t, c0, vs);
+    for (int k = 0; k < V; ++k) {
+      if (c0 + k >= C) break;
+      float q[4];
+      for (int i = 0; i < 4; ++i) q[i] = expf(vs[i][k] - mx[i]) * inv[i];
+      const float v = t.oy[0] * (t.ox[0] * q[0] + t.ox[1] * q[1]) + t.oy[1] * (t.ox[0] * q[2] + t.ox[1] * q[3]);
+      if (v > best) { best = v; arg = c0 + k; }     // first index on ties
+    }
+  }
+  return best > threshold ? arg : 255;             // strictly greater (trainV2_simt.py:359)
+}
+
+// 512-thread blocks: the two-scale float4 gather holds ~220 VGPRs (2 waves per SIMD, as upsample2_sum_argmax_kernel runs), which a
+// 1024-thread block (128 VGPRs at most) would spill; at most 1024 of them keeps the count flush at ~20 k atomics per frame.
+constexpr int PL2_BLOCK = 512, PL2_MAX_GRID = 1024;
+template <int MODE, int V>
+__global__ __launch_bounds__(PL2_BLOCK) void pseudo_label2_u8_kernel(Pseudo2Args a) {
+  __shared__ unsigned int sh[256];
+  pl_hist_init<PL2_BLOCK>(sh, a.C + 1);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL2_BLOCK; base < P; base += (long)gridDim.x * PL2_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      const int y = (int)(t % a.H), b = (int)(t / a.H);
+      lab = (unsigned int)(MODE == 0 ? up2_argmax<V>(a.s, a.nscales, a.C, b, y, x) : up2_confident<V>(a.s[0], a.C, a.threshold, b, y, x));
+    }
+    pl_store(lab, p, P, a.C, a.out, sh);
+  }
+  pl_hist_flush<PL2_BLOCK>(sh, a.C + 1, a.counts);
+}
+
+extern "C" int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb, int ldb,
+                                     int hib, int wib, int B, int H, int W, int C, int mode, float threshold, uint8_t* out, int64_t* counts,
+                                     simt_stream_t stream) {
+  SIMT_CHECK(la && out && counts && B > 0 && H > 0 && W > 0 && C > 0 && C <= 255 && C <= lda && ha > 0 && wa > 0 && hia > 0 && wia > 0);
+  SIMT_CHECK((mode == 0 && (!lb || (C <= ldb && hb > 0 && wb > 0 && hib > 0 && wib > 0))) || (mode == 1 && !lb));
+  SIMT_CHECK((long)B * ha * wa * lda < 2147483647L && (!lb || (long)B * hb * wb * ldb < 2147483647L));
+  SIMT_CHECK(((uintptr_t)out & 3) == 0);
+  Pseudo2Args a;
+  a.nscales = lb ? 2 : 1;
+  fill_up2(a.s[0], la, ha, wa, lda, hia, wia, H, W);
+  fill_up2(a.s[1], lb ? lb : la, lb ? hb : ha, lb ? wb : wa, lb ? ldb : lda, lb ? hib : hia, lb ? wib : wia, H, W);
+  a.out = out; a.counts = (unsigned long long*)counts;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.threshold = threshold;
+  const bool vec = lda % 4 == 0 && ((uintptr_t)la & 15) == 0 && (!lb || (ldb % 4 == 0 && ((uintptr_t)lb & 15) == 0));
+  const long P = (long)B * H * W;
+  long grid = (P + PL2_BLOCK - 1) / PL2_BLOCK;
+  if (grid > PL2_MAX_GRID) grid = PL2_MAX_GRID;
+  const dim3 g((unsigned)grid), blk(PL2_BLOCK);
+  if (mode == 0 && vec)
+    hipLaunchKernelGGL((pseudo_label2_u8_kernel<0, 4>), g, blk, 0, (hipStream_t)stream, a);
+  else if (mode == 0)
+    hipLaunchKernelGGL((pseudo_label2_u8_kernel<0, 1>), g, blk, 0, (hipStream_t)stream, a);
+  else if (vec)
+    hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 4>), g, blk, 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 1>), g, blk, 0, (hipStream_t)stream, a);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }

@@ -39,6 +39,29 @@ def label_mapping(inp, mapping):
     return np.array(out, dtype=np.int64)
 
 
+def v3_low_res_forward(plan):
+    """The forward of an eval-mode V3Plan without its last launch, the in-model upsample to the input size: the label kernels
+    (simt_upsample2_sum_argmax, simt_pseudo_label2_u8) apply it per label pixel from the low-res logits, as step_single.SimTSingleTrainer
+    trims its forward.  -> a LaunchList that stops at plan.logits."""
+    from simt_amd.engine import LaunchList
+    assert plan.fwd_list.items[-1].tag == "simt_upsample_nchw"
+    lst = LaunchList()
+    lst.items = plan.fwd_list.items[:-1]
+    return lst
+
+
+def v3_low_res_logits(plans, fwds, images, scales, dev):
+    """Run each trimmed V3Plan forward on its image.  -> [(logits [B*h*w, ld], h, w, ld, hi, wi)] per scale, (hi, wi) = the plan's input
+    size (the in-model upsample's target)."""
+    outs = []
+    for plan, lst, img, (hi, wi) in zip(plans, fwds, images, scales):
+        plan.x_in.copy_(img.to(dev))
+        lst.run()
+        (h, w) = plan.feat_hw
+        outs.append((plan.logits, h, w, plan.ldq, hi, wi))
+    return outs
+
+
 class Evaluator:
     MODELS = ("v2", "v3", "vgg")
 
@@ -61,18 +84,10 @@ class Evaluator:
             self.plans = [TrunkPlan(params, batch, h, w, multi_heads(num_classes, open_classes, openset), dtype=dtype, train=False, **kw)
                           for (h, w) in scales]
         elif model == "v3":
-            from simt_amd.engine import LaunchList
             from simt_amd.engine_v3 import V3Plan
             kw = {"layers": tuple(layers)} if layers is not None else {}
             self.plans = [V3Plan(params, batch, h, w, num_classes, open_classes, openset, dtype=dtype, train=False, **kw) for (h, w) in scales]
-            # the in-model upsample to the input size (the last forward launch) is folded into simt_upsample2_sum_argmax: the plans stop at
-            # the low-res logits, trimmed as step_single.SimTSingleTrainer trims its forward
-            self._fwd = []
-            for plan in self.plans:
-                assert plan.fwd_list.items[-1].tag == "simt_upsample_nchw"
-                lst = LaunchList()
-                lst.items = plan.fwd_list.items[:-1]
-                self._fwd.append(lst)
+            self._fwd = [v3_low_res_forward(plan) for plan in self.plans]
         else:
             from simt_amd.engine_vgg import VggPlan
             kw = {"vgg_layers": list(layers)} if layers is not None else {}
@@ -96,12 +111,7 @@ class Evaluator:
     def predict(self, *images):
         """images: one [B,3,h,w] fp32 tensor per scale.  Returns the arg-max label map [B,H,W] int32 (device)."""
         if self.model == "v3":
-            outs = []
-            for plan, lst, img, (hi, wi) in zip(self.plans, self._fwd, images, self.scales):
-                plan.x_in.copy_(img.to(self.dev))
-                lst.run()
-                (h, w) = plan.feat_hw
-                outs.append((plan.logits, h, w, plan.ldq, hi, wi))
+            outs = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
             (la, ha, wa, lda, hia, wia) = outs[0]
             lb, hb, wb, ldb, hib, wib = (outs[1] if len(outs) > 1 else (None, 0, 0, 0, 0, 0))
             L.call("simt_upsample2_sum_argmax", ops._p(la), ha, wa, lda, hia, wia, ops._p(lb), hb, wb, ldb, hib, wib, self.B, self.H, self.W,

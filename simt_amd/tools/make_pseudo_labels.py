@@ -10,9 +10,16 @@ rule of trainV2_simt.py:353-359 (high threshold only): softmax at low resolution
     python -m simt_amd.tools.make_pseudo_labels --restore-from src.pth --arch single --data-dir $CS --data-list train.txt \
         --out-name pseudo_mine --list-out pseudo_mine.lst [--threshold 0.8] [--save-color --devkit-dir dataset/cityscapes_list]
 
-Device: both eval-mode forwards (engine.TrunkPlan, BN folded), the resizes (data.pipeline.InputPrep, Pillow-exact) and one fused
-upsample + arg-max kernel (simt_pseudo_label_u8) that writes the uint8 label map and the class counts.  Host: PNG decoding on a bounded
-thread pool, pinned copies of the label maps (guarded by events), PNG encoding on a writer pool, atomic file writes."""
+--arch: multi (DeeplabMulti, the SimT DeepLab-v2), single (Res_Deeplab), v3 (DeepLabv3 at --v3-layers) or vgg (DeeplabVGG).  A v3 / vgg
+checkpoint is read like the warm-up stage reads it (the module's own keys; a torchvision ImageNet file is mapped, but its classifier is
+not, so it is refused); with --open-classes K it is the SimT model, DeepLabv3(C, K, openset=True) / DeeplabVGG(C + K).  The labels
+always come from the first C channels.  DeepLabv3 upsamples inside the model (align_corners=False, to the input size): its confidence
+rule takes the softmax of that input-size map before the align_corners=True resample to the label size.
+
+Device: both eval-mode forwards (engine.TrunkPlan / engine_v3.V3Plan / engine_vgg.VggPlan, BN folded), the resizes
+(data.pipeline.InputPrep, Pillow-exact) and one fused upsample + arg-max kernel (simt_pseudo_label_u8; simt_pseudo_label2_u8 for v3,
+both resamples per label pixel) that writes the uint8 label map and the class counts.  Host: PNG decoding on a bounded thread pool,
+pinned copies of the label maps (guarded by events), PNG encoding on a writer pool, atomic file writes."""
 import argparse
 import json
 import os
@@ -26,23 +33,27 @@ import torch
 from simt_amd import _lib as L
 from simt_amd import ops
 from simt_amd.engine import TrunkPlan, multi_heads, single_head
+from simt_amd.tools.evaluate_cityscapes import v3_low_res_forward, v3_low_res_logits
 
 MAX_WORKERS = 16
+ARCHS = ("multi", "single", "v3", "vgg")
 DEFAULT_SCALES = ((512, 1024), (640, 1280))          # (h, w): the crop sizes (1024, 512) and (1280, 640) of evaluate_simt :103-106
 
 
 class PseudoLabeller:
-    """Eval-mode plans of a DeepLab-v2 ResNet at each input scale + the fused label kernel.
+    """Eval-mode plans of the model at each input scale + the fused label kernel.
 
     arch "multi": DeeplabMulti(C, K, K > 0), head x2, first C channels (evaluate_simt :128, :133).  arch "single": Res_Deeplab(C)
-    (model/deeplab.py), head x.  mode "argmax": up(logits) summed over the scales, arg-max (one scale = evaluate_warmup).
-    mode "confidence": first scale only, softmax -> up -> arg-max where max > threshold, else 255.
+    (model/deeplab.py), head x.  arch "v3": DeepLabv3(C, K, openset=K > 0), the plans trimmed before the in-model upsample
+    (simt_pseudo_label2_u8 applies it).  arch "vgg": DeeplabVGG(C + K), head x.  layers: the plans' trunk depth, as for Evaluator.
+    mode "argmax": up(logits) summed over the scales, arg-max (one scale = evaluate_warmup).
+    mode "confidence": first scale only, softmax -> up -> arg-max where max > threshold, else 255 (v3: the softmax of the input-size map).
     label(*images) -> uint8 [B, H, W] on the device; `counts` accumulates int64 [C+1] (classes, then the 255s)."""
 
     def __init__(self, state, *, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
                  mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, batch=1):
-        if arch not in ("multi", "single"):
-            raise ValueError(f"arch must be 'multi' or 'single', not {arch!r}")
+        if arch not in ARCHS:
+            raise ValueError(f"arch must be one of {ARCHS}, not {arch!r}")
         if mode not in ("argmax", "confidence"):
             raise ValueError(f"mode must be 'argmax' or 'confidence', not {mode!r}")
         if arch == "single" and open_classes:
@@ -54,32 +65,51 @@ class PseudoLabeller:
         scales = tuple(tuple(s) for s in scales)
         if mode == "confidence":
             scales = scales[:1]
-        if arch == "multi":
-            heads, self.head = multi_heads(num_classes, open_classes, open_classes > 0), "x2"
-        else:
-            heads, self.head = single_head(num_classes), "x"
+        self.arch = arch
         params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
-        kw = {"layers": layers} if layers is not None else {}
-        self.plans = [TrunkPlan(params, batch, h, w, heads, dtype=dtype, train=False, **kw) for (h, w) in scales]
+        if arch == "v3":
+            from simt_amd.engine_v3 import V3Plan
+            kw = {"layers": tuple(layers)} if layers is not None else {}
+            self.plans = [V3Plan(params, batch, h, w, num_classes, open_classes, open_classes > 0, dtype=dtype, train=False, **kw)
+                          for (h, w) in scales]
+            self._fwd = [v3_low_res_forward(plan) for plan in self.plans]
+        elif arch == "vgg":
+            from simt_amd.engine_vgg import VggPlan
+            kw = {"vgg_layers": list(layers)} if layers is not None else {}
+            self.plans = [VggPlan(params, batch, h, w, num_classes + open_classes, dtype=dtype, train=False, **kw) for (h, w) in scales]
+            self.head = "x"
+        else:
+            if arch == "multi":
+                heads, self.head = multi_heads(num_classes, open_classes, open_classes > 0), "x2"
+            else:
+                heads, self.head = single_head(num_classes), "x"
+            kw = {"layers": layers} if layers is not None else {}
+            self.plans = [TrunkPlan(params, batch, h, w, heads, dtype=dtype, train=False, **kw) for (h, w) in scales]
         self.scales = scales
         self.B, (self.H, self.W) = batch, tuple(label_hw)
         self.labels = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.uint8)
         self.counts = torch.zeros(num_classes + 1, device=self.dev, dtype=torch.int64)
-        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode == "confidence" else None
+        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode == "confidence" and arch != "v3" else None
 
     def label(self, *images):
         """images: one [B,3,h,w] fp32 tensor (BGR - mean) per scale.  Returns the label map uint8 [B,H,W] (device, reused by the next
         call) and adds its class counts to `counts`."""
         if len(images) != len(self.plans):
             raise ValueError(f"{len(self.plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+        mode = 1 if self.mode == "confidence" else 0
+        if self.arch == "v3":
+            outs = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
+            (la, ha, wa, lda, hia, wia) = outs[0]
+            lb, hb, wb, ldb, hib, wib = (outs[1] if len(outs) > 1 else (None, 0, 0, 0, 0, 0))
+            L.call("simt_pseudo_label2_u8", ops._p(la), ha, wa, lda, hia, wia, ops._p(lb), hb, wb, ldb, hib, wib, self.B, self.H, self.W,
+                   self.C, mode, self.threshold, ops._p(self.labels), ops._p(self.counts), ops.stream_ptr())
+            return self.labels
         outs = [plan.forward(img.to(self.dev))[self.head] for plan, img in zip(self.plans, images)]
         if self.mode == "confidence":
             o = outs[0]
             B, h, w, ld = o.shape
             ops.softmax_rows(o, ld, self.prob, ld, B * h * w, self.C)
-            outs, mode = [self.prob], 1
-        else:
-            mode = 0
+            outs = [self.prob]
         la = outs[0]
         lb = outs[1] if len(outs) > 1 else None
         hb, wb, ldb = (lb.shape[1], lb.shape[2], lb.shape[3]) if lb is not None else (0, 0, 0)
@@ -257,12 +287,16 @@ def _wh(s):
 
 
 def get_arguments(argv=None):
-    p = argparse.ArgumentParser(description="Export pseudo labels (PNG + list + class prior) from a DeepLab-v2 checkpoint on MI355X")
+    from simt_amd.tools.trainV2_simt import add_v3_layers
+    p = argparse.ArgumentParser(description="Export pseudo labels (PNG + list + class prior) from a DeepLab-v2, DeepLabv3 or DeepLab-VGG16 "
+                                            "checkpoint on MI355X")
     p.add_argument("--restore-from", type=str, required=True, help="source checkpoint (the same key forms as the training tools)")
-    p.add_argument("--arch", choices=["multi", "single"], default="multi",
-                   help="multi: DeeplabMulti (head layer6, first C channels); single: Res_Deeplab of model/deeplab.py")
+    p.add_argument("--arch", choices=list(ARCHS), default="multi",
+                   help="multi: DeeplabMulti (head layer6, first C channels); single: Res_Deeplab of model/deeplab.py; "
+                        "v3: DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers); vgg: DeeplabVGG (model/deeplab_vgg.py)")
     p.add_argument("--num-classes", type=int, default=19)
-    p.add_argument("--open-classes", type=int, default=0, help="open-set classes of a SimT (multi) checkpoint; 0 for a source model")
+    p.add_argument("--open-classes", type=int, default=0,
+                   help="open-set classes of a SimT checkpoint (--arch multi, v3 or vgg); 0 for a source model")
     p.add_argument("--data-dir", type=str, default="")
     p.add_argument("--data-list", type=str, default="../dataset/cityscapes_list/train.txt")
     p.add_argument("--set", type=str, default="train")
@@ -280,22 +314,57 @@ def get_arguments(argv=None):
                    help="arithmetic of the forwards: fp32 like the reference; bf16 is a labelled opt-in")
     p.add_argument("--num-workers", type=int, default=8, help=f"decode / encode threads each (capped at {MAX_WORKERS})")
     p.add_argument("--gpu", type=int, default=0)
-    return p.parse_args(argv)
+    add_v3_layers(p)
+    args = p.parse_args(argv)
+    if args.arch == "single" and args.open_classes:
+        p.error("--arch single: Res_Deeplab has no open-set classes (--open-classes must be 0)")
+    return args
+
+
+SINGLE_MODELS = {"v3": "DeepLabv3", "vgg": "DeepLabVGG"}     # --arch -> the trainV2_simt --model name
+HEAD_PREFIX = {"v3": "conv.", "vgg": "classifier."}         # the classifier producing the first C channels
+
+
+def restore_single_model(arch, path, num_classes, open_classes, v3_layers):
+    """The state of DeepLabv3 / DeeplabVGG (--arch v3 | vgg; the SimT model with open_classes > 0) with `path` loaded the way the warm-up
+    stage loads it (trainV1_warmup.restore_single: the module's keys, or a torchvision ImageNet file mapped onto the trunk).  Raises
+    FileNotFoundError / RuntimeError (no file, no tensor matched) and SystemExit when no classifier tensor was restored: labels from a
+    head left at its init would look like results.  -> (state, tensors restored, layout name)."""
+    from simt_amd.tools.trainV1_warmup import restore_single
+    from simt_amd.tools.trainV2_simt import single_model_state, single_model_states
+    name = SINGLE_MODELS[arch]
+    if open_classes:
+        state, _ = single_model_states(name, num_classes, open_classes, v3_layers)
+    else:
+        state = single_model_state(name, num_classes, v3_layers)
+    init = {k: v for k, v in state.items() if k.startswith(HEAD_PREFIX[arch])}
+    n, layout = restore_single(state, path, arch, required=True)
+    if all(state[k] is v for k, v in init.items()):
+        shapes = ", ".join(f"{k} {tuple(v.shape)}" for k, v in init.items() if k.endswith("weight"))
+        raise SystemExit(f"--restore-from {path!r} ({layout} layout): no classifier tensor ({HEAD_PREFIX[arch]}*) matched {shapes}; "
+                         f"check --num-classes {num_classes} / --open-classes {open_classes}"
+                         + (f" / --v3-layers {' '.join(map(str, v3_layers))}" if arch == "v3" else "")
+                         + " (an ImageNet trunk file has no classifier to export labels from)")
+    return state, n, layout
 
 
 def main(argv=None):
     args = get_arguments(argv)
     from simt_amd import model_spec as ms
     from simt_amd.tools.trainV2_simt import restore
+    C, K = args.num_classes, args.open_classes
+    if args.arch in SINGLE_MODELS:                                   # checked before the GPU is touched
+        state, n, _ = restore_single_model(args.arch, args.restore_from, C, K, tuple(args.v3_layers))
     if not torch.cuda.is_available():
         raise SystemExit("make_pseudo_labels needs a GPU: the forward and the label kernel have no CPU fallback")
     dev = torch.device("cuda", args.gpu)
     torch.cuda.set_device(dev)
-    C, K = args.num_classes, args.open_classes
-    single = args.arch == "single"
-    shapes = ms.state_shapes(C, single_head=True) if single else ms.state_shapes(C, K, K > 0)
-    state = ms.reference_init(shapes)
-    n = restore(state, args.restore_from, strip_prefix=6, required=True)
+    if args.arch not in SINGLE_MODELS:
+        single = args.arch == "single"
+        shapes = ms.state_shapes(C, single_head=True) if single else ms.state_shapes(C, K, K > 0)
+        state = ms.reference_init(shapes)
+        n = restore(state, args.restore_from, strip_prefix=6, required=True)
+    layers = tuple(args.v3_layers) if args.arch == "v3" else None
     sizes = args.input_size or [(1024, 512), (1280, 640)]
     dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     list_out = args.list_out or f"{args.out_name}.lst"
@@ -306,7 +375,7 @@ def main(argv=None):
     export(state, args.data_dir, args.data_list, args.out_name, list_out, set_name=args.set, save_color=args.save_color,
            devkit_dir=args.devkit_dir, workers=args.num_workers, class_dist_out=args.class_dist_out, num_classes=C, open_classes=K,
            arch=args.arch, scales=[(h, w) for (w, h) in sizes], label_hw=(args.label_size[1], args.label_size[0]), mode=mode,
-           threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev)
+           threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev, layers=layers)
 
 
 if __name__ == "__main__":
