@@ -477,6 +477,29 @@ int simt_image_to_input(const unsigned char* rgb, float* x, int N, int H, int W,
 int simt_label_nearest(const unsigned char* src, long long* dst, int N, int H, int W, int Ho, int Wo, const int* ytab,
                        const int* xtab, int flip_x, simt_stream_t stream);
 
+/* ---- device-resident dataset cache (simt_amd/data/cache.py; csrc/dataset_cache.hip) -------------------------------------
+ * The resized frame is uint8 (Pillow's resize returns uint8), so it can be kept in HBM exactly: image slot [h][w][3] u8 RGB
+ * (what simt_resample_u8 writes), label slot [h][w] u8.
+ * simt_label_nearest_u8: dst[n][y][x] = src[n][ytab[y]][xtab[x]] -- simt_label_nearest with a uint8 destination and no flip.
+ * simt_cache_gather: one launch per batch.  For item b < B: x[b][c][y][x'] = img[b][y][x'][mirror[b] ? c : 2 - c] - mean[c]
+ * (simt_image_to_input, rgb_order = mirror[b]) and lab_out[b][y][x'] = (int64) lab[b][y][mirror[b] ? w-1-x' : x']
+ * (simt_label_nearest's flip_x), bit for bit.  Slots are given by pointer (any order, any slab, repeats allowed), each 16-byte
+ * aligned like x and lab_out; lab_out NULL: images only (lab[] is not read).  The descriptor is read on the host during the call
+ * and travels as kernel arguments: nothing is copied to the device and nothing synchronises.  Any h, w; B <= SIMT_GATHER_MAX. */
+#define SIMT_GATHER_MAX 64
+typedef struct {
+  const unsigned char* img[SIMT_GATHER_MAX];
+  const unsigned char* lab[SIMT_GATHER_MAX];
+  unsigned char mirror[SIMT_GATHER_MAX];
+  float* x;              /* [B][3][h][w] fp32 */
+  long long* lab_out;    /* [B][h][w] int64, or NULL */
+  int32_t B, h, w;
+  float mean[3];
+} simt_gather_desc;
+int simt_label_nearest_u8(const unsigned char* src, unsigned char* dst, int N, int H, int W, int Ho, int Wo, const int* ytab,
+                          const int* xtab, simt_stream_t stream);
+int simt_cache_gather(const simt_gather_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

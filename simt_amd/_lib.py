@@ -103,6 +103,15 @@ class SgdDesc(C.Structure):
                 ("momentum", f32), ("dampening", f32), ("first_step", i32), ("skip_if", c_p)]
 
 
+GATHER_MAX = 64          # include/simt_hip.h SIMT_GATHER_MAX
+
+
+class GatherDesc(C.Structure):
+    """simt_gather_desc (include/simt_hip.h): one batch of dataset-cache slots -> network input."""
+    _fields_ = [("img", c_p * GATHER_MAX), ("lab", c_p * GATHER_MAX), ("mirror", C.c_uint8 * GATHER_MAX), ("x", c_p), ("lab_out", c_p),
+                ("B", i32), ("h", i32), ("w", i32), ("mean", f32 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -186,6 +195,8 @@ SIGNATURES = {
     "simt_resample_u8": (_I, [c_p, c_p, _I, _I, _I, _I, _I, _I, c_p, c_p, _I, c_p]),
     "simt_image_to_input": (_I, [c_p, c_p, _I, _I, _I, f32, f32, f32, _I, c_p]),
     "simt_label_nearest": (_I, [c_p, c_p, _I, _I, _I, _I, _I, c_p, c_p, _I, c_p]),
+    "simt_label_nearest_u8": (_I, [c_p, c_p, _I, _I, _I, _I, _I, c_p, c_p, c_p]),
+    "simt_cache_gather": (_I, [C.POINTER(GatherDesc), c_p]),
 }
 
 _lib = None

@@ -5,6 +5,8 @@ Reference (CPU, per item, inside 4 DataLoader workers): dataset/cityscapes_datas
 Here only file IO + PNG decoding stay on host threads; resize (Pillow-exact, csrc/input_prep.hip), BGR - mean, CHW and the label's
 int64 conversion run on the GPU, and uploads go through pinned double buffers on a copy stream so that batch i+1 crosses PCIe
 while batch i trains.  PyTorch supplies memory and streams only.
+With a DatasetCache (simt_amd/data/cache.py) the resized uint8 frames stay in HBM: an item is decoded, uploaded and resized once, and every
+batch is one gather over B cache slots (csrc/dataset_cache.hip).
 """
 import ctypes as C
 import threading
@@ -82,6 +84,57 @@ class InputPrep:
                        self.ytab.data_ptr(), self.xtab.data_ptr(), f, st)
             b0 = b1
 
+    # ---- the cached path (simt_amd/data/cache.py): misses are resized into uint8 slots, one gather per batch reads B slots ----------
+    def resize_into(self, rgb, lab, dests, stream):
+        """rgb [M,Hs,Ws,3] u8 / lab [M,Hs,Ws] u8 | None on the device (M <= B decoded misses); dests[m] = (image u8 [h*w*3] view,
+        label u8 [h*w] view | None): where item m's resized frame goes (a cache slot or a transient one).  Destinations that lie
+        back to back share a launch: a batch of misses whose new slots are consecutive (the usual case) is resized with N = M."""
+        M = len(dests)
+        assert 0 < M <= self.B and tuple(rgb.shape) == (M, self.Hs, self.Ws, 3) and rgb.is_contiguous()
+        runs, m0 = [], 0
+        for m in range(1, M + 1):
+            if m == M or dests[m][0].data_ptr() != dests[m - 1][0].data_ptr() + self.h * self.w * 3 or (
+                    lab is not None and dests[m][1].data_ptr() != dests[m - 1][1].data_ptr() + self.h * self.w):
+                runs.append((m0, m - m0))
+                m0 = m
+        if self.need_x and self.need_y:
+            L.call("simt_resample_u8", rgb.data_ptr(), self.tmp_x.data_ptr(), M, self.Hs, self.Ws, 3, self.w, 1,
+                   self.bx.data_ptr(), self.cx.data_ptr(), self.kx, stream)
+        for m0, n in runs:
+            dst = dests[m0][0].data_ptr()
+            if self.need_y:
+                src = self.tmp_x[m0] if self.need_x else rgb[m0]
+                L.call("simt_resample_u8", src.data_ptr(), dst, n, self.Hs, self.w, 3, self.h, 0,
+                       self.by.data_ptr(), self.cy.data_ptr(), self.ky, stream)
+            elif self.need_x:
+                L.call("simt_resample_u8", rgb[m0].data_ptr(), dst, n, self.Hs, self.Ws, 3, self.w, 1,
+                       self.bx.data_ptr(), self.cx.data_ptr(), self.kx, stream)
+            else:                                       # the files already have the crop's size
+                for m in range(m0, m0 + n):
+                    dests[m][0].copy_(rgb[m].reshape(-1), non_blocking=True)
+            if lab is not None:
+                L.call("simt_label_nearest_u8", lab[m0].data_ptr(), dests[m0][1].data_ptr(), n, self.Hs, self.Ws, self.h, self.w,
+                       self.ytab.data_ptr(), self.xtab.data_ptr(), stream)
+
+    def gather(self, img_ptrs, lab_ptrs, mirror, x_out, lab_out, stream):
+        """One simt_cache_gather per batch (per SIMT_GATHER_MAX items): slot pointers + per-item mirror flags -> x_out [B,3,h,w] f32,
+        lab_out [B,h,w] i64 | None.  Pointers and flags travel as kernel arguments: no copy, no synchronisation."""
+        assert x_out.dtype == torch.float32 and tuple(x_out.shape) == (self.B, 3, self.h, self.w) and x_out.is_contiguous()
+        assert lab_out is None or (lab_out.dtype == torch.int64 and tuple(lab_out.shape) == (self.B, self.h, self.w) and lab_out.is_contiguous())
+        flags = [bool(m) for m in mirror] if isinstance(mirror, (list, tuple, np.ndarray)) else [bool(mirror)] * self.B
+        assert len(flags) == self.B == len(img_ptrs)
+        for b0 in range(0, self.B, L.GATHER_MAX):
+            n = min(L.GATHER_MAX, self.B - b0)
+            d = L.GatherDesc()
+            for k in range(n):
+                d.img[k] = img_ptrs[b0 + k]
+                d.lab[k] = lab_ptrs[b0 + k] if lab_out is not None else None
+                d.mirror[k] = 1 if flags[b0 + k] else 0
+            d.x, d.lab_out = x_out[b0].data_ptr(), (lab_out[b0].data_ptr() if lab_out is not None else None)
+            d.B, d.h, d.w = n, self.h, self.w
+            d.mean[0], d.mean[1], d.mean[2] = self.mean
+            L.call("simt_cache_gather", C.byref(d), stream)
+
 
 class DevicePrefetcher:
     """Pinned double-buffered upload + device transform, one batch ahead of the consumer.
@@ -96,8 +149,8 @@ class DevicePrefetcher:
     that stream up to that point -- the step that consumed batch k included -- precedes the refill), and the copy stream waits for
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
-    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None):
-        self.src, self.prep, self.mirror_fn = iter(source), prep, mirror_fn
+    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None):
+        self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -113,6 +166,9 @@ class DevicePrefetcher:
                 s["lab_h"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8).pin_memory()
                 s["lab_d"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8, device=dev)
                 s["lab"] = torch.empty(B, prep.h, prep.w, dtype=torch.int64, device=dev)
+            if cache is not None:                      # transient slots for the items the cache has no room for
+                s["sp_img"] = torch.empty(B * cache.img_stride, dtype=torch.uint8, device=dev)
+                s["sp_lab"] = torch.empty(B * cache.lab_stride, dtype=torch.uint8, device=dev) if prep.with_label else None
             self.slots.append(s)
         self.head = 0          # next slot to hand out
         self.filled = 0
@@ -136,6 +192,8 @@ class DevicePrefetcher:
         s = self.slots[i]
         if s.get("used"):
             s["ready"].synchronize()           # the previous upload out of this slot's pinned buffers has completed
+        if self.cache is not None:
+            return self._fill_cached(s, rgb, lab, meta)
         rgb = self._host(rgb)
         if not rgb.is_pinned():
             s["rgb_h"].copy_(rgb)
@@ -157,6 +215,46 @@ class DevicePrefetcher:
                           mirror=mirror, stream=cs.cuda_stream)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
+        self.filled += 1
+
+    def _fill_cached(self, s, rgb, lab, meta):
+        """With a cache the source yields only the batch's MISSES: rgb [M,Hs,Ws,3] (None when M = 0), lab likewise, and
+        meta = (meta, plan) with plan[b] = (cache slot | None, index into the misses | None) per item of the batch.  Upload the
+        misses, resize them straight into their slots (an item the cache has no room for: into this prefetcher slot's transient
+        ones), then ONE gather over the batch's B slots.  Slot write and gather are both on the copy stream: no other ordering edge."""
+        meta, plan = meta
+        prep, cache, cs = self.prep, self.cache, self.copy_stream
+        has_lab = prep.with_label
+        M = 0 if rgb is None else len(rgb)
+        if M:
+            s["rgb_h"][:M].copy_(self._host(rgb))
+            if has_lab:
+                s["lab_h"][:M].copy_(self._host(lab))
+        img_ptrs, lab_ptrs, dests, spilled = [], [], [None] * M, 0
+        for slot, m in plan:
+            if slot is not None:
+                iv, lv = cache.img_view(slot), (cache.lab_view(slot) if has_lab else None)
+            else:
+                o = spilled * cache.img_stride
+                iv = s["sp_img"][o:o + cache.img_bytes]
+                lv = s["sp_lab"][spilled * cache.lab_stride:spilled * cache.lab_stride + cache.lab_bytes] if has_lab else None
+                spilled += 1
+            if m is not None:
+                dests[m] = (iv, lv)
+            img_ptrs.append(iv.data_ptr())
+            lab_ptrs.append(lv.data_ptr() if has_lab else None)
+        if s["free"] is not None:
+            cs.wait_event(s["free"])
+        with torch.cuda.stream(cs):
+            if M:
+                s["rgb_d"][:M].copy_(s["rgb_h"][:M], non_blocking=True)
+                if has_lab:
+                    s["lab_d"][:M].copy_(s["lab_h"][:M], non_blocking=True)
+                prep.resize_into(s["rgb_d"][:M], s["lab_d"][:M] if has_lab else None, dests, cs.cuda_stream)
+            mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
+            prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+            s["ready"].record(cs)
+        s["meta"], s["has_lab"], s["used"] = meta, has_lab, True
         self.filled += 1
 
     def __iter__(self):
@@ -194,14 +292,22 @@ class GpuLoader:
     `num_workers` host threads read + decode PNGs (Pillow releases the GIL while decoding), batches of decoded frames are uploaded
     and transformed by DevicePrefetcher.  Yields (images f32 [B,3,h,w], labels i64 [B,h,w] | None, sizes, names) like the
     reference's batches (`images, labels, _, _ = batch`), already on the device.  Incomplete last batches are dropped (the
-    reference repeats the list to max_iters, so it never sees one)."""
+    reference repeats the list to max_iters, so it never sees one).
+
+    cache: a simt_amd.data.cache.DatasetCache for the dataset's crop, or None.  With one, only an item's first sighting is decoded,
+    uploaded and resized (into its cache slot); every batch is then one gather over B slots.  Order, sharding, the dropped batch and
+    the mirror draws are those of the uncached loader: the batches are bit-identical.  on_epoch(epoch, hits, misses, cache bytes) is
+    called when an epoch's last batch has been planned (the prefetcher runs a few batches ahead of the consumer)."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
-                 hold=1):
+                 hold=1, cache=None, on_epoch=None):
         self.ds, self.B, self.shuffle, self.workers = dataset, batch_size, shuffle, max(1, num_workers)
         self.hold = hold            # batches the consumer keeps at once (= --iter-size): see DevicePrefetcher
         self.dev, self.seed, self.rank, self.world, self.epochs = torch.device(device), seed, rank, world, epochs
         self._prep = None
+        self.cache, self.on_epoch = cache, on_epoch
+        if cache is not None:
+            assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
         self._rng = np.random.default_rng(seed + 7919 * rank)
         self._lock = threading.Lock()
 
@@ -231,14 +337,59 @@ class GpuLoader:
                     yield rgb, lab, (sizes, [it[2] for it in items])
                 epoch += 1
 
+    def _host_batches_cached(self):
+        """_host_batches with a cache: same epochs, order and batches, but only the misses are decoded.  Yields (rgb of the misses
+        [M,Hs,Ws,3] | None, labels likewise, ((sizes, names), plan)); plan[b] = (cache slot | None, index into the misses | None).
+        A slot is reserved when the item's decode is submitted, so a later sighting -- in the same batch, or in one of the batches
+        planned ahead -- is a hit; batches reach the copy stream in this order, so the slot's write precedes every gather from it."""
+        cache, ds = self.cache, self.ds
+        epoch = 0
+
+        def plan(pool, ids):
+            out = []
+            for i in ids:
+                key = ds.cache_key(i)
+                slot = cache.lookup(key)
+                if slot is not None:
+                    cache.hits += 1
+                    out.append((slot, None, i))
+                else:
+                    cache.misses += 1
+                    out.append((cache.reserve(key), pool.submit(ds.decode, i), i))
+            return out
+
+        with ThreadPoolExecutor(self.workers) as pool:
+            while self.epochs is None or epoch < self.epochs:
+                idx = self._order(epoch)
+                nb = len(idx) // self.B
+                h0, m0 = cache.hits, cache.misses
+                pending = [plan(pool, idx[b * self.B:(b + 1) * self.B]) for b in range(min(2, nb))]
+                for b in range(nb):
+                    entries = pending.pop(0)
+                    if b + 2 < nb:
+                        pending.append(plan(pool, idx[(b + 2) * self.B:(b + 3) * self.B]))
+                    items = [fut.result() for (_slot, fut, _i) in entries if fut is not None]
+                    rgb = np.stack([it[0] for it in items]) if items else None
+                    lab = np.stack([it[1] for it in items]) if items and items[0][1] is not None else None
+                    sizes = np.stack([np.array([ds.crop_size[1], ds.crop_size[0], 3]) for _ in entries])
+                    m, where = 0, []
+                    for slot, fut, _i in entries:
+                        where.append((slot, m if fut is not None else None))
+                        m += fut is not None
+                    yield rgb, lab, ((sizes, [ds.files[i]["name"] for (_s, _f, i) in entries]), where)
+                if self.on_epoch is not None:
+                    self.on_epoch(epoch, cache.hits - h0, cache.misses - m0, cache.bytes)
+                epoch += 1
+
     def __iter__(self):
         first = None
-        gen = self._host_batches()
+        gen = self._host_batches() if self.cache is None else self._host_batches_cached()
         try:
             first = next(gen)
         except StopIteration:
             return iter(())
         Hs, Ws = first[0].shape[1:3]
+        assert self.cache is None or self.cache.with_label or first[1] is None, "the dataset has labels, the cache no label slab"
         self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None)
 
         def chain():
@@ -246,5 +397,5 @@ class GpuLoader:
             yield from gen
         # `flip = np.random.choice(2) * 2 - 1` per item (cityscapes_dataset.py:109)
         mirror_fn = (lambda n: (self._rng.integers(0, 2, n) == 0).tolist()) if getattr(self.ds, "is_mirror", False) else None
-        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold)
+        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

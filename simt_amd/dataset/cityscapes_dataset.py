@@ -28,6 +28,11 @@ class _Base:
     def __len__(self):
         return len(self.files)
 
+    def cache_key(self, index):
+        """What identifies an item's decoded content: its file paths (max_iters repeats the list; the repeats are one item)."""
+        f = self.files[index]
+        return (f["img"], f.get("label"))
+
     @staticmethod
     def _open_rgb(path):
         from PIL import Image

@@ -4,6 +4,7 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 `evaluate_warmup` + best-mIoU snapshot rotation of :241-256 keeps the reference's file names; data: `cityscapesPseudo` through the device input pipeline (simt_amd/data/pipeline.py) or, with
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
+--cache-dataset device [--cache-gb G] as in trainV2_simt (both tools share its `batches`).
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -22,7 +23,8 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
-from simt_amd.tools.trainV2_simt import ENGINE_MODEL, MODELS, SnapshotKeeper, add_v3_layers, batches, restore, save_atomic
+from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, SnapshotKeeper, add_cache_args, add_v3_layers, batches, restore,
+                                          save_atomic)
 
 
 def get_arguments(argv=None):
@@ -75,6 +77,7 @@ def get_arguments(argv=None):
     p.add_argument("--gt-dir-val", type=str, default="", help="directory of *_gtFine_labelIds.png (evaluate_cityscapes.py:140)")
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     add_v3_layers(p)
+    add_cache_args(p)
     return p.parse_args(argv)
 
 

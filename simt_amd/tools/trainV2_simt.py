@@ -14,7 +14,9 @@ without --synthetic is an error (a run that silently trains on noise would still
 Every --save-pred-every iterations: evaluate_simt on the validation set (--data-dir-val ...) and the best-mIoU snapshot rotation of
 trainV2_simt.py:452-464.  Additions over the reference (all optional): --synthetic, --compute-dtype, --eval-dtype (fp32 like the
 reference unless bf16 is asked for), --print-every, --data-dir-val,
---data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels).
+--data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels),
+--cache-dataset device [--cache-gb G]: the resized uint8 training set stays in HBM after the first epoch (simt_amd/data/cache.py; default off:
+the batches are the same, bit for bit, only PNG decoding after epoch one is saved).
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -88,12 +90,21 @@ def get_arguments(argv=None):
     p.add_argument("--class-dist", type=str, default=None,
                    help="class prior .npy of the pseudo labels (make_pseudo_labels writes it); default: ClassDist_bapa.npy")
     add_v3_layers(p)
+    add_cache_args(p)
     return p.parse_args(argv)
 
 
 MODELS = ("DeepLab", "DeepLabv3", "DeepLabVGG")
 ENGINE_MODEL = {"DeepLab": "v2", "DeepLabv3": "v3", "DeepLabVGG": "vgg"}      # --model -> Evaluator / SimTSingleTrainer model name
 RESTORE_LAST = {"DeepLab": ("layer5", "layer6"), "DeepLabv3": ("conv.", "conv_1."), "DeepLabVGG": ("classifier.",)}   # --not-restore-last
+
+
+def add_cache_args(p):
+    p.add_argument("--cache-dataset", choices=["off", "device"], default="off",
+                   help="device: keep every training item's resized uint8 frame in HBM after its first decode (simt_amd/data/cache.py); "
+                        "PNGs are decoded in the first epoch only.  Ignored with --synthetic")
+    p.add_argument("--cache-gb", type=float, default=None,
+                   help="cache budget in GB (1e9 bytes); default: what holds the whole list at the run's crop (4*h*w bytes per item)")
 
 
 def add_v3_layers(p):
@@ -237,8 +248,20 @@ def batches(args, B, H, W, cd, rank, world, dev):
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN)
+    cache, on_epoch = None, None
+    if getattr(args, "cache_dataset", "off") == "device":
+        from simt_amd.data.cache import DatasetCache, default_budget_bytes
+        gb = getattr(args, "cache_gb", None)
+        n_distinct = len({ds.cache_key(i) for i in range(len(ds))})
+        budget = default_budget_bytes(n_distinct, (W, H)) if gb is None else int(gb * 1e9)
+        cache = DatasetCache((W, H), with_label=True, budget_bytes=budget, device=dev)
+
+        def on_epoch(epoch, hits, misses, nbytes):
+            print(f"dataset cache: rank {rank} epoch {epoch}: {hits} hits, {misses} misses, {nbytes / 1e9:.3f} GB of {budget / 1e9:.3f} GB "
+                  f"in {len(cache)} slots", flush=True)
     loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=args.random_seed, rank=rank, world=world,
-                       hold=max(1, getattr(args, "iter_size", 1)))     # the loop keeps iter_size micro-batches alive per step
+                       hold=max(1, getattr(args, "iter_size", 1)),     # the loop keeps iter_size micro-batches alive per step
+                       cache=cache, on_epoch=on_epoch)
     return ((img, lab) for (img, lab, _sizes, _names) in loader)
 
 
