@@ -287,6 +287,29 @@ class DevicePrefetcher:
         return all(((self.head + k) % n) != j for k in range(self.filled))
 
 
+def loader_position(n_items, batch_size, rank, world, start_batch):
+    """Where batch number `start_batch` (counted from the loader's first batch, over every epoch) lies: -> (epoch, batch within the
+    epoch, batches per epoch).  A rank's shard is every `world`-th item of the epoch's order from `rank` on; its incomplete last batch is
+    dropped.  Pure arithmetic (GpuLoader(start_batch=...), tests/test_resume_cpu.py)."""
+    shard = len(range(rank, n_items, world))
+    per_epoch = shard // batch_size
+    if start_batch < 0:
+        raise ValueError(f"start_batch {start_batch} is negative")
+    if per_epoch == 0:
+        if start_batch:
+            raise ValueError(f"start_batch {start_batch}: the shard of rank {rank} ({shard} items) holds no batch of {batch_size}")
+        return 0, 0, 0
+    return start_batch // per_epoch, start_batch % per_epoch, per_epoch
+
+
+def skip_mirror_draws(rng, batch_size, n_batches):
+    """Advance the loader's mirror generator by the draws `n_batches` batches make: one `integers(0, 2, batch_size)` per batch, in batch
+    order (GpuLoader.__iter__'s mirror_fn)."""
+    for _ in range(n_batches):
+        rng.integers(0, 2, batch_size)
+    return rng
+
+
 class GpuLoader:
     """DataLoader(dataset, batch_size, shuffle, num_workers, pin_memory=True) of tools/trainV2_simt.py:287-294, feeding the GPU:
     `num_workers` host threads read + decode PNGs (Pillow releases the GIL while decoding), batches of decoded frames are uploaded
@@ -297,10 +320,14 @@ class GpuLoader:
     cache: a simt_amd.data.cache.DatasetCache for the dataset's crop, or None.  With one, only an item's first sighting is decoded,
     uploaded and resized (into its cache slot); every batch is then one gather over B slots.  Order, sharding, the dropped batch and
     the mirror draws are those of the uncached loader: the batches are bit-identical.  on_epoch(epoch, hits, misses, cache bytes) is
-    called when an epoch's last batch has been planned (the prefetcher runs a few batches ahead of the consumer)."""
+    called when an epoch's last batch has been planned (the prefetcher runs a few batches ahead of the consumer).
+
+    start_batch = n: the loader yields exactly what the default loader yields from its n-th batch on (a resumed run): it starts inside
+    epoch n // batches-per-epoch of `_order`, the mirror generator has made the n skipped batches' draws, and no skipped item is
+    decoded.  A cache starts empty and refills; the batches are the same."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
-                 hold=1, cache=None, on_epoch=None):
+                 hold=1, cache=None, on_epoch=None, start_batch=0):
         self.ds, self.B, self.shuffle, self.workers = dataset, batch_size, shuffle, max(1, num_workers)
         self.hold = hold            # batches the consumer keeps at once (= --iter-size): see DevicePrefetcher
         self.dev, self.seed, self.rank, self.world, self.epochs = torch.device(device), seed, rank, world, epochs
@@ -310,6 +337,10 @@ class GpuLoader:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
         self._rng = np.random.default_rng(seed + 7919 * rank)
         self._lock = threading.Lock()
+        self.start_batch = int(start_batch)
+        self._epoch0, self._batch0, _ = loader_position(len(dataset), batch_size, rank, world, self.start_batch)
+        if self.start_batch and getattr(dataset, "is_mirror", False):
+            skip_mirror_draws(self._rng, batch_size, self.start_batch)
 
     def _order(self, epoch):
         n = len(self.ds)
@@ -321,13 +352,13 @@ class GpuLoader:
         return idx[self.rank::self.world]               # data parallel: disjoint strided shards of one global order
 
     def _host_batches(self):
-        epoch = 0
+        epoch, b0 = self._epoch0, self._batch0         # (start_batch: the first epoch begins at its batch b0)
         with ThreadPoolExecutor(self.workers) as pool:
             while self.epochs is None or epoch < self.epochs:
                 idx = self._order(epoch)
                 nb = len(idx) // self.B
-                pending = [pool.map(self.ds.decode, idx[b * self.B:(b + 1) * self.B]) for b in range(min(2, nb))]
-                for b in range(nb):
+                pending = [pool.map(self.ds.decode, idx[b * self.B:(b + 1) * self.B]) for b in range(b0, min(b0 + 2, nb))]
+                for b in range(b0, nb):
                     items = list(pending.pop(0))
                     if b + 2 < nb:
                         pending.append(pool.map(self.ds.decode, idx[(b + 2) * self.B:(b + 3) * self.B]))
@@ -335,7 +366,7 @@ class GpuLoader:
                     lab = np.stack([it[1] for it in items]) if items[0][1] is not None else None
                     sizes = np.stack([np.array([self.ds.crop_size[1], self.ds.crop_size[0], 3]) for _ in items])
                     yield rgb, lab, (sizes, [it[2] for it in items])
-                epoch += 1
+                epoch, b0 = epoch + 1, 0
 
     def _host_batches_cached(self):
         """_host_batches with a cache: same epochs, order and batches, but only the misses are decoded.  Yields (rgb of the misses
@@ -343,7 +374,7 @@ class GpuLoader:
         A slot is reserved when the item's decode is submitted, so a later sighting -- in the same batch, or in one of the batches
         planned ahead -- is a hit; batches reach the copy stream in this order, so the slot's write precedes every gather from it."""
         cache, ds = self.cache, self.ds
-        epoch = 0
+        epoch, b0 = self._epoch0, self._batch0
 
         def plan(pool, ids):
             out = []
@@ -363,8 +394,8 @@ class GpuLoader:
                 idx = self._order(epoch)
                 nb = len(idx) // self.B
                 h0, m0 = cache.hits, cache.misses
-                pending = [plan(pool, idx[b * self.B:(b + 1) * self.B]) for b in range(min(2, nb))]
-                for b in range(nb):
+                pending = [plan(pool, idx[b * self.B:(b + 1) * self.B]) for b in range(b0, min(b0 + 2, nb))]
+                for b in range(b0, nb):
                     entries = pending.pop(0)
                     if b + 2 < nb:
                         pending.append(plan(pool, idx[(b + 2) * self.B:(b + 3) * self.B]))
@@ -379,7 +410,7 @@ class GpuLoader:
                     yield rgb, lab, ((sizes, [ds.files[i]["name"] for (_s, _f, i) in entries]), where)
                 if self.on_epoch is not None:
                     self.on_epoch(epoch, cache.hits - h0, cache.misses - m0, cache.bytes)
-                epoch += 1
+                epoch, b0 = epoch + 1, 0
 
     def __iter__(self):
         first = None

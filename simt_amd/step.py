@@ -25,6 +25,7 @@ from . import _lib as L
 from . import ops
 from . import trace
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
+from .train_state import TrainStateMixin, state_sha256
 
 
 class Hyper:
@@ -63,7 +64,7 @@ def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer
     return g0, g1
 
 
-class SimTTrainer:
+class SimTTrainer(TrainStateMixin):
     def __init__(self, state, fixed_state, ntm1, ntm2, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
                  openset=True, process_group=None, w_init=None, layers=None):
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
@@ -75,6 +76,7 @@ class SimTTrainer:
         self.params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
         self.fixed_params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone()
                              for k, v in fixed_state.items()}
+        self.frozen_sha256 = state_sha256(self.fixed_params)      # a train state is refused beside another frozen model (train_state.py)
         kw = {"layers": layers} if layers is not None else {}
         self.plan = TrunkPlan(self.params, B, H, W, multi_heads(Cn, K, openset), dtype=dtype, train=True,
                               grads_from_layer=3 if getattr(hp, "skip_unapplied_grads", False) else 0,
@@ -389,7 +391,7 @@ class SimTTrainer:
         sd = {}
         for k, v in self.params.items():
             sd[k] = (v.detach().cpu() if not k.endswith("num_batches_tracked") else
-                     torch.tensor(int(v.item()) + self.it_done * self.hp.iter_size, dtype=torch.long))
+                     torch.tensor(int(v.item()) + self._nbt_steps(k), dtype=torch.long))
         return sd
 
     def timed_lists(self):
@@ -414,7 +416,7 @@ class SimTTrainer:
         return dict(zip(keys, v))
 
 
-class WarmupTrainer:
+class WarmupTrainer(TrainStateMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
@@ -514,7 +516,7 @@ class WarmupTrainer:
         sd = {}
         for k, v in self.params.items():
             sd[k] = (v.detach().cpu() if not k.endswith("num_batches_tracked") else
-                     torch.tensor(int(v.item()) + self.it_done * self.hp.iter_size, dtype=torch.long))
+                     torch.tensor(int(v.item()) + self._nbt_steps(k), dtype=torch.long))
         return sd
 
     def losses(self):

@@ -27,9 +27,10 @@ from . import _lib as L
 from . import ops
 from .engine import LaunchList, side_stream
 from .step import lr_poly
+from .train_state import TrainStateMixin, state_sha256
 
 
-class SimTSingleTrainer:
+class SimTSingleTrainer(TrainStateMixin):
     def __init__(self, model, state, fixed_state, ntm, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
                  process_group=None, arch=None):
         """model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
@@ -45,6 +46,7 @@ class SimTSingleTrainer:
         f32 = torch.float32
         conv = lambda d: {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in d.items()}
         self.params, self.fixed_params = conv(state), conv(fixed_state)
+        self.frozen_sha256 = state_sha256(self.fixed_params)      # a train state is refused beside another frozen model (train_state.py)
         arch = dict(arch or {})
         if model == "v3":
             from .engine_v3 import V3Plan
@@ -230,11 +232,10 @@ class SimTSingleTrainer:
         for `num_batches_tracked`).  Trained tensors and running statistics are the current ones; keys the plan never touches (DeepLabv3's
         layer4 / fc, DeeplabVGG's classifier branches 2 and 3) come back as given.  `num_batches_tracked` grows by the number of steps
         taken for the BatchNorms that run (nn.BatchNorm2d bumps it once per train-mode forward; DeepLabv3._dead_bns: not layer4's)."""
-        live = set(self.plan.bn) if self.model == "v3" else set()
         sd = {}
         for k, v in self.params.items():
             if k.endswith(".num_batches_tracked"):
-                sd[k] = torch.tensor(int(v.item()) + (self.it_done if k[:-len(".num_batches_tracked")] in live else 0), dtype=torch.long)
+                sd[k] = torch.tensor(int(v.item()) + self._nbt_steps(k), dtype=torch.long)
             else:
                 sd[k] = v.detach().cpu()
         return sd
@@ -255,7 +256,7 @@ class SimTSingleTrainer:
                 "vol_ok": v[9]}
 
 
-class WarmupSingleTrainer:
+class WarmupSingleTrainer(TrainStateMixin):
     """The warm-up stage (tools/trainV1_warmup.py:156-256) over a ONE-OUTPUT model: DeepLabv3(nc) or DeeplabVGG(nc), trained by cross-entropy
     on the pseudo labels, loss = CE(interp_target(model(x)), label) with ignore_index 255 (:212-231 without the auxiliary head; for
     DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
@@ -378,12 +379,10 @@ class WarmupSingleTrainer:
     def state_dict(self):
         """Every key the trainer was given, fp32 (int64 for `num_batches_tracked`); loads strict=True into DeepLabv3(nc) / DeeplabVGG(nc).
         `num_batches_tracked` grows by steps x iter_size for the BatchNorms that run (see SimTSingleTrainer.state_dict)."""
-        live = set(self.plan.bn) if self.model == "v3" else set()
-        n = self.it_done * self.hp.iter_size
         sd = {}
         for k, v in self.params.items():
             if k.endswith(".num_batches_tracked"):
-                sd[k] = torch.tensor(int(v.item()) + (n if k[:-len(".num_batches_tracked")] in live else 0), dtype=torch.long)
+                sd[k] = torch.tensor(int(v.item()) + self._nbt_steps(k), dtype=torch.long)
             else:
                 sd[k] = v.detach().cpu()
         return sd

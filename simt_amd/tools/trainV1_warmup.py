@@ -5,6 +5,7 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
 --cache-dataset device [--cache-gb G] as in trainV2_simt (both tools share its `batches`).
+--train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -23,8 +24,8 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
-from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, SnapshotKeeper, add_cache_args, add_v3_layers, batches, restore,
-                                          save_atomic)
+from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, SnapshotKeeper, TrainStateFile, add_cache_args, add_train_state_args,
+                                          add_v3_layers, batches, restore, save_atomic, shutdown)
 
 
 def get_arguments(argv=None):
@@ -78,6 +79,7 @@ def get_arguments(argv=None):
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     add_v3_layers(p)
     add_cache_args(p)
+    add_train_state_args(p)
     return p.parse_args(argv)
 
 
@@ -129,10 +131,14 @@ def main(argv=None):
     if rank == 0:
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
+    resume = TrainStateFile(args, rank, world, cd)
+    start = resume.resume(tr, keeper)
+    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
+        return shutdown(world)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     t0 = time.time()
-    for i_iter in range(args.num_steps):
+    for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
         img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
         tr.step(img, lab, i_iter)
@@ -141,11 +147,12 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
             # :241-256: evaluate_warmup on the validation set, keep only the best-mIoU snapshot `GTA5_BAPA_warmup_iter<i>_mIoU<m>.pth`
@@ -162,9 +169,8 @@ def main(argv=None):
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             # no validation set given (the reference hard-codes one, evaluate_cityscapes.py:26-28): a rolling periodic snapshot instead
             keeper.rolling(tr.state_dict(), i_iter)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        resume.after_iteration(i_iter, tr, keeper)
+    shutdown(world)
 
 
 def restore_single(state, path, model, required):
@@ -205,10 +211,14 @@ def main_single(args):
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
+    resume = TrainStateFile(args, rank, world, cd)
+    start = resume.resume(tr, keeper)
+    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
+        return shutdown(world)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     t0 = time.time()
-    for i_iter in range(args.num_steps):
+    for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
         img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
         tr.step(img, lab, i_iter)
@@ -217,11 +227,12 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
             from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
@@ -237,9 +248,8 @@ def main_single(args):
                 keeper.best(tr.state_dict(), i_iter, mIoU)
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        resume.after_iteration(i_iter, tr, keeper)
+    shutdown(world)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,12 @@ trainV2_simt.py:452-464.  Additions over the reference (all optional): --synthet
 reference unless bf16 is asked for), --print-every, --data-dir-val,
 --data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels),
 --cache-dataset device [--cache-gb G]: the resized uint8 training set stays in HBM after the first epoch (simt_amd/data/cache.py; default off:
-the batches are the same, bit for bit, only PNG decoding after epoch one is saved).
+the batches are the same, bit for bit, only PNG decoding after epoch one is saved),
+--train-state FILE [--train-state-every N]: resume from FILE if it exists and keep it current (simt_amd/train_state.py).  The snapshots hold
+the model only; FILE also holds the SGD momentum, both NTMs and W with their Adam moments, the iteration counter, the snapshot rotation's
+bookkeeping -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
+command line (with a later --num-steps-stop) continues bit for bit as if nothing had happened.  --restore-from stays the same: the frozen
+model is not in FILE, its SHA-256 is.  Without the flag the tool writes and prints what it always did.
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -33,6 +38,7 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, SimTTrainer, lr_poly
+from simt_amd.train_state import save_atomic      # (its home; the tools and their users keep importing it from here)
 
 
 def get_arguments(argv=None):
@@ -91,6 +97,7 @@ def get_arguments(argv=None):
                    help="class prior .npy of the pseudo labels (make_pseudo_labels writes it); default: ClassDist_bapa.npy")
     add_v3_layers(p)
     add_cache_args(p)
+    add_train_state_args(p)
     return p.parse_args(argv)
 
 
@@ -105,6 +112,15 @@ def add_cache_args(p):
                         "PNGs are decoded in the first epoch only.  Ignored with --synthetic")
     p.add_argument("--cache-gb", type=float, default=None,
                    help="cache budget in GB (1e9 bytes); default: what holds the whole list at the run's crop (4*h*w bytes per item)")
+
+
+def add_train_state_args(p):
+    p.add_argument("--train-state", type=str, default=None, metavar="FILE",
+                   help="resume from FILE if it exists, and keep it current (weights, momentum, NTM / W with their Adam moments, iteration, "
+                        "snapshot rotation: simt_amd/train_state.py): written at every snapshot decision (--save-pred-every) and at the stop.  "
+                        "Re-issue the same command line until the run is finished")
+    p.add_argument("--train-state-every", type=int, default=None, metavar="N",
+                   help="write --train-state every N iterations instead of at the snapshot cadence")
 
 
 def add_v3_layers(p):
@@ -198,13 +214,6 @@ def restore(state, path, not_restore_last=False, strip_prefix=0, required=False,
     return n
 
 
-def save_atomic(obj, path):
-    """torch.save to a temporary name, then os.replace: a crash or a full disk during the save leaves the previous file intact."""
-    tmp = path + ".tmp"
-    torch.save(obj, tmp)
-    os.replace(tmp, path)
-
-
 class SnapshotKeeper:
     """The snapshot rotation of trainV2_simt.py:452-464 / trainV1_warmup.py:243-256: after an evaluation keep ONE file
     `<stem><iter>_mIoU<mIoU>.pth` for the best mIoU so far; without a validation set (the reference hard-codes one) keep ONE rolling
@@ -233,12 +242,91 @@ class SnapshotKeeper:
                 os.remove(old_file)
         self.rolling_iter = i_iter
 
+    def state(self):
+        """What a resumed run needs to go on rotating: it still removes the file it supersedes."""
+        return {"best_mIoU": self.best_mIoU, "best_iter": self.best_iter, "rolling_iter": self.rolling_iter}
 
-def batches(args, B, H, W, cd, rank, world, dev):
-    """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device."""
+    def load_state(self, st):
+        self.best_mIoU, self.best_iter, self.rolling_iter = st["best_mIoU"], st["best_iter"], st["rolling_iter"]
+
+
+def run_identity(args, class_dist):
+    """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror draws, synthetic batches), the mirror
+    switch, where the data comes from (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
+    import hashlib
+    ident = {"random_seed": int(args.random_seed), "random_mirror": bool(args.random_mirror), "synthetic": bool(args.synthetic),
+             "class_dist_sha256": hashlib.sha256(np.ascontiguousarray(np.asarray(class_dist, dtype=np.float32)).tobytes()).hexdigest()}
+    if not args.synthetic and osp.isfile(args.data_list_target):
+        ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
+    return ident
+
+
+class TrainStateFile:
+    """--train-state FILE of both training tools: `resume()` / `complete()` before the loop, `after_iteration()` at its end, `write()` where it breaks.
+    Without the flag every method does nothing.  Rank 0 writes; every rank loads (rank 0's state is the state: INTEGRATION.md)."""
+
+    def __init__(self, args, rank, world, class_dist=None):
+        self.path, self.every = getattr(args, "train_state", None), getattr(args, "train_state_every", None)
+        self.run = run_identity(args, class_dist) if self.path and class_dist is not None else {}
+        self.save_pred_every, self.rank, self.world = args.save_pred_every, rank, world
+        if self.every is not None and self.every < 1:
+            raise SystemExit(f"--train-state-every {self.every}: expected a positive number of iterations")
+        if self.every is not None and not self.path:
+            raise SystemExit("--train-state-every needs --train-state FILE")
+
+    def resume(self, tr, keeper):
+        """-> the iteration the loop continues at (0: FILE does not exist yet, a fresh run)."""
+        if not self.path or not osp.exists(self.path):
+            return 0
+        from simt_amd import train_state
+        ts, ks, ls = train_state.load(self.path)
+        if ls.get("world", self.world) != self.world:
+            raise SystemExit(f"--train-state {self.path!r} was written by a run over {ls['world']} GPU(s), this one has {self.world}")
+        other = [k for k, v in self.run.items() if k in ls.get("run", {}) and ls["run"][k] != v]
+        if other:
+            raise SystemExit(f"--train-state {self.path!r} was written by a run that differs in: " +
+                             ", ".join(f"{k} (state: {ls['run'][k]!r}, this run: {self.run[k]!r})" for k in other))
+        try:
+            tr.load_training_state(ts)
+        except ValueError as e:
+            raise SystemExit(f"--train-state {self.path!r}: {e}")
+        if ks is not None:
+            keeper.load_state(ks)
+        if self.rank == 0:
+            print(f"resumed {type(tr).__name__} from {self.path} at iteration {tr.it_done}")
+        return tr.it_done
+
+    def write(self, tr, keeper):
+        if self.path and self.rank == 0:
+            from simt_amd import train_state
+            train_state.save(self.path, tr.training_state(), keeper.state(), {"world": self.world, "run": self.run})
+
+    def after_iteration(self, i_iter, tr, keeper):
+        if self.every is not None:
+            due = (i_iter + 1) % self.every == 0
+        else:
+            due = i_iter % self.save_pred_every == 0 and i_iter != 0          # the loop's snapshot decision, evaluated or not
+        if due:
+            self.write(tr, keeper)
+
+    def complete(self, start, stop, tr, snapshot_dir):
+        """A resumed run that has nothing left to do: say so and make sure the final snapshot exists."""
+        if start < stop:
+            return False
+        if self.rank == 0:
+            final = osp.join(snapshot_dir, "GTA5_" + str(stop) + ".pth")
+            print(f"the run is complete: {start} of {stop} iterations done" + ("" if osp.exists(final) else f"; writing {final}"))
+            if not osp.exists(final):
+                save_atomic(tr.state_dict(), final)
+        return True
+
+
+def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
+    """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
+    resumed run: iterations done x iter_size)."""
     if args.synthetic:
         def synth():
-            it = 0
+            it = start_batch
             while True:                                     # one global sequence of seeds, dealt round-robin to the ranks
                 yield ms.synthetic_batch(B, H, W, cd, seed=args.random_seed + it * world + rank, device=dev)
                 it += 1
@@ -261,8 +349,14 @@ def batches(args, B, H, W, cd, rank, world, dev):
                   f"in {len(cache)} slots", flush=True)
     loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=args.random_seed, rank=rank, world=world,
                        hold=max(1, getattr(args, "iter_size", 1)),     # the loop keeps iter_size micro-batches alive per step
-                       cache=cache, on_epoch=on_epoch)
+                       cache=cache, on_epoch=on_epoch, start_batch=start_batch)
     return ((img, lab) for (img, lab, _sizes, _names) in loader)
+
+
+def shutdown(world):
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
 
 def main(argv=None):
@@ -306,10 +400,14 @@ def main(argv=None):
         print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
+    resume = TrainStateFile(args, rank, world, cd)
+    start = resume.resume(tr, keeper)
+    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
+        return shutdown(world)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     t0 = time.time()
-    for i_iter in range(args.num_steps):
+    for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]           # gradient accumulation: iter_size micro-batches per step
         img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
         tr.step(img, lab, i_iter)
@@ -320,11 +418,12 @@ def main(argv=None):
                       "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
                           i_iter, args.num_steps, l["loss_p1"] + l["loss_p2"], l["loss_y1"] + l["loss_y2"], l["convex"], l["volume"],
                           l["anchor"], l["place"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                          args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))               # :438-441 (p1+p2, y1+y2)
+                          args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))               # :438-441 (p1+p2, y1+y2)
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))   # :447-450
+            resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
             # :452-464: evaluate, keep only the best-mIoU snapshot
@@ -342,9 +441,8 @@ def main(argv=None):
             # no validation set given (the reference hard-codes one, :452-464): without an evaluation there is no best-mIoU snapshot,
             # so keep a rolling periodic one -- a crash must not lose the run
             keeper.rolling(tr.state_dict(), i_iter)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        resume.after_iteration(i_iter, tr, keeper)
+    shutdown(world)
 
 
 def main_single(args):
@@ -389,10 +487,14 @@ def main_single(args):
         print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
+    resume = TrainStateFile(args, rank, world, cd)
+    start = resume.resume(tr, keeper)
+    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
+        return shutdown(world)
+    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     t0 = time.time()
-    for i_iter in range(args.num_steps):
+    for i_iter in range(start, args.num_steps):
         img, lab = next(data)
         tr.step(img, lab, i_iter)
         if i_iter % args.print_every == 0:
@@ -402,11 +504,12 @@ def main_single(args):
                       "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
                           i_iter, args.num_steps, l["loss_p"], l["loss_y"], l["convex"], l["volume"], l["anchor"], l["place"],
                           lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                          args.batch_size * world * (i_iter + 1) / max(time.time() - t0, 1e-9)))
+                          args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
             from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
@@ -421,9 +524,8 @@ def main_single(args):
                 keeper.best(tr.state_dict(), i_iter, mIoU)
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        resume.after_iteration(i_iter, tr, keeper)
+    shutdown(world)
 
 
 if __name__ == "__main__":

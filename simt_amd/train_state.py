@@ -1,0 +1,203 @@
+"""The train-state file: everything a training run needs to be CONTINUED, not just re-started.
+
+A snapshot written by the tools holds `state_dict()` only.  What the next step also depends on lives in the trainer: the SGD momentum
+buffers, both noise-transition matrices with their Adam moments, the raw W of the inner loop with its moments, the iteration counter
+(poly learning rate, Adam bias correction, the inner loop's `step0`) and the cumulative bad-label counter.  `TrainStateMixin` gives the four
+trainers `training_state()` / `load_training_state(ts)`; `save` / `load` put that dict, the snapshot rotation's bookkeeping and the loop's
+position into ONE file, written through `save_atomic`.  The check of a resume is bitwise: k steps, save, load into a fresh trainer, n - k
+steps == n steps (tests/test_gpu_resume.py).
+
+Stored: what is not derived from something else in the dict.  NOT stored: T (the inner loop rewrites it every step), every packed operand
+(`plan.repack()` rebuilds them from the masters on load) and the frozen model -- a resumed run is given the same --restore-from and the
+SHA-256 of the frozen tensors is compared instead, which keeps the file at weights + momentum.
+"""
+import hashlib
+import os
+
+import torch
+
+FORMAT_VERSION = 1
+
+# Hyper fields that change the parameter trajectory: a state is refused by a trainer that differs in one of them.  (`skip_unapplied_grads`
+# is not among them: it drops gradients no optimiser applies, the trajectory is the same.)
+TRAJECTORY_FIELDS = ("lr", "lr_T", "momentum", "weight_decay", "power", "num_steps", "lambda_seg", "lambda_place", "lambda_convex",
+                     "lambda_volume", "lambda_anchor", "th_high", "th_low", "num_classes", "open_classes", "iter_size")
+CHECKED_FIELDS = TRAJECTORY_FIELDS + ("B", "H", "W", "dtype", "trainer", "model", "arch", "format_version")
+NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# pure helpers (no GPU)
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def state_sha256(state):
+    """SHA-256 over a {name: tensor} dict in sorted key order: name, dtype, shape and bytes of every tensor.  Independent of the dict's
+    order and of where the tensors live; one changed element changes it."""
+    h = hashlib.sha256()
+    for k in sorted(state):
+        t = state[k].detach().cpu().contiguous()
+        h.update(f"{k}|{t.dtype}|{tuple(t.shape)}|".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+def _norm(v):
+    """Lists and tuples compare equal (a file round trip may turn one into the other)."""
+    if isinstance(v, (list, tuple)):
+        return tuple(_norm(x) for x in v)
+    if isinstance(v, dict):
+        return tuple(sorted((k, _norm(x)) for k, x in v.items()))
+    return v
+
+
+def hyper_mismatches(saved, current, fields=CHECKED_FIELDS):
+    """Names of the checked fields in which two `hyper` dicts differ, in the order of `fields`.  Fields outside `fields` are ignored."""
+    missing = object()
+    return [f for f in fields if _norm(saved.get(f, missing)) != _norm(current.get(f, missing))]
+
+
+def save_atomic(obj, path):
+    """torch.save to a temporary name, then os.replace: a crash or a full disk during the save leaves the previous file intact."""
+    tmp = path + ".tmp"
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def save(path, trainer_state, keeper_state=None, loop_state=None):
+    """ONE file: the trainer's `training_state()`, `SnapshotKeeper.state()` and what the loop itself must find unchanged (the tools: world
+    size, seed, data, class prior).  Atomic: a crash during the write leaves the previous file intact (a stale `<path>.tmp` may remain;
+    `load` never reads it)."""
+    save_atomic({"format_version": FORMAT_VERSION, "trainer": trainer_state, "keeper": keeper_state, "loop": loop_state or {}}, path)
+
+
+def load(path):
+    """-> (trainer_state, keeper_state, loop_state).  ValueError if `path` is not a train-state file of this format version."""
+    obj = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(obj, dict) or "trainer" not in obj or "format_version" not in obj:
+        raise ValueError(f"{path!r} is not a train-state file (a snapshot holds the model only: pass it to --restore-from)")
+    if obj["format_version"] != FORMAT_VERSION:
+        raise ValueError(f"{path!r}: train-state format_version {obj['format_version']}, this build reads {FORMAT_VERSION}")
+    return obj["trainer"], obj.get("keeper"), obj.get("loop") or {}
+
+
+def transition_parameters(path):
+    """The learned noise-transition parameters of a train-state file: {"ntm": ..., "wraw": ...} (lists of two for DeepLab, single tensors
+    for the one-output models).  No snapshot holds them; T itself is sig_NTM(ntm) times the class prior (model/deeplab_multi.py:255-261)."""
+    ts, _k, _l = load(path)
+    if "ntm" not in ts:
+        raise ValueError(f"{path!r} is the state of a {ts['hyper'].get('trainer')}: the warm-up stage learns no transition matrix")
+    return {"ntm": ts["ntm"], "wraw": ts["wraw"]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# the trainers' side
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def _host(v):
+    return [t.detach().cpu() for t in v] if isinstance(v, list) else v.detach().cpu()
+
+
+def _arch(tr):
+    plan = tr.plan
+    if hasattr(plan, "v3_layers"):
+        return {"layers": list(plan.v3_layers), "width": plan.width, "assp_ch": plan.assp_ch}
+    if hasattr(plan, "vgg_layers"):
+        return {"vgg_layers": [list(l) for l in plan.vgg_layers]}
+    return {"layers": list(plan.layers)}
+
+
+class TrainStateMixin:
+    """`training_state()` / `load_training_state()` of SimTTrainer, WarmupTrainer, SimTSingleTrainer and WarmupSingleTrainer."""
+
+    def _hyper_state(self):
+        hy = {k: v for k, v in self.hp.__dict__.items() if isinstance(v, (bool, int, float, str))}
+        hy.update(B=self.B, H=self.H, W=self.W, dtype={torch.bfloat16: "bf16", torch.float32: "f32"}[self.dtype],
+                  trainer=type(self).__name__, model=getattr(self, "model", "v2"), arch=_arch(self), format_version=FORMAT_VERSION)
+        return hy
+
+    def _nbt_steps(self, key):
+        """What state_dict() adds to the `num_batches_tracked` the trainer was given: the train-mode forwards of that BatchNorm so far.  Every
+        BatchNorm of DeepLab-v2 runs; of DeepLabv3 those of the plan (not layer4's: DeepLabv3._dead_bns); DeepLab-VGG16 has none."""
+        model = getattr(self, "model", "v2")
+        live = model == "v2" or (model == "v3" and key[:-len(".num_batches_tracked")] in self.plan.bn)
+        return self.it_done * self.hp.iter_size if live else 0
+
+    def training_state(self):
+        """Everything the next `step()` depends on, as a plain dict of host tensors and Python scalars: `model` (= state_dict()),
+        `momentum`, the NTM / W tensors with their Adam moments (SimT trainers), `it_done`, the device-side accumulators that outlive a step
+        and reach `losses()` (the scalars of the last step with the cumulative bad-label count, and its host twin `bad_reported`), `hyper`
+        and (SimT trainers) `frozen_sha256`.  Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
+        stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
+        it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
+        run -- RuntimeError (`TrunkPlan.raise_on_fbn_error`), no dict, and a file written earlier stays the last good state.  Data parallel: every rank holds the same parameters, momentum and NTM state after the exchange, so rank 0's dict is THE
+        state and every rank loads it; the rank-local BatchNorm running statistics of ranks >= 1 are not preserved."""
+        torch.cuda.synchronize(self.dev)
+        self.plan.raise_on_fbn_error()
+        ts = {"model": self.state_dict(), "momentum": {n: t.detach().cpu() for n, t in self.mom.items()}, "it_done": int(self.it_done),
+              "bad_reported": int(self._bad_reported), "hyper": self._hyper_state()}
+        for f in NTM_FIELDS:
+            if hasattr(self, f):
+                ts[f] = _host(getattr(self, f))
+        if hasattr(self, "frozen_sha256"):
+            ts["frozen_sha256"] = self.frozen_sha256
+        if hasattr(self, "lout"):
+            ts["accumulators"] = {"lout": self.lout.detach().cpu()}
+        else:      # the warm-up trainers: the head's scalars (overwritten by every launch) and the bad-label accumulator beside them
+            ts["accumulators"] = {"hout": self.hout[:16].detach().cpu(), "bad_labels": self.bad_labels.detach().cpu()}
+        return ts
+
+    def load_training_state(self, ts):
+        """Continue where `ts` (a `training_state()` dict, e.g. of `train_state.load`) was taken: the next `step()` computes, bit for bit,
+        what the trainer that wrote it would have computed.  The trainer must have been constructed like that one -- same geometry, dtype,
+        model / arch, hyper-parameters and frozen model; which weights it was given does not matter, they are replaced.  ValueError,
+        naming what differs, otherwise; nothing has been changed then.  Every packed operand is rebuilt from the loaded masters
+        (`plan.repack()`).  `state_dict()` afterwards reports the `num_batches_tracked` an uninterrupted run reports (the steps taken are
+        counted once).  Data parallel: every rank loads the same dict (see training_state)."""
+        bad = hyper_mismatches(ts["hyper"], self._hyper_state())
+        if bad:
+            mine = self._hyper_state()
+            raise ValueError("the train state was written by a different run: " +
+                             ", ".join(f"{f} (state: {ts['hyper'].get(f)!r}, this trainer: {mine.get(f)!r})" for f in bad))
+        if hasattr(self, "frozen_sha256") and ts.get("frozen_sha256") != self.frozen_sha256:
+            raise ValueError(f"frozen_sha256 differs: the train state was written beside another frozen model (state: {ts.get('frozen_sha256')}, "
+                             f"this trainer: {self.frozen_sha256}); give the resumed run the same --restore-from")
+        problems = []
+        for what, theirs, mine in (("momentum", ts["momentum"], self.mom), ("model", ts["model"], self.params)):
+            for n in mine:
+                if n not in theirs:
+                    problems.append(f"{what} {n}: missing")
+                elif tuple(theirs[n].shape) != tuple(mine[n].shape):
+                    problems.append(f"{what} {n}: shape {tuple(theirs[n].shape)}, expected {tuple(mine[n].shape)}")
+            problems += [f"{what} {n}: unknown to this trainer" for n in theirs if n not in mine]
+        for f in NTM_FIELDS:
+            if hasattr(self, f):
+                mine, theirs = getattr(self, f), ts.get(f)
+                pairs = list(zip(mine, theirs)) if isinstance(mine, list) and isinstance(theirs, list) and len(mine) == len(theirs) else \
+                    [(mine, theirs)] if torch.is_tensor(mine) and torch.is_tensor(theirs) else None
+                if pairs is None or any(tuple(a.shape) != tuple(b.shape) for a, b in pairs):
+                    problems.append(f"{f}: missing or of another shape")
+        if problems:
+            raise ValueError("the train state does not fit this trainer: " + "; ".join(problems[:8]) +
+                             (f" (and {len(problems) - 8} more)" if len(problems) > 8 else ""))
+        it_done = int(ts["it_done"])
+        self.it_done = it_done
+        for k, p in self.params.items():
+            if k.endswith("num_batches_tracked"):
+                p.fill_(int(ts["model"][k]) - self._nbt_steps(k))       # state_dict() adds the steps taken: count them once
+            else:
+                p.copy_(ts["model"][k])
+        for n, buf in self.mom.items():
+            buf.copy_(ts["momentum"][n])
+        for f in NTM_FIELDS:
+            if hasattr(self, f):
+                mine, theirs = getattr(self, f), ts[f]
+                for a, b in (zip(mine, theirs) if isinstance(mine, list) else [(mine, theirs)]):
+                    a.copy_(b)
+        acc = ts["accumulators"]
+        if hasattr(self, "lout"):
+            self.lout.copy_(acc["lout"])
+        else:
+            self.hout[:16].copy_(acc["hout"])
+            self.bad_labels.copy_(acc["bad_labels"])
+        self._bad_reported = int(ts["bad_reported"])
+        self.plan.repack()
+        torch.cuda.synchronize(self.dev)
+
