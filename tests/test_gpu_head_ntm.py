@@ -4,6 +4,10 @@ simt_head_grad, simt_sig_ntm, simt_sig_w, simt_adam_step) against the golden vec
 
 Tolerance: fp32 throughout.  Scalars 1e-4 (north_star: "loss within 1e-4 fp32"); gradients 1e-5 relative to max|ref|;
 integer decisions (confidence labels are not exported by the kernel, but N_valid counts are) exact.
+
+`close` is an ABSOLUTE bar for tensors far below 1, which the head's gradients are; beside it every gradient is held element by element on
+its own scale against the float64 oracle, with a threshold measured from the fp32 oracle (tests/_head_bar.py; proven on the CPU by
+tests/test_head_bar_cpu.py).
 """
 import ctypes as C
 import os
@@ -12,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+import _head_bar as hb
+from _launch_oracle import SENTINEL
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
 from simt_amd import ops
@@ -32,15 +38,21 @@ def nhwc_pad(x, ld):
     return out
 
 
-def run_head(dev, d, pred1, pred2, fixed2, label, ntm, *, steps=10, lr_T=None, label_ws=False):
-    """Drives the head/NTM kernels exactly like SimTTrainer.step does, on explicit low-res logits."""
+def run_head(dev, d, pred1, pred2, fixed2, label, ntm, *, steps=10, lr_T=None, label_ws=False, f32=True, grad_dtype=None, ld_t=0, gscale=1.0,
+             ldp=None):
+    """Drives the head/NTM kernels exactly like SimTTrainer.step does, on explicit low-res logits.
+
+    One launch can ask for everything the trainers ask for (simt_amd/step.py: dpred*_f32 = NULL, dpred*_t in the plan's dtype with the plan's
+    pitch, gscale = 1 / iter_size, conf_out + label_ws): f32=False drops the fp32 outputs; grad_dtype (torch.bfloat16 / torch.float32) adds
+    dpred*_t with pitch ld_t, pre-filled with SENTINEL -> r["dt1"], r["dt2"] (the raw [B*h*w, ld_t] buffers); gscale goes to simt_head_grad
+    and simt_ntm_post."""
     K = int(d["K"]); Cn = 19; Q = Cn + K
     B, _, h, w = pred1.shape
     H, W = label.shape[1:]
     lam = d["lam"]
     lib = L.load()
     st = ops.stream_ptr()
-    ldp = max(32, ops.round_up(Q, 8))
+    ldp = max(32, ops.round_up(Q, 8)) if ldp is None else ldp          # (the trainers: the plan's pitch of the logits)
     p1 = nhwc_pad(pred1, ldp).to(dev); p2 = nhwc_pad(pred2, ldp).to(dev)
     fl = nhwc_pad(fixed2, 32).to(dev)
     fixp = torch.zeros_like(fl)
@@ -75,10 +87,17 @@ def run_head(dev, d, pred1, pred2, fixed2, label, ntm, *, steps=10, lr_T=None, l
     hd.T1, hd.T2 = T[0].data_ptr(), T[1].data_ptr()
     hd.part, hd.keys, hd.hout, hd.g1 = part.data_ptr(), keys.data_ptr(), hout.data_ptr(), g1.data_ptr()
     hd.dpred1_f32, hd.dpred2_f32, hd.dpred1_t, hd.dpred2_t = dp1.data_ptr(), dp2.data_ptr(), None, None
+    if not f32:
+        hd.dpred1_f32, hd.dpred2_f32 = None, None
     hd.B, hd.h, hd.w, hd.H, hd.W, hd.C, hd.Q = B, h, w, H, W, Cn, Q
     hd.ldp, hd.ldf, hd.QP, hd.ld_f32, hd.ld_t, hd.grad_dtype = ldp, 32, QP, ldp, 0, L.SIMT_F32
+    dt = [None, None]
+    if grad_dtype is not None:
+        assert ld_t >= QP
+        dt = [torch.full((B * h * w, ld_t), SENTINEL, dtype=grad_dtype, device=dev) for _ in range(2)]
+        hd.dpred1_t, hd.dpred2_t, hd.ld_t, hd.grad_dtype = dt[0].data_ptr(), dt[1].data_ptr(), ld_t, ops.dt_code(grad_dtype)
     hd.th_high, hd.th_low = float(d["th"][0]), float(d["th"][1])
-    hd.lambda_seg, hd.lambda_place, hd.gscale = float(d["lambda_seg"]), float(d["lambda_place"]), 1.0
+    hd.lambda_seg, hd.lambda_place, hd.gscale = float(d["lambda_seg"]), float(d["lambda_place"]), gscale
     conf = torch.full((B, H, W), 77, dtype=torch.uint8, device=dev)       # per-pixel Conf_label_target (optional export)
     hd.conf_out = conf.data_ptr()
     if label_ws:          # the trainers' form: the gradient pass reads both byte maps back instead of deciding the labels again
@@ -90,7 +109,7 @@ def run_head(dev, d, pred1, pred2, fixed2, label, ntm, *, steps=10, lr_T=None, l
         npd.ntm[k], npd.w[k], npd.ntm_grad[k] = ntm_d[k].data_ptr(), wraw[k].data_ptr(), ngrad[k].data_ptr()
     npd.class_dist, npd.hout, npd.lout, npd.Q, npd.C = cd.data_ptr(), hout.data_ptr(), lout.data_ptr(), Q, Cn
     npd.lambda_seg, npd.lambda_convex, npd.lambda_volume, npd.lambda_anchor = float(d["lambda_seg"]), float(lam[0]), float(lam[1]), float(lam[2])
-    npd.gscale = 1.0
+    npd.gscale = gscale
     L.call("simt_ntm_post", C.byref(npd), st)
     L.call("simt_head_grad", C.byref(hd), st)
     # Adam on NTM (first step)
@@ -104,7 +123,9 @@ def run_head(dev, d, pred1, pred2, fixed2, label, ntm, *, steps=10, lr_T=None, l
 
     def back(g):  # [B*h*w, ldp] -> [B,Q,h,w]
         return g.cpu()[:, :Q].reshape(B, h, w, Q).permute(0, 3, 1, 2)
-    return dict(lout=lout.cpu(), hout=hout.cpu(), dpred1=back(dp1), dpred2=back(dp2), dp1_raw=dp1.cpu(), conf=conf.cpu().long(),
+    return dict(lout=lout.cpu(), hout=hout.cpu(), dpred1=back(dp1), dpred2=back(dp2), dp1_raw=dp1.cpu(), dp2_raw=dp2.cpu(), conf=conf.cpu().long(),
+                dt1=None if dt[0] is None else dt[0].cpu(), dt2=None if dt[1] is None else dt[1].cpu(), back=back,
+                lws=lws.cpu().long() if label_ws else None,
                 ntm_grad=[g.cpu() for g in ngrad], w=[x.cpu() for x in wraw], wm=[x.cpu() for x in wm],
                 wv=[x.cpu() for x in wv], T=[x.cpu() for x in T], ntm_after=[x.cpu() for x in ntm_after])
 
@@ -143,6 +164,12 @@ def test_head_against_reference_golden(dev, name):
     close(r["ntm_grad"][1], d["ntm_grad2"], 2e-5, "ntm_grad2")
     close(r["ntm_after"][0], d["ntm1_after"], 1e-5, "NTM1 after Adam")
     close(r["ntm_after"][1], d["ntm2_after"], 1e-5, "NTM2 after Adam")
+    # ... and every element on its own scale against the float64 oracle on the golden inputs (tests/_head_bar.py)
+    ins = (t("pred_lr1"), t("pred_lr2"), t("fixed_lr2"), t("label"), [t("ntm1"), t("ntm2")])
+    r64, r32 = hb.ref_pair(("golden", name), lambda dt: hb.two_head_ref(*ins, d, CD, dt))
+    assert torch.equal(r["conf"], r32["out"]["conf"].long().view_as(r["conf"]))
+    for k, got in (("dpred1", r["dpred1"]), ("dpred2", r["dpred2"]), ("ntm_grad1", r["ntm_grad"][0]), ("ntm_grad2", r["ntm_grad"][1])):
+        hb.report(name, k, hb.grad_bar(got, r64[k], r32[k], f"{name} {k}"))
 
 
 # (B, h, w, H, W): pass 2's x-reduction takes a different route per geometry -- runs of <= 8 pixels per low-res column (the production
@@ -193,6 +220,10 @@ def test_head_bigger_than_one_block_vs_oracle(dev, geom, K, lws):
     close(r["dpred1"], q1.grad, 1e-5, "dpred1")
     close(r["dpred2"], q2.grad, 1e-5, "dpred2")
     close(r["ntm_grad"][0], n[0].grad, 2e-5, "ntm grad")
+    # ... and every element on its own scale against the float64 oracle (tests/_head_bar.py)
+    r64, r32 = hb.ref_pair(("geom", geom, K), lambda dt: hb.two_head_ref(p1, p2, f2, lab, ntm, dict(d, K=K), CD, dt))
+    for k, got in (("dpred1", r["dpred1"]), ("dpred2", r["dpred2"]), ("ntm_grad1", r["ntm_grad"][0]), ("ntm_grad2", r["ntm_grad"][1])):
+        hb.report(f"{geom} K={K}{' label_ws' if lws else ''}", k, hb.grad_bar(got, r64[k], r32[k], f"{geom} K={K} {k}"))
     # anchors: arg-max pixel per channel, first index
     QM = 40
     ai = r["hout"][16 + 2 * Q * Cn + 2 * QM: 16 + 2 * Q * Cn + 2 * QM + Q].view(torch.int32)

@@ -16,8 +16,10 @@ On top of the per-launch bars:
   * the production schedule (two streams, the fused BatchNorm backward as the default selects it, same weights / image / dlogits) must give
     the serial replay's logits, gradients and BatchNorm running statistics bit for bit, which carries the per-launch evidence over to the
     schedule bench.py times.
-The step-level launches outside TrunkPlan (SimT head, NTM, softmax, optimisers) are held by test_head_production_size_vs_oracle and
-tests/test_gpu_bn_pool.py.
+The step-level launches outside TrunkPlan: the SimT head and the NTM gradients are held element by element on their own scale against the
+float64 oracle (tests/_head_bar.py) by test_head_production_size_vs_oracle and, in the form the trainers launch it (bf16 gradient at the plan's
+pitch, gscale, byte maps), by test_head_production_form_v2_simt / _v2_warmup; softmax and the optimisers by tests/test_gpu_bn_pool.py and
+tests/test_gpu_optim.py.
 """
 import time
 

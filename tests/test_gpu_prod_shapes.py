@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _head_bar as hb
 from _launch_oracle import tight_bf16 as _tight_bf16
 from _launch_oracle import ulp_bf16 as _ulp_bf16
 from oracle import ops_ref
@@ -572,38 +573,124 @@ def test_direct_stem_plan_matches_the_im2col_plan(dev, monkeypatch):
     assert _rel(a["gw"], b["gw"]) < 0.25       # (the gradient passes back through the whole train-mode toy net: same order of magnitude is the claim)
 
 
+HEAD_D = {"K": 3, "lam": np.array([0.5, 0.1, 0.5]), "lr_T": 6e-3, "th": np.array([0.8, 0.2]), "lambda_seg": 0.1, "lambda_place": 0.1}
+
+
+def _prod_head_inputs():
+    """4 x 768 x 768 labels over 97 x 97 logits, K = 3: seed 5 (logits) / 11 (labels)."""
+    return hb.cached("prod inputs", lambda: hb.head_inputs((B4, HW, HW, 768, 768), 3, CD, block=16))
+
+
+def _prod_head_refs():
+    """(float64, fp32) CPU oracle on _prod_head_inputs (tests/_head_bar.py two_head_ref), computed once for every test of this module."""
+    _threads()
+    return hb.ref_pair("prod refs", lambda dt: hb.two_head_ref(*_prod_head_inputs(), HEAD_D, CD, dt))
+
+
 def test_head_production_size_vs_oracle(dev):
     """head_pass1 / head_pass2 / yreduce + ntm kernels at 4 x 768 x 768 (P = 2 359 296 pixels, 9 216 blocks) from 97 x 97 logits,
-    against the CPU oracle: losses 1e-4, gradients 1e-5, confidence-label count exact (trainV2_simt.py:351-409)."""
+    against the CPU oracle: losses 1e-4, gradients 1e-5, confidence-label count exact (trainV2_simt.py:351-409).
+
+    On top of that (tests/_head_bar.py): both heads' gradients and both NTM gradients element by element on their own scale against the float64
+    oracle, the per-pixel confidence labels equal to the fp32 oracle's, and the trainers' route (label_ws: the gradient pass reads the two
+    byte maps of the loss pass back) bit for bit the same outputs."""
     from test_gpu_head_ntm import close, run_head
     _threads()
     K, Cn = 3, 19
     Q = Cn + K
-    g = torch.Generator().manual_seed(5)
-    B, h, w, H, W = B4, HW, HW, 768, 768
-    p1 = torch.randn(B, Q, h, w, generator=g) * 3
-    p2 = torch.randn(B, Q, h, w, generator=g) * 3
-    f2 = torch.randn(B, Cn, h, w, generator=g) * 4
-    _, lab = so.synthetic_batch(B, H, W, CD.numpy(), seed=11)
-    ntm = [so.ntm_init(Cn, K, 1), so.ntm_init(Cn, K, 2)]
-    d = {"K": K, "lam": np.array([0.5, 0.1, 0.5]), "lr_T": 6e-3, "th": np.array([0.8, 0.2]), "lambda_seg": 0.1, "lambda_place": 0.1}
+    p1, p2, f2, lab, ntm = _prod_head_inputs()
+    d = HEAD_D
     r = run_head(dev, d, p1, p2, f2, lab, ntm)
-    hp = so.Hyper(num_classes=Cn, open_classes=K, lambda_convex=0.5, lambda_volume=0.1, lambda_anchor=0.5)
-    n = [x.clone().requires_grad_(True) for x in ntm]
-    wr = [so.w_init(Cn, K).requires_grad_(True) for _ in range(2)]
-    state = {"step": 0, "m1": torch.zeros(Q, Q), "v1": torch.zeros(Q, Q), "m2": torch.zeros(Q, Q), "v2": torch.zeros(Q, Q)}
-    so.inner_w_loop(n[0], n[1], wr[0], wr[1], state, CD, hp, 6e-3)
-    q1, q2 = p1.clone().requires_grad_(True), p2.clone().requires_grad_(True)
-    T1, T2 = so.sig_ntm_forward(n[0], CD, Cn), so.sig_ntm_forward(n[1], CD, Cn)
-    out = so.simt_losses(q1, q2, f2, lab, T1, T2, so.sig_w_forward(wr[0]), so.sig_w_forward(wr[1]), hp, (H, W))
-    out["total"].backward()
+    r64, r32 = _prod_head_refs()
+    out = r32["out"]                 # (the fp32 oracle run this test has always compared with)
     for idx, key in [(0, "total"), (1, "loss_p1"), (2, "loss_p2"), (3, "loss_y1"), (4, "loss_y2"), (5, "place"), (6, "convex"),
                      (7, "volume"), (8, "anchor")]:
         close(r["lout"][idx], out[key].detach(), 1e-4, key)
     assert int(r["hout"][6]) == int((out["conf"] != 255).sum())
-    close(r["dpred1"], q1.grad, 1e-5, "dpred1")
-    close(r["dpred2"], q2.grad, 1e-5, "dpred2")
-    close(r["ntm_grad"][0], n[0].grad, 2e-5, "ntm grad")
+    close(r["dpred1"], r32["dpred1"], 1e-5, "dpred1")
+    close(r["dpred2"], r32["dpred2"], 1e-5, "dpred2")
+    close(r["ntm_grad"][0], r32["ntm_grad1"], 2e-5, "ntm grad")
+    nflip = int((r["conf"] != out["conf"].long().view_as(r["conf"])).sum())
+    print(f"[head-bar] v2 4x768x768: {nflip} confidence labels differ from the fp32 oracle's; the references differ on "
+          f"{int((r64['out']['conf'] != out['conf']).sum())} (conf) / {int((r64['out']['conf0'] != out['conf0']).sum())} (conf0)", flush=True)
+    assert nflip == 0, f"{nflip} confidence labels differ"
+    for k, got in (("dpred1", r["dpred1"]), ("dpred2", r["dpred2"]), ("ntm_grad1", r["ntm_grad"][0]), ("ntm_grad2", r["ntm_grad"][1])):
+        hb.report("v2 4x768x768", k, hb.grad_bar(got, r64[k], r32[k], f"v2 4x768x768 {k}"))
+    r2 = run_head(dev, d, p1, p2, f2, lab, ntm, label_ws=True)
+    for k in ("lout", "dp1_raw", "dp2_raw", "conf"):                  # (compared as bit patterns)
+        a, b = (x.view(torch.int32) if x.dtype == torch.float32 else x for x in (r[k], r2[k]))
+        assert torch.equal(a, b), f"{k}: the label_ws route differs at {(a != b).nonzero()[:4].tolist()}"
+    for k in ("ntm_grad", "w", "T", "ntm_after"):
+        assert all(torch.equal(a, b) for a, b in zip(r[k], r2[k])), f"{k}: the label_ws route differs"
+
+
+def _v2_head_plan_geometry(dev, warmup):
+    """(h, w, pitch of the logits, pitch of the bf16 gradient) of the two heads of the plan SimTTrainer (warmup: WarmupTrainer) builds at the
+    benchmarked B = 4, 768 x 768, bf16 (simt_amd/step.py: hd.ldp = plan.ldp["x1"], hd.ld_t = plan.dlogits["x1"].shape[1])."""
+    def make():
+        K = 0 if warmup else 3
+        st = so.recipe_state(so.state_shapes(19, K, not warmup), seed=1234)
+        plan = TrunkPlan({k: v.clone().to(dev) for k, v in st.items()}, B4, 768, 768, multi_heads(19, K, not warmup), dtype=BF, train=True)
+        hd = plan.heads[1]
+        geo = (hd.h, hd.w, plan.ldp["x1"], plan.dlogits["x1"].shape[1])
+        assert (plan.heads[0].h, plan.heads[0].w, plan.ldp["x2"], plan.dlogits["x2"].shape[1]) == geo and plan.dlogits["x1"].dtype == BF
+        del plan
+        torch.cuda.empty_cache()
+        return geo
+    return hb.cached(("v2 plan geometry", warmup), make)
+
+
+@pytest.mark.parametrize("gscale", [1.0, 0.5])
+def test_head_production_form_v2_simt(dev, gscale):
+    """simt_head_loss / simt_head_grad as SimTTrainer launches them at the benchmarked size (simt_amd/step.py:124-141): bf16 dpred*_t with the
+    plan's pitch, the plan's logits pitch, gscale = 1 / iter_size, conf_out + label_ws -- and dpred*_f32 from the SAME launch, so that the
+    bf16 store is held bit for bit against the fp32 one.  The bars of tests/_head_bar.py against the float64 oracle; pad columns; the fp32
+    output at gscale = 0.5 bit for bit half the one at gscale = 1 (gscale enters once, in the factors gscale * lambda / N of head_pass2: a
+    power of two is exact); lout[0] = total * gscale."""
+    from test_gpu_head_ntm import close, run_head
+    h, w, ldp, ld_t = _v2_head_plan_geometry(dev, False)
+    p1, p2, f2, lab, ntm = _prod_head_inputs()
+    assert (h, w) == tuple(p1.shape[2:]) and ld_t > ops.round_up(22, 8)
+    r64, r32 = _prod_head_refs()
+    run = lambda gs: run_head(dev, HEAD_D, p1, p2, f2, lab, ntm, label_ws=True, grad_dtype=BF, ld_t=ld_t, gscale=gs, ldp=ldp)
+    base = hb.cached(("gpu v2 simt", 1.0), lambda: run(1.0))
+    r = base if gscale == 1.0 else run(gscale)
+    tag = "v2 simt 4x768x768"
+    assert torch.equal(r["conf"], r32["out"]["conf"].long().view_as(r["conf"]))
+    for k, f32_raw, dt_raw in (("dpred1", r["dp1_raw"], r["dt1"]), ("dpred2", r["dp2_raw"], r["dt2"])):
+        hb.trainer_form(tag, k, f32_raw, dt_raw, r["back"], 22, 24, r64[k], r32[k], gscale)
+    close(r["lout"][0], r64["out"]["total"] * gscale, 1e-4, "lout[0] = total * gscale")
+    if gscale == 0.5:
+        for k in ("dp1_raw", "dp2_raw"):
+            hb.half_is_bitwise(tag, k, r[k], base[k])
+
+
+@pytest.mark.parametrize("gscale", [1.0, 0.5])
+def test_head_production_form_v2_warmup(dev, gscale):
+    """The warm-up stage's launch of the same kernels (mode = 1, simt_amd/step.py:447-457: C = Q = 19, both heads against the labels, the
+    auxiliary one weighted lambda_seg) in WarmupTrainer's form at B = 4, 768 x 768: as test_head_production_form_v2_simt; the references are
+    float64 / fp32 autograd of oracle.simt_oracle.warmup_losses' cross entropies."""
+    from test_gpu_warmup_single import _run_head
+    h, w, ldp, ld_t = _v2_head_plan_geometry(dev, True)
+    g = torch.Generator().manual_seed(23)
+    pa, pb = torch.randn(B4, 19, h, w, generator=g) * 3, torch.randn(B4, 19, h, w, generator=g) * 3
+    _, lab = so.synthetic_batch(B4, 768, 768, CD.numpy(), seed=13)
+    lam = 0.1
+    _threads()
+    r64, r32 = hb.ref_pair("v2 warmup refs", lambda dt: hb.warmup_ref(pa, pb, lab, lam, False, dt))
+    run = lambda gs: _run_head(dev, pb.to(dev), lab.to(dev), False, single=False, pred1=pa.to(dev), lambda_seg=lam, grad_dtype=BF, ld_t=ld_t,
+                               gscale=gs, ldp=ldp, byte_maps=True, full=True)
+    base = hb.cached(("gpu v2 warmup", 1.0), lambda: run(1.0))
+    r = base if gscale == 1.0 else run(gscale)
+    tag = "v2 warm-up 4x768x768"
+    assert torch.equal(r["conf"], lab)               # (mode 1: the confidence label is the label itself)
+    for k, f32_raw, dt_raw in (("dpred1", r["dp1_raw"], r["dt1"]), ("dpred2", r["dp2_raw"], r["dt2"])):
+        hb.trainer_form(tag, k, f32_raw, dt_raw, r["back"], 19, 24, r64[k], r32[k], gscale)
+    tot = float(r64["total"])
+    assert abs(float(r["hout"][14]) - tot) <= 1e-4 * abs(tot), (float(r["hout"][14]), tot)
+    if gscale == 0.5:
+        for k in ("dp1_raw", "dp2_raw"):                           # (the columns the kernel writes: this driver pre-fills the fp32 buffers)
+            hb.half_is_bitwise(tag, k, r[k][:, :24], base[k][:, :24])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

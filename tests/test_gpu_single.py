@@ -14,11 +14,14 @@ the two TRUNKS are restatements of files that cannot be imported here (torchvisi
   * bf16 (throughput mode): finite, within 0.1 * (1 + |ref|).
 """
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 import torch
 
+import _head_bar as hb
+from _launch_oracle import SENTINEL
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
 from simt_amd import ops
@@ -45,6 +48,73 @@ def nhwc_pad(x, ld):
     return out
 
 
+def run_single_head(dev, pred, fix, lab, ntm, K, half, *, label_ws=False, f32=True, grad_dtype=None, ld_t=0, gscale=1.0, ldp=None, ldf=32,
+                    d=hb.DEFAULT_D):
+    """The head / NTM launches of SimTSingleTrainer.step (single = 1, mode 0) on explicit low-res logits.  half: DeepLabv3 (half-pixel
+    upsample, fixp = the frozen model's LOGITS); else DeepLab-VGG16 (align_corners=True, fixp = its low-res probabilities).
+
+    One launch can ask for everything the trainer asks for (simt_amd/step_single.py: dpred2_f32 = NULL, dpred2_t in the plan's dtype with the
+    plan's pitch, gscale = 1 / iter_size, conf_out + label_ws): label_ws gives both byte maps; f32=False drops the fp32 output; grad_dtype adds
+    dpred2_t with pitch ld_t, pre-filled with SENTINEL (-> r["dt"], the raw buffer); gscale goes to simt_head_grad and simt_ntm_post."""
+    Cn = 19
+    Q = Cn + K
+    B, _, h, w = pred.shape
+    H, W = lab.shape[1:]
+    st = ops.stream_ptr()
+    ldp = max(32, ops.round_up(Q, 8)) if ldp is None else ldp
+    p_d, f_d = nhwc_pad(pred, ldp).to(dev), nhwc_pad(fix, ldf).to(dev)
+    fixp = f_d
+    if not half:
+        fixp = torch.zeros_like(f_d)
+        ops.softmax_rows(f_d, ldf, fixp, ldf, B * h * w, Cn)
+    cd = CD.float().to(dev)
+    ntm_d, ngrad = ntm.clone().to(dev), torch.zeros(Q, Cn, device=dev)
+    wraw, wm, wv, T = so.w_init(Cn, K).to(dev), torch.zeros(Q, Q, device=dev), torch.zeros(Q, Q, device=dev), torch.zeros(Q, Cn, device=dev)
+    ni = L.NtmInnerDesc()
+    ni.ntm[1], ni.w[1], ni.ntm_grad[1], ni.w_m[1], ni.w_v[1], ni.T_out[1] = (t.data_ptr() for t in (ntm_d, wraw, ngrad, wm, wv, T))
+    ni.class_dist, ni.Q, ni.C, ni.steps, ni.step0, ni.single = cd.data_ptr(), Q, Cn, 10, 0, 1
+    ni.lr, ni.beta1, ni.beta2, ni.eps = float(d["lr_T"]), 0.9, 0.999, 1e-8
+    L.call("simt_ntm_inner_loop", C.byref(ni), st)
+    lib = L.load()
+    part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Q, Cn), device=dev)
+    keys = torch.zeros(lib.simt_head_keys_count(), device=dev, dtype=torch.int64)
+    hout, lout = torch.zeros(lib.simt_head_hout_floats(Q, Cn), device=dev), torch.zeros(16, device=dev)
+    QP = ops.round_up(Q, 8)
+    g1 = torch.zeros(2, B, H, w, QP, device=dev)
+    dp = torch.zeros(B * h * w, ldp, device=dev)
+    lab_d = lab.to(dev)
+    hd = L.HeadDesc()
+    hd.pred1, hd.pred2, hd.fixp, hd.label, hd.T1, hd.T2 = None, p_d.data_ptr(), fixp.data_ptr(), lab_d.data_ptr(), None, T.data_ptr()
+    hd.part, hd.keys, hd.hout, hd.g1 = part.data_ptr(), keys.data_ptr(), hout.data_ptr(), g1.data_ptr()
+    hd.dpred1_f32, hd.dpred2_f32, hd.dpred1_t, hd.dpred2_t = None, dp.data_ptr() if f32 else None, None, None
+    hd.B, hd.h, hd.w, hd.H, hd.W, hd.C, hd.Q = B, h, w, H, W, Cn, Q
+    hd.ldp, hd.ldf, hd.QP, hd.ld_f32, hd.ld_t, hd.grad_dtype = ldp, ldf, QP, ldp, 0, L.SIMT_F32
+    dt = None
+    if grad_dtype is not None:
+        assert ld_t >= QP
+        dt = torch.full((B * h * w, ld_t), SENTINEL, dtype=grad_dtype, device=dev)
+        hd.dpred2_t, hd.ld_t, hd.grad_dtype = dt.data_ptr(), ld_t, ops.dt_code(grad_dtype)
+    hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = float(d["th"][0]), float(d["th"][1]), 0.0, float(d["lambda_place"]), gscale
+    hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 0, 1, int(half), int(half)
+    conf_ws = lab_ws = None
+    if label_ws:
+        conf_ws, lab_ws = (torch.full((B, H, W), 77, dtype=torch.uint8, device=dev) for _ in range(2))
+        hd.conf_out, hd.label_ws = conf_ws.data_ptr(), lab_ws.data_ptr()
+    L.call("simt_head_loss", C.byref(hd), st)
+    npd = L.NtmPostDesc()
+    npd.ntm[1], npd.w[1], npd.ntm_grad[1] = ntm_d.data_ptr(), wraw.data_ptr(), ngrad.data_ptr()
+    npd.class_dist, npd.hout, npd.lout, npd.Q, npd.C = cd.data_ptr(), hout.data_ptr(), lout.data_ptr(), Q, Cn
+    npd.lambda_seg, npd.lambda_convex, npd.lambda_volume, npd.lambda_anchor = 0.0, float(d["lam"][0]), float(d["lam"][1]), float(d["lam"][2])
+    npd.gscale, npd.single = gscale, 1
+    L.call("simt_ntm_post", C.byref(npd), st)
+    L.call("simt_head_grad", C.byref(hd), st)
+    torch.cuda.synchronize()
+    back = lambda g: g.cpu()[:, :Q].reshape(B, h, w, Q).permute(0, 3, 1, 2)
+    return dict(lout=lout.cpu(), hout=hout.cpu(), dp_raw=dp.cpu(), dpred=back(dp), dt=None if dt is None else dt.cpu(), back=back,
+                ntm_grad=ngrad.cpu(), w=wraw.cpu(), conf=None if conf_ws is None else conf_ws.cpu().long(),
+                lws=None if lab_ws is None else lab_ws.cpu().long())
+
+
 @pytest.mark.parametrize("flavour,K", [("v3", 6), ("vgg", 3), ("v3", 15), ("v3rows", 6), ("vggrows", 3)])
 def test_single_head_kernel_vs_oracle(dev, flavour, K):
     """*rows: enough image rows (B * H >= 1536) that the gradient pass takes groups of 4 (v3, half-pixel) / 8 (vgg, align_corners) rows per block,
@@ -64,48 +134,8 @@ def test_single_head_kernel_vs_oracle(dev, flavour, K):
     hp = so.Hyper(num_classes=Cn, open_classes=K, lambda_convex=0.5, lambda_volume=0.1, lambda_anchor=0.5)
     half = flavour == "v3"
     # ---- device
-    st = ops.stream_ptr()
-    ldp = max(32, ops.round_up(Q, 8))
-    p_d, f_d = nhwc_pad(pred, ldp).to(dev), nhwc_pad(fix, 32).to(dev)
-    fixp = f_d
-    if not half:
-        fixp = torch.zeros_like(f_d)
-        ops.softmax_rows(f_d, 32, fixp, 32, B * h * w, Cn)
-    cd = CD.float().to(dev)
-    ntm_d, ngrad = ntm.clone().to(dev), torch.zeros(Q, Cn, device=dev)
-    wraw, wm, wv, T = so.w_init(Cn, K).to(dev), torch.zeros(Q, Q, device=dev), torch.zeros(Q, Q, device=dev), torch.zeros(Q, Cn, device=dev)
-    ni = L.NtmInnerDesc()
-    ni.ntm[1], ni.w[1], ni.ntm_grad[1], ni.w_m[1], ni.w_v[1], ni.T_out[1] = (t.data_ptr() for t in (ntm_d, wraw, ngrad, wm, wv, T))
-    ni.class_dist, ni.Q, ni.C, ni.steps, ni.step0, ni.single = cd.data_ptr(), Q, Cn, 10, 0, 1
-    ni.lr, ni.beta1, ni.beta2, ni.eps = 6e-3, 0.9, 0.999, 1e-8
-    L.call("simt_ntm_inner_loop", C.byref(ni), st)
-    lib = L.load()
-    part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Q, Cn), device=dev)
-    keys = torch.zeros(lib.simt_head_keys_count(), device=dev, dtype=torch.int64)
-    hout, lout = torch.zeros(lib.simt_head_hout_floats(Q, Cn), device=dev), torch.zeros(16, device=dev)
-    QP = ops.round_up(Q, 8)
-    g1 = torch.zeros(2, B, H, w, QP, device=dev)
-    dp = torch.zeros(B * h * w, ldp, device=dev)
-    lab_d = lab.to(dev)
-    hd = L.HeadDesc()
-    hd.pred1, hd.pred2, hd.fixp, hd.label, hd.T1, hd.T2 = None, p_d.data_ptr(), fixp.data_ptr(), lab_d.data_ptr(), None, T.data_ptr()
-    hd.part, hd.keys, hd.hout, hd.g1 = part.data_ptr(), keys.data_ptr(), hout.data_ptr(), g1.data_ptr()
-    hd.dpred1_f32, hd.dpred2_f32, hd.dpred1_t, hd.dpred2_t = None, dp.data_ptr(), None, None
-    hd.B, hd.h, hd.w, hd.H, hd.W, hd.C, hd.Q = B, h, w, H, W, Cn, Q
-    hd.ldp, hd.ldf, hd.QP, hd.ld_f32, hd.ld_t, hd.grad_dtype = ldp, 32, QP, ldp, 0, L.SIMT_F32
-    hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 0.8, 0.2, 0.0, 0.1, 1.0
-    hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 0, 1, int(half), int(half)
-    if rows:
-        conf_ws, lab_ws = (torch.full((B, H, W), 77, dtype=torch.uint8, device=dev) for _ in range(2))
-        hd.conf_out, hd.label_ws = conf_ws.data_ptr(), lab_ws.data_ptr()
-    L.call("simt_head_loss", C.byref(hd), st)
-    npd = L.NtmPostDesc()
-    npd.ntm[1], npd.w[1], npd.ntm_grad[1] = ntm_d.data_ptr(), wraw.data_ptr(), ngrad.data_ptr()
-    npd.class_dist, npd.hout, npd.lout, npd.Q, npd.C = cd.data_ptr(), hout.data_ptr(), lout.data_ptr(), Q, Cn
-    npd.lambda_seg, npd.lambda_convex, npd.lambda_volume, npd.lambda_anchor, npd.gscale, npd.single = 0.0, 0.5, 0.1, 0.5, 1.0, 1
-    L.call("simt_ntm_post", C.byref(npd), st)
-    L.call("simt_head_grad", C.byref(hd), st)
-    torch.cuda.synchronize()
+    r = run_single_head(dev, pred, fix, lab, ntm, K, half, label_ws=rows)
+    lout, hout, dp, ngrad, wraw = r["lout"], r["hout"], r["dp_raw"], r["ntm_grad"], r["w"]
     # ---- oracle
     n = ntm.clone().requires_grad_(True)
     wr = so.w_init(Cn, K).requires_grad_(True)
@@ -129,6 +159,77 @@ def test_single_head_kernel_vs_oracle(dev, flavour, K):
     assert torch.all(dp.cpu()[:, Q:] == 0)
     close(ngrad.cpu(), n.grad, 2e-5, "dNTM (leak + main)")
     close(wraw.cpu(), wr.detach(), 1e-5, "W after 10 Adam steps")
+    # ... and every element on its own scale against the float64 oracle (tests/_head_bar.py)
+    r64, r32 = hb.ref_pair(("single", flavour, rows, K), lambda dt: hb.single_ref(pred, fix, lab, ntm, K, half, CD, dt))
+    if rows:
+        assert torch.equal(r["conf"], r32["out"]["conf"].long().view_as(r["conf"]))
+    for k, gk in (("dpred2", got), ("ntm_grad2", ngrad)):
+        hb.report(f"{flavour}{'rows' if rows else ''} K={K}", k, hb.grad_bar(gk, r64[k], r32[k], f"{flavour} K={K} {k}"))
+
+
+PROD = {"v3": (4, 512, 1024, 6), "vgg": (8, 512, 512, 3)}           # (B, H, W, K) of bench.py --model v3 / vgg (its `dflt` table)
+
+
+def single_plan_geometry(dev, model, warmup=False):
+    """(h, w, pitch of the logits, pitch of the bf16 gradient) of the plan SimTSingleTrainer (warmup: WarmupSingleTrainer) builds at the
+    benchmarked size in bf16 (simt_amd/step_single.py: hd.ldp = plan.ldq / plan.ldp["x"], hd.ld_t = plan.dlogits["x"].shape[1])."""
+    def make():
+        from simt_amd import model_spec as ms
+        B, H, W, K = PROD[model]
+        K = 0 if warmup else K
+        if model == "v3":
+            from simt_amd.engine_v3 import V3Plan
+            st = ms.kaiming_init(v3_state_shapes(19, K, not warmup), seed=1234)
+            plan = V3Plan({k: v.to(dev) for k, v in st.items()}, B, H, W, 19, K, not warmup, dtype=torch.bfloat16, train=True)
+            (h, w), ldp = plan.feat_hw, plan.ldq
+        else:
+            from simt_amd.engine_vgg import VggPlan
+            st = ms.kaiming_init(vgg_state_shapes(19 + K), seed=1234)
+            plan = VggPlan({k: v.to(dev) for k, v in st.items()}, B, H, W, 19 + K, dtype=torch.bfloat16, train=True)
+            h, w, ldp = plan.heads[0].h, plan.heads[0].w, plan.ldp["x"]
+        dl = plan.dlogits["x"]
+        assert dl.dtype == torch.bfloat16 and dl.shape[0] == B * h * w
+        geo = (h, w, ldp, dl.shape[1])
+        del plan, dl
+        torch.cuda.empty_cache()
+        return geo
+    return hb.cached(("single plan geometry", model, warmup), make)
+
+
+@pytest.mark.parametrize("gscale", [1.0, 0.5])
+@pytest.mark.parametrize("model", ["v3", "vgg"])
+def test_single_head_production_form(dev, model, gscale):
+    """simt_head_loss / simt_head_grad as SimTSingleTrainer launches them at the benchmarked sizes (DeepLabv3: B = 4, 512 x 1024, K = 6,
+    up_half_pixel = fix_logits = 1; DeepLab-VGG16: B = 8, 512 x 512, K = 3): bf16 dpred2_t with the plan's pitch, the plan's logits pitch,
+    gscale = 1 / iter_size, conf_out + label_ws -- and dpred2_f32 from the SAME launch, so that the bf16 store is held bit for bit against
+    the fp32 one.  The bars of tests/_head_bar.py against the float64 oracle (so.simt_losses_single); the confidence labels equal to the fp32
+    oracle's; pad columns; the fp32 output at gscale = 0.5 bit for bit half the one at gscale = 1 (gscale enters once, in the factors
+    gscale * lambda / N of head_pass2: a power of two is exact); lout[0] = total * gscale."""
+    torch.set_num_threads(max(1, min(32, os.cpu_count() or 8)))
+    B, H, W, K = PROD[model]
+    h, w, ldp, ld_t = single_plan_geometry(dev, model)
+    Cn, half = 19, model == "v3"
+    Q = Cn + K
+    g = torch.Generator().manual_seed(29 + K)
+    pred = torch.randn(B, Q, h, w, generator=g) * 3
+    fix = torch.randn(B, Cn, h, w, generator=g) * 4
+    _, lab = so.synthetic_batch(B, H, W, CD.numpy(), seed=11)
+    ntm = so.ntm_init(Cn, K, 3)
+    r64, r32 = hb.ref_pair(("single prod refs", model), lambda dt: hb.single_ref(pred, fix, lab, ntm, K, half, CD, dt))
+    run = lambda gs: run_single_head(dev, pred, fix, lab, ntm, K, half, label_ws=True, grad_dtype=torch.bfloat16, ld_t=ld_t, gscale=gs, ldp=ldp)
+    base = hb.cached(("gpu single", model, 1.0), lambda: run(1.0))
+    r = base if gscale == 1.0 else run(gscale)
+    tag = f"{model} simt {B}x{H}x{W}"
+    nflip = int((r["conf"] != r32["out"]["conf"].long().view_as(r["conf"])).sum())
+    print(f"[head-bar] {tag}: {nflip} confidence labels differ from the fp32 oracle's; the references differ on "
+          f"{int((r64['out']['conf'] != r32['out']['conf']).sum())}", flush=True)
+    assert nflip == 0
+    hb.trainer_form(tag, "dpred", r["dp_raw"], r["dt"], r["back"], Q, ops.round_up(Q, 8), r64["dpred2"], r32["dpred2"], gscale)
+    close(r["lout"][0], r64["out"]["total"] * gscale, 1e-4, "lout[0] = total * gscale")
+    if gscale == 1.0:
+        hb.report(tag, "ntm_grad", hb.grad_bar(r["ntm_grad"], r64["ntm_grad2"], r32["ntm_grad2"], f"{tag} ntm_grad"))
+    else:
+        hb.half_is_bitwise(tag, "dpred", r["dp_raw"], base["dp_raw"])
 
 
 VGG_SMALL = [(0, 3, 32, 1, False), (2, 32, 32, 1, True), (5, 32, 64, 1, False), (7, 64, 64, 1, True), (10, 64, 64, 1, False),

@@ -18,6 +18,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
+import _head_bar as hb
+from _launch_oracle import SENTINEL
 from _warmup_single_oracle import OracleWarmupSingleTrainer
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
@@ -40,16 +42,27 @@ def _v3_feat_hw(H, W):
     return h, w
 
 
-def _run_head(dev, pred, lab, half, single=True):
+def _run_head(dev, pred, lab, half, single=True, *, pred1=None, lambda_seg=0.0, f32=True, grad_dtype=None, ld_t=0, gscale=1.0, ldp=None,
+              byte_maps=False, full=False):
     """One-head warm-up flavour (single = 1, mode = 1) of simt_head_loss + simt_head_grad on low-res logits pred [B, Q, h, w] (fp32, device)
     and labels lab [B, H, W] (int64, device): -> (hout, d/dpred [B, Q, h, w], g1).  single=False: the DeepLab-v2 warm-up mode with both heads
-    fed the same logits."""
+    fed the same logits, or the auxiliary head fed pred1 (weighted lambda_seg).
+
+    One launch can ask for everything the warm-up trainers ask for (simt_amd/step.py WarmupTrainer, step_single.py WarmupSingleTrainer:
+    dpred*_f32 = NULL, dpred*_t in the plan's dtype with the plan's pitch, gscale = 1 / iter_size): f32=False drops the fp32 outputs;
+    grad_dtype adds dpred*_t with pitch ld_t, pre-filled with SENTINEL; byte_maps gives conf_out + label_ws (these trainers leave them NULL);
+    full=True returns a dict instead (hout, dpred1, dpred2, dt1, dt2 raw, dp1_raw, dp2_raw, conf, g1)."""
     B, Q, h, w = pred.shape
     H, W = lab.shape[1:]
     lib = L.load()
-    ldp = ops.round_up(Q, 8)
+    ldp = ops.round_up(Q, 8) if ldp is None else ldp
     p_d = torch.zeros(B * h * w, ldp, device=dev)
     p_d[:, :Q] = pred.permute(0, 2, 3, 1).reshape(-1, Q)
+    p1_d = p_d
+    if pred1 is not None:
+        assert not single
+        p1_d = torch.zeros(B * h * w, ldp, device=dev)
+        p1_d[:, :Q] = pred1.permute(0, 2, 3, 1).reshape(-1, Q)
     part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Q, Q), device=dev)
     keys = torch.zeros(lib.simt_head_keys_count(), device=dev, dtype=torch.int64)
     hout = torch.zeros(lib.simt_head_hout_floats(Q, Q), device=dev)
@@ -58,18 +71,35 @@ def _run_head(dev, pred, lab, half, single=True):
     dp = torch.full((B * h * w, ldp), 5.0, device=dev)
     dp1 = torch.zeros(B * h * w, ldp, device=dev)
     hd = L.HeadDesc()
-    hd.pred1 = None if single else p_d.data_ptr()
+    hd.pred1 = None if single else p1_d.data_ptr()
     hd.pred2, hd.fixp, hd.label, hd.T1, hd.T2 = p_d.data_ptr(), None, lab.data_ptr(), None, None
     hd.part, hd.keys, hd.hout, hd.g1 = part.data_ptr(), keys.data_ptr(), hout.data_ptr(), g1.data_ptr()
     hd.dpred1_f32, hd.dpred2_f32, hd.dpred1_t, hd.dpred2_t = (None if single else dp1.data_ptr()), dp.data_ptr(), None, None
+    if not f32:
+        hd.dpred1_f32, hd.dpred2_f32 = None, None
     hd.B, hd.h, hd.w, hd.H, hd.W, hd.C, hd.Q = B, h, w, H, W, Q, Q
     hd.ldp, hd.ldf, hd.QP, hd.ld_f32, hd.ld_t, hd.grad_dtype = ldp, ldp, QP, ldp, 0, L.SIMT_F32
-    hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 2.0, -1.0, 0.0, 0.0, 1.0
+    dt = [None, None]
+    if grad_dtype is not None:
+        assert ld_t >= QP
+        dt = [torch.full((B * h * w, ld_t), SENTINEL, dtype=grad_dtype, device=dev) for _ in range(2)]
+        hd.dpred1_t, hd.dpred2_t = (None if single else dt[0].data_ptr()), dt[1].data_ptr()
+        hd.ld_t, hd.grad_dtype = ld_t, ops.dt_code(grad_dtype)
+    hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 2.0, -1.0, lambda_seg, 0.0, gscale
     hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 1, int(single), int(half), 0
+    conf = lws = None
+    if byte_maps:
+        conf, lws = (torch.full((B, H, W), 77, dtype=torch.uint8, device=dev) for _ in range(2))
+        hd.conf_out, hd.label_ws = conf.data_ptr(), lws.data_ptr()
     st = ops.stream_ptr()
     L.call("simt_head_loss", C.byref(hd), st)
     L.call("simt_head_grad", C.byref(hd), st)
     torch.cuda.synchronize()
+    if full:
+        back = lambda g: g.cpu()[:, :Q].reshape(B, h, w, Q).permute(0, 3, 1, 2)
+        return dict(hout=hout.cpu(), dpred1=back(dp1), dpred2=back(dp), dp1_raw=dp1.cpu(), dp2_raw=dp.cpu(), back=back, g1=g1,
+                    dt1=None if (dt[0] is None or single) else dt[0].cpu(), dt2=None if dt[1] is None else dt[1].cpu(),
+                    conf=None if conf is None else conf.cpu().long())
     return hout.cpu(), dp[:, :Q].reshape(B, h, w, Q).permute(0, 3, 1, 2).cpu(), dp[:, Q:].cpu(), g1
 
 
@@ -106,6 +136,39 @@ def test_one_head_warmup_kernel_vs_float64(dev, case):
     close(got, q.grad.cpu(), 1e-5, "d/dlogits")
     assert torch.all(pad == 0)
     assert torch.all(g1[0] == 7.0), "the one-head flavour wrote head-1 gradient rows"
+    # ... and every element on its own scale (tests/_head_bar.py): the float64 reference above, the same in fp32 on the CPU for the threshold
+    r32 = hb.cached(("warm1", case), lambda: hb.warmup_ref(None, pred, lab, 0.0, half, torch.float32))
+    hb.report(case, "d/dlogits", hb.grad_bar(got, q.grad.cpu(), r32["dpred2"], f"{case} d/dlogits"))
+
+
+@pytest.mark.parametrize("gscale", [1.0, 0.5])
+@pytest.mark.parametrize("model", ["v3", "vgg"])
+def test_one_head_warmup_production_form(dev, model, gscale):
+    """The one-head warm-up launch (single = 1, mode = 1) as WarmupSingleTrainer asks for it at the benchmarked sizes (DeepLabv3: B = 4,
+    512 x 1024; DeepLab-VGG16: B = 8, 512 x 512): bf16 dpred2_t with the plan's pitch, the plan's logits pitch, gscale = 1 / iter_size -- and
+    dpred2_f32 from the SAME launch, so that the bf16 store is held bit for bit against the fp32 one.  The bars of tests/_head_bar.py
+    against float64 autograd of the cross entropy; pad columns; the fp32 output at gscale = 0.5 bit for bit half the one at gscale = 1
+    (gscale enters once, in the factor gscale / N_valid of head_pass2: a power of two is exact); hout[14] = the unscaled loss."""
+    from test_gpu_single import PROD, single_plan_geometry
+    torch.set_num_threads(max(1, min(32, os.cpu_count() or 8)))
+    B, H, W, _K = PROD[model]
+    h, w, ldp, ld_t = single_plan_geometry(dev, model, warmup=True)
+    half = model == "v3"
+    assert (B, h, w, H, W) == SHAPES[model + "prod"]
+    pred = torch.randn(B, CN, h, w, generator=torch.Generator().manual_seed(31)) * 3
+    _, lab = so.synthetic_batch(B, H, W, CD.numpy(), seed=13)
+    r64, r32 = hb.ref_pair(("warm prod refs", model), lambda dt: hb.warmup_ref(None, pred, lab, 0.0, half, dt))
+    run = lambda gs: _run_head(dev, pred.to(dev), lab.to(dev), half, grad_dtype=torch.bfloat16, ld_t=ld_t, gscale=gs, ldp=ldp, full=True)
+    base = hb.cached(("gpu warm", model, 1.0), lambda: run(1.0))
+    r = base if gscale == 1.0 else run(gscale)
+    tag = f"{model} warm-up {B}x{H}x{W}"
+    hb.trainer_form(tag, "dpred", r["dp2_raw"], r["dt2"], r["back"], CN, ops.round_up(CN, 8), r64["dpred2"], r32["dpred2"], gscale)
+    tot = float(r64["total"])
+    assert abs(float(r["hout"][14]) - tot) <= 1e-4 * abs(tot) and float(r["hout"][14]) == float(r["hout"][1])
+    assert torch.all(r["g1"][0] == 7.0), "the one-head flavour wrote head-1 gradient rows"
+    if gscale == 0.5:
+        QP = ops.round_up(CN, 8)                                   # (the columns the kernel writes: the driver pre-fills the fp32 buffer)
+        hb.half_is_bitwise(tag, "dpred", r["dp2_raw"][:, :QP], base["dp2_raw"][:, :QP])
 
 
 @pytest.mark.parametrize("half", [True, False])
