@@ -446,6 +446,19 @@ int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* 
 int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb, int ldb,
                           int hib, int wib, int B, int H, int W, int C, int mode, float threshold, uint8_t* out, int64_t* counts,
                           simt_stream_t stream);
+/* class-balanced pseudo labels (CBST / BDL: per-class confidence thresholds).  (arg, conf) of a pixel are the arg-max and the maximum
+ * of mode 1 above, bit for bit: simt_pseudo_conf_u8 over the geometry of simt_pseudo_label_u8 (la = low-res PROBABILITIES),
+ * simt_pseudo_conf2_u8 over that of simt_pseudo_label2_u8 (la = LOGITS), one scale.
+ * hist != NULL: hist[arg][bin] += 1 for every pixel, bin = min(SIMT_CONF_BINS-1, max(0, (int)floorf(conf * SIMT_CONF_BINS))); int64
+ *   [C][SIMT_CONF_BINS], accumulated across calls, exact and order independent; needs C <= 64.
+ * out != NULL: out = arg where conf >= thr[arg], 255 elsewhere (uint8 [B][H][W], 4-byte aligned); counts as simt_pseudo_label_u8.
+ *   thr: C floats in HOST memory, copied into the launch (no device buffer, no synchronisation); out needs thr and counts.
+ * Both in one launch do both; both NULL is refused.  C <= 255. */
+#define SIMT_CONF_BINS 256
+int simt_pseudo_conf_u8(const float* la, int ha, int wa, int lda, int B, int H, int W, int C, const float* thr, uint8_t* out,
+                        int64_t* counts, int64_t* hist, simt_stream_t stream);
+int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, int B, int H, int W, int C, const float* thr,
+                         uint8_t* out, int64_t* counts, int64_t* hist, simt_stream_t stream);
 /* F.interpolate(bilinear) of an NHWC fp32 map [B][h][w][lds] (first C channels) to NCHW fp32 [B][C][H][W] and its adjoint
  * (model/deeplabv3.py:137 upsamples inside the model with align_corners=False; align_corners=1 = interp_target) */
 int simt_upsample_nchw(const float* src, int B, int h, int w, int lds, int C, int H, int W, int align_corners, float* dst,

@@ -13,6 +13,7 @@ SIMT_F32, SIMT_BF16 = 0, 1
 MAX_TAPS = 36
 ABI_VERSION = 2          # include/simt_hip.h SIMT_ABI_VERSION
 QMAX = 40
+CONF_BINS = 256          # include/simt_hip.h SIMT_CONF_BINS: confidence bins per class of simt_pseudo_conf*_u8
 
 c_p = C.c_void_p
 i32 = C.c_int32
@@ -185,6 +186,8 @@ SIGNATURES = {
     "simt_upsample2_sum_argmax": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_pseudo_label_u8": (_I, [c_p, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
     "simt_pseudo_label2_u8": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
+    "simt_pseudo_conf_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
+    "simt_pseudo_conf2_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),
     "simt_loss_ws_bytes": (_I, []),
@@ -221,7 +224,11 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:      # a library built before the symbol was added (the ABI version only counts layout changes)
+            raise SimtHipError(f"{LIB_PATH} does not export {name}: it was built from older sources, rebuild it "
+                               "(python -c 'import __graft_entry__ as g; g.build()')") from None
         fn.restype = res
         fn.argtypes = args
     if lib.simt_abi_version() != ABI_VERSION:      # a stale libsimt_hip.so reads past the end of the shorter descriptors it was built for

@@ -90,9 +90,16 @@ struct PseudoArgs {
 };
 
 // MODE 0: arg-max of up(la) + up(lb) -- the arithmetic of upsample_sum_argmax_kernel, statement for statement, so the labels are its
-// labels bit for bit.  MODE 1: max / arg-max of up(la); the arg-max where max > threshold, 255 elsewhere.
+// labels bit for bit.  MODE 1: max / arg-max of up(la); the caller keeps the arg-max where max > threshold (255 elsewhere).  `conf` is
+// the maximum: the confidence of mode 1, which the class-balanced kernels below bin and threshold per class -- one function, so their
+// (arg, conf) are the old kernel's bit for bit.
+struct ArgConf {
+  int arg;             // first-index arg-max
+  float conf;          // the maximum
+};
+
 template <int MODE>
-__device__ __forceinline__ int pseudo_pixel(const PseudoArgs& a, int b, int y, int x) {
+__device__ __forceinline__ ArgConf pseudo_pixel(const PseudoArgs& a, int b, int y, int x) {
   int a00, a01, a10, a11, b00 = 0, b01 = 0, b10 = 0, b11 = 0;
   float ay0, ay1, ax0, ax1, by0 = 0, by1 = 0, bx0 = 0, bx1 = 0;
   bil_taps(y, x, a.ha, a.wa, a.sya, a.sxa, a00, a01, a10, a11, ay0, ay1, ax0, ax1);
@@ -114,8 +121,7 @@ __device__ __forceinline__ int pseudo_pixel(const PseudoArgs& a, int b, int y, i
     }
     if (v > best) { best = v; arg = c; }     // first index on ties
   }
-  if (MODE == 1) return best > a.threshold ? arg : 255;   // strictly greater (:359)
-  return arg;
+  return {arg, best};
 }
 
 // One pixel per lane, so that neighbouring lanes gather neighbouring taps exactly as upsample_sum_argmax_kernel does (a version in which
@@ -164,6 +170,92 @@ __device__ __forceinline__ void pl_hist_flush(const unsigned int* sh, int nbins,
     if (sh[i]) atomicAdd(&counts[i], (unsigned long long)sh[i]);
 }
 
+// ---- class-balanced pseudo labels (CBST / the label generator of BDL): per class, the threshold is the confidence at a fixed rank among
+// that class's own predictions, so the export needs the per-class distribution of the confidence over the whole data list.  The kernels
+// below take (arg, conf) from the functions of the confidence mode and either count them into hist[arg][bin] (bin = floor(conf * 256)
+// clamped to [0, 255]: the scaling by a power of two is exact, so the bin is a pure function of the float), label with a per-class
+// threshold (kept iff conf >= thr[arg]; the output side is pl_store / pl_hist_flush), or both.
+//
+// The histogram is the hot path: on real frames a large share of the pixels of a frame fall into ONE word (road at conf ~ 1), and one
+// global word takes ~88 atomics / us.  So (1) the counters are private to the workgroup in LDS (C * 256 words, C <= 64), (2) equal keys
+// are aggregated within the wave before the LDS atomic: up to CONF_AGG_ROUNDS times the first lane still to do broadcasts its key, the
+// lanes holding that key are found with one ballot and the first lane adds their number -- a wave whose 64 lanes hit the hot bin
+// issues one add; the lanes left after the rounds (keys spread over many bins: little contention) add 1 each -- and (3) only the
+// non-zero bins are flushed, one 64-bit global atomic each.  Integer counts: exact and order independent.
+constexpr int CONF_BINS = SIMT_CONF_BINS, CONF_MAX_C = 64, CONF_AGG_ROUNDS = 4;
+
+struct ConfOut {
+  unsigned char* out;           // [B][H][W] labels, 4-byte aligned, or NULL
+  unsigned long long* counts;   // [C+1], accumulated (with out)
+  unsigned long long* hist;     // [C][CONF_BINS], accumulated, or NULL
+  float thr[255];               // per-class thresholds (with out)
+};
+
+__device__ __forceinline__ int conf_bin(float conf) {
+  const float f = fminf(fmaxf(floorf(conf * (float)CONF_BINS), 0.f), (float)(CONF_BINS - 1));
+  return (int)f;
+}
+
+// every lane of the wave calls this together (the callers' loop bounds are uniform over the block)
+__device__ __forceinline__ void conf_hist_add(bool valid, unsigned int key, unsigned int* sh) {
+  const int lane = (int)(threadIdx.x & 63);
+  unsigned long long todo = __ballot(valid);
+  for (int r = 0; r < CONF_AGG_ROUNDS && todo; ++r) {
+    const int leader = __ffsll(todo) - 1;
+    const unsigned int k = (unsigned int)__builtin_amdgcn_readlane((int)key, leader);
+    const unsigned long long m = __ballot(valid && key == k) & todo;
+    if (lane == leader) atomicAdd(&sh[k], (unsigned int)__popcll(m));
+    todo &= ~m;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(&sh[key], 1u);
+}
+
+// LDS of the class-balanced kernels: the label counts and thresholds of pl_store's side, and the confidence histogram
+template <bool STATS>
+struct ConfShared {
+  unsigned int counts[256];
+  float thr[256];
+  unsigned int hist[STATS ? CONF_MAX_C * CONF_BINS : 1];
+};
+
+template <int BLOCK, bool STATS, bool LABELS>
+__device__ __forceinline__ void conf_init(ConfShared<STATS>& sh, const ConfOut& o, int C) {
+  if (LABELS)
+    for (int i = threadIdx.x; i < C; i += BLOCK) sh.thr[i] = o.thr[i];
+  if (STATS)
+    for (int i = threadIdx.x; i < C * CONF_BINS; i += BLOCK) sh.hist[i] = 0u;
+  pl_hist_init<BLOCK>(sh.counts, C + 1);
+}
+// one grid-stride step: every lane of the block calls conf_emit with the key / label conf_pixel gave for pixel p (anything for p >= P)
+template <bool STATS, bool LABELS>
+__device__ __forceinline__ void conf_pixel(const ConfShared<STATS>& sh, ArgConf r, unsigned int& key, unsigned int& lab) {
+  if (STATS) key = (unsigned int)(r.arg * CONF_BINS + conf_bin(r.conf));
+  if (LABELS) lab = r.conf >= sh.thr[r.arg] ? (unsigned int)r.arg : 255u;
+}
+template <bool STATS, bool LABELS>
+__device__ __forceinline__ void conf_emit(ConfShared<STATS>& sh, const ConfOut& o, unsigned int key, unsigned int lab, long p, long P, int C) {
+  if (STATS) conf_hist_add(p < P, key, sh.hist);
+  if (LABELS) pl_store(lab, p, P, C, o.out, sh.counts);
+}
+template <int BLOCK, bool STATS, bool LABELS>
+__device__ __forceinline__ void conf_flush(const ConfShared<STATS>& sh, const ConfOut& o, int C) {
+  if (LABELS) {
+    pl_hist_flush<BLOCK>(sh.counts, C + 1, o.counts);
+    if (STATS) pl_hist_flush<BLOCK>(sh.hist, C * CONF_BINS, o.hist);
+  } else {
+    pl_hist_flush<BLOCK>(sh.hist, C * CONF_BINS, o.hist);
+  }
+}
+// the checks of the output side, and its arguments
+static int conf_out_fill(ConfOut& o, int C, const float* thr, uint8_t* out, int64_t* counts, int64_t* hist) {
+  SIMT_CHECK(out || hist);
+  SIMT_CHECK(!out || (thr && counts && ((uintptr_t)out & 3) == 0));
+  SIMT_CHECK(!hist || C <= CONF_MAX_C);
+  o.out = out; o.counts = (unsigned long long*)counts; o.hist = (unsigned long long*)hist;
+  for (int c = 0; c < 255; ++c) o.thr[c] = (out && c < C) ? thr[c] : 0.f;
+  return SIMT_OK;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(PL_BLOCK) void pseudo_label_u8_kernel(PseudoArgs a) {
   __shared__ unsigned int sh[256];
@@ -175,7 +267,8 @@ __global__ __launch_bounds__(PL_BLOCK) void pseudo_label_u8_kernel(PseudoArgs a)
     if (p < P) {
       const int x = (int)(p % a.W);
       const long t = p / a.W;
-      lab = (unsigned int)pseudo_pixel<MODE>(a, (int)(t / a.H), (int)(t % a.H), x);
+      const ArgConf r = pseudo_pixel<MODE>(a, (int)(t / a.H), (int)(t % a.H), x);
+      lab = (unsigned int)(MODE == 1 && !(r.conf > a.threshold) ? 255 : r.arg);   // strictly greater (:359)
     }
     pl_store(lab, p, P, a.C, a.out, sh);
   }
@@ -202,6 +295,54 @@ extern "C" int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, co
     hipLaunchKernelGGL(pseudo_label_u8_kernel<0>, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(pseudo_label_u8_kernel<1>, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+struct PseudoConfArgs {
+  PseudoArgs g;        // la, the geometry and C of mode 1 (lb, out, counts, threshold unused)
+  ConfOut o;
+};
+
+template <bool STATS, bool LABELS>
+__global__ __launch_bounds__(PL_BLOCK) void pseudo_conf_u8_kernel(PseudoConfArgs a) {
+  __shared__ ConfShared<STATS> sh;
+  conf_init<PL_BLOCK, STATS, LABELS>(sh, a.o, a.g.C);
+  const long P = (long)a.g.B * a.g.H * a.g.W;
+  for (long base = (long)blockIdx.x * PL_BLOCK; base < P; base += (long)gridDim.x * PL_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int key = 0u, lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.g.W);
+      const long t = p / a.g.W;
+      conf_pixel<STATS, LABELS>(sh, pseudo_pixel<1>(a.g, (int)(t / a.g.H), (int)(t % a.g.H), x), key, lab);
+    }
+    conf_emit<STATS, LABELS>(sh, a.o, key, lab, p, P, a.g.C);
+  }
+  conf_flush<PL_BLOCK, STATS, LABELS>(sh, a.o, a.g.C);
+}
+
+extern "C" int simt_pseudo_conf_u8(const float* la, int ha, int wa, int lda, int B, int H, int W, int C, const float* thr, uint8_t* out,
+                                   int64_t* counts, int64_t* hist, simt_stream_t stream) {
+  SIMT_CHECK(la && B > 0 && H > 0 && W > 0 && ha > 0 && wa > 0 && C > 0 && C <= 255 && C <= lda);
+  PseudoConfArgs a;
+  if (int rc = conf_out_fill(a.o, C, thr, out, counts, hist)) return rc;
+  PseudoArgs& g = a.g;
+  g.la = la; g.lb = nullptr; g.out = nullptr; g.counts = nullptr;
+  g.B = B; g.ha = ha; g.wa = wa; g.lda = lda; g.hb = 0; g.wb = 0; g.ldb = 0; g.H = H; g.W = W; g.C = C;
+  g.sya = H > 1 ? (float)(ha - 1) / (float)(H - 1) : 0.f;
+  g.sxa = W > 1 ? (float)(wa - 1) / (float)(W - 1) : 0.f;
+  g.syb = 0.f; g.sxb = 0.f; g.threshold = 0.f;
+  const long P = (long)B * H * W;
+  long grid = (P + PL_BLOCK - 1) / PL_BLOCK;
+  if (grid > PL_MAX_GRID) grid = PL_MAX_GRID;
+  const dim3 gr((unsigned)grid), blk(PL_BLOCK);
+  if (hist && out)
+    hipLaunchKernelGGL((pseudo_conf_u8_kernel<true, true>), gr, blk, 0, (hipStream_t)stream, a);
+  else if (hist)
+    hipLaunchKernelGGL((pseudo_conf_u8_kernel<true, false>), gr, blk, 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((pseudo_conf_u8_kernel<false, true>), gr, blk, 0, (hipStream_t)stream, a);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }
@@ -518,8 +659,10 @@ struct Pseudo2Args {
   float threshold;
 };
 
-template <int V>
-__device__ __forceinline__ int up2_confident(const Up2Scale& s, int C, float threshold, int b, int y, int x) {
+// PAIR: -> the first-index arg-max of the resampled probabilities and their maximum, the confidence, for the class-balanced kernels below
+// (one function, so the two agree bit for bit; `threshold` unused)
+template <int V, bool PAIR = false>
+__device__ __forceinline__ auto up2_confident(const Up2Scale& s, int C, float threshold, int b, int y, int x) {
   Up2Taps t;
   up2_taps(s, b, y, x, t);
   float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, inv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -551,7 +694,10 @@ __device__ __forceinline__ int up2_confident(const Up2Scale& s, int C, float thr
       if (v > best) { best = v; arg = c0 + k; }     // first index on ties
     }
   }
-  return best > threshold ? arg : 255;             // strictly greater (trainV2_simt.py:359)
+  if constexpr (PAIR)
+    return ArgConf{arg, best};
+  else
+    return best > threshold ? arg : 255;             // strictly greater (trainV2_simt.py:359)
 }
 
 // 512-thread blocks: the two-scale float4 gather holds ~220 VGPRs (2 waves per SIMD, as upsample2_sum_argmax_kernel runs), which a
@@ -602,6 +748,64 @@ extern "C" int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, i
     hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 4>), g, blk, 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 1>), g, blk, 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+// the class-balanced kernels over the gather of mode 1 above (up2_confident<V, true>): same block size and grid cap, for the same reasons.
+// The float4 kernels hold 128-139 VGPRs, so the label and combined ones run 3 waves per SIMD where pseudo_label2_u8_kernel<1, 4> (121)
+// runs 4; a form of the label kernel that fit 124 had its 16-byte loads of the last sweep split into elements and ran 370 us against
+// 319 us for this one and 317 us for that kernel: the gather is bound by its load instructions, not by occupancy.
+struct PseudoConf2Args {
+  Up2Scale s;
+  int B, H, W, C;
+  ConfOut o;
+};
+
+template <bool STATS, bool LABELS, int V>
+__global__ __launch_bounds__(PL2_BLOCK) void pseudo_conf2_u8_kernel(PseudoConf2Args a) {
+  __shared__ ConfShared<STATS> sh;
+  conf_init<PL2_BLOCK, STATS, LABELS>(sh, a.o, a.C);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL2_BLOCK; base < P; base += (long)gridDim.x * PL2_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int key = 0u, lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      conf_pixel<STATS, LABELS>(sh, up2_confident<V, true>(a.s, a.C, 0.f, (int)(t / a.H), (int)(t % a.H), x), key, lab);
+    }
+    conf_emit<STATS, LABELS>(sh, a.o, key, lab, p, P, a.C);
+  }
+  conf_flush<PL2_BLOCK, STATS, LABELS>(sh, a.o, a.C);
+}
+
+template <int V>
+static void launch_conf2(const PseudoConf2Args& a, dim3 g, hipStream_t stream) {
+  const dim3 blk(PL2_BLOCK);
+  if (a.o.hist && a.o.out)
+    hipLaunchKernelGGL((pseudo_conf2_u8_kernel<true, true, V>), g, blk, 0, stream, a);
+  else if (a.o.hist)
+    hipLaunchKernelGGL((pseudo_conf2_u8_kernel<true, false, V>), g, blk, 0, stream, a);
+  else
+    hipLaunchKernelGGL((pseudo_conf2_u8_kernel<false, true, V>), g, blk, 0, stream, a);
+}
+
+extern "C" int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, int B, int H, int W, int C,
+                                    const float* thr, uint8_t* out, int64_t* counts, int64_t* hist, simt_stream_t stream) {
+  SIMT_CHECK(la && B > 0 && H > 0 && W > 0 && C > 0 && C <= 255 && C <= lda && ha > 0 && wa > 0 && hia > 0 && wia > 0);
+  SIMT_CHECK((long)B * ha * wa * lda < 2147483647L);
+  PseudoConf2Args a;
+  if (int rc = conf_out_fill(a.o, C, thr, out, counts, hist)) return rc;
+  fill_up2(a.s, la, ha, wa, lda, hia, wia, H, W);
+  a.B = B; a.H = H; a.W = W; a.C = C;
+  const long P = (long)B * H * W;
+  long grid = (P + PL2_BLOCK - 1) / PL2_BLOCK;
+  if (grid > PL2_MAX_GRID) grid = PL2_MAX_GRID;
+  if (lda % 4 == 0 && ((uintptr_t)la & 15) == 0)
+    launch_conf2<4>(a, dim3((unsigned)grid), (hipStream_t)stream);
+  else
+    launch_conf2<1>(a, dim3((unsigned)grid), (hipStream_t)stream);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }

@@ -6,9 +6,13 @@ The reference made its lists from its evaluation loop: the commented-out save li
 (evaluate_simt: main head at two input scales, upsampled to 1024 x 2048 with align_corners=True, summed, arg-maxed) and :214-219
 (evaluate_warmup: one scale), and compute_ClassDistribution.py:66-92 for the prior.  `--threshold T` instead applies the SimT confidence
 rule of trainV2_simt.py:353-359 (high threshold only): softmax at low resolution, upsampled, arg-max where max > T, 255 elsewhere.
+`--class-balanced P` is the class-balanced rule of CBST / the label generator of BDL: the same confidence, but one threshold per class,
+the confidence at the rank that keeps the share P of that class's own predictions (BDL: the median, P = 0.5), capped at
+`--threshold-cap` (0.9); a pixel is kept iff conf >= thres[class].  It takes two passes over the list: statistics, then labels.
 
     python -m simt_amd.tools.make_pseudo_labels --restore-from src.pth --arch single --data-dir $CS --data-list train.txt \
-        --out-name pseudo_mine --list-out pseudo_mine.lst [--threshold 0.8] [--save-color --devkit-dir dataset/cityscapes_list]
+        --out-name pseudo_mine --list-out pseudo_mine.lst [--threshold 0.8 | --class-balanced 0.5 [--threshold-cap 0.9]]
+        [--thresholds-from pseudo_subset_thresholds.json] [--save-color --devkit-dir dataset/cityscapes_list]
 
 --arch: multi (DeeplabMulti, the SimT DeepLab-v2), single (Res_Deeplab), v3 (DeepLabv3 at --v3-layers) or vgg (DeeplabVGG).  A v3 / vgg
 checkpoint is read like the warm-up stage reads it (the module's own keys; a torchvision ImageNet file is mapped, but its classifier is
@@ -18,7 +22,9 @@ rule takes the softmax of that input-size map before the align_corners=True resa
 
 Device: both eval-mode forwards (engine.TrunkPlan / engine_v3.V3Plan / engine_vgg.VggPlan, BN folded), the resizes
 (data.pipeline.InputPrep, Pillow-exact) and one fused upsample + arg-max kernel (simt_pseudo_label_u8; simt_pseudo_label2_u8 for v3,
-both resamples per label pixel) that writes the uint8 label map and the class counts.  Host: PNG decoding on a bounded thread pool,
+both resamples per label pixel) that writes the uint8 label map and the class counts; for the class-balanced rule
+simt_pseudo_conf_u8 / simt_pseudo_conf2_u8, which also count the confidence per class into 256 bins.  Host: the thresholds from that
+histogram (class_thresholds), PNG decoding on a bounded thread pool,
 pinned copies of the label maps (guarded by events), PNG encoding on a writer pool, atomic file writes."""
 import argparse
 import json
@@ -37,6 +43,9 @@ from simt_amd.tools.evaluate_cityscapes import v3_low_res_forward, v3_low_res_lo
 
 MAX_WORKERS = 16
 ARCHS = ("multi", "single", "v3", "vgg")
+MODES = ("argmax", "confidence", "class_balanced")
+CONF_BINS = L.CONF_BINS                                # confidence bins per class (SIMT_CONF_BINS)
+MAX_CB_CLASSES = 64                                    # the histogram kernel's LDS holds 64 x 256 counters
 DEFAULT_SCALES = ((512, 1024), (640, 1280))          # (h, w): the crop sizes (1024, 512) and (1280, 640) of evaluate_simt :103-106
 
 
@@ -48,22 +57,26 @@ class PseudoLabeller:
     (simt_pseudo_label2_u8 applies it).  arch "vgg": DeeplabVGG(C + K), head x.  layers: the plans' trunk depth, as for Evaluator.
     mode "argmax": up(logits) summed over the scales, arg-max (one scale = evaluate_warmup).
     mode "confidence": first scale only, softmax -> up -> arg-max where max > threshold, else 255 (v3: the softmax of the input-size map).
+    mode "class_balanced": the confidence of mode "confidence"; accumulate(*images) adds its per-class histogram to `conf_hist` (int64
+    [C, 256], device), set_thresholds(thr) installs per-class thresholds, label(*images) then keeps arg-max where conf >= thr[arg-max].
     label(*images) -> uint8 [B, H, W] on the device; `counts` accumulates int64 [C+1] (classes, then the 255s)."""
 
     def __init__(self, state, *, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
                  mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, batch=1):
         if arch not in ARCHS:
             raise ValueError(f"arch must be one of {ARCHS}, not {arch!r}")
-        if mode not in ("argmax", "confidence"):
-            raise ValueError(f"mode must be 'argmax' or 'confidence', not {mode!r}")
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, not {mode!r}")
         if arch == "single" and open_classes:
             raise ValueError("the single-head model has no open-set classes")
         if not 0 < num_classes <= 255:
             raise ValueError("uint8 labels hold at most 255 classes (255 = ignore)")
+        if mode == "class_balanced" and num_classes > MAX_CB_CLASSES:
+            raise ValueError(f"class-balanced labels take at most {MAX_CB_CLASSES} classes")
         self.dev = torch.device(device)
         self.C, self.mode, self.threshold, self.dtype = num_classes, mode, float(threshold), dtype
         scales = tuple(tuple(s) for s in scales)
-        if mode == "confidence":
+        if mode != "argmax":
             scales = scales[:1]
         self.arch = arch
         params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
@@ -89,13 +102,50 @@ class PseudoLabeller:
         self.B, (self.H, self.W) = batch, tuple(label_hw)
         self.labels = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.uint8)
         self.counts = torch.zeros(num_classes + 1, device=self.dev, dtype=torch.int64)
-        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode == "confidence" and arch != "v3" else None
+        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode != "argmax" and arch != "v3" else None
+        self.conf_hist = torch.zeros(num_classes, CONF_BINS, device=self.dev, dtype=torch.int64) if mode == "class_balanced" else None
+        self.thresholds = None
+
+    def set_thresholds(self, thr):
+        """Install the per-class thresholds of mode "class_balanced": C float32 values (kept iff conf >= thr[class])."""
+        if self.mode != "class_balanced":
+            raise ValueError("per-class thresholds belong to mode 'class_balanced'")
+        thr = np.ascontiguousarray(np.asarray(thr, dtype=np.float32).reshape(-1))
+        if thr.shape != (self.C,) or np.isnan(thr).any():
+            raise ValueError(f"{self.C} thresholds expected (no NaN), got {thr!r}")
+        self.thresholds = thr
+
+    def _conf_launch(self, images, thr, out, counts, hist):
+        """The forward of the first scale, then one class-balanced launch (labels, statistics or both)."""
+        if len(images) != len(self.plans):
+            raise ValueError(f"{len(self.plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+        tail = (self.B, self.H, self.W, self.C, thr.ctypes.data if thr is not None else None, ops._p(out), ops._p(counts), ops._p(hist),
+                ops.stream_ptr())
+        if self.arch == "v3":
+            (la, ha, wa, lda, hia, wia), = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
+            L.call("simt_pseudo_conf2_u8", ops._p(la), ha, wa, lda, hia, wia, *tail)
+            return
+        o = self.plans[0].forward(images[0].to(self.dev))[self.head]
+        B, h, w, ld = o.shape
+        ops.softmax_rows(o, ld, self.prob, ld, B * h * w, self.C)
+        L.call("simt_pseudo_conf_u8", ops._p(self.prob), h, w, ld, *tail)
+
+    def accumulate(self, *images):
+        """Mode "class_balanced": add the frame's confidence histogram to `conf_hist` (no labels are written)."""
+        if self.mode != "class_balanced":
+            raise ValueError("accumulate() belongs to mode 'class_balanced'")
+        self._conf_launch(images, None, None, None, self.conf_hist)
 
     def label(self, *images):
         """images: one [B,3,h,w] fp32 tensor (BGR - mean) per scale.  Returns the label map uint8 [B,H,W] (device, reused by the next
         call) and adds its class counts to `counts`."""
         if len(images) != len(self.plans):
             raise ValueError(f"{len(self.plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+        if self.mode == "class_balanced":
+            if self.thresholds is None:
+                raise RuntimeError("class-balanced labels need thresholds: accumulate() over the list, class_thresholds(), set_thresholds()")
+            self._conf_launch(images, self.thresholds, self.labels, self.counts, None)
+            return self.labels
         mode = 1 if self.mode == "confidence" else 0
         if self.arch == "v3":
             outs = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
@@ -162,6 +212,82 @@ def class_dist(counts, num_classes):
     return c / (np.sum(c) + 10e-10)
 
 
+def class_thresholds(hist, portion, cap=0.9):
+    """Per-class confidence thresholds of the class-balanced rule from the binned confidences: float32 [C].
+
+    hist: [C, bins] counts, bin = min(bins-1, floor(conf * bins)) (simt_pseudo_conf*_u8).  BDL sorts a class's confidences ascending and
+    takes x[round(n * 0.5)], then caps at 0.9; with the share `portion` to keep that index is k = min(round(n * (1 - portion)), n - 1)
+    (np.round: half to even).  Here the threshold is the LOWER EDGE of the bin holding x[k]: b = the smallest bin whose inclusive
+    cumulative count exceeds k, t = min(float32(b / bins), float32(cap)).  So, uncapped, t <= x[k] < t + 1/bins (a resolution of 1/256),
+    the pixels with conf >= t are exactly hist[c][b:].sum() -- at least the n - k asked for, never fewer -- and, t being a float,
+    conf >= t is conf > nextafter(t, -inf): the strict rule of the confidence mode.  A class without pixels gets 0; portion = 1 (k = 0) gives the lower edge of the
+    class's lowest occupied bin -- 0 for a class with a pixel below 1/bins -- and keeps every pixel."""
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or not np.issubdtype(hist.dtype, np.integer) or (hist < 0).any():
+        raise ValueError("hist must be a [C, bins] array of non-negative integer counts")
+    if not 0 < portion <= 1:
+        raise ValueError(f"portion must be in (0, 1], not {portion}")
+    bins = hist.shape[1]
+    thr = np.zeros(hist.shape[0], np.float32)
+    for c, row in enumerate(hist.astype(np.int64)):
+        n = int(row.sum())
+        if n == 0:
+            continue
+        k = min(int(np.round(n * (1 - portion))), n - 1)
+        b = int(np.searchsorted(np.cumsum(row), k, side="right"))
+        thr[c] = min(np.float32(b / bins), np.float32(cap))
+    return thr
+
+
+def thresholds_path(list_out, out_name):
+    """<out-name>_thresholds.json beside the list file."""
+    return osp.join(osp.dirname(osp.abspath(list_out)), f"{out_name}_thresholds.json")
+
+
+def thresholds_record(thr, counts, hist, *, portion, cap, data_list, source=None):
+    """The contents of <out-name>_thresholds.json.  Per class: the pixels predicted as it and their confidence histogram (null / absent
+    when the thresholds were given, not computed from this list), the threshold, the pixels kept and their share."""
+    thr = np.asarray(thr, np.float32)
+    C = len(thr)
+    classes = []
+    for c in range(C):
+        n = int(hist[c].sum()) if hist is not None else None
+        kept = int(counts[c])
+        e = {"class": c, "pixels": n, "threshold": float(thr[c]), "kept": kept, "kept_share": kept / n if n else None}
+        if hist is not None:
+            e["hist"] = [int(v) for v in hist[c]]
+        classes.append(e)
+    return {"num_classes": C, "bins": CONF_BINS, "portion": portion, "cap": cap, "data_list": data_list, "thresholds_from": source,
+            "classes": classes}
+
+
+def save_json_atomic(obj, path):
+    tmp = f"{path}.{os.getpid()}.tmp"
+    try:
+        with open(tmp, "w") as f:
+            json.dump(obj, f, indent=1)
+            f.write("\n")
+        os.replace(tmp, path)
+    finally:
+        if osp.exists(tmp):
+            os.remove(tmp)
+
+
+def load_thresholds(path, num_classes):
+    """The thresholds of a file written by an earlier class-balanced export (--thresholds-from): -> (float32 [C], the record).
+    Raises ValueError naming the field when the file was made for another class count or binning."""
+    with open(path, "r") as f:
+        rec = json.load(f)
+    for field, want in (("num_classes", num_classes), ("bins", CONF_BINS)):
+        if rec.get(field) != want:
+            raise ValueError(f"{path}: {field} is {rec.get(field)!r}, this export has {field} = {want}")
+    classes = rec.get("classes")
+    if not isinstance(classes, list) or len(classes) != num_classes:
+        raise ValueError(f"{path}: 'classes' must list {num_classes} entries")
+    thr = np.array([e["threshold"] for e in classes], dtype=np.float32)       # floats were written from float32: exact
+    return thr, rec
+
+
 def save_png_atomic(img, path):
     """Encode to a temporary name in the target directory, then os.replace: a reader never sees a partial file."""
     tmp = f"{path}.{os.getpid()}.tmp"
@@ -198,10 +324,16 @@ def _bounded_map(pool, fn, items, depth):
 
 def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", save_color=False, devkit_dir=None, workers=8,
            class_dist_out=None, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
-           mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, labeller=None, verbose=True):
+           mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, labeller=None, verbose=True,
+           portion=0.5, cap=0.9, thresholds=None, thresholds_source=None):
     """Label every frame of cityscapesDataSet(data_dir, data_list, set=set_name) and write
     <data_dir>/<out_name>/<basename>.png (8-bit trainIds, 255 = ignore; with save_color also <basename>_color.png), the list file
-    `list_out` and the prior `class_dist_out` (default: ClassDist_<out_name>.npy beside the list).  Returns the int64 counts [C+1]."""
+    `list_out` and the prior `class_dist_out` (default: ClassDist_<out_name>.npy beside the list).  Returns the int64 counts [C+1].
+
+    mode "class_balanced": a first pass over the whole list only accumulates the per-class confidence histogram (nothing is written),
+    class_thresholds(hist, portion, cap) gives the thresholds, and the second pass labels with them; `thresholds` (C floats, e.g. of
+    load_thresholds) skips the first pass.  Also writes <out_name>_thresholds.json beside the list; the prior is that of the kept
+    pixels, as in confidence mode."""
     from PIL import Image
 
     from simt_amd.data.pipeline import IMG_MEAN, InputPrep
@@ -220,6 +352,9 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
     if lab.B != 1:
         raise ValueError("export labels one frame at a time (batch 1)")
     C = lab.C
+    balanced = lab.mode == "class_balanced"
+    if balanced and not 0 < portion <= 1:
+        raise ValueError(f"portion must be in (0, 1], not {portion}")
     ds = cityscapesDataSet(data_dir, data_list, crop_size=(lab.scales[0][1], lab.scales[0][0]), mean=IMG_MEAN, scale=False, mirror=False,
                            set=set_name)
     os.makedirs(osp.join(data_dir, out_name), exist_ok=True)
@@ -236,17 +371,33 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
     # pinned staging buffers, one per label map in flight: the GPU labels frame i+1 while the writers encode frame i
     slots = [{"host": torch.empty(1, lab.H, lab.W, dtype=torch.uint8).pin_memory(), "ready": torch.cuda.Event(), "job": None}
              for _ in range(workers + 2)]
-    preps, xs = {}, None
-    lines = []
-    with ThreadPoolExecutor(workers) as readers, ThreadPoolExecutor(workers) as writers:
+    preps = {}
+    xs = [torch.empty(1, 3, h, w, device=dev) for (h, w) in lab.scales]
+
+    def frames(readers):
+        """(index, name) of every frame of the list, in order, with its resized inputs in `xs`."""
         for i, (rgb, _, name) in enumerate(_bounded_map(readers, ds.decode, range(len(ds)), 2 * workers)):
             key = rgb.shape[:2]
             if key not in preps:
                 preps[key] = [InputPrep(1, key, (w, h), dev, with_label=False) for (h, w) in lab.scales]
-                xs = [torch.empty(1, 3, h, w, device=dev) for (h, w) in lab.scales]
             rgb_d = torch.from_numpy(rgb[None]).to(dev)
             for prep, x in zip(preps[key], xs):
                 prep.run(rgb_d, x)
+            yield i, name
+
+    hist = None
+    if balanced:
+        if thresholds is None:                           # pass 1: statistics only
+            lab.conf_hist.zero_()
+            with ThreadPoolExecutor(workers) as readers:
+                for _ in frames(readers):
+                    lab.accumulate(*xs)
+            hist = lab.conf_hist.cpu().numpy()
+            thresholds = class_thresholds(hist, portion, cap)
+        lab.set_thresholds(thresholds)
+    lines = []
+    with ThreadPoolExecutor(workers) as readers, ThreadPoolExecutor(workers) as writers:
+        for i, name in frames(readers):
             out = lab.label(*xs)
             slot = slots[i % len(slots)]
             if slot["job"] is not None:
@@ -264,12 +415,16 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
         f.write("".join(line + "\n" for line in lines))
     os.replace(tmp, list_out)
     save_npy_atomic(class_dist(counts, C), class_dist_out)
+    if balanced:
+        given = hist is None
+        save_json_atomic(thresholds_record(lab.thresholds, counts, hist, portion=None if given else portion, cap=None if given else cap,
+                                           data_list=data_list, source=thresholds_source), thresholds_path(list_out, out_name))
     if verbose:
         total = max(int(counts.sum()), 1)
         share = counts[:C] / max(int(counts[:C].sum()), 1)
         print(f"{len(lines)} label maps -> {osp.join(data_dir, out_name)}; list {list_out}; prior {class_dist_out}")
         for c in range(C):
-            print(f"class {c:3d}: {100 * share[c]:6.2f} %")
+            print(f"class {c:3d}: {100 * share[c]:6.2f} %" + (f"   threshold {lab.thresholds[c]:.6f}" if balanced else ""))
         print(f"ignored (255): {100 * counts[C] / total:.2f} % of the pixels")
     return counts
 
@@ -308,6 +463,13 @@ def get_arguments(argv=None):
     p.add_argument("--class-dist-out", type=str, default=None, help="class prior .npy (default ClassDist_<out-name>.npy beside the list)")
     p.add_argument("--threshold", type=float, default=None,
                    help="confidence mode: softmax arg-max where max > T, 255 elsewhere (trainV2_simt.py:353-359); default: plain arg-max")
+    p.add_argument("--class-balanced", type=float, default=None, metavar="P",
+                   help="class-balanced mode (CBST / BDL): per class, keep the share P (0 < P <= 1) of its most confident predictions; "
+                        "the threshold is the lower edge of the 1/256 confidence bin at that rank, capped at --threshold-cap")
+    p.add_argument("--threshold-cap", type=float, default=0.9, metavar="T", help="upper limit of the class-balanced thresholds")
+    p.add_argument("--thresholds-from", type=str, default=None, metavar="FILE",
+                   help="class-balanced mode with the thresholds of <out-name>_thresholds.json of an earlier export (e.g. of a subset "
+                        "list): no statistics pass")
     p.add_argument("--save-color", action="store_true", help="also write <name>_color.png with the palette of <devkit-dir>/info.json")
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     p.add_argument("--eval-dtype", choices=["f32", "bf16"], default="f32",
@@ -318,6 +480,16 @@ def get_arguments(argv=None):
     args = p.parse_args(argv)
     if args.arch == "single" and args.open_classes:
         p.error("--arch single: Res_Deeplab has no open-set classes (--open-classes must be 0)")
+    if args.threshold is not None and (args.class_balanced is not None or args.thresholds_from):
+        p.error("--threshold (one global threshold) and --class-balanced / --thresholds-from (one per class) exclude each other")
+    if args.class_balanced is not None and not 0 < args.class_balanced <= 1:
+        p.error(f"--class-balanced P: the share to keep must be in (0, 1], not {args.class_balanced}")
+    if args.class_balanced is not None and args.thresholds_from:
+        p.error("--thresholds-from takes the thresholds as they are: give it without --class-balanced P")
+    if not 0 < args.threshold_cap <= 1:
+        p.error(f"--threshold-cap must be in (0, 1], not {args.threshold_cap}")
+    if (args.class_balanced is not None or args.thresholds_from) and args.num_classes > MAX_CB_CLASSES:
+        p.error(f"class-balanced labels take at most {MAX_CB_CLASSES} classes")
     return args
 
 
@@ -353,6 +525,12 @@ def main(argv=None):
     from simt_amd import model_spec as ms
     from simt_amd.tools.trainV2_simt import restore
     C, K = args.num_classes, args.open_classes
+    thresholds = None
+    if args.thresholds_from:                                         # checked before the GPU is touched, like everything below
+        try:
+            thresholds, _ = load_thresholds(args.thresholds_from, C)
+        except (OSError, ValueError, KeyError, TypeError) as e:
+            raise SystemExit(f"--thresholds-from: {e}")
     if args.arch in SINGLE_MODELS:                                   # checked before the GPU is touched
         state, n, _ = restore_single_model(args.arch, args.restore_from, C, K, tuple(args.v3_layers))
     if not torch.cuda.is_available():
@@ -368,14 +546,19 @@ def main(argv=None):
     sizes = args.input_size or [(1024, 512), (1280, 640)]
     dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     list_out = args.list_out or f"{args.out_name}.lst"
-    mode = "argmax" if args.threshold is None else "confidence"
+    balanced = args.class_balanced is not None or thresholds is not None
+    mode = "class_balanced" if balanced else "argmax" if args.threshold is None else "confidence"
     print(f"restored {n} tensors from {args.restore_from}; arch {args.arch}, {mode}"
           + (f" (threshold {args.threshold})" if args.threshold is not None else "")
+          + (f" (keep {args.class_balanced} per class, cap {args.threshold_cap})" if args.class_balanced is not None else "")
+          + (f" (thresholds of {args.thresholds_from})" if thresholds is not None else "")
           + ("" if dtype == torch.float32 else "   (bf16 plans: not the reference's fp32 arithmetic)"))
     export(state, args.data_dir, args.data_list, args.out_name, list_out, set_name=args.set, save_color=args.save_color,
            devkit_dir=args.devkit_dir, workers=args.num_workers, class_dist_out=args.class_dist_out, num_classes=C, open_classes=K,
            arch=args.arch, scales=[(h, w) for (w, h) in sizes], label_hw=(args.label_size[1], args.label_size[0]), mode=mode,
-           threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev, layers=layers)
+           threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev, layers=layers,
+           portion=args.class_balanced if args.class_balanced is not None else 0.5, cap=args.threshold_cap, thresholds=thresholds,
+           thresholds_source=args.thresholds_from)
 
 
 if __name__ == "__main__":
