@@ -459,6 +459,40 @@ int simt_pseudo_conf_u8(const float* la, int ha, int wa, int lda, int B, int H, 
                         int64_t* counts, int64_t* hist, simt_stream_t stream);
 int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, int B, int H, int W, int C, const float* thr,
                          uint8_t* out, int64_t* counts, int64_t* hist, simt_stream_t stream);
+/* test-time augmentation (mirror / multi-scale): the label of n <= SIMT_TTA_MAX maps ("terms", one forward each), any of which may belong
+ * to the horizontally mirrored frame.  Value of term t, channel c, at label pixel (b, y, x), fp32:
+ *   one-resample family (hi == wi == 0): the value simt_upsample_sum_argmax forms for that map (align_corners=True, ATen's association);
+ *     with `flip` every tap's column index ix is read at w-1-ix, weights unchanged -- bit for bit the plain term on the column-reversed map;
+ *   two-resample family (hi, wi > 0): the value simt_upsample2_sum_argmax forms; with `flip` each virtual column vx of the outer
+ *     (align_corners=True) taps becomes wi-1-vx before the inner (align_corners=False) taps are formed.
+ * mode 0: s[c] = ((v_0[c] + v_1[c]) + v_2[c]) + ... in term order; label = first-index arg-max; written to pred and / or out (+ counts,
+ *   whose 255 bin stays 0).
+ * mode 1 (one-resample family; maps = simt_softmax_rows PROBABILITIES): p[c] = (v_0[c] + ... + v_{n-1}[c]) * (1.0f / n); (arg, conf) = its
+ *   first-index arg-max and maximum; out (+ counts) as simt_pseudo_label_u8 mode 1 (thr == NULL: kept where conf > threshold) or as
+ *   simt_pseudo_conf_u8 (thr != NULL: kept where conf >= thr[arg]); hist as simt_pseudo_conf_u8.  out, hist or both in one launch.
+ * Refused (SIMT_ERR_INVALID, nothing launched): n outside 1..SIMT_TTA_MAX, terms of both families, mode 1 in the two-resample family, pred
+ * in mode 1, thr / hist in mode 0, out without counts, nothing to write, C > ld of a term, hist with C > 64, B*h*w*ld >= 2^31 for a term.
+ * The descriptor is read on the host during the call and travels as kernel arguments: no device copy, no synchronisation. */
+#define SIMT_TTA_MAX 8
+typedef struct {
+  const float* l;          /* [B][h][w][ld] fp32, first C channels used */
+  int32_t h, w, ld;
+  int32_t hi, wi;          /* 0, 0: one resample (h, w) -> (H, W); > 0: two resamples through a virtual [hi][wi] map */
+  int32_t flip;            /* the map belongs to the horizontally mirrored frame */
+} simt_tta_term;
+typedef struct {
+  simt_tta_term t[SIMT_TTA_MAX];
+  int32_t n;               /* 1 .. SIMT_TTA_MAX; all terms of one family */
+  int32_t B, H, W, C;      /* C <= 255; C <= ld of every term */
+  int32_t mode;            /* 0: logits, summed.  1: probabilities, averaged */
+  float threshold;         /* mode 1 with thr == NULL */
+  const float* thr;        /* mode 1: C floats in HOST memory (copied into the launch), or NULL */
+  int32_t* pred;           /* [B][H][W] int32 arg-max, or NULL (mode 0 only) */
+  uint8_t* out;            /* [B][H][W] uint8 labels, 4-byte aligned, or NULL */
+  int64_t* counts;         /* [C+1] accumulated, required with out */
+  int64_t* hist;           /* mode 1: [C][SIMT_CONF_BINS] accumulated, C <= 64, or NULL */
+} simt_tta_desc;
+int simt_tta_label(const simt_tta_desc* d, simt_stream_t stream);
 /* F.interpolate(bilinear) of an NHWC fp32 map [B][h][w][lds] (first C channels) to NCHW fp32 [B][C][H][W] and its adjoint
  * (model/deeplabv3.py:137 upsamples inside the model with align_corners=False; align_corners=1 = interp_target) */
 int simt_upsample_nchw(const float* src, int B, int h, int w, int lds, int C, int H, int W, int align_corners, float* dst,

@@ -113,6 +113,20 @@ class GatherDesc(C.Structure):
                 ("B", i32), ("h", i32), ("w", i32), ("mean", f32 * 3)]
 
 
+TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
+
+
+class TtaTerm(C.Structure):
+    """simt_tta_term (include/simt_hip.h): one forward's low-res map of a test-time-augmentation label launch."""
+    _fields_ = [("l", c_p), ("h", i32), ("w", i32), ("ld", i32), ("hi", i32), ("wi", i32), ("flip", i32)]
+
+
+class TtaDesc(C.Structure):
+    """simt_tta_desc (include/simt_hip.h)."""
+    _fields_ = [("t", TtaTerm * TTA_MAX), ("n", i32), ("B", i32), ("H", i32), ("W", i32), ("C", i32), ("mode", i32), ("threshold", f32),
+                ("thr", c_p), ("pred", c_p), ("out", c_p), ("counts", c_p), ("hist", c_p)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -188,6 +202,7 @@ SIGNATURES = {
     "simt_pseudo_label2_u8": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
     "simt_pseudo_conf_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
     "simt_pseudo_conf2_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
+    "simt_tta_label": (_I, [C.POINTER(TtaDesc), c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),
     "simt_loss_ws_bytes": (_I, []),

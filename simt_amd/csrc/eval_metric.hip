@@ -810,6 +810,218 @@ extern "C" int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, in
   return SIMT_OK;
 }
 
+// ---- test-time augmentation: the label of up to SIMT_TTA_MAX maps, each of which may belong to the horizontally mirrored frame (the
+// reference's offline tools import ttach, compute_ClassDistribution.py:6, compute_ConfusionMatrix.py:6, and never use it).  A term is one
+// forward's low-res map; its value at a label pixel is the old kernels' value -- bil_taps + ATen's association for the one-resample
+// family (FAM 1), up2_taps / up2_value for a model that upsamples inside (FAM 2) -- read at mirrored COLUMN INDICES when the term is
+// flipped: the weights are untouched, so a flipped term is bit for bit the plain term on the column-reversed map ("un-mirror the
+// model's output, then resample").  Terms are added in term order (mode 0: logits, arg-max of the sum; mode 1: probabilities, the sum
+// times 1/n, then the rules of pseudo_label_u8_kernel<1> / pseudo_conf_u8_kernel).
+// C is a run-time value up to 255 and the taps of 8 terms do not fit in registers, so the channels go in chunks of TTA_CH = 32 sums per
+// lane (C = 19 / 22 / 25: one chunk), terms outermost inside a chunk: a term's taps are formed once per chunk.  The output side is
+// pl_store / conf_emit as they are.
+constexpr int TTA_CH = 32;
+struct TtaTerm {
+  Up2Scale s;          // FAM 1: l, h, w, ld and osy / osx = (h-1)/(H-1), (w-1)/(W-1); FAM 2: as fill_up2 leaves it
+  int flip;
+};
+struct TtaArgs {
+  TtaTerm t[SIMT_TTA_MAX];
+  int n, B, H, W, C;
+  int strict;          // mode 1 labels: 1 = keep where conf > threshold (no thr given), 0 = where conf >= thr[arg]
+  float inv_n, threshold;
+  int* pred;           // mode 0: [B][H][W] or NULL
+  ConfOut o;
+};
+
+// s[j] (+)= the term's value of channel c_lo + j, for the channels of the chunk below C (V = 4: up to the next multiple of 4, inside ld)
+template <int V, bool FIRST>
+__device__ __forceinline__ void tta_term1(const TtaTerm& tm, int b, int y, int x, int c_lo, int C, float (&s)[TTA_CH]) {
+  const Up2Scale& g = tm.s;
+  int o00, o01, o10, o11;
+  float wy0, wy1, wx0, wx1;
+  bil_taps(y, x, g.h, g.w, g.osy, g.osx, o00, o01, o10, o11, wy0, wy1, wx0, wx1);
+  if (tm.flip) {       // column ix -> w-1-ix in all four taps; ix0 as bil_taps forms it
+    int ix0 = (int)(g.osx * (float)x);
+    if (ix0 > g.w - 1) ix0 = g.w - 1;
+    const int ix1 = ix0 + (o01 - o00);
+    const int d0 = g.w - 1 - 2 * ix0, d1 = g.w - 1 - 2 * ix1;
+    o00 += d0; o10 += d0; o01 += d1; o11 += d1;
+  }
+  const float* p = g.l + (long)b * g.h * g.w * g.ld + c_lo;
+  const float *p00 = p + (long)o00 * g.ld, *p01 = p + (long)o01 * g.ld, *p10 = p + (long)o10 * g.ld, *p11 = p + (long)o11 * g.ld;
+#pragma unroll
+  for (int j = 0; j < TTA_CH; j += V) {
+    if (c_lo + j < C) {
+      VecF<V> q00, q01, q10, q11;
+      q00.load(p00 + j); q01.load(p01 + j); q10.load(p10 + j); q11.load(p11 + j);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        // same association as ATen (upsample_sum_argmax_kernel): h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
+        const float v = wy0 * (wx0 * q00.v[k] + wx1 * q01.v[k]) + wy1 * (wx0 * q10.v[k] + wx1 * q11.v[k]);
+        if (FIRST) s[j + k] = v; else s[j + k] = s[j + k] + v;
+      }
+    }
+  }
+}
+
+// up2_taps with the mirror applied to the virtual [hi][wi] map: the outer (align_corners=True) columns vx become wi-1-vx before the inner
+// (align_corners=False) taps are formed
+__device__ __forceinline__ void tta_up2_taps(const Up2Scale& s, int flip, int b, int y, int x, Up2Taps& t) {
+  int vy[2], vx[2], iy[2][2], ix[2][2];
+  up_taps(y, s.hi, s.osy, 1, vy[0], vy[1], t.oy[0], t.oy[1]);
+  up_taps(x, s.wi, s.osx, 1, vx[0], vx[1], t.ox[0], t.ox[1]);
+  if (flip) { vx[0] = s.wi - 1 - vx[0]; vx[1] = s.wi - 1 - vx[1]; }
+  for (int i = 0; i < 2; ++i) {
+    up_taps(vy[i], s.h, s.isy, 0, iy[i][0], iy[i][1], t.ly[i][0], t.ly[i][1]);
+    up_taps(vx[i], s.w, s.isx, 0, ix[i][0], ix[i][1], t.lx[i][0], t.lx[i][1]);
+  }
+  const int base = b * s.h * s.w;
+  for (int yi = 0; yi < 2; ++yi)
+    for (int xi = 0; xi < 2; ++xi)
+      for (int yj = 0; yj < 2; ++yj)
+        for (int xj = 0; xj < 2; ++xj)
+          t.off[yi * 2 + xi][yj * 2 + xj] = (base + iy[yi][yj] * s.w + ix[xi][xj]) * s.ld;
+}
+
+template <int V, bool FIRST>
+__device__ __forceinline__ void tta_term2(const TtaTerm& tm, int b, int y, int x, int c_lo, int C, float (&s)[TTA_CH]) {
+  Up2Taps t;
+  tta_up2_taps(tm.s, tm.flip, b, y, x, t);
+#pragma unroll
+  for (int j = 0; j < TTA_CH; j += V) {
+    if (c_lo + j < C) {
+      float v[V];
+      up2_value<V>(tm.s.l, t, c_lo + j, v);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        if (FIRST) s[j + k] = v[k]; else s[j + k] = s[j + k] + v[k];
+      }
+    }
+  }
+}
+
+// the first-index arg-max and the maximum of the combined terms at one pixel
+template <int FAM, int V, int MODE>
+__device__ __forceinline__ ArgConf tta_pixel(const TtaArgs& a, int b, int y, int x) {
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c_lo = 0; c_lo < a.C; c_lo += TTA_CH) {
+    float s[TTA_CH];
+    if (FAM == 1) tta_term1<V, true>(a.t[0], b, y, x, c_lo, a.C, s); else tta_term2<V, true>(a.t[0], b, y, x, c_lo, a.C, s);
+    for (int t = 1; t < a.n; ++t) {
+      if (FAM == 1) tta_term1<V, false>(a.t[t], b, y, x, c_lo, a.C, s); else tta_term2<V, false>(a.t[t], b, y, x, c_lo, a.C, s);
+    }
+#pragma unroll
+    for (int j = 0; j < TTA_CH; ++j) {
+      if (c_lo + j < a.C) {
+        const float v = MODE == 1 ? s[j] * a.inv_n : s[j];
+        if (v > best) { best = v; arg = c_lo + j; }     // first index on ties
+      }
+    }
+  }
+  return {arg, best};
+}
+
+// KIND 0: mode 0 (pred and / or out + counts).  Mode 1: 1 labels, 2 confidence histogram, 3 both.  Block sizes as the kernels of the same
+// family: FAM 1 PL_BLOCK (the chunk's 32 sums + one term's 4 float4 taps stay below the 128 VGPRs of a 1024-thread block), FAM 2 PL2_BLOCK
+// (Up2Taps + 16 float4 gathers in flight on top of the sums).
+template <int FAM, int V, int KIND>
+__global__ __launch_bounds__(FAM == 1 ? PL_BLOCK : PL2_BLOCK) void tta_label_kernel(TtaArgs a) {
+  constexpr int BLOCK = FAM == 1 ? PL_BLOCK : PL2_BLOCK;
+  constexpr bool STATS = KIND >= 2, LABELS = KIND == 1 || KIND == 3;
+  __shared__ ConfShared<STATS> sh;
+  conf_init<BLOCK, STATS, LABELS>(sh, a.o, a.C);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * BLOCK; base < P; base += (long)gridDim.x * BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int key = 0u, lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      const ArgConf r = tta_pixel<FAM, V, KIND ? 1 : 0>(a, (int)(t / a.H), (int)(t % a.H), x);
+      if (KIND == 0) {
+        lab = (unsigned int)r.arg;
+        if (a.pred) a.pred[p] = r.arg;
+      } else {
+        conf_pixel<STATS, LABELS>(sh, r, key, lab);                      // the bin, and the per-class rule: conf >= thr[arg]
+        if (LABELS && a.strict) lab = (unsigned int)(!(r.conf > a.threshold) ? 255 : r.arg);     // the rule of pseudo_label_u8_kernel<1>
+      }
+    }
+    if (KIND == 0) {
+      if (a.o.out) pl_store(lab, p, P, a.C, a.o.out, sh.counts);
+    } else {
+      conf_emit<STATS, LABELS>(sh, a.o, key, lab, p, P, a.C);
+    }
+  }
+  if (KIND == 0) {
+    if (a.o.out) pl_hist_flush<BLOCK>(sh.counts, a.C + 1, a.o.counts);
+  } else {
+    conf_flush<BLOCK, STATS, LABELS>(sh, a.o, a.C);
+  }
+}
+
+template <int FAM, int V>
+static void launch_tta(const TtaArgs& a, int kind, hipStream_t stream) {
+  constexpr int BLOCK = FAM == 1 ? PL_BLOCK : PL2_BLOCK, MAX_GRID = FAM == 1 ? PL_MAX_GRID : PL2_MAX_GRID;
+  const long P = (long)a.B * a.H * a.W;
+  long grid = (P + BLOCK - 1) / BLOCK;
+  if (grid > MAX_GRID) grid = MAX_GRID;
+  const dim3 g((unsigned)grid), blk(BLOCK);
+  if (kind == 0) hipLaunchKernelGGL((tta_label_kernel<FAM, V, 0>), g, blk, 0, stream, a);
+  if constexpr (FAM == 1) {
+    if (kind == 1) hipLaunchKernelGGL((tta_label_kernel<1, V, 1>), g, blk, 0, stream, a);
+    if (kind == 2) hipLaunchKernelGGL((tta_label_kernel<1, V, 2>), g, blk, 0, stream, a);
+    if (kind == 3) hipLaunchKernelGGL((tta_label_kernel<1, V, 3>), g, blk, 0, stream, a);
+  }
+}
+
+extern "C" int simt_tta_label(const simt_tta_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->n >= 1 && d->n <= SIMT_TTA_MAX);
+  SIMT_CHECK(d->B > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->C <= 255);
+  SIMT_CHECK(d->mode == 0 || d->mode == 1);
+  const bool two = d->t[0].hi > 0;
+  bool vec = true;
+  for (int i = 0; i < d->n; ++i) {
+    const simt_tta_term& t = d->t[i];
+    SIMT_CHECK(t.l && t.h > 0 && t.w > 0 && d->C <= t.ld);
+    SIMT_CHECK(two ? (t.hi > 0 && t.wi > 0) : (t.hi == 0 && t.wi == 0));          // one family per call
+    SIMT_CHECK((long)d->B * t.h * t.w * t.ld < 2147483647L);
+    vec = vec && t.ld % 4 == 0 && ((uintptr_t)t.l & 15) == 0;
+  }
+  SIMT_CHECK(!(d->mode == 1 && two));                                           // mode 1 of the two-resample family is not built
+  SIMT_CHECK(!(d->mode == 1 && d->pred));
+  SIMT_CHECK(!d->out || (d->counts && ((uintptr_t)d->out & 3) == 0));
+  SIMT_CHECK(d->mode == 0 ? (d->pred || d->out) && !d->hist && !d->thr : (d->out || d->hist));   // something to write; thr / hist are mode 1's
+  SIMT_CHECK(!d->hist || d->C <= CONF_MAX_C);
+  TtaArgs a;
+  for (int i = 0; i < SIMT_TTA_MAX; ++i) {
+    const simt_tta_term& t = d->t[i < d->n ? i : 0];
+    if (two) {
+      fill_up2(a.t[i].s, t.l, t.h, t.w, t.ld, t.hi, t.wi, d->H, d->W);
+    } else {
+      Up2Scale& s = a.t[i].s;
+      s.l = t.l; s.h = t.h; s.w = t.w; s.ld = t.ld; s.hi = 0; s.wi = 0; s.isy = 0.f; s.isx = 0.f;
+      s.osy = d->H > 1 ? (float)(t.h - 1) / (float)(d->H - 1) : 0.f;
+      s.osx = d->W > 1 ? (float)(t.w - 1) / (float)(d->W - 1) : 0.f;
+    }
+    a.t[i].flip = t.flip ? 1 : 0;
+  }
+  a.n = d->n; a.B = d->B; a.H = d->H; a.W = d->W; a.C = d->C;
+  a.strict = d->thr ? 0 : 1;
+  a.inv_n = 1.0f / (float)d->n;
+  a.threshold = d->threshold;
+  a.pred = d->pred;
+  a.o.out = d->out; a.o.counts = (unsigned long long*)d->counts; a.o.hist = (unsigned long long*)d->hist;
+  for (int c = 0; c < 255; ++c) a.o.thr[c] = (d->thr && c < d->C) ? d->thr[c] : 0.f;
+  const int kind = d->mode == 0 ? 0 : (d->out ? 1 : 0) + (d->hist ? 2 : 0);
+  const hipStream_t st = (hipStream_t)stream;
+  if (two) { if (vec) launch_tta<2, 4>(a, kind, st); else launch_tta<2, 1>(a, kind, st); }
+  else     { if (vec) launch_tta<1, 4>(a, kind, st); else launch_tta<1, 1>(a, kind, st); }
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
 // ---- offline NTM utilities (tools/compute_ClassDistribution.py:49-51,66-86; tools/compute_ConfusionMatrix.py:54-56,68-98) ----------
 // hist[na_idx * nb + b] += 1 over uint8 label images: a = row class (optional 256-entry LUT = label_mapping; NULL a -> row 0, i.e. the
 // 1-D class histogram of compute_CD), b = column class.  Entries with a (after the LUT) >= na or b >= nb are skipped: 255 = ignore.

@@ -354,3 +354,41 @@ def sig_ntm(ntm, class_dist, T_out=None, dT=None, dN_out=None):
 def sig_w(weight, W_out=None, dW=None, dweight_out=None):
     Q = weight.shape[0]
     L.call("simt_sig_w", _p(weight), _p(dW), _p(W_out), _p(dweight_out), Q, stream_ptr())
+
+
+# ---- test-time augmentation (simt_tta_label) ----------------------------------------------------------------------------------------
+TTA_MAX = L.TTA_MAX
+
+
+def tta_terms(scales, flip=False):
+    """The ordered term list of a test-time-augmented label: [(h, w, False), (h, w, True), ...] -- per input scale the plain frame, then
+    (with `flip`) the horizontally mirrored one.  Raises ValueError above TTA_MAX terms."""
+    terms = [(int(h), int(w), bool(f)) for (h, w) in scales for f in ((False, True) if flip else (False,))]
+    if not terms:
+        raise ValueError("at least one input scale is needed")
+    if len(terms) > TTA_MAX:
+        raise ValueError(f"{len(terms)} terms ({len(list(scales))} scale(s){' x flip' if flip else ''}): one label launch takes at most "
+                         f"{TTA_MAX}")
+    return terms
+
+
+def make_tta_desc(maps, *, B, H, W, Cn, mode=0, threshold=0.0, thr=None, pred=None, out=None, counts=None, hist=None):
+    """maps: [(tensor [B*h*w, ld] or [B, h, w, ld] fp32, h, w, ld, hi, wi, flip)] in term order ((hi, wi) = (0, 0): the one-resample
+    family).  thr: C float32 values in host memory (numpy), read during the call.  No check is made here: simt_tta_label refuses."""
+    d = L.TtaDesc()
+    d.n = len(maps)
+    for i, (t, h, w, ld, hi, wi, flip) in enumerate(maps[:TTA_MAX]):
+        d.t[i].l, d.t[i].h, d.t[i].w, d.t[i].ld, d.t[i].hi, d.t[i].wi, d.t[i].flip = _p(t), h, w, ld, hi, wi, int(bool(flip))
+    d.B, d.H, d.W, d.C, d.mode, d.threshold = B, H, W, Cn, mode, float(threshold)
+    d.thr = thr.ctypes.data if thr is not None else None
+    d.pred, d.out, d.counts, d.hist = _p(pred), _p(out), _p(counts), _p(hist)
+    return d
+
+
+def tta_label(maps, **kw):
+    """One simt_tta_label launch on the current stream (see make_tta_desc)."""
+    thr = kw.get("thr")
+    if thr is not None:
+        assert thr.dtype.name == "float32" and thr.flags["C_CONTIGUOUS"] and thr.size >= kw["Cn"], "thr: C contiguous float32 values"
+    d = make_tta_desc(maps, **kw)
+    L.call("simt_tta_label", C.byref(d), stream_ptr())

@@ -13,7 +13,12 @@ integer atomics.  Dataset IO (PIL decoding, file lists) stays outside: `add` tak
 model: "v2" DeepLab-v2 (DeeplabMulti, the reference's), "v3" DeepLabv3(nc, openc, openset=True), "vgg" DeeplabVGG(nc + openc).
 DeepLabv3 upsamples inside the model (model/deeplabv3.py:137, align_corners=False, to the input size); its plans stop at the
 low-res logits and simt_upsample2_sum_argmax applies both resamples per label pixel without storing the input-size map.
-DeeplabVGG returns low-res logits like DeepLab-v2: the same kernel as v2 over its first nc channels."""
+DeeplabVGG returns low-res logits like DeepLab-v2: the same kernel as v2 over its first nc channels.
+
+Test-time augmentation: Evaluator(..., scales=<any number of sizes>, flip=True) runs one forward per term of ops.tta_terms(scales, flip)
+-- per scale the frame, then its horizontal mirror (the same plan on x.flip(3)) -- keeps every term's low-res logits and labels them
+with ONE simt_tta_label launch, which reads a mirrored term at mirrored column indices.  Up to two scales without flip take the
+reference's recipe and launches above, unchanged."""
 import numpy as np
 import torch
 
@@ -50,6 +55,41 @@ def v3_low_res_forward(plan):
     return lst
 
 
+def tta_low_res_maps(plans, fwds, head, images, scales, flip, hold, dev, prob_classes=None):
+    """One forward per term of ops.tta_terms(scales, flip), in its order: scale k's plan on images[k], then (flip) on images[k].flip(3) --
+    the prepared input mirrored, no second resize.  A plan's output is reused by its next forward, so every term's low-res logits are
+    copied into hold[term] (tensors shaped like the plan's output, owned by the caller) -- or, with prob_classes = C, their softmax over
+    the first C channels is written there instead (simt_softmax_rows: the probabilities of simt_tta_label's mode 1).
+    fwds: the trimmed V3Plan forwards (v3_low_res_forward), or None: plans whose forward returns {head: NHWC logits}.
+    -> the `maps` of ops.tta_label: [(hold[term], h, w, ld, hi, wi, flipped)], (hi, wi) = the input size for v3, (0, 0) otherwise."""
+    if len(images) != len(plans):
+        raise ValueError(f"{len(plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+    maps = []
+    for k, (plan, img) in enumerate(zip(plans, images)):
+        x = img.to(dev)
+        for f in ((False, True) if flip else (False,)):
+            xin = x.flip(3) if f else x
+            if fwds is not None:
+                plan.x_in.copy_(xin)
+                fwds[k].run()
+                lg, (h, w), ld, (hi, wi) = plan.logits, plan.feat_hw, plan.ldq, scales[k]
+            else:
+                lg = plan.forward(xin)[head]
+                (h, w, ld), (hi, wi) = lg.shape[1:], (0, 0)
+            buf = hold[len(maps)]
+            if prob_classes is None:
+                buf.copy_(lg)
+            else:
+                ops.softmax_rows(lg, ld, buf, ld, buf.numel() // ld, prob_classes)
+            maps.append((buf, h, w, ld, hi, wi, f))
+    return maps
+
+
+def tta_hold_buffers(plans, head, flip):
+    """The holding buffers of tta_low_res_maps: per term a tensor like its plan's low-res output (head None: V3Plan.logits)."""
+    return [torch.zeros_like(plan.logits if head is None else plan.out[head]) for plan in plans for _ in range(2 if flip else 1)]
+
+
 def v3_low_res_logits(plans, fwds, images, scales, dev):
     """Run each trimmed V3Plan forward on its image.  -> [(logits [B*h*w, ld], h, w, ld, hi, wi)] per scale, (hi, wi) = the plan's input
     size (the in-model upsample's target)."""
@@ -66,10 +106,12 @@ class Evaluator:
     MODELS = ("v2", "v3", "vgg")
 
     def __init__(self, state, *, num_classes=19, open_classes=0, openset=None, batch=1, label_hw=(1024, 2048),
-                 scales=((512, 1024), (640, 1280)), dtype=torch.float32, device="cuda:0", layers=None, model="v2"):
+                 scales=((512, 1024), (640, 1280)), dtype=torch.float32, device="cuda:0", layers=None, model="v2", flip=False):
         # dtype: fp32 by default -- the reference evaluates in fp32 (evaluate_cityscapes.py:96-162) and the metric is defined "argmax bit-exact";
         # bf16 plans are an explicit, labelled opt-in (tools: --eval-dtype bf16; < 0.2 % of the arg-max positions differ)
         # layers: trunk depth of the plans -- v2: ResNet layers (4 entries), v3: layer1..layer3 of the ResNet, vgg: the VGG_LAYERS list
+        # scales / flip: the terms of the label (ops.tta_terms).  Up to two scales, no flip: the reference's recipe on the two-map kernels;
+        # anything else (more scales, the mirrored frames): one forward per term and one simt_tta_label launch
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {self.MODELS}, got {model!r}")
         self.model = model
@@ -79,6 +121,9 @@ class Evaluator:
         openset = (open_classes > 0) if openset is None else openset
         params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
         self.scales = [tuple(s) for s in scales]
+        self.flip = bool(flip)
+        self.terms = ops.tta_terms(self.scales, self.flip)                   # ValueError above TTA_MAX terms, before any plan is built
+        self.tta = self.flip or len(self.scales) > 2
         if model == "v2":
             kw = {"layers": layers} if layers is not None else {}
             self.plans = [TrunkPlan(params, batch, h, w, multi_heads(num_classes, open_classes, openset), dtype=dtype, train=False, **kw)
@@ -94,6 +139,8 @@ class Evaluator:
             self.plans = [VggPlan(params, batch, h, w, num_classes + (open_classes if openset else 0), dtype=dtype, train=False, **kw)
                           for (h, w) in scales]
         self.B, (self.H, self.W) = batch, label_hw
+        self._head = {"v2": "x2", "v3": None, "vgg": "x"}[model]
+        self._hold = tta_hold_buffers(self.plans, self._head, self.flip) if self.tta else None
         self.pred = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.int32)
         self.hist = torch.zeros(num_classes * num_classes, device=self.dev, dtype=torch.int64)
 
@@ -110,6 +157,11 @@ class Evaluator:
 
     def predict(self, *images):
         """images: one [B,3,h,w] fp32 tensor per scale.  Returns the arg-max label map [B,H,W] int32 (device)."""
+        if self.tta:
+            maps = tta_low_res_maps(self.plans, self._fwd if self.model == "v3" else None, self._head, images, self.scales, self.flip,
+                                    self._hold, self.dev)
+            ops.tta_label(maps, B=self.B, H=self.H, W=self.W, Cn=self.C, mode=0, pred=self.pred)
+            return self.pred
         if self.model == "v3":
             outs = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
             (la, ha, wa, lda, hia, wia) = outs[0]
@@ -141,14 +193,16 @@ class Evaluator:
 
 def evaluate_simt(state, data_dir, data_list, gt_dir, devkit_dir="../dataset/cityscapes_list", *, num_classes=19, open_classes=0, set_name="val",
                   device="cuda:0", dtype=torch.float32, evaluator=None, rank=0, world=1, process_group=None, verbose=True, workers=4,
-                  model="v2", layers=None):
+                  model="v2", layers=None, scales=None, flip=False):
     """File-based evaluation loop of the reference (evaluate_cityscapes.py:96-162): every validation frame at crop sizes (1024, 512) and
     (1280, 640) -> logits[:, :num_classes] of the main head, upsampled to 1024 x 2048, summed, arg-maxed -> fast_hist against the
     ground-truth label ids mapped with info.json's label2train -> mIoU (round(nanmean * 100, 2)).
     dtype: fp32 like the reference; torch.bfloat16 is an opt-in whose mIoU is printed with a "(bf16 plans)" label.
     Host: file lists, PNG decoding (threads), the label LUT.  Device: both resizes (Pillow-exact), BGR - mean, both forwards, the fused
     upsample + sum + arg-max, the histogram.  Data parallel: ranks take strided shards of the list and the histogram is all-reduced.
-    model / layers: see Evaluator ("v2", "v3" or "vgg"; the plans' trunk depth)."""
+    model / layers: see Evaluator ("v2", "v3" or "vgg"; the plans' trunk depth).
+    scales: the input sizes (h, w), default the reference's pair; flip: also the mirrored frame of every scale (test-time augmentation,
+    see Evaluator).  A given `evaluator` brings its own."""
     import json
     from concurrent.futures import ThreadPoolExecutor
     from os.path import join
@@ -162,7 +216,9 @@ def evaluate_simt(state, data_dir, data_list, gt_dir, devkit_dir="../dataset/cit
     name_classes = info.get("label", [str(i) for i in range(num_classes)])
     lut = mapping_lut(np.array(info["label2train"]))
     ds = cityscapesDataSet(data_dir, data_list, crop_size=(1024, 512), mean=IMG_MEAN, scale=False, mirror=False, set=set_name)
-    ev = evaluator or Evaluator(state, num_classes=num_classes, open_classes=open_classes, dtype=dtype, device=dev, model=model, layers=layers)
+    scales = tuple(tuple(s) for s in scales) if scales is not None else ((512, 1024), (640, 1280))
+    ev = evaluator or Evaluator(state, num_classes=num_classes, open_classes=open_classes, dtype=dtype, device=dev, model=model, layers=layers,
+                                scales=scales, flip=flip)
     if evaluator is not None:
         ev.load(state)
     from PIL import Image
@@ -173,20 +229,19 @@ def evaluate_simt(state, data_dir, data_list, gt_dir, devkit_dir="../dataset/cit
         return rgb, lut[np.array(Image.open(gt_path))], name
     idx = list(range(rank, len(ds), world))
     preps = {}
-    xa = xb = None
+    xs = [torch.empty(1, 3, h, w, device=dev) for (h, w) in ev.scales]
     with ThreadPoolExecutor(max(1, workers)) as pool:
         for rgb, label, name in pool.map(fetch, idx):
             key = rgb.shape[:2]
             if key not in preps:
-                preps[key] = (InputPrep(1, key, (1024, 512), dev, with_label=False), InputPrep(1, key, (1280, 640), dev, with_label=False))
-                xa, xb = torch.empty(1, 3, 512, 1024, device=dev), torch.empty(1, 3, 640, 1280, device=dev)
+                preps[key] = [InputPrep(1, key, (w, h), dev, with_label=False) for (h, w) in ev.scales]
             if label.size != ev.H * ev.W:
                 print("Skipping: len(gt) = {:d}, len(pred) = {:d}, {:s}".format(label.size, ev.H * ev.W, name))
                 continue
             rgb_d = torch.from_numpy(rgb[None]).to(dev)
-            preps[key][0].run(rgb_d, xa)
-            preps[key][1].run(rgb_d, xb)
-            ev.add(xa, xb, torch.from_numpy(label[None].astype(np.int64)))
+            for prep, x in zip(preps[key], xs):
+                prep.run(rgb_d, x)
+            ev.add(*xs, torch.from_numpy(label[None].astype(np.int64)))
     if process_group is not None and world > 1:
         import torch.distributed as dist
         dist.all_reduce(ev.hist, group=process_group)

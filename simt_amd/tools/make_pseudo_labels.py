@@ -12,7 +12,12 @@ the confidence at the rank that keeps the share P of that class's own prediction
 
     python -m simt_amd.tools.make_pseudo_labels --restore-from src.pth --arch single --data-dir $CS --data-list train.txt \
         --out-name pseudo_mine --list-out pseudo_mine.lst [--threshold 0.8 | --class-balanced 0.5 [--threshold-cap 0.9]]
-        [--thresholds-from pseudo_subset_thresholds.json] [--save-color --devkit-dir dataset/cityscapes_list]
+        [--thresholds-from pseudo_subset_thresholds.json] [--save-color --devkit-dir dataset/cityscapes_list] [--tta | --tta-flip]
+
+`--tta` is test-time augmentation: every `--input-size` counts in every mode (the confidence modes otherwise use the first only), and
+`--tta-flip` adds the horizontally mirrored frame of every scale.  One forward per term, then ONE simt_tta_label launch: the logits are
+summed (plain arg-max) or the per-term softmax probabilities averaged (confidence rules); a mirrored term is read at mirrored column
+indices of its low-res map.  Not built: the confidence rules of --arch v3 with --tta (the softmax of a model that upsamples inside).
 
 --arch: multi (DeeplabMulti, the SimT DeepLab-v2), single (Res_Deeplab), v3 (DeepLabv3 at --v3-layers) or vgg (DeeplabVGG).  A v3 / vgg
 checkpoint is read like the warm-up stage reads it (the module's own keys; a torchvision ImageNet file is mapped, but its classifier is
@@ -39,7 +44,7 @@ import torch
 from simt_amd import _lib as L
 from simt_amd import ops
 from simt_amd.engine import TrunkPlan, multi_heads, single_head
-from simt_amd.tools.evaluate_cityscapes import v3_low_res_forward, v3_low_res_logits
+from simt_amd.tools.evaluate_cityscapes import tta_hold_buffers, tta_low_res_maps, v3_low_res_forward, v3_low_res_logits
 
 MAX_WORKERS = 16
 ARCHS = ("multi", "single", "v3", "vgg")
@@ -59,10 +64,14 @@ class PseudoLabeller:
     mode "confidence": first scale only, softmax -> up -> arg-max where max > threshold, else 255 (v3: the softmax of the input-size map).
     mode "class_balanced": the confidence of mode "confidence"; accumulate(*images) adds its per-class histogram to `conf_hist` (int64
     [C, 256], device), set_thresholds(thr) installs per-class thresholds, label(*images) then keeps arg-max where conf >= thr[arg-max].
-    label(*images) -> uint8 [B, H, W] on the device; `counts` accumulates int64 [C+1] (classes, then the 255s)."""
+    label(*images) -> uint8 [B, H, W] on the device; `counts` accumulates int64 [C+1] (classes, then the 255s).
+    tta=True (test-time augmentation): every scale counts in every mode and, with flip=True, so does each scale's mirrored frame -- the
+    terms of ops.tta_terms(scales, flip), one forward each and one simt_tta_label launch.  "argmax": the logits summed (Evaluator's labels
+    for the same scales / flip).  "confidence" / "class_balanced": softmax per term at low resolution, the upsampled probabilities
+    averaged, then the same rules.  arch "v3" has no such confidence rule (ValueError)."""
 
     def __init__(self, state, *, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
-                 mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, batch=1):
+                 mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, batch=1, tta=False, flip=False):
         if arch not in ARCHS:
             raise ValueError(f"arch must be one of {ARCHS}, not {arch!r}")
         if mode not in MODES:
@@ -73,11 +82,18 @@ class PseudoLabeller:
             raise ValueError("uint8 labels hold at most 255 classes (255 = ignore)")
         if mode == "class_balanced" and num_classes > MAX_CB_CLASSES:
             raise ValueError(f"class-balanced labels take at most {MAX_CB_CLASSES} classes")
+        if flip and not tta:
+            raise ValueError("flip=True belongs to tta=True")
+        if tta and arch == "v3" and mode != "argmax":
+            raise ValueError(f"arch 'v3' with mode {mode!r} and tta=True: mode 1 (averaged probabilities) of the two-resample family of "
+                             "simt_tta_label is not built")
         self.dev = torch.device(device)
         self.C, self.mode, self.threshold, self.dtype = num_classes, mode, float(threshold), dtype
         scales = tuple(tuple(s) for s in scales)
-        if mode != "argmax":
+        if mode != "argmax" and not tta:
             scales = scales[:1]
+        self.tta, self.flip = bool(tta), bool(flip)
+        self.terms = ops.tta_terms(scales, self.flip) if self.tta else None      # ValueError above TTA_MAX terms, before any plan is built
         self.arch = arch
         params = {k: v.detach().to(self.dev, torch.float32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
         if arch == "v3":
@@ -102,7 +118,9 @@ class PseudoLabeller:
         self.B, (self.H, self.W) = batch, tuple(label_hw)
         self.labels = torch.zeros(batch, self.H, self.W, device=self.dev, dtype=torch.uint8)
         self.counts = torch.zeros(num_classes + 1, device=self.dev, dtype=torch.int64)
-        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode != "argmax" and arch != "v3" else None
+        self.prob = torch.zeros_like(self.plans[0].out[self.head]) if mode != "argmax" and arch != "v3" and not tta else None
+        if self.tta:         # per term: its low-res logits (arg-max) or their softmax (confidence rules)
+            self._hold = tta_hold_buffers(self.plans, None if arch == "v3" else self.head, self.flip)
         self.conf_hist = torch.zeros(num_classes, CONF_BINS, device=self.dev, dtype=torch.int64) if mode == "class_balanced" else None
         self.thresholds = None
 
@@ -119,6 +137,9 @@ class PseudoLabeller:
         """The forward of the first scale, then one class-balanced launch (labels, statistics or both)."""
         if len(images) != len(self.plans):
             raise ValueError(f"{len(self.plans)} input scale(s) expected, got {len(images)} image tensor(s)")
+        if self.tta:
+            self._tta_launch(images, 1, thr, out, counts, hist)
+            return
         tail = (self.B, self.H, self.W, self.C, thr.ctypes.data if thr is not None else None, ops._p(out), ops._p(counts), ops._p(hist),
                 ops.stream_ptr())
         if self.arch == "v3":
@@ -129,6 +150,13 @@ class PseudoLabeller:
         B, h, w, ld = o.shape
         ops.softmax_rows(o, ld, self.prob, ld, B * h * w, self.C)
         L.call("simt_pseudo_conf_u8", ops._p(self.prob), h, w, ld, *tail)
+
+    def _tta_launch(self, images, mode, thr, out, counts, hist):
+        """One forward per term, then one simt_tta_label launch.  mode 1: the terms hold probabilities (one simt_softmax_rows each)."""
+        maps = tta_low_res_maps(self.plans, self._fwd if self.arch == "v3" else None, None if self.arch == "v3" else self.head, images,
+                                self.scales, self.flip, self._hold, self.dev, prob_classes=self.C if mode == 1 else None)
+        ops.tta_label(maps, B=self.B, H=self.H, W=self.W, Cn=self.C, mode=mode, threshold=self.threshold, thr=thr, out=out, counts=counts,
+                      hist=hist)
 
     def accumulate(self, *images):
         """Mode "class_balanced": add the frame's confidence histogram to `conf_hist` (no labels are written)."""
@@ -147,6 +175,9 @@ class PseudoLabeller:
             self._conf_launch(images, self.thresholds, self.labels, self.counts, None)
             return self.labels
         mode = 1 if self.mode == "confidence" else 0
+        if self.tta:
+            self._tta_launch(images, mode, None, self.labels, self.counts, None)
+            return self.labels
         if self.arch == "v3":
             outs = v3_low_res_logits(self.plans, self._fwd, images, self.scales, self.dev)
             (la, ha, wa, lda, hia, wia) = outs[0]
@@ -244,9 +275,10 @@ def thresholds_path(list_out, out_name):
     return osp.join(osp.dirname(osp.abspath(list_out)), f"{out_name}_thresholds.json")
 
 
-def thresholds_record(thr, counts, hist, *, portion, cap, data_list, source=None):
+def thresholds_record(thr, counts, hist, *, portion, cap, data_list, source=None, terms=None):
     """The contents of <out-name>_thresholds.json.  Per class: the pixels predicted as it and their confidence histogram (null / absent
-    when the thresholds were given, not computed from this list), the threshold, the pixels kept and their share."""
+    when the thresholds were given, not computed from this list), the threshold, the pixels kept and their share.  terms: the
+    test-time-augmentation term list [(h, w, mirrored)] the confidences were averaged over (absent without --tta)."""
     thr = np.asarray(thr, np.float32)
     C = len(thr)
     classes = []
@@ -257,8 +289,11 @@ def thresholds_record(thr, counts, hist, *, portion, cap, data_list, source=None
         if hist is not None:
             e["hist"] = [int(v) for v in hist[c]]
         classes.append(e)
-    return {"num_classes": C, "bins": CONF_BINS, "portion": portion, "cap": cap, "data_list": data_list, "thresholds_from": source,
-            "classes": classes}
+    rec = {"num_classes": C, "bins": CONF_BINS, "portion": portion, "cap": cap, "data_list": data_list, "thresholds_from": source,
+           "classes": classes}
+    if terms is not None:
+        rec["tta_terms"] = [{"h": int(h), "w": int(w), "flip": bool(f)} for (h, w, f) in terms]
+    return rec
 
 
 def save_json_atomic(obj, path):
@@ -325,7 +360,7 @@ def _bounded_map(pool, fn, items, depth):
 def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", save_color=False, devkit_dir=None, workers=8,
            class_dist_out=None, num_classes=19, open_classes=0, arch="multi", scales=DEFAULT_SCALES, label_hw=(1024, 2048),
            mode="argmax", threshold=0.8, dtype=torch.float32, device="cuda:0", layers=None, labeller=None, verbose=True,
-           portion=0.5, cap=0.9, thresholds=None, thresholds_source=None):
+           portion=0.5, cap=0.9, thresholds=None, thresholds_source=None, tta=False, flip=False):
     """Label every frame of cityscapesDataSet(data_dir, data_list, set=set_name) and write
     <data_dir>/<out_name>/<basename>.png (8-bit trainIds, 255 = ignore; with save_color also <basename>_color.png), the list file
     `list_out` and the prior `class_dist_out` (default: ClassDist_<out_name>.npy beside the list).  Returns the int64 counts [C+1].
@@ -333,7 +368,8 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
     mode "class_balanced": a first pass over the whole list only accumulates the per-class confidence histogram (nothing is written),
     class_thresholds(hist, portion, cap) gives the thresholds, and the second pass labels with them; `thresholds` (C floats, e.g. of
     load_thresholds) skips the first pass.  Also writes <out_name>_thresholds.json beside the list; the prior is that of the kept
-    pixels, as in confidence mode."""
+    pixels, as in confidence mode.
+    tta / flip: test-time augmentation (PseudoLabeller); a class-balanced export records the term list in its thresholds file."""
     from PIL import Image
 
     from simt_amd.data.pipeline import IMG_MEAN, InputPrep
@@ -348,7 +384,8 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
         class_dist_out = osp.join(osp.dirname(osp.abspath(list_out)), f"ClassDist_{out_name}.npy")
     dev = torch.device(device)
     lab = labeller or PseudoLabeller(state, num_classes=num_classes, open_classes=open_classes, arch=arch, scales=scales,
-                                     label_hw=label_hw, mode=mode, threshold=threshold, dtype=dtype, device=dev, layers=layers)
+                                     label_hw=label_hw, mode=mode, threshold=threshold, dtype=dtype, device=dev, layers=layers,
+                                     tta=tta, flip=flip)
     if lab.B != 1:
         raise ValueError("export labels one frame at a time (batch 1)")
     C = lab.C
@@ -418,7 +455,8 @@ def export(state, data_dir, data_list, out_name, list_out, *, set_name="train", 
     if balanced:
         given = hist is None
         save_json_atomic(thresholds_record(lab.thresholds, counts, hist, portion=None if given else portion, cap=None if given else cap,
-                                           data_list=data_list, source=thresholds_source), thresholds_path(list_out, out_name))
+                                           data_list=data_list, source=thresholds_source, terms=lab.terms),
+                         thresholds_path(list_out, out_name))
     if verbose:
         total = max(int(counts.sum()), 1)
         share = counts[:C] / max(int(counts[:C].sum()), 1)
@@ -470,6 +508,10 @@ def get_arguments(argv=None):
     p.add_argument("--thresholds-from", type=str, default=None, metavar="FILE",
                    help="class-balanced mode with the thresholds of <out-name>_thresholds.json of an earlier export (e.g. of a subset "
                         "list): no statistics pass")
+    p.add_argument("--tta", action="store_true",
+                   help="test-time augmentation: every --input-size counts in every mode (logits summed / probabilities averaged over the "
+                        "scales, one label launch)")
+    p.add_argument("--tta-flip", action="store_true", help="--tta, and the horizontally mirrored frame of every scale as well")
     p.add_argument("--save-color", action="store_true", help="also write <name>_color.png with the palette of <devkit-dir>/info.json")
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     p.add_argument("--eval-dtype", choices=["f32", "bf16"], default="f32",
@@ -478,6 +520,14 @@ def get_arguments(argv=None):
     p.add_argument("--gpu", type=int, default=0)
     add_v3_layers(p)
     args = p.parse_args(argv)
+    args.tta = args.tta or args.tta_flip
+    if args.tta:
+        if args.arch == "v3" and (args.threshold is not None or args.class_balanced is not None or args.thresholds_from):
+            p.error("--tta with the confidence rules of --arch v3 is not built (the averaged softmax of a model that upsamples inside)")
+        try:
+            ops.tta_terms([(h, w) for (w, h) in (args.input_size or [(1024, 512), (1280, 640)])], args.tta_flip)
+        except ValueError as e:
+            p.error(f"--tta: {e}")
     if args.arch == "single" and args.open_classes:
         p.error("--arch single: Res_Deeplab has no open-set classes (--open-classes must be 0)")
     if args.threshold is not None and (args.class_balanced is not None or args.thresholds_from):
@@ -552,13 +602,14 @@ def main(argv=None):
           + (f" (threshold {args.threshold})" if args.threshold is not None else "")
           + (f" (keep {args.class_balanced} per class, cap {args.threshold_cap})" if args.class_balanced is not None else "")
           + (f" (thresholds of {args.thresholds_from})" if thresholds is not None else "")
+          + (f"; test-time augmentation over {len(sizes)} scale(s)" + (" x mirror" if args.tta_flip else "") if args.tta else "")
           + ("" if dtype == torch.float32 else "   (bf16 plans: not the reference's fp32 arithmetic)"))
     export(state, args.data_dir, args.data_list, args.out_name, list_out, set_name=args.set, save_color=args.save_color,
            devkit_dir=args.devkit_dir, workers=args.num_workers, class_dist_out=args.class_dist_out, num_classes=C, open_classes=K,
            arch=args.arch, scales=[(h, w) for (w, h) in sizes], label_hw=(args.label_size[1], args.label_size[0]), mode=mode,
            threshold=args.threshold if args.threshold is not None else 0.0, dtype=dtype, device=dev, layers=layers,
            portion=args.class_balanced if args.class_balanced is not None else 0.5, cap=args.threshold_cap, thresholds=thresholds,
-           thresholds_source=args.thresholds_from)
+           thresholds_source=args.thresholds_from, tta=args.tta, flip=args.tta_flip)
 
 
 if __name__ == "__main__":

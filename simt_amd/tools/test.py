@@ -10,7 +10,8 @@ not used there either, and the same holds here).  Used: --model (DeepLab | DeepL
 --restore-from (required: a missing file, or a file none of whose tensors matches the model's keys and shapes, is an error), --gpu,
 --random-seed (the constructor init of the keys the checkpoint does not hold).  Additions: the validation data of trainV2_simt
 (--data-dir-val, --data-list-val, --gt-dir-val, --devkit-dir), --eval-dtype (fp32 like the reference; bf16 is a labelled opt-in) and
---v3-layers (the DeepLabv3 trunk depth the checkpoint was trained with).  Unlike the reference, the checkpoint is filtered by key AND
+--v3-layers (the DeepLabv3 trunk depth the checkpoint was trained with), --eval-scales W,H [W,H ...] (the input sizes whose logits are
+summed; default the reference's 1024,512 and 1280,640) and --eval-flip (test-time augmentation: also the mirrored frame of every scale).  Unlike the reference, the checkpoint is filtered by key AND
 shape (trainV2_simt.restore), the filter the training tools use.
 """
 import argparse
@@ -22,6 +23,16 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.tools.trainV2_simt import ENGINE_MODEL, MODELS, add_v3_layers, restore, single_model_states
+
+
+def _wh(s):
+    try:
+        w, h = (int(v) for v in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected W,H, got {s!r}")
+    if w <= 0 or h <= 0:
+        raise argparse.ArgumentTypeError(f"expected positive W,H, got {s!r}")
+    return w, h
 
 
 def get_arguments(argv=None):
@@ -72,8 +83,19 @@ def get_arguments(argv=None):
     p.add_argument("--devkit-dir", type=str, default="../dataset/cityscapes_list")
     p.add_argument("--eval-dtype", choices=["f32", "bf16"], default="f32",
                    help="arithmetic of the evaluation: fp32 like the reference (evaluate_cityscapes.py:96-162); bf16 is a labelled opt-in")
+    p.add_argument("--eval-scales", type=_wh, nargs="+", default=None, metavar="W,H",
+                   help="input sizes of the evaluation, their logits are summed (default 1024,512 1280,640, evaluate_cityscapes.py:103-106)")
+    p.add_argument("--eval-flip", action="store_true",
+                   help="test-time augmentation: every scale also on the horizontally mirrored frame (one label launch over all terms)")
     add_v3_layers(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.eval_scales is not None or args.eval_flip:
+        from simt_amd import ops
+        try:
+            ops.tta_terms([(h, w) for (w, h) in (args.eval_scales or [(1024, 512), (1280, 640)])], args.eval_flip)
+        except ValueError as e:
+            p.error(f"--eval-scales / --eval-flip: {e}")
+    return args
 
 
 def model_state(args):
@@ -118,7 +140,8 @@ def main(argv=None):
     mIoU = evaluate_simt(state, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=args.num_classes,
                          open_classes=args.open_classes, device=dev, workers=args.num_workers,
                          dtype=torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32, model=model,
-                         layers=tuple(args.v3_layers) if model == "v3" else None)
+                         layers=tuple(args.v3_layers) if model == "v3" else None,
+                         scales=[(h, w) for (w, h) in args.eval_scales] if args.eval_scales else None, flip=args.eval_flip)
     print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
     return mIoU
 
