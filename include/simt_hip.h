@@ -547,6 +547,44 @@ int simt_label_nearest_u8(const unsigned char* src, unsigned char* dst, int N, i
                           const int* xtab, simt_stream_t stream);
 int simt_cache_gather(const simt_gather_desc* d, simt_stream_t stream);
 
+/* ---- random scale + crop on the device (simt_amd/data/scale_crop.py; csrc/scale_crop.hip) ---------------------------------
+ * simt_scale_crop: one launch per batch.  Item b < B is the window of size w x h at origin (ox[b], oy[b]) of
+ * S = Image.resize((ws, hs), BICUBIC) of its Hs x Ws source frame, ws / hs those of choice c[choice[b]]:
+ *   x[b][p][y][x'] = S[y + oy][x' + ox][mirror[b] ? p : 2 - p] - mean[p] inside S, 0.0f outside;
+ *   lab_out[b][y][x'] = (int64) lab[b][ytab[y + oy]][xtab[x'' + ox]], x'' = mirror[b] ? w-1-x' : x', inside, 255 outside
+ * (the mirror rule of simt_cache_gather).  S is never stored: a workgroup owns SIMT_SCALE_CROP_TILE_H x SIMT_SCALE_CROP_TILE_W output
+ * pixels, runs Pillow's horizontal pass for the source rows they need into LDS as uint8 and the vertical pass out of LDS, so the
+ * result equals Pillow's byte for byte.  `tables` is ONE device buffer of int32; per choice the offsets (in int32) of bounds_x
+ * [ws][2], coefficients_x [ws][ksx], bounds_y [hs][2], coefficients_y [hs][ksy] (resample.bicubic_tables) and of the NEAREST index
+ * tables xtab [ws], ytab [hs].  max_rows: the most source rows one tile's vertical pass reads, over all choices, origins and tiles
+ * (the caller computes it from bounds_y); the LDS the launch needs, simt_scale_crop_lds_bytes, must not exceed
+ * SIMT_SCALE_CROP_LDS_MAX.  lab_out NULL: images only.  The descriptor travels as kernel arguments, like simt_gather_desc. */
+#define SIMT_SCALE_CROP_MAX 64
+#define SIMT_SCALE_CROP_CHOICES 16
+#define SIMT_SCALE_CROP_TILE_H 16
+#define SIMT_SCALE_CROP_TILE_W 64
+#define SIMT_SCALE_CROP_LDS_MAX 65536
+typedef struct {
+  int32_t ws, hs, ksx, ksy;
+  int32_t bounds_x, coef_x, bounds_y, coef_y, xtab, ytab;
+} simt_scale_crop_choice;
+typedef struct {
+  const unsigned char* img[SIMT_SCALE_CROP_MAX];   /* [Hs][Ws][3] u8 RGB */
+  const unsigned char* lab[SIMT_SCALE_CROP_MAX];   /* [Hs][Ws] u8 */
+  int32_t ox[SIMT_SCALE_CROP_MAX], oy[SIMT_SCALE_CROP_MAX];
+  unsigned char choice[SIMT_SCALE_CROP_MAX];
+  unsigned char mirror[SIMT_SCALE_CROP_MAX];
+  simt_scale_crop_choice c[SIMT_SCALE_CROP_CHOICES];
+  const int32_t* tables;
+  float* x;              /* [B][3][h][w] fp32 */
+  long long* lab_out;    /* [B][h][w] int64, or NULL */
+  int32_t B, Hs, Ws, h, w, n_choices, max_rows;
+  int32_t n_tables;      /* int32 elements in `tables`: every offset + extent above is checked against it */
+  float mean[3];
+} simt_scale_crop_desc;
+long simt_scale_crop_lds_bytes(const simt_scale_crop_desc* d);   /* < 0: the descriptor is invalid */
+int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,26 @@ class GatherDesc(C.Structure):
                 ("B", i32), ("h", i32), ("w", i32), ("mean", f32 * 3)]
 
 
+SCALE_CROP_MAX = 64      # include/simt_hip.h SIMT_SCALE_CROP_MAX
+SCALE_CROP_CHOICES = 16  # SIMT_SCALE_CROP_CHOICES
+SCALE_CROP_LDS_MAX = 65536
+
+
+class ScaleCropChoice(C.Structure):
+    """simt_scale_crop_choice (include/simt_hip.h): one scale's sizes and the offsets of its six tables."""
+    _fields_ = [("ws", i32), ("hs", i32), ("ksx", i32), ("ksy", i32), ("bounds_x", i32), ("coef_x", i32), ("bounds_y", i32),
+                ("coef_y", i32), ("xtab", i32), ("ytab", i32)]
+
+
+class ScaleCropDesc(C.Structure):
+    """simt_scale_crop_desc (include/simt_hip.h): one batch of source frames -> scaled, cropped network input."""
+    _fields_ = [("img", c_p * SCALE_CROP_MAX), ("lab", c_p * SCALE_CROP_MAX), ("ox", i32 * SCALE_CROP_MAX), ("oy", i32 * SCALE_CROP_MAX),
+                ("choice", C.c_uint8 * SCALE_CROP_MAX), ("mirror", C.c_uint8 * SCALE_CROP_MAX), ("c", ScaleCropChoice * SCALE_CROP_CHOICES),
+                ("tables", c_p), ("x", c_p), ("lab_out", c_p),
+                ("B", i32), ("Hs", i32), ("Ws", i32), ("h", i32), ("w", i32), ("n_choices", i32), ("max_rows", i32), ("n_tables", i32),
+                ("mean", f32 * 3)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -215,6 +235,8 @@ SIGNATURES = {
     "simt_label_nearest": (_I, [c_p, c_p, _I, _I, _I, _I, _I, c_p, c_p, _I, c_p]),
     "simt_label_nearest_u8": (_I, [c_p, c_p, _I, _I, _I, _I, _I, c_p, c_p, c_p]),
     "simt_cache_gather": (_I, [C.POINTER(GatherDesc), c_p]),
+    "simt_scale_crop_lds_bytes": (_L, [C.POINTER(ScaleCropDesc)]),
+    "simt_scale_crop": (_I, [C.POINTER(ScaleCropDesc), c_p]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@ import torch
 
 from .. import _lib as L
 from . import resample as rs
+from . import scale_crop as sc
 
 IMG_MEAN = (104.00698793, 116.66876762, 122.67891434)      # tools/trainV2_simt.py:34 (BGR)
 
@@ -29,12 +30,22 @@ class InputPrep:
     """Device transform of a batch of decoded frames of ONE source geometry: [B, Hs, Ws, 3] u8 RGB (+ [B, Hs, Ws] u8 labels) ->
     [B, 3, h, w] fp32 (BGR - mean) (+ [B, h, w] int64).  crop = (w, h) like the reference's `crop_size` / --input-size-target."""
 
-    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True):
+    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None):
         self.B, (self.Hs, self.Ws), (self.w, self.h) = B, src_hw, crop_wh
         self.dev = torch.device(device)
         self.mean = tuple(_f32(m) for m in mean)
         self.with_label = with_label
         dev = self.dev
+        self.sc = None
+        if scale_crop is not None:          # the scale-crop mode (simt_amd/data/scale_crop.py): `scale_crop_batch` is the only entry point
+            self.sc = sc.Tables(src_hw, crop_wh, scale_crop)
+            if self.sc.lds_bytes() > L.SCALE_CROP_LDS_MAX:
+                raise ValueError(f"--scale-crop: frames of {self.Ws} x {self.Hs} at crop {self.w} x {self.h} with choices "
+                                 f"{' '.join(self.sc.choices)} need {self.sc.lds_bytes()} bytes of LDS per tile ({self.sc.max_rows} source "
+                                 f"rows), the kernel has {L.SCALE_CROP_LDS_MAX}: drop the smallest choices")
+            self.sc_tables = torch.from_numpy(self.sc.data).to(dev)
+            self.need_x = self.need_y = False
+            return
         self.need_x, self.need_y = self.w != self.Ws, self.h != self.Hs
         if self.need_x:
             self.kx, bx, cx = rs.bicubic_tables(self.Ws, self.w)
@@ -135,6 +146,32 @@ class InputPrep:
             d.mean[0], d.mean[1], d.mean[2] = self.mean
             L.call("simt_cache_gather", C.byref(d), stream)
 
+    def scale_crop_batch(self, img_ptrs, lab_ptrs, draws, x_out, lab_out, stream):
+        """One simt_scale_crop per batch (per SIMT_SCALE_CROP_MAX items): B pointers to source frames [Hs,Ws,3] u8 (+ labels [Hs,Ws] u8)
+        on the device -- rows of an upload buffer or dataset-cache slots -- and draws = (mirror flags, choice indices, ox, oy), one per
+        item (scale_crop.draw_batch) -> x_out [B,3,h,w] f32, lab_out [B,h,w] i64 | None."""
+        assert self.sc is not None, "built without scale_crop choices"
+        assert x_out.dtype == torch.float32 and tuple(x_out.shape) == (self.B, 3, self.h, self.w) and x_out.is_contiguous()
+        assert lab_out is None or (lab_out.dtype == torch.int64 and tuple(lab_out.shape) == (self.B, self.h, self.w) and lab_out.is_contiguous())
+        mirror, pick, ox, oy = draws
+        assert len(img_ptrs) == len(mirror) == len(pick) == len(ox) == len(oy) == self.B
+        for b0 in range(0, self.B, L.SCALE_CROP_MAX):
+            n = min(L.SCALE_CROP_MAX, self.B - b0)
+            d = L.ScaleCropDesc()
+            for k in range(n):
+                d.img[k] = img_ptrs[b0 + k]
+                d.lab[k] = lab_ptrs[b0 + k] if lab_out is not None else None
+                d.ox[k], d.oy[k], d.choice[k], d.mirror[k] = ox[b0 + k], oy[b0 + k], pick[b0 + k], 1 if mirror[b0 + k] else 0
+            for c, e in enumerate(self.sc.entries):
+                for name, v in e.items():
+                    setattr(d.c[c], name, v)
+            d.tables, d.n_tables = self.sc_tables.data_ptr(), self.sc_tables.numel()
+            d.x, d.lab_out = x_out[b0].data_ptr(), (lab_out[b0].data_ptr() if lab_out is not None else None)
+            d.B, d.Hs, d.Ws, d.h, d.w = n, self.Hs, self.Ws, self.h, self.w
+            d.n_choices, d.max_rows = len(self.sc.entries), self.sc.max_rows
+            d.mean[0], d.mean[1], d.mean[2] = self.mean
+            L.call("simt_scale_crop", C.byref(d), stream)
+
 
 class DevicePrefetcher:
     """Pinned double-buffered upload + device transform, one batch ahead of the consumer.
@@ -149,8 +186,10 @@ class DevicePrefetcher:
     that stream up to that point -- the step that consumed batch k included -- precedes the refill), and the copy stream waits for
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
-    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None):
+    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
+        self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
+        assert (draw_fn is not None) == (prep.sc is not None)
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -210,9 +249,14 @@ class DevicePrefetcher:
             s["rgb_d"].copy_(rgb, non_blocking=True)
             if lab is not None:
                 s["lab_d"].copy_(lab, non_blocking=True)
-            mirror = self.mirror_fn(self.prep.B) if self.mirror_fn is not None else False
-            self.prep.run(s["rgb_d"], s["x"], s["lab_d"] if lab is not None else None, s["lab"] if lab is not None else None,
-                          mirror=mirror, stream=cs.cuda_stream)
+            if self.draw_fn is not None:           # one launch replaces the resample, image_to_input and label_nearest launches
+                self.prep.scale_crop_batch([s["rgb_d"][b].data_ptr() for b in range(self.prep.B)],
+                                           [s["lab_d"][b].data_ptr() if lab is not None else None for b in range(self.prep.B)],
+                                           self.draw_fn(self.prep.B), s["x"], s["lab"] if lab is not None else None, cs.cuda_stream)
+            else:
+                mirror = self.mirror_fn(self.prep.B) if self.mirror_fn is not None else False
+                self.prep.run(s["rgb_d"], s["x"], s["lab_d"] if lab is not None else None, s["lab"] if lab is not None else None,
+                              mirror=mirror, stream=cs.cuda_stream)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
         self.filled += 1
@@ -250,9 +294,18 @@ class DevicePrefetcher:
                 s["rgb_d"][:M].copy_(s["rgb_h"][:M], non_blocking=True)
                 if has_lab:
                     s["lab_d"][:M].copy_(s["lab_h"][:M], non_blocking=True)
-                prep.resize_into(s["rgb_d"][:M], s["lab_d"][:M] if has_lab else None, dests, cs.cuda_stream)
-            mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
-            prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+                if self.draw_fn is not None:       # the cache holds the ORIGINAL frames: a miss goes into its slot as it is
+                    for m, (iv, lv) in enumerate(dests):
+                        iv.copy_(s["rgb_d"][m].reshape(-1), non_blocking=True)
+                        if has_lab:
+                            lv.copy_(s["lab_d"][m].reshape(-1), non_blocking=True)
+                else:
+                    prep.resize_into(s["rgb_d"][:M], s["lab_d"][:M] if has_lab else None, dests, cs.cuda_stream)
+            if self.draw_fn is not None:
+                prep.scale_crop_batch(img_ptrs, lab_ptrs, self.draw_fn(prep.B), s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+            else:
+                mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
+                prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, has_lab, True
         self.filled += 1
@@ -324,7 +377,12 @@ class GpuLoader:
 
     start_batch = n: the loader yields exactly what the default loader yields from its n-th batch on (a resumed run): it starts inside
     epoch n // batches-per-epoch of `_order`, the mirror generator has made the n skipped batches' draws, and no skipped item is
-    decoded.  A cache starts empty and refills; the batches are the same."""
+    decoded.  A cache starts empty and refills; the batches are the same.
+
+    dataset.scale_crop = decimal scale choices (cityscapesPseudo(scale_crop=...), --scale-crop) turns on random scale + crop
+    (simt_amd/data/scale_crop.py): per batch the generator draws, after the mirror flags, a choice and a window origin per item, and ONE
+    simt_scale_crop launch makes the batch from the decoded frames.  A cache then holds the ORIGINAL frames (DatasetCache((Ws, Hs))).
+    Cached and uncached batches are bit-identical and start_batch skips the same draws.  Without it not one draw changes."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -333,14 +391,30 @@ class GpuLoader:
         self.dev, self.seed, self.rank, self.world, self.epochs = torch.device(device), seed, rank, world, epochs
         self._prep = None
         self.cache, self.on_epoch = cache, on_epoch
-        if cache is not None:
+        self.scale_crop = getattr(dataset, "scale_crop", None)
+        if self.scale_crop is not None:
+            self.scale_crop = sc.parse_choices(self.scale_crop)
+        self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
+        if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
         self._rng = np.random.default_rng(seed + 7919 * rank)
         self._lock = threading.Lock()
         self.start_batch = int(start_batch)
         self._epoch0, self._batch0, _ = loader_position(len(dataset), batch_size, rank, world, self.start_batch)
-        if self.start_batch and getattr(dataset, "is_mirror", False):
+        if self.start_batch and self.scale_crop is not None:
+            sc.skip_scale_crop_draws(self._rng, batch_size, self.start_batch, len(self.scale_crop), bool(getattr(dataset, "is_mirror", False)))
+        elif self.start_batch and getattr(dataset, "is_mirror", False):
             skip_mirror_draws(self._rng, batch_size, self.start_batch)
+
+    def _same_geometry(self, items, ids):
+        """All items of a run share one source geometry: a frame of another size raises, with its path."""
+        for it, i in zip(items, ids):
+            with self._lock:
+                if self._src_hw is None:
+                    self._src_hw = it[0].shape[:2]
+            if it[0].shape[:2] != self._src_hw:
+                raise ValueError(f"{self.ds.files[i]['img']}: the frame is {it[0].shape[1]} x {it[0].shape[0]}, the frames of this run are "
+                                 f"{self._src_hw[1]} x {self._src_hw[0]} (one source geometry per run)")
 
     def _order(self, epoch):
         n = len(self.ds)
@@ -360,6 +434,7 @@ class GpuLoader:
                 pending = [pool.map(self.ds.decode, idx[b * self.B:(b + 1) * self.B]) for b in range(b0, min(b0 + 2, nb))]
                 for b in range(b0, nb):
                     items = list(pending.pop(0))
+                    self._same_geometry(items, idx[b * self.B:(b + 1) * self.B])
                     if b + 2 < nb:
                         pending.append(pool.map(self.ds.decode, idx[(b + 2) * self.B:(b + 3) * self.B]))
                     rgb = np.stack([it[0] for it in items])
@@ -400,6 +475,7 @@ class GpuLoader:
                     if b + 2 < nb:
                         pending.append(plan(pool, idx[(b + 2) * self.B:(b + 3) * self.B]))
                     items = [fut.result() for (_slot, fut, _i) in entries if fut is not None]
+                    self._same_geometry(items, [i for (_slot, fut, i) in entries if fut is not None])
                     rgb = np.stack([it[0] for it in items]) if items else None
                     lab = np.stack([it[1] for it in items]) if items and items[0][1] is not None else None
                     sizes = np.stack([np.array([ds.crop_size[1], ds.crop_size[0], 3]) for _ in entries])
@@ -421,12 +497,19 @@ class GpuLoader:
             return iter(())
         Hs, Ws = first[0].shape[1:3]
         assert self.cache is None or self.cache.with_label or first[1] is None, "the dataset has labels, the cache no label slab"
-        self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None)
+        self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None,
+                               scale_crop=self.scale_crop)
+        if self.scale_crop is not None and self.cache is not None:
+            assert (self.cache.w, self.cache.h) == (Ws, Hs), "with scale-crop the cache holds the ORIGINAL frames: DatasetCache((Ws, Hs))"
 
         def chain():
             yield first
             yield from gen
         # `flip = np.random.choice(2) * 2 - 1` per item (cityscapes_dataset.py:109)
         mirror_fn = (lambda n: (self._rng.integers(0, 2, n) == 0).tolist()) if getattr(self.ds, "is_mirror", False) else None
-        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache)
+        draw_fn = None
+        if self.scale_crop is not None:
+            mirror_on = bool(getattr(self.ds, "is_mirror", False))
+            draw_fn = lambda n: sc.draw_batch(self._rng, n, self.scale_crop, tuple(self.ds.crop_size), mirror_on)
+        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

@@ -17,6 +17,8 @@ reference unless bf16 is asked for), --print-every, --data-dir-val,
 --data-list-val, --gt-dir-val, --devkit-dir, --class-dist (the prior of other pseudo labels: simt_amd.tools.make_pseudo_labels),
 --cache-dataset device [--cache-gb G]: the resized uint8 training set stays in HBM after the first epoch (simt_amd/data/cache.py; default off:
 the batches are the same, bit for bit, only PNG decoding after epoch one is saved),
+--scale-crop [S ...]: random scale + crop of every training item on the device, one launch per batch (simt_amd/data/scale_crop.py; default
+off; --random-scale stays what the reference makes of it: parsed and ignored),
 --train-state FILE [--train-state-every N]: resume from FILE if it exists and keep it current (simt_amd/train_state.py).  The snapshots hold
 the model only; FILE also holds the SGD momentum, both NTMs and W with their Adam moments, the iteration counter, the snapshot rotation's
 bookkeeping -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
@@ -97,6 +99,7 @@ def get_arguments(argv=None):
                    help="class prior .npy of the pseudo labels (make_pseudo_labels writes it); default: ClassDist_bapa.npy")
     add_v3_layers(p)
     add_cache_args(p)
+    add_scale_crop_args(p)
     add_train_state_args(p)
     return p.parse_args(argv)
 
@@ -112,6 +115,27 @@ def add_cache_args(p):
                         "PNGs are decoded in the first epoch only.  Ignored with --synthetic")
     p.add_argument("--cache-gb", type=float, default=None,
                    help="cache budget in GB (1e9 bytes); default: what holds the whole list at the run's crop (4*h*w bytes per item)")
+
+
+def add_scale_crop_args(p):
+    p.add_argument("--scale-crop", type=str, nargs="*", default=None, metavar="S",
+                   help="random scale + crop on the device (simt_amd/data/scale_crop.py): per item a scale is drawn from the decimal choices S "
+                        "(no values: 0.5 0.6 ... 1.5; at most 16), the frame is resized once to round(crop * s) and the crop-sized window at a "
+                        "uniformly drawn origin goes to the network (mean / label 255 around a smaller frame).  Default: off.  With "
+                        "--cache-dataset device the cache then holds the ORIGINAL frames and the default --cache-gb is 4*Hs*Ws bytes per "
+                        "item (about 25 GB for the 2 975 Cityscapes training frames).  Ignored with --synthetic")
+
+
+def scale_crop_choices(args):
+    """--scale-crop -> tuple of decimal strings, or None when the flag is off (a bad value is a SystemExit naming it)."""
+    texts = getattr(args, "scale_crop", None)
+    if texts is None:
+        return None
+    from simt_amd.data.scale_crop import parse_choices
+    try:
+        return parse_choices(texts)
+    except ValueError as e:
+        raise SystemExit(f"--scale-crop: {e}")
 
 
 def add_train_state_args(p):
@@ -250,12 +274,20 @@ class SnapshotKeeper:
         self.best_mIoU, self.best_iter, self.rolling_iter = st["best_mIoU"], st["best_iter"], st["rolling_iter"]
 
 
+RUN_DEFAULTS = {"scale_crop": False}      # run_identity keys that are absent when their flag is off: what absence means
+
+
 def run_identity(args, class_dist):
-    """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror draws, synthetic batches), the mirror
-    switch, where the data comes from (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
+    """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror and scale-crop draws, synthetic batches), the
+    mirror switch, the scale-crop choices (RUN_DEFAULTS: the key is absent when the flag is off, and absent means False -- the state files
+    of runs from before the flag existed are those of runs without it; with --synthetic the flag does nothing), where the data comes from
+    (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
     import hashlib
+    choices = None if args.synthetic else scale_crop_choices(args)
     ident = {"random_seed": int(args.random_seed), "random_mirror": bool(args.random_mirror), "synthetic": bool(args.synthetic),
              "class_dist_sha256": hashlib.sha256(np.ascontiguousarray(np.asarray(class_dist, dtype=np.float32)).tobytes()).hexdigest()}
+    if choices is not None:
+        ident["scale_crop"] = list(choices)
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -282,10 +314,15 @@ class TrainStateFile:
         ts, ks, ls = train_state.load(self.path)
         if ls.get("world", self.world) != self.world:
             raise SystemExit(f"--train-state {self.path!r} was written by a run over {ls['world']} GPU(s), this one has {self.world}")
-        other = [k for k, v in self.run.items() if k in ls.get("run", {}) and ls["run"][k] != v]
+        saved, mine = dict(ls.get("run", {})), dict(self.run)
+        if saved and mine:
+            for k, v in RUN_DEFAULTS.items():
+                saved.setdefault(k, v)
+                mine.setdefault(k, v)
+        other = [k for k, v in mine.items() if k in saved and saved[k] != v]
         if other:
             raise SystemExit(f"--train-state {self.path!r} was written by a run that differs in: " +
-                             ", ".join(f"{k} (state: {ls['run'][k]!r}, this run: {self.run[k]!r})" for k in other))
+                             ", ".join(f"{k} (state: {saved[k]!r}, this run: {mine[k]!r})" for k in other))
         try:
             tr.load_training_state(ts)
         except ValueError as e:
@@ -324,7 +361,11 @@ class TrainStateFile:
 def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
     resumed run: iterations done x iter_size)."""
+    choices = scale_crop_choices(args)
     if args.synthetic:
+        if choices is not None and rank == 0:
+            print("--scale-crop does nothing with --synthetic: the synthetic batches are made at the crop's size")
+
         def synth():
             it = start_batch
             while True:                                     # one global sequence of seeds, dealt round-robin to the ranks
@@ -335,14 +376,20 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
         raise SystemExit(f"--data-dir-target {args.data_dir_target!r} is not a directory; pass --synthetic for synthetic batches")
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
-    ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN)
+    ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
+                          scale_crop=choices)
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
         gb = getattr(args, "cache_gb", None)
         n_distinct = len({ds.cache_key(i) for i in range(len(ds))})
-        budget = default_budget_bytes(n_distinct, (W, H)) if gb is None else int(gb * 1e9)
-        cache = DatasetCache((W, H), with_label=True, budget_bytes=budget, device=dev)
+        held = (W, H)
+        if choices is not None:             # the cache holds the ORIGINAL frames: their size is the first item's (read from the file's header)
+            from PIL import Image
+            with Image.open(ds.files[0]["img"]) as im:
+                held = im.size
+        budget = default_budget_bytes(n_distinct, held) if gb is None else int(gb * 1e9)
+        cache = DatasetCache(held, with_label=True, budget_bytes=budget, device=dev)
 
         def on_epoch(epoch, hits, misses, nbytes):
             print(f"dataset cache: rank {rank} epoch {epoch}: {hits} hits, {misses} misses, {nbytes / 1e9:.3f} GB of {budget / 1e9:.3f} GB "
