@@ -585,6 +585,34 @@ typedef struct {
 long simt_scale_crop_lds_bytes(const simt_scale_crop_desc* d);   /* < 0: the descriptor is invalid */
 int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stream);
 
+/* ---- ClassMix: class-mask mixing of batch items on the device (simt_amd/data/class_mix.py; csrc/class_mix.hip) ---------------
+ * x [B][3][h][w] fp32 and lab [B][h][w] int64 are a finished batch; a label outside [0, n_classes) is "ignore".  Item i's partner is
+ * j = partner[i].  P_j = the classes c < n_classes that occur in lab[j], n = |P_j|, k = (n + 1) / 2, S_j = the k classes of P_j with the
+ * smallest rank[i][c] (rank[i] is a permutation of 0 .. n_classes-1).  For every pixel p: m = apply[i] && lab[j][p] in S_j;
+ *   lab_out[i][p] = m ? lab[j][p] : lab[i][p];   x_out[i][ch][p] = m ? x[j][ch][p] : x[i][ch][p]   (a selection: no bit changes).
+ * Output goes to separate buffers (x_out != x, lab_out != lab).  apply[i] == 0: a copy of item i, the partner is not read.
+ * simt_label_presence: part[b * SIMT_CLASS_MIX_PARTS + g] = OR of 1u << l over the valid labels l of item b that workgroup g of
+ * SIMT_CLASS_MIX_PARTS visits; every word is written with a plain store on every call (no atomics, nothing to zero).
+ * simt_class_mix reads the partner's SIMT_CLASS_MIX_PARTS words of `part`, so simt_label_presence(lab, B, h * w, n_classes, part) runs
+ * before it on the same stream.  The four batch bases are 16-byte aligned; any h, w with h * w < 2^31; B <= SIMT_CLASS_MIX_MAX (partners
+ * cross any chunk's edge: a larger batch is refused, not split).  The descriptor travels as kernel arguments, like simt_gather_desc. */
+#define SIMT_CLASS_MIX_MAX 32
+#define SIMT_CLASS_MIX_CLASSES 32
+#define SIMT_CLASS_MIX_PARTS 64
+typedef struct {
+  const float* x;            /* [B][3][h][w] fp32 */
+  const long long* lab;      /* [B][h][w] int64 */
+  float* x_out;              /* [B][3][h][w] fp32 */
+  long long* lab_out;        /* [B][h][w] int64 */
+  const uint32_t* part;      /* [B][SIMT_CLASS_MIX_PARTS]: simt_label_presence's words for `lab` */
+  int32_t B, h, w, n_classes;
+  uint8_t partner[SIMT_CLASS_MIX_MAX];
+  uint8_t apply[SIMT_CLASS_MIX_MAX];
+  uint8_t rank[SIMT_CLASS_MIX_MAX][SIMT_CLASS_MIX_CLASSES];
+} simt_class_mix_desc;
+int simt_label_presence(const long long* lab, int B, long hw, int n_classes, uint32_t* part, simt_stream_t stream);
+int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

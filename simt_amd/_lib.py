@@ -133,6 +133,19 @@ class ScaleCropDesc(C.Structure):
                 ("mean", f32 * 3)]
 
 
+CLASS_MIX_MAX = 32       # include/simt_hip.h SIMT_CLASS_MIX_MAX
+CLASS_MIX_CLASSES = 32   # SIMT_CLASS_MIX_CLASSES
+CLASS_MIX_PARTS = 64     # SIMT_CLASS_MIX_PARTS
+
+
+class ClassMixDesc(C.Structure):
+    """simt_class_mix_desc (include/simt_hip.h): one finished batch -> the class-mixed batch."""
+    _fields_ = [("x", c_p), ("lab", c_p), ("x_out", c_p), ("lab_out", c_p), ("part", c_p),
+                ("B", i32), ("h", i32), ("w", i32), ("n_classes", i32),
+                ("partner", C.c_uint8 * CLASS_MIX_MAX), ("apply", C.c_uint8 * CLASS_MIX_MAX),
+                ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -237,6 +250,8 @@ SIGNATURES = {
     "simt_cache_gather": (_I, [C.POINTER(GatherDesc), c_p]),
     "simt_scale_crop_lds_bytes": (_L, [C.POINTER(ScaleCropDesc)]),
     "simt_scale_crop": (_I, [C.POINTER(ScaleCropDesc), c_p]),
+    "simt_label_presence": (_I, [c_p, _I, _L, _I, c_p, c_p]),
+    "simt_class_mix": (_I, [C.POINTER(ClassMixDesc), c_p]),
 }
 
 _lib = None

@@ -1,0 +1,211 @@
+// ClassMix (Olsson et al., WACV'21) on a finished batch (simt_amd/data/class_mix.py): item i receives, from its partner j, the pixels
+// -- labels included -- of half of the classes that occur in lab[j].  Pure selection: no arithmetic touches a value.  Two streaming
+// kernels in the style of cache_gather_kernel (csrc/dataset_cache.hip): descriptor by value in the kernel-argument segment, 4 consecutive
+// pixels per lane, flat over h*w, 16-byte loads and stores when h*w % 4 == 0 (every plane and label row then starts on a 16-byte
+// boundary), dwords / qwords otherwise, one lane takes the h*w % 4 tail.
+//   label_presence_kernel  grid (PARTS, B): workgroup (g, b) ORs 1u << l over its strided share of item b's valid labels and lane 0
+//                          stores ONE word, part[b][g] -- every word is written on every call: no atomics, nothing to zero.
+//   class_mix_kernel       grid (quads / 256, B): every wave builds the paste mask S_j from the partner's PARTS words and the item's
+//                          rank permutation (a few dozen instructions, no LDS, no barrier), then selects quad by quad.
+// Byte floor per pixel: the mix writes 12 + 8 bytes and reads at least 8 (lab[j]) + 12 (one image), plus 8 more (lab[i]) where the pixel
+// is not pasted: 40-48 bytes, 94-113 MB at B = 4, 768 x 768.  Presence reads 8 bytes per pixel: 19 MB there.  A quad whose four pixels
+// agree loads one source only, so the floor is what the kernel moves except on class boundaries.
+#include "common.h"
+
+typedef __attribute__((ext_vector_type(2))) long long i64x2;
+
+__device__ __forceinline__ uint32_t label_bit(long long l, int C) { return (l >= 0 && l < C) ? (1u << (int)l) : 0u; }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void label_presence_kernel(const long long* __restrict__ lab, long HW, int C, uint32_t* __restrict__ part) {
+  const int b = blockIdx.y;
+  const long long* __restrict__ l = lab + (long)b * HW;
+  const long nquad = HW >> 2;
+  const long last = (HW & 3) ? nquad : nquad - 1;          // lane index `nquad` takes the tail, when there is one
+  uint32_t bits = 0;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q <= last; q += (long)SIMT_CLASS_MIX_PARTS * 256) {
+    if (q < nquad) {
+      const long p = q << 2;
+      long long v0, v1, v2, v3;
+      if (VEC) {
+        const i64x2 u = *(const i64x2*)(l + p), v = *(const i64x2*)(l + p + 2);
+        v0 = u.x; v1 = u.y; v2 = v.x; v3 = v.y;
+      } else {
+        v0 = l[p]; v1 = l[p + 1]; v2 = l[p + 2]; v3 = l[p + 3];
+      }
+      bits |= label_bit(v0, C) | label_bit(v1, C) | label_bit(v2, C) | label_bit(v3, C);
+    } else {
+      for (long p = nquad << 2; p < HW; ++p) bits |= label_bit(l[p], C);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o, 64);
+  __shared__ uint32_t wave_bits[4];
+  if ((threadIdx.x & 63) == 0) wave_bits[threadIdx.x >> 6] = bits;
+  __syncthreads();
+  if (threadIdx.x == 0) part[b * SIMT_CLASS_MIX_PARTS + blockIdx.x] = wave_bits[0] | wave_bits[1] | wave_bits[2] | wave_bits[3];
+}
+
+extern "C" int simt_label_presence(const long long* lab, int B, long hw, int n_classes, uint32_t* part, simt_stream_t stream) {
+  SIMT_CHECK(lab && part && ((uintptr_t)lab & 15) == 0 && ((uintptr_t)part & 3) == 0);
+  SIMT_CHECK(B > 0 && B <= SIMT_CLASS_MIX_MAX && hw > 0 && hw < (1L << 31));
+  SIMT_CHECK(n_classes >= 1 && n_classes <= SIMT_CLASS_MIX_CLASSES);
+  const dim3 grid(SIMT_CLASS_MIX_PARTS, (unsigned)B);
+  if ((hw & 3) == 0)
+    hipLaunchKernelGGL((label_presence_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, lab, hw, n_classes, part);
+  else
+    hipLaunchKernelGGL((label_presence_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, lab, hw, n_classes, part);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+// The paste mask of item i, the same word in every lane.  Lane r < C plays RANK r: a wave-uniform walk over the classes (rank[i][c] is a
+// scalar load from the kernel arguments) tells it which class holds its rank; the ballot of "my class is present" then is the present
+// classes in rank order, and the class of rank r is chosen when fewer than k present ones rank below it.
+__device__ __forceinline__ uint32_t paste_mask(const simt_class_mix_desc& d, int i, int j) {
+  const int lane = threadIdx.x & 63;
+  const int C = d.n_classes;
+  uint32_t present = d.part[j * SIMT_CLASS_MIX_PARTS + lane];           // PARTS = 64 = one word per lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) present |= (uint32_t)__shfl_xor((int)present, o, 64);
+  present &= C >= 32 ? 0xffffffffu : ((1u << C) - 1u);
+  const int k = (__popc(present) + 1) >> 1;
+  int cls = -1;
+  const uint32_t* row = (const uint32_t*)d.rank[i];                      // 32 bytes at a 4-byte boundary of the descriptor: 8 scalar dwords
+#pragma unroll
+  for (int c = 0; c < SIMT_CLASS_MIX_CLASSES; ++c)
+    if (c < C && (int)((row[c >> 2] >> (8 * (c & 3))) & 255u) == lane) cls = c;
+  const bool here = cls >= 0 && ((present >> cls) & 1u);
+  const unsigned long long order = __ballot(here);                       // bit r: the class of rank r is present
+  const int below = __popcll(order & ((1ull << lane) - 1ull));
+  uint32_t mask = (here && below < k) ? (1u << cls) : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mask |= (uint32_t)__shfl_xor((int)mask, o, 64);
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)mask);
+}
+
+__device__ __forceinline__ bool pasted(long long l, int C, uint32_t mask) { return l >= 0 && l < C && ((mask >> (int)l) & 1u); }
+
+// One lane: pixels p .. p+3 of item i = blockIdx.y.  lab[j] is read always (when apply[i]); a quad whose four decisions agree reads one
+// source only, a mixed quad reads both and selects.  Values travel as integer words.
+template <bool VEC>
+__global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_desc d) {
+  const int i = blockIdx.y;
+  const int apply = d.apply[i];
+  const int j = d.partner[i];
+  const int C = d.n_classes;
+  const long HW = (long)d.h * d.w;
+  const long nquad = HW >> 2;
+  const uint32_t* __restrict__ xi = (const uint32_t*)d.x + (long)i * 3 * HW;
+  const long long* __restrict__ li = d.lab + (long)i * HW;
+  uint32_t* __restrict__ xo = (uint32_t*)d.x_out + (long)i * 3 * HW;
+  long long* __restrict__ lo = d.lab_out + (long)i * HW;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (!apply) {                                          // a straight copy of item i (wave-uniform branch): the partner is not read
+    if (q < nquad) {
+      const long p = q << 2;
+      if (VEC) {
+        *(i64x2*)(lo + p) = *(const i64x2*)(li + p);
+        *(i64x2*)(lo + p + 2) = *(const i64x2*)(li + p + 2);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) *(uint4*)(xo + ch * HW + p) = *(const uint4*)(xi + ch * HW + p);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          lo[p + e] = li[p + e];
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p + e] = xi[ch * HW + p + e];
+        }
+      }
+    } else if (q == nquad) {
+      for (long p = nquad << 2; p < HW; ++p) {
+        lo[p] = li[p];
+        for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = xi[ch * HW + p];
+      }
+    }
+    return;
+  }
+  const uint32_t mask = paste_mask(d, i, j);
+  const uint32_t* __restrict__ xj = (const uint32_t*)d.x + (long)j * 3 * HW;
+  const long long* __restrict__ lj = d.lab + (long)j * HW;
+  if (q < nquad) {
+    const long p = q << 2;
+    long long a[4];                                      // the partner's labels, then the output's
+    if (VEC) {
+      const i64x2 u = *(const i64x2*)(lj + p), v = *(const i64x2*)(lj + p + 2);
+      a[0] = u.x; a[1] = u.y; a[2] = v.x; a[3] = v.y;
+    } else {
+      a[0] = lj[p]; a[1] = lj[p + 1]; a[2] = lj[p + 2]; a[3] = lj[p + 3];
+    }
+    const bool m0 = pasted(a[0], C, mask), m1 = pasted(a[1], C, mask), m2 = pasted(a[2], C, mask), m3 = pasted(a[3], C, mask);
+    const bool all = m0 && m1 && m2 && m3, none = !(m0 || m1 || m2 || m3);
+    if (!all) {
+      long long o0, o1, o2, o3;
+      if (VEC) {
+        const i64x2 u = *(const i64x2*)(li + p), v = *(const i64x2*)(li + p + 2);
+        o0 = u.x; o1 = u.y; o2 = v.x; o3 = v.y;
+      } else {
+        o0 = li[p]; o1 = li[p + 1]; o2 = li[p + 2]; o3 = li[p + 3];
+      }
+      a[0] = m0 ? a[0] : o0; a[1] = m1 ? a[1] : o1; a[2] = m2 ? a[2] : o2; a[3] = m3 ? a[3] : o3;
+    }
+    if (VEC) {
+      const i64x2 u = {a[0], a[1]}, v = {a[2], a[3]};
+      *(i64x2*)(lo + p) = u;
+      *(i64x2*)(lo + p + 2) = v;
+    } else {
+      lo[p] = a[0]; lo[p + 1] = a[1]; lo[p + 2] = a[2]; lo[p + 3] = a[3];
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const long o = ch * HW + p;
+      uint4 r;
+      if (VEC) {
+        if (all) {
+          r = *(const uint4*)(xj + o);
+        } else if (none) {
+          r = *(const uint4*)(xi + o);
+        } else {
+          const uint4 s = *(const uint4*)(xj + o), t = *(const uint4*)(xi + o);
+          r = make_uint4(m0 ? s.x : t.x, m1 ? s.y : t.y, m2 ? s.z : t.z, m3 ? s.w : t.w);
+        }
+        *(uint4*)(xo + o) = r;
+      } else {
+        r.x = m0 ? xj[o] : xi[o];
+        r.y = m1 ? xj[o + 1] : xi[o + 1];
+        r.z = m2 ? xj[o + 2] : xi[o + 2];
+        r.w = m3 ? xj[o + 3] : xi[o + 3];
+        xo[o] = r.x; xo[o + 1] = r.y; xo[o + 2] = r.z; xo[o + 3] = r.w;
+      }
+    }
+  } else if (q == nquad) {                               // scalar tail: h*w % 4 pixels
+    for (long p = nquad << 2; p < HW; ++p) {
+      const long long l = lj[p];
+      const bool m = pasted(l, C, mask);
+      lo[p] = m ? l : li[p];
+      for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = m ? xj[ch * HW + p] : xi[ch * HW + p];
+    }
+  }
+}
+
+extern "C" int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->x && d->lab && d->x_out && d->lab_out && d->part);
+  SIMT_CHECK(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->lab & 15) == 0 && ((uintptr_t)d->x_out & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0);
+  SIMT_CHECK(((uintptr_t)d->part & 3) == 0 && (const void*)d->x != (const void*)d->x_out && (const void*)d->lab != (const void*)d->lab_out);
+  SIMT_CHECK(d->B > 0 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0);
+  SIMT_CHECK(d->n_classes >= 1 && d->n_classes <= SIMT_CLASS_MIX_CLASSES);
+  const long HW = (long)d->h * d->w;
+  SIMT_CHECK(HW < (1L << 31));
+  for (int b = 0; b < d->B; ++b) {
+    SIMT_CHECK(d->partner[b] < d->B);
+    for (int c = 0; c < d->n_classes; ++c) SIMT_CHECK(d->rank[b][c] < d->n_classes);
+  }
+  const long lanes = (HW >> 2) + ((HW & 3) ? 1 : 0);
+  const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)d->B);
+  if ((HW & 3) == 0)
+    hipLaunchKernelGGL((class_mix_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else
+    hipLaunchKernelGGL((class_mix_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}

@@ -17,6 +17,7 @@ import torch
 
 from .. import _lib as L
 from . import resample as rs
+from . import class_mix as cm
 from . import scale_crop as sc
 
 IMG_MEAN = (104.00698793, 116.66876762, 122.67891434)      # tools/trainV2_simt.py:34 (BGR)
@@ -30,12 +31,18 @@ class InputPrep:
     """Device transform of a batch of decoded frames of ONE source geometry: [B, Hs, Ws, 3] u8 RGB (+ [B, Hs, Ws] u8 labels) ->
     [B, 3, h, w] fp32 (BGR - mean) (+ [B, h, w] int64).  crop = (w, h) like the reference's `crop_size` / --input-size-target."""
 
-    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None):
+    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None, class_mix=None):
         self.B, (self.Hs, self.Ws), (self.w, self.h) = B, src_hw, crop_wh
         self.dev = torch.device(device)
         self.mean = tuple(_f32(m) for m in mean)
         self.with_label = with_label
         dev = self.dev
+        self.cm, self.part = None, None
+        if class_mix is not None:           # (n_classes, prob): `class_mix_batch` mixes a finished batch (simt_amd/data/class_mix.py)
+            if not with_label:
+                raise ValueError("--class-mix needs labels: the classes to paste are read from the partner's label")
+            self.cm = cm.parse(class_mix[1], class_mix[0], B)
+            self.part = torch.empty(B * L.CLASS_MIX_PARTS, dtype=torch.int32, device=dev)      # simt_label_presence's words
         self.sc = None
         if scale_crop is not None:          # the scale-crop mode (simt_amd/data/scale_crop.py): `scale_crop_batch` is the only entry point
             self.sc = sc.Tables(src_hw, crop_wh, scale_crop)
@@ -172,6 +179,28 @@ class InputPrep:
             d.mean[0], d.mean[1], d.mean[2] = self.mean
             L.call("simt_scale_crop", C.byref(d), stream)
 
+    def class_mix_batch(self, x, lab, draws, x_out, lab_out, stream):
+        """ClassMix of a finished batch: x [B,3,h,w] f32 / lab [B,h,w] i64 -> x_out / lab_out (other buffers: item i reads item
+        (i + 1) % B while another workgroup writes it).  draws = (apply [B] bool, rank [B, n_classes] permutations)
+        (class_mix.draw_batch).  Two launches on `stream`: simt_label_presence, then simt_class_mix."""
+        assert self.cm is not None, "built without class_mix"
+        n_classes = self.cm[0]
+        for t, o in ((x, x_out), (lab, lab_out)):
+            assert t.shape == o.shape and t.dtype == o.dtype and t.is_contiguous() and o.is_contiguous() and t.data_ptr() != o.data_ptr()
+        assert x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.h, self.w)
+        assert lab.dtype == torch.int64 and tuple(lab.shape) == (self.B, self.h, self.w)
+        apply, rank = draws
+        rank = np.ascontiguousarray(rank, dtype=np.uint8)
+        assert len(apply) == self.B and rank.shape == (self.B, n_classes)
+        d = L.ClassMixDesc()
+        d.x, d.lab, d.x_out, d.lab_out, d.part = x.data_ptr(), lab.data_ptr(), x_out.data_ptr(), lab_out.data_ptr(), self.part.data_ptr()
+        d.B, d.h, d.w, d.n_classes = self.B, self.h, self.w, n_classes
+        for i in range(self.B):
+            d.partner[i], d.apply[i] = (i + 1) % self.B, 1 if apply[i] else 0
+            C.memmove(d.rank[i], rank[i].ctypes.data, n_classes)
+        L.call("simt_label_presence", lab.data_ptr(), self.B, self.h * self.w, n_classes, self.part.data_ptr(), stream)
+        L.call("simt_class_mix", C.byref(d), stream)
+
 
 class DevicePrefetcher:
     """Pinned double-buffered upload + device transform, one batch ahead of the consumer.
@@ -186,10 +215,12 @@ class DevicePrefetcher:
     that stream up to that point -- the step that consumed batch k included -- precedes the refill), and the copy stream waits for
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
-    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None):
+    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
         assert (draw_fn is not None) == (prep.sc is not None)
+        self.mix_fn = mix_fn            # class-mix mode (prep.cm): B -> (apply, rank); the slot's finished batch is mixed into xm / labm
+        assert (mix_fn is not None) == (prep.cm is not None)
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -205,6 +236,8 @@ class DevicePrefetcher:
                 s["lab_h"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8).pin_memory()
                 s["lab_d"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8, device=dev)
                 s["lab"] = torch.empty(B, prep.h, prep.w, dtype=torch.int64, device=dev)
+            if mix_fn is not None:                     # what __next__ hands out in class-mix mode: same life time as x / lab
+                s["xm"], s["labm"] = torch.empty_like(s["x"]), torch.empty_like(s["lab"])
             if cache is not None:                      # transient slots for the items the cache has no room for
                 s["sp_img"] = torch.empty(B * cache.img_stride, dtype=torch.uint8, device=dev)
                 s["sp_lab"] = torch.empty(B * cache.lab_stride, dtype=torch.uint8, device=dev) if prep.with_label else None
@@ -257,9 +290,18 @@ class DevicePrefetcher:
                 mirror = self.mirror_fn(self.prep.B) if self.mirror_fn is not None else False
                 self.prep.run(s["rgb_d"], s["x"], s["lab_d"] if lab is not None else None, s["lab"] if lab is not None else None,
                               mirror=mirror, stream=cs.cuda_stream)
+            self._mix(s, lab is not None, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
         self.filled += 1
+
+    def _mix(self, s, has_lab, cs):
+        """Class-mix mode: the slot's finished batch x / lab -> xm / labm, on the copy stream, behind the launches that made it."""
+        if self.mix_fn is None:
+            return
+        if not has_lab:
+            raise ValueError("--class-mix: a batch without labels cannot be mixed")
+        self.prep.class_mix_batch(s["x"], s["lab"], self.mix_fn(self.prep.B), s["xm"], s["labm"], cs.cuda_stream)
 
     def _fill_cached(self, s, rgb, lab, meta):
         """With a cache the source yields only the batch's MISSES: rgb [M,Hs,Ws,3] (None when M = 0), lab likewise, and
@@ -306,6 +348,7 @@ class DevicePrefetcher:
             else:
                 mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
                 prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+            self._mix(s, has_lab, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, has_lab, True
         self.filled += 1
@@ -320,7 +363,10 @@ class DevicePrefetcher:
         s = self.slots[i]
         cur = torch.cuda.current_stream(self.prep.dev)
         cur.wait_event(s["ready"])
-        out = (s["x"], s["lab"] if s["has_lab"] else None, s["meta"])
+        if self.mix_fn is not None:
+            out = (s["xm"], s["labm"], s["meta"])
+        else:
+            out = (s["x"], s["lab"] if s["has_lab"] else None, s["meta"])
         self.filled -= 1
         self.calls += 1
         self.head = (i + 1) % len(self.slots)
@@ -382,7 +428,12 @@ class GpuLoader:
     dataset.scale_crop = decimal scale choices (cityscapesPseudo(scale_crop=...), --scale-crop) turns on random scale + crop
     (simt_amd/data/scale_crop.py): per batch the generator draws, after the mirror flags, a choice and a window origin per item, and ONE
     simt_scale_crop launch makes the batch from the decoded frames.  A cache then holds the ORIGINAL frames (DatasetCache((Ws, Hs))).
-    Cached and uncached batches are bit-identical and start_batch skips the same draws.  Without it not one draw changes."""
+    Cached and uncached batches are bit-identical and start_batch skips the same draws.  Without it not one draw changes.
+
+    dataset.class_mix = (n_classes, prob) (cityscapesPseudo(class_mix=...), --class-mix) turns on ClassMix (simt_amd/data/class_mix.py):
+    every finished batch -- plain, scale-cropped, cached or not -- is mixed on the copy stream, item i with item (i + 1) % B, before it
+    is handed out.  Its draws come from a generator of their own, class_mix.generator(seed, rank): the batch underneath is the batch
+    of the loader without the flag, bit for bit, and start_batch skips the mix draws too."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -394,6 +445,11 @@ class GpuLoader:
         self.scale_crop = getattr(dataset, "scale_crop", None)
         if self.scale_crop is not None:
             self.scale_crop = sc.parse_choices(self.scale_crop)
+        self.class_mix = getattr(dataset, "class_mix", None)
+        self._mix_rng = None
+        if self.class_mix is not None:
+            self.class_mix = cm.parse(self.class_mix[1], self.class_mix[0], batch_size)
+            self._mix_rng = cm.skip_draws(cm.generator(seed, rank), batch_size, int(start_batch), self.class_mix[0])
         self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
         if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
@@ -497,8 +553,10 @@ class GpuLoader:
             return iter(())
         Hs, Ws = first[0].shape[1:3]
         assert self.cache is None or self.cache.with_label or first[1] is None, "the dataset has labels, the cache no label slab"
+        if self.class_mix is not None and first[1] is None:
+            raise ValueError("--class-mix: the dataset yields no labels, and the classes to paste are read from the partner's label")
         self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None,
-                               scale_crop=self.scale_crop)
+                               scale_crop=self.scale_crop, class_mix=self.class_mix)
         if self.scale_crop is not None and self.cache is not None:
             assert (self.cache.w, self.cache.h) == (Ws, Hs), "with scale-crop the cache holds the ORIGINAL frames: DatasetCache((Ws, Hs))"
 
@@ -511,5 +569,8 @@ class GpuLoader:
         if self.scale_crop is not None:
             mirror_on = bool(getattr(self.ds, "is_mirror", False))
             draw_fn = lambda n: sc.draw_batch(self._rng, n, self.scale_crop, tuple(self.ds.crop_size), mirror_on)
-        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn)
+        mix_fn = None
+        if self.class_mix is not None:
+            mix_fn = lambda n: cm.draw_batch(self._mix_rng, n, *self.class_mix)
+        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

@@ -19,6 +19,8 @@ reference unless bf16 is asked for), --print-every, --data-dir-val,
 the batches are the same, bit for bit, only PNG decoding after epoch one is saved),
 --scale-crop [S ...]: random scale + crop of every training item on the device, one launch per batch (simt_amd/data/scale_crop.py; default
 off; --random-scale stays what the reference makes of it: parsed and ignored),
+--class-mix [P]: ClassMix of every batch on the device -- with probability P (no value: 1) an item receives the pixels and labels of half
+of the classes of its neighbour in the batch (simt_amd/data/class_mix.py; default off; needs --batch-size 2 ... 32, --num-classes <= 32),
 --train-state FILE [--train-state-every N]: resume from FILE if it exists and keep it current (simt_amd/train_state.py).  The snapshots hold
 the model only; FILE also holds the SGD momentum, both NTMs and W with their Adam moments, the iteration counter, the snapshot rotation's
 bookkeeping -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
@@ -100,6 +102,7 @@ def get_arguments(argv=None):
     add_v3_layers(p)
     add_cache_args(p)
     add_scale_crop_args(p)
+    add_class_mix_args(p)
     add_train_state_args(p)
     return p.parse_args(argv)
 
@@ -136,6 +139,26 @@ def scale_crop_choices(args):
         return parse_choices(texts)
     except ValueError as e:
         raise SystemExit(f"--scale-crop: {e}")
+
+
+def add_class_mix_args(p):
+    p.add_argument("--class-mix", type=str, nargs="?", const="1.0", default=None, metavar="P",
+                   help="ClassMix on the device (simt_amd/data/class_mix.py): with probability P (no value: 1.0) item i of a batch receives, "
+                        "labels included, the pixels of half of the classes (rounded up) found in the label of item (i + 1) %% B; two "
+                        "launches per batch on the copy stream.  Needs --batch-size 2 ... 32 and --num-classes <= 32.  Default: off.  "
+                        "Ignored with --synthetic")
+
+
+def class_mix_setting(args):
+    """--class-mix -> (n_classes, P), or None when the flag is off (a bad P, batch size or class count is a SystemExit naming it)."""
+    value = getattr(args, "class_mix", None)
+    if value is None:
+        return None
+    from simt_amd.data.class_mix import parse
+    try:
+        return parse(value, args.num_classes, args.batch_size)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def add_train_state_args(p):
@@ -274,13 +297,13 @@ class SnapshotKeeper:
         self.best_mIoU, self.best_iter, self.rolling_iter = st["best_mIoU"], st["best_iter"], st["rolling_iter"]
 
 
-RUN_DEFAULTS = {"scale_crop": False}      # run_identity keys that are absent when their flag is off: what absence means
+RUN_DEFAULTS = {"scale_crop": False, "class_mix": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
     """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror and scale-crop draws, synthetic batches), the
-    mirror switch, the scale-crop choices (RUN_DEFAULTS: the key is absent when the flag is off, and absent means False -- the state files
-    of runs from before the flag existed are those of runs without it; with --synthetic the flag does nothing), where the data comes from
+    mirror switch, the scale-crop choices and the class-mix probability (RUN_DEFAULTS: a key is absent when its flag is off, and absent means
+    False -- the state files of runs from before a flag existed are those of runs without it; with --synthetic the flags do nothing), where the data comes from
     (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
     import hashlib
     choices = None if args.synthetic else scale_crop_choices(args)
@@ -288,6 +311,9 @@ def run_identity(args, class_dist):
              "class_dist_sha256": hashlib.sha256(np.ascontiguousarray(np.asarray(class_dist, dtype=np.float32)).tobytes()).hexdigest()}
     if choices is not None:
         ident["scale_crop"] = list(choices)
+    mix = None if args.synthetic else class_mix_setting(args)
+    if mix is not None:
+        ident["class_mix"] = mix[1]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -362,9 +388,12 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
     resumed run: iterations done x iter_size)."""
     choices = scale_crop_choices(args)
+    mix = class_mix_setting(args)
     if args.synthetic:
         if choices is not None and rank == 0:
             print("--scale-crop does nothing with --synthetic: the synthetic batches are made at the crop's size")
+        if mix is not None and rank == 0:
+            print("--class-mix does nothing with --synthetic: the synthetic batches are not mixed")
 
         def synth():
             it = start_batch
@@ -377,7 +406,7 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
-                          scale_crop=choices)
+                          scale_crop=choices, class_mix=mix)
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
