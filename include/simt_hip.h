@@ -613,6 +613,61 @@ typedef struct {
 int simt_label_presence(const long long* lab, int B, long hw, int n_classes, uint32_t* part, simt_stream_t stream);
 int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream);
 
+/* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
+ * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
+ * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another
+ * buffer x_out.  Labels are not touched.
+ * All arithmetic below is IEEE float32.  Every multiply and every add is rounded on its own (no contraction into FMA), in the order
+ * written.  clamp(v) = min(max(v, 0), 1).
+ * Per item i the descriptor carries jit[i], blur[i] (bytes), fb, fc, omfc, a 3x3 matrix A (row-major: A[3 * p + c]) and six blur weights
+ * wk[0..5].  The three planes are treated as B, G, R by position, with grey weights wg = (0.114, 0.587, 0.299) as float32.  A mirrored
+ * item, whose planes the reference's loader leaves in RGB order, and pixels pasted from such an item, get the weights of their plane
+ * position.  This is documented, not corrected.
+ *   Normalise.  v_p = clamp((x_p + mean[p]) * c255), with c255 = float32(1/255).
+ *   Jitter (only if jit[i]), in fixed order:
+ *     Brightness: v_p = clamp(fb * v_p).
+ *     Contrast:   v_p = clamp(fc * v_p + omfc * m), with omfc = float32(1 - fc) from the host.  m is the item's grey mean after
+ *                 brightness, defined exactly: g = (wg0*v0 + wg1*v1) + wg2*v2;  q = rint(g * 65536), ties to even, as an unsigned integer;
+ *                 S = sum of q over the item, as a 64-bit integer (exact and order-free);  m = float32(float64(S) * inv), with
+ *                 inv = float64(1 / (65536*h*w)) from the host.
+ *     Saturation and hue, as one matrix: v'_p = clamp((A[p][0]*v0 + A[p][1]*v1) + A[p][2]*v2).  The host computes
+ *                 A = H(theta) . (fs.I + (1-fs).1.wg^T) in float64, H(theta) the rotation by theta turns about the grey axis in YIQ space,
+ *                 expressed in the plane order above; A is rounded once to float32.
+ *   Blur (only if blur[i]): separable, radius 5, horizontal pass then vertical pass.  Indices outside the frame are reflected without
+ *     repeating the edge: -k -> k, n-1+k -> n-1-k.  Per pass and plane: acc = wk0*c, then for k = 1..5 acc = acc + wk[k] * (l_k + r_k)
+ *     (the neighbour sum is rounded first, then the product, then the add).  After the vertical pass, one clamp.  The host computes
+ *     exp(-k^2 / 2 sigma^2) in float64 and sets any weight below 2^-24 to exactly 0, so no denormal ever arises; it then normalises so that
+ *     wk0 + 2 sum wk[k] = 1, and rounds to float32.
+ *   Back.  x_out_p = v_p * 255 - mean[p].
+ *   Neither flag set: item i is copied bit for bit (NaN payloads and -0.0 survive, as in ClassMix).  With a flag set, inputs must be
+ *     finite.
+ * simt_grey_mean_parts (grid SIMT_PHOTOMETRIC_PARTS x B): part[b * SIMT_PHOTOMETRIC_PARTS + g] = the sum of q over the pixels of item b
+ * that workgroup g visits; every word is written with a plain store on every call (no atomics, nothing to zero); 0, without reading x,
+ * for an item with jit[b] == 0.  It reads x, part, B, h, w, mean, jit and fb of the descriptor.  simt_photometric reads the item's
+ * SIMT_PHOTOMETRIC_PARTS words, so simt_grey_mean_parts runs before it on the same stream with the same descriptor.
+ * Any h, w >= 6 (the reflection is defined) with h * w < 2^31; x_out != x; x and x_out 16-byte, part 8-byte aligned;
+ * 1 <= B <= SIMT_PHOTOMETRIC_MAX (items are independent: a larger batch is split by the caller).  Anything else is refused with an error
+ * code and no launch.  The descriptor travels as kernel arguments, like simt_class_mix_desc. */
+#define SIMT_PHOTOMETRIC_MAX 32
+#define SIMT_PHOTOMETRIC_PARTS 64
+typedef struct {
+  const float* x;                          /* [B][3][h][w] fp32 */
+  float* x_out;                            /* [B][3][h][w] fp32 */
+  unsigned long long* part;                /* [B][SIMT_PHOTOMETRIC_PARTS]: simt_grey_mean_parts writes, simt_photometric reads */
+  double inv;                              /* 1 / (65536 * h * w) */
+  int32_t B, h, w;
+  float mean[3];
+  float fb[SIMT_PHOTOMETRIC_MAX];
+  float fc[SIMT_PHOTOMETRIC_MAX];
+  float omfc[SIMT_PHOTOMETRIC_MAX];
+  float A[SIMT_PHOTOMETRIC_MAX][9];
+  float wk[SIMT_PHOTOMETRIC_MAX][6];
+  uint8_t jit[SIMT_PHOTOMETRIC_MAX];
+  uint8_t blur[SIMT_PHOTOMETRIC_MAX];
+} simt_photometric_desc;
+int simt_grey_mean_parts(const simt_photometric_desc* d, simt_stream_t stream);
+int simt_photometric(const simt_photometric_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,19 @@ class ClassMixDesc(C.Structure):
                 ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
 
 
+PHOTOMETRIC_MAX = 32     # include/simt_hip.h SIMT_PHOTOMETRIC_MAX
+PHOTOMETRIC_PARTS = 64   # SIMT_PHOTOMETRIC_PARTS
+
+
+class PhotometricDesc(C.Structure):
+    """simt_photometric_desc (include/simt_hip.h): one finished batch -> the colour-jittered, blurred batch."""
+    _fields_ = [("x", c_p), ("x_out", c_p), ("part", c_p), ("inv", C.c_double),
+                ("B", i32), ("h", i32), ("w", i32), ("mean", f32 * 3),
+                ("fb", f32 * PHOTOMETRIC_MAX), ("fc", f32 * PHOTOMETRIC_MAX), ("omfc", f32 * PHOTOMETRIC_MAX),
+                ("A", (f32 * 9) * PHOTOMETRIC_MAX), ("wk", (f32 * 6) * PHOTOMETRIC_MAX),
+                ("jit", C.c_uint8 * PHOTOMETRIC_MAX), ("blur", C.c_uint8 * PHOTOMETRIC_MAX)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -252,6 +265,8 @@ SIGNATURES = {
     "simt_scale_crop": (_I, [C.POINTER(ScaleCropDesc), c_p]),
     "simt_label_presence": (_I, [c_p, _I, _L, _I, c_p, c_p]),
     "simt_class_mix": (_I, [C.POINTER(ClassMixDesc), c_p]),
+    "simt_grey_mean_parts": (_I, [C.POINTER(PhotometricDesc), c_p]),
+    "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
 }
 
 _lib = None

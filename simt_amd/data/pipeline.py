@@ -18,6 +18,7 @@ import torch
 from .. import _lib as L
 from . import resample as rs
 from . import class_mix as cm
+from . import photometric as ph
 from . import scale_crop as sc
 
 IMG_MEAN = (104.00698793, 116.66876762, 122.67891434)      # tools/trainV2_simt.py:34 (BGR)
@@ -31,7 +32,7 @@ class InputPrep:
     """Device transform of a batch of decoded frames of ONE source geometry: [B, Hs, Ws, 3] u8 RGB (+ [B, Hs, Ws] u8 labels) ->
     [B, 3, h, w] fp32 (BGR - mean) (+ [B, h, w] int64).  crop = (w, h) like the reference's `crop_size` / --input-size-target."""
 
-    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None, class_mix=None):
+    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None, class_mix=None, photometric=None):
         self.B, (self.Hs, self.Ws), (self.w, self.h) = B, src_hw, crop_wh
         self.dev = torch.device(device)
         self.mean = tuple(_f32(m) for m in mean)
@@ -43,6 +44,10 @@ class InputPrep:
                 raise ValueError("--class-mix needs labels: the classes to paste are read from the partner's label")
             self.cm = cm.parse(class_mix[1], class_mix[0], B)
             self.part = torch.empty(B * L.CLASS_MIX_PARTS, dtype=torch.int32, device=dev)      # simt_label_presence's words
+        self.ph, self.grey_part = None, None
+        if photometric is not None:         # (S | None, P | None): `photometric_batch` jitters and blurs a finished batch (simt_amd/data/photometric.py)
+            self.ph = tuple(photometric)
+            self.grey_part = torch.empty(B * L.PHOTOMETRIC_PARTS, dtype=torch.int64, device=dev)      # simt_grey_mean_parts' words
         self.sc = None
         if scale_crop is not None:          # the scale-crop mode (simt_amd/data/scale_crop.py): `scale_crop_batch` is the only entry point
             self.sc = sc.Tables(src_hw, crop_wh, scale_crop)
@@ -201,6 +206,31 @@ class InputPrep:
         L.call("simt_label_presence", lab.data_ptr(), self.B, self.h * self.w, n_classes, self.part.data_ptr(), stream)
         L.call("simt_class_mix", C.byref(d), stream)
 
+    def photometric_batch(self, x, draws, x_out, stream):
+        """Colour jitter + Gaussian blur of a finished batch: x [B,3,h,w] f32 -> x_out (another buffer: a blurred pixel reads its
+        neighbours).  draws = photometric.draw_batch's dict of [B] arrays.  Two launches on `stream` per SIMT_PHOTOMETRIC_MAX items
+        (items are independent, so a larger batch is split): simt_grey_mean_parts, then simt_photometric."""
+        assert self.ph is not None, "built without photometric settings"
+        assert x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.h, self.w) and x.is_contiguous()
+        assert x_out.dtype == torch.float32 and x_out.shape == x.shape and x_out.is_contiguous() and x_out.data_ptr() != x.data_ptr()
+        assert all(len(draws[k]) == self.B for k in ("jit", "blur", "fb", "fc", "fs", "theta", "sigma"))
+        for b0 in range(0, self.B, L.PHOTOMETRIC_MAX):
+            n = min(L.PHOTOMETRIC_MAX, self.B - b0)
+            d = L.PhotometricDesc()
+            d.x, d.x_out, d.part = x[b0].data_ptr(), x_out[b0].data_ptr(), self.grey_part[b0 * L.PHOTOMETRIC_PARTS:].data_ptr()
+            d.inv = ph.inv_pixels(self.h, self.w)
+            d.B, d.h, d.w = n, self.h, self.w
+            d.mean[0], d.mean[1], d.mean[2] = self.mean
+            for k in range(n):
+                i = b0 + k
+                fb, fc, omfc, A, wk = ph.item_params(draws["fb"][i], draws["fc"][i], draws["fs"][i], draws["theta"][i], draws["sigma"][i])
+                d.jit[k], d.blur[k] = 1 if draws["jit"][i] else 0, 1 if draws["blur"][i] else 0
+                d.fb[k], d.fc[k], d.omfc[k] = float(fb), float(fc), float(omfc)
+                C.memmove(d.A[k], np.ascontiguousarray(A, dtype=np.float32).ctypes.data, 36)
+                C.memmove(d.wk[k], np.ascontiguousarray(wk, dtype=np.float32).ctypes.data, 24)
+            L.call("simt_grey_mean_parts", C.byref(d), stream)
+            L.call("simt_photometric", C.byref(d), stream)
+
 
 class DevicePrefetcher:
     """Pinned double-buffered upload + device transform, one batch ahead of the consumer.
@@ -215,12 +245,14 @@ class DevicePrefetcher:
     that stream up to that point -- the step that consumed batch k included -- precedes the refill), and the copy stream waits for
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
-    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None):
+    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None, photo_fn=None):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
         assert (draw_fn is not None) == (prep.sc is not None)
         self.mix_fn = mix_fn            # class-mix mode (prep.cm): B -> (apply, rank); the slot's finished batch is mixed into xm / labm
         assert (mix_fn is not None) == (prep.cm is not None)
+        self.photo_fn = photo_fn        # photometric mode (prep.ph): B -> draws; the finished (mixed) batch is jittered and blurred into xp
+        assert (photo_fn is not None) == (prep.ph is not None)
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -238,6 +270,8 @@ class DevicePrefetcher:
                 s["lab"] = torch.empty(B, prep.h, prep.w, dtype=torch.int64, device=dev)
             if mix_fn is not None:                     # what __next__ hands out in class-mix mode: same life time as x / lab
                 s["xm"], s["labm"] = torch.empty_like(s["x"]), torch.empty_like(s["lab"])
+            if photo_fn is not None:                   # what __next__ hands out in photometric mode: same life time as x
+                s["xp"] = torch.empty_like(s["x"])
             if cache is not None:                      # transient slots for the items the cache has no room for
                 s["sp_img"] = torch.empty(B * cache.img_stride, dtype=torch.uint8, device=dev)
                 s["sp_lab"] = torch.empty(B * cache.lab_stride, dtype=torch.uint8, device=dev) if prep.with_label else None
@@ -291,6 +325,7 @@ class DevicePrefetcher:
                 self.prep.run(s["rgb_d"], s["x"], s["lab_d"] if lab is not None else None, s["lab"] if lab is not None else None,
                               mirror=mirror, stream=cs.cuda_stream)
             self._mix(s, lab is not None, cs)
+            self._photo(s, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
         self.filled += 1
@@ -302,6 +337,13 @@ class DevicePrefetcher:
         if not has_lab:
             raise ValueError("--class-mix: a batch without labels cannot be mixed")
         self.prep.class_mix_batch(s["x"], s["lab"], self.mix_fn(self.prep.B), s["xm"], s["labm"], cs.cuda_stream)
+
+    def _photo(self, s, cs):
+        """Photometric mode: the slot's finished batch -- xm when it was mixed, else x -> xp, on the copy stream, behind `_mix`."""
+        if self.photo_fn is None:
+            return
+        src = s["xm"] if self.mix_fn is not None else s["x"]
+        self.prep.photometric_batch(src, self.photo_fn(self.prep.B), s["xp"], cs.cuda_stream)
 
     def _fill_cached(self, s, rgb, lab, meta):
         """With a cache the source yields only the batch's MISSES: rgb [M,Hs,Ws,3] (None when M = 0), lab likewise, and
@@ -349,6 +391,7 @@ class DevicePrefetcher:
                 mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
                 prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
             self._mix(s, has_lab, cs)
+            self._photo(s, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, has_lab, True
         self.filled += 1
@@ -367,6 +410,8 @@ class DevicePrefetcher:
             out = (s["xm"], s["labm"], s["meta"])
         else:
             out = (s["x"], s["lab"] if s["has_lab"] else None, s["meta"])
+        if self.photo_fn is not None:      # the label that would have been handed out anyway
+            out = (s["xp"], out[1], out[2])
         self.filled -= 1
         self.calls += 1
         self.head = (i + 1) % len(self.slots)
@@ -433,7 +478,13 @@ class GpuLoader:
     dataset.class_mix = (n_classes, prob) (cityscapesPseudo(class_mix=...), --class-mix) turns on ClassMix (simt_amd/data/class_mix.py):
     every finished batch -- plain, scale-cropped, cached or not -- is mixed on the copy stream, item i with item (i + 1) % B, before it
     is handed out.  Its draws come from a generator of their own, class_mix.generator(seed, rank): the batch underneath is the batch
-    of the loader without the flag, bit for bit, and start_batch skips the mix draws too."""
+    of the loader without the flag, bit for bit, and start_batch skips the mix draws too.
+
+    dataset.photometric = (S | None, P | None) (cityscapesPseudo(photometric=...), --colour-jitter / --gaussian-blur) turns on colour
+    jitter and Gaussian blur (simt_amd/data/photometric.py): the finished batch -- after the mix, when there is one -- is jittered and
+    blurred on the copy stream into a buffer of its own; labels are not touched (a dataset without labels works).  Its draws come from
+    photometric.generator(seed, rank): the batch underneath is the batch of the loader without the flags, bit for bit, and start_batch
+    skips these draws too."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -450,6 +501,13 @@ class GpuLoader:
         if self.class_mix is not None:
             self.class_mix = cm.parse(self.class_mix[1], self.class_mix[0], batch_size)
             self._mix_rng = cm.skip_draws(cm.generator(seed, rank), batch_size, int(start_batch), self.class_mix[0])
+        self.photometric = getattr(dataset, "photometric", None)
+        self._photo_rng = None
+        if self.photometric is not None:
+            self.photometric = ph.parse(*self.photometric)      # (S, P) validated like the flags: S in (0, 0.5], P in (0, 1]
+            if self.photometric is None:
+                raise ValueError("dataset.photometric is (None, None): pass None for no photometric augmentation")
+            self._photo_rng = ph.skip_draws(ph.generator(seed, rank), batch_size, int(start_batch))
         self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
         if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
@@ -556,7 +614,7 @@ class GpuLoader:
         if self.class_mix is not None and first[1] is None:
             raise ValueError("--class-mix: the dataset yields no labels, and the classes to paste are read from the partner's label")
         self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None,
-                               scale_crop=self.scale_crop, class_mix=self.class_mix)
+                               scale_crop=self.scale_crop, class_mix=self.class_mix, photometric=self.photometric)
         if self.scale_crop is not None and self.cache is not None:
             assert (self.cache.w, self.cache.h) == (Ws, Hs), "with scale-crop the cache holds the ORIGINAL frames: DatasetCache((Ws, Hs))"
 
@@ -572,5 +630,9 @@ class GpuLoader:
         mix_fn = None
         if self.class_mix is not None:
             mix_fn = lambda n: cm.draw_batch(self._mix_rng, n, *self.class_mix)
-        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn)
+        photo_fn = None
+        if self.photometric is not None:
+            photo_fn = lambda n: ph.draw_batch(self._photo_rng, n, self.photometric)
+        pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn,
+                              photo_fn=photo_fn)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

@@ -4,7 +4,7 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 `evaluate_warmup` + best-mIoU snapshot rotation of :241-256 keeps the reference's file names; data: `cityscapesPseudo` through the device input pipeline (simt_amd/data/pipeline.py) or, with
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
---cache-dataset device [--cache-gb G], --scale-crop [S ...] and --class-mix [P] as in trainV2_simt (both tools share its `batches`).
+--cache-dataset device [--cache-gb G], --scale-crop [S ...], --class-mix [P], --colour-jitter [S] and --gaussian-blur [P] as in trainV2_simt (both tools share its `batches`).
 --train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
@@ -25,7 +25,7 @@ import torch
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
 from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
-                                          add_scale_crop_args, add_train_state_args, add_v3_layers, batches, restore, save_atomic, shutdown)
+                                          add_photometric_args, add_scale_crop_args, add_train_state_args, add_v3_layers, batches, restore, save_atomic, shutdown)
 
 
 def get_arguments(argv=None):
@@ -81,6 +81,7 @@ def get_arguments(argv=None):
     add_cache_args(p)
     add_scale_crop_args(p)
     add_class_mix_args(p)
+    add_photometric_args(p)
     add_train_state_args(p)
     return p.parse_args(argv)
 

@@ -21,6 +21,10 @@ the batches are the same, bit for bit, only PNG decoding after epoch one is save
 off; --random-scale stays what the reference makes of it: parsed and ignored),
 --class-mix [P]: ClassMix of every batch on the device -- with probability P (no value: 1) an item receives the pixels and labels of half
 of the classes of its neighbour in the batch (simt_amd/data/class_mix.py; default off; needs --batch-size 2 ... 32, --num-classes <= 32),
+--colour-jitter [S] / --gaussian-blur [P]: the photometric half of the strong augmentation, on the finished (mixed) batch on the device:
+with probability 0.8 brightness, contrast and saturation factors from [1 - S, 1 + S] and a hue turn from [-S, S] (no value: S = 0.2;
+0 < S <= 0.5), then with probability P (no value: 0.5) a Gaussian blur, sigma from [0.15, 1.15] (simt_amd/data/photometric.py; default off;
+either flag alone is allowed),
 --train-state FILE [--train-state-every N]: resume from FILE if it exists and keep it current (simt_amd/train_state.py).  The snapshots hold
 the model only; FILE also holds the SGD momentum, both NTMs and W with their Adam moments, the iteration counter, the snapshot rotation's
 bookkeeping -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
@@ -103,6 +107,7 @@ def get_arguments(argv=None):
     add_cache_args(p)
     add_scale_crop_args(p)
     add_class_mix_args(p)
+    add_photometric_args(p)
     add_train_state_args(p)
     return p.parse_args(argv)
 
@@ -157,6 +162,29 @@ def class_mix_setting(args):
     from simt_amd.data.class_mix import parse
     try:
         return parse(value, args.num_classes, args.batch_size)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+def add_photometric_args(p):
+    from simt_amd.data.photometric import DEFAULT_BLUR, DEFAULT_JITTER
+    p.add_argument("--colour-jitter", type=str, nargs="?", const=DEFAULT_JITTER, default=None, metavar="S",
+                   help="colour jitter of every batch on the device (simt_amd/data/photometric.py): with probability 0.8 an item's brightness, "
+                        "contrast and saturation are scaled by factors drawn from [1 - S, 1 + S] and its hue is turned by [-S, S] turns (no "
+                        "value: S = 0.2; 0 < S <= 0.5), after --class-mix.  Default: off.  Ignored with --synthetic")
+    p.add_argument("--gaussian-blur", type=str, nargs="?", const=DEFAULT_BLUR, default=None, metavar="P",
+                   help="Gaussian blur of every batch on the device, after the colour jitter: with probability P (no value: 0.5) an item is "
+                        "blurred with a sigma drawn from [0.15, 1.15] (radius 5, reflected edges).  Default: off.  Ignored with --synthetic")
+
+
+def photometric_setting(args):
+    """--colour-jitter / --gaussian-blur -> (S | None, P | None), or None when both flags are off (a bad value is a SystemExit naming it)."""
+    jitter, blur = getattr(args, "colour_jitter", None), getattr(args, "gaussian_blur", None)
+    if jitter is None and blur is None:
+        return None
+    from simt_amd.data.photometric import parse
+    try:
+        return parse(jitter, blur)
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -297,12 +325,12 @@ class SnapshotKeeper:
         self.best_mIoU, self.best_iter, self.rolling_iter = st["best_mIoU"], st["best_iter"], st["rolling_iter"]
 
 
-RUN_DEFAULTS = {"scale_crop": False, "class_mix": False}      # run_identity keys that are absent when their flag is off: what absence means
+RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
     """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror and scale-crop draws, synthetic batches), the
-    mirror switch, the scale-crop choices and the class-mix probability (RUN_DEFAULTS: a key is absent when its flag is off, and absent means
+    mirror switch, the scale-crop choices, the class-mix probability and the photometric pair [S, P] (RUN_DEFAULTS: a key is absent when its flag is off, and absent means
     False -- the state files of runs from before a flag existed are those of runs without it; with --synthetic the flags do nothing), where the data comes from
     (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
     import hashlib
@@ -314,6 +342,9 @@ def run_identity(args, class_dist):
     mix = None if args.synthetic else class_mix_setting(args)
     if mix is not None:
         ident["class_mix"] = mix[1]
+    photo = None if args.synthetic else photometric_setting(args)
+    if photo is not None:
+        ident["photometric"] = list(photo)          # [colour-jitter S | None, gaussian-blur P | None]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -389,11 +420,14 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     resumed run: iterations done x iter_size)."""
     choices = scale_crop_choices(args)
     mix = class_mix_setting(args)
+    photo = photometric_setting(args)
     if args.synthetic:
         if choices is not None and rank == 0:
             print("--scale-crop does nothing with --synthetic: the synthetic batches are made at the crop's size")
         if mix is not None and rank == 0:
             print("--class-mix does nothing with --synthetic: the synthetic batches are not mixed")
+        if photo is not None and rank == 0:
+            print("--colour-jitter / --gaussian-blur do nothing with --synthetic: the synthetic batches are not augmented")
 
         def synth():
             it = start_batch
@@ -406,7 +440,7 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
-                          scale_crop=choices, class_mix=mix)
+                          scale_crop=choices, class_mix=mix, photometric=photo)
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
