@@ -366,7 +366,8 @@ typedef struct {
   float* T_out[2];      /* [Q][C] T = sig_NTM() */
   const float* class_dist; /* [C] */
   int32_t Q, C, steps, step0; /* step0 = Adam steps already taken on w */
-  float lr, beta1, beta2, eps;
+  float lr, beta1, beta2, eps; /* torch.optim.Adam semantics.  1 - beta and beta^step are formed in double from the betas as written (the shortest
+                                * decimal that rounds to the float: 0.999f -> 0.999) and rounded once, as torch does from its double betas */
   int32_t single;       /* 1: only NTM / W number 1 (index [1]) exist -- one-output models; index [0] pointers may be NULL */
   const uint64_t* skip_if;   /* ABI 2.  Optional device word (simt_fbn_desc.err): the launch changes nothing while it is non-zero; NULL: always run */
 } simt_ntm_inner_desc;

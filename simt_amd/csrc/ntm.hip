@@ -8,6 +8,8 @@
 //   Adam on NTM1/NTM2                                              (tools/trainV2_simt.py:435-436)
 #include "common.h"
 #include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #define NQ 40   // max Q
 #define NC 20   // max C
@@ -22,6 +24,8 @@ struct NtmInnerArgs {
   const float* class_dist;
   int Q, C, steps, step0;
   float lr, beta1, beta2, eps;
+  float omb1, omb2;     // 1 - beta1, 1 - beta2 of the betas as the caller wrote them (as_written), rounded once
+  double beta1d, beta2d;
   int k0;      // first NTM index this launch handles (1 for one-output models)
   const unsigned long long* skip_if;   // simt_ntm_inner_desc.skip_if
 };
@@ -125,15 +129,15 @@ __global__ __launch_bounds__(256) void ntm_inner_kernel(NtmInnerArgs a) {
     }
     __syncthreads();
     const int step = a.step0 + it + 1;
-    const double bc1 = 1.0 - pow((double)a.beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)a.beta2, (double)step);
+    const double bc1 = 1.0 - pow(a.beta1d, (double)step);
+    const double bc2 = 1.0 - pow(a.beta2d, (double)step);
     const float step_size = (float)((double)a.lr / bc1);
     const float bc2s = (float)sqrt(bc2);
     for (int i = tid; i < Q * Q; i += 256) {
       int j = i / Q;
       float g = sm[i] * (dW[i] - dot[j]);
-      float m = am[i] + (g - am[i]) * (1.f - a.beta1);
-      float v = av[i] * a.beta2 + (1.f - a.beta2) * g * g;
+      float m = am[i] + (g - am[i]) * a.omb1;
+      float v = av[i] * a.beta2 + a.omb2 * g * g;
       am[i] = m;
       av[i] = v;
       float denom = sqrtf(v) / bc2s + a.eps;
@@ -146,6 +150,20 @@ __global__ __launch_bounds__(256) void ntm_inner_kernel(NtmInnerArgs a) {
     a.T_out[k][i] = T[i];
   }
   for (int i = tid; i < Q * Q; i += 256) { a.w[k][i] = wraw[i]; a.w_m[k][i] = am[i]; a.w_v[k][i] = av[i]; }
+}
+
+// The double a float hyper-parameter was narrowed from: the shortest decimal that rounds to it (0.999f -> 0.999), which is what the caller
+// wrote.  torch.optim.Adam forms 1 - beta and beta^step from the double and rounds the RESULT: `1.f - 0.999f` is 0.00099998713, 1.3e-5 below
+// float(0.001), and every exp_avg_sq carried that factor; pow(0.999f, step) is off by 1.3e-8 * step.  A float that is no short decimal comes
+// back as itself (9 digits).
+static double as_written(float x) {
+  char buf[32];
+  for (int prec = 1; prec <= 9; ++prec) {
+    snprintf(buf, sizeof buf, "%.*g", prec, (double)x);
+    const double d = strtod(buf, nullptr);
+    if ((float)d == x) return d;
+  }
+  return (double)x;
 }
 
 extern "C" int simt_ntm_inner_loop(const simt_ntm_inner_desc* d, simt_stream_t stream) {
@@ -161,6 +179,8 @@ extern "C" int simt_ntm_inner_loop(const simt_ntm_inner_desc* d, simt_stream_t s
   }
   a.class_dist = d->class_dist; a.Q = d->Q; a.C = d->C; a.steps = d->steps; a.step0 = d->step0;
   a.lr = d->lr; a.beta1 = d->beta1; a.beta2 = d->beta2; a.eps = d->eps;
+  a.beta1d = as_written(d->beta1); a.beta2d = as_written(d->beta2);
+  a.omb1 = (float)(1.0 - a.beta1d); a.omb2 = (float)(1.0 - a.beta2d);
   a.skip_if = (const unsigned long long*)d->skip_if;
   hipLaunchKernelGGL(ntm_inner_kernel, dim3(2 - a.k0), dim3(256), 0, (hipStream_t)stream, a);
   SIMT_LAUNCH_CHECK();
@@ -347,7 +367,7 @@ __global__ __launch_bounds__(256) void ntm_post_kernel(NtmPostArgs a) {
 }
 
 extern "C" int simt_ntm_post(const simt_ntm_post_desc* d, simt_stream_t stream) {
-  SIMT_CHECK(d && d->Q <= NQ && d->C <= NC && d->hout && d->lout && d->class_dist);
+  SIMT_CHECK(d && d->Q <= NQ && d->C <= NC && d->C <= d->Q && d->hout && d->lout && d->class_dist);
   NtmPostArgs a;
   a.k0 = d->single ? 1 : 0;
   for (int k = 0; k < 2; ++k) {

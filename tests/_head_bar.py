@@ -199,7 +199,7 @@ DEFAULT_D = {"lam": np.array([0.5, 0.1, 0.5]), "lr_T": 6e-3, "th": np.array([0.8
 def two_head_ref(p1, p2, f2, lab, ntm, d, cd, dtype, total_of=None):
     """tests/test_gpu_head_ntm.py's oracle run (inner W loop, simt_losses, backward) in `dtype`: logits, NTMs, W and the class prior cast.
     total_of(out, hp): the scalar to differentiate instead of out["total"] (the mutants of tests/test_head_bar_cpu.py).
-    -> dict(dpred1, dpred2, ntm_grad1, ntm_grad2, out)."""
+    -> dict(dpred1, dpred2, ntm_grad1, ntm_grad2, out; w, m, v: sig_W's raw weights and their Adam moments after the inner loop, two each)."""
     K = int(d["K"]); Cn = cd.numel(); Q = Cn + K
     H, W = lab.shape[1:]
     hp = hyper(d, K, Cn)
@@ -214,19 +214,22 @@ def two_head_ref(p1, p2, f2, lab, ntm, d, cd, dtype, total_of=None):
     out = so.simt_losses(q1, q2, f2.to(dtype), lab, T1, T2, so.sig_w_forward(wr[0]), so.sig_w_forward(wr[1]), hp, (H, W))
     (out["total"] if total_of is None else total_of(out, hp)).backward()
     return {"dpred1": q1.grad, "dpred2": q2.grad, "ntm_grad1": n[0].grad, "ntm_grad2": n[1].grad,
-            "out": {k: v.detach() for k, v in out.items()}}
+            "out": {k: v.detach() for k, v in out.items()}, "w": [x.detach() for x in wr], "m": [state["m1"], state["m2"]],
+            "v": [state["v1"], state["v2"]]}
 
 
 def single_ref(pred, fix, lab, ntm, K, half, cd, dtype, d=DEFAULT_D):
     """tests/test_gpu_single.py's oracle run for the one-output models in `dtype`.  half: DeepLabv3 (half-pixel upsample, softmax after the
-    upsample); else DeepLab-VGG16 (align_corners=True, softmax before).  -> dict(dpred2, ntm_grad2, out)."""
+    upsample); else DeepLab-VGG16 (align_corners=True, softmax before).  -> dict(dpred2, ntm_grad2, out; w, m, v: sig_W's raw weight and its
+    Adam moments after the inner loop)."""
     Cn = cd.numel(); Q = Cn + K
     H, W = lab.shape[1:]
     hp = hyper(dict(d, K=K), K, Cn)
     cdt = cd.to(dtype)
     n = ntm.to(dtype).clone().requires_grad_(True)
     wr = so.w_init(Cn, K).to(dtype).requires_grad_(True)
-    so.inner_w_loop_single(n, wr, {"step": 0, "m": torch.zeros(Q, Q, dtype=dtype), "v": torch.zeros(Q, Q, dtype=dtype)}, cdt, hp, float(d["lr_T"]))
+    state = {"step": 0, "m": torch.zeros(Q, Q, dtype=dtype), "v": torch.zeros(Q, Q, dtype=dtype)}
+    so.inner_w_loop_single(n, wr, state, cdt, hp, float(d["lr_T"]))
     q = pred.to(dtype).clone().requires_grad_(True)
     fx = fix.to(dtype)
     Tm = so.sig_ntm_forward(n, cdt, Cn)
@@ -236,7 +239,7 @@ def single_ref(pred, fix, lab, ntm, K, half, cd, dtype, d=DEFAULT_D):
         up, prob = so.upsample(q, (H, W)), so.upsample(torch.softmax(fx, 1), (H, W))
     out = so.simt_losses_single(up, prob, lab, Tm, so.sig_w_forward(wr), hp)
     out["total"].backward()
-    return {"dpred2": q.grad, "ntm_grad2": n.grad, "out": {k: v.detach() for k, v in out.items()}}
+    return {"dpred2": q.grad, "ntm_grad2": n.grad, "out": {k: v.detach() for k, v in out.items()}, "w": wr.detach(), "m": state["m"], "v": state["v"]}
 
 
 def warmup_ref(pred1, pred2, lab, lambda_seg, half, dtype):

@@ -183,7 +183,10 @@ def test_g8b_wellconditioned_reference_iterations(dev):
                 assert rel <= _update_bound(k), f"it {it} {k}: {rel:.3e}"
                 assert abs(ratio - 1.0) <= 0.03, f"it {it} {k}: |update_gpu| / |update_ref| = {ratio:.4f} (scale of the update)"
     np.testing.assert_allclose(tr.ntm[0].cpu().numpy(), d["ntm1"], atol=1e-4)
-    np.testing.assert_allclose(tr.wraw[0].cpu().numpy(), d["w1"], atol=1e-4 * (1 + np.abs(d["w1"]).max()))
+    # sig_W: the diagonal exactly -1e4; the bar's scale is the OFF-diagonal entries (with the diagonal in max|ref| it was an absolute 1.0)
+    w1, off = tr.wraw[0].cpu().numpy(), ~np.eye(d["w1"].shape[0], dtype=bool)
+    assert np.all(np.diag(w1) == -1e4) and np.all(np.diag(d["w1"]) == -1e4)
+    np.testing.assert_allclose(w1[off], d["w1"][off], atol=1e-4 * (1 + np.abs(d["w1"][off]).max()))
 
 
 def _tags(tr):

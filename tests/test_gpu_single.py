@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import _head_bar as hb
+import _ntm_ref as nr
 from _launch_oracle import SENTINEL
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
@@ -111,7 +112,7 @@ def run_single_head(dev, pred, fix, lab, ntm, K, half, *, label_ws=False, f32=Tr
     torch.cuda.synchronize()
     back = lambda g: g.cpu()[:, :Q].reshape(B, h, w, Q).permute(0, 3, 1, 2)
     return dict(lout=lout.cpu(), hout=hout.cpu(), dp_raw=dp.cpu(), dpred=back(dp), dt=None if dt is None else dt.cpu(), back=back,
-                ntm_grad=ngrad.cpu(), w=wraw.cpu(), conf=None if conf_ws is None else conf_ws.cpu().long(),
+                ntm_grad=ngrad.cpu(), w=wraw.cpu(), wm=wm.cpu(), wv=wv.cpu(), conf=None if conf_ws is None else conf_ws.cpu().long(),
                 lws=None if lab_ws is None else lab_ws.cpu().long())
 
 
@@ -158,13 +159,15 @@ def test_single_head_kernel_vs_oracle(dev, flavour, K):
     close(got, q.grad, 1e-5, "d/dlogits")
     assert torch.all(dp.cpu()[:, Q:] == 0)
     close(ngrad.cpu(), n.grad, 2e-5, "dNTM (leak + main)")
-    close(wraw.cpu(), wr.detach(), 1e-5, "W after 10 Adam steps")
     # ... and every element on its own scale against the float64 oracle (tests/_head_bar.py)
     r64, r32 = hb.ref_pair(("single", flavour, rows, K), lambda dt: hb.single_ref(pred, fix, lab, ntm, K, half, CD, dt))
     if rows:
         assert torch.equal(r["conf"], r32["out"]["conf"].long().view_as(r["conf"]))
     for k, gk in (("dpred2", got), ("ntm_grad2", ngrad)):
         hb.report(f"{flavour}{'rows' if rows else ''} K={K}", k, hb.grad_bar(gk, r64[k], r32[k], f"{flavour} K={K} {k}"))
+    # sig_W after the ten Adam steps: diagonal exactly -1e4, every off-diagonal entry and both moments on their own scale (tests/_ntm_ref.py)
+    for f, gk in (("w", wraw), ("m", r["wm"]), ("v", r["wv"])):
+        nr.report(f"{flavour}{'rows' if rows else ''} K={K}", f, nr.square_bar(gk, r64[f], r32[f], f"{flavour} K={K} {f}"))
 
 
 PROD = {"v3": (4, 512, 1024, 6), "vgg": (8, 512, 512, 3)}           # (B, H, W, K) of bench.py --model v3 / vgg (its `dflt` table)
