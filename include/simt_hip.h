@@ -669,6 +669,28 @@ typedef struct {
 int simt_grey_mean_parts(const simt_photometric_desc* d, simt_stream_t stream);
 int simt_photometric(const simt_photometric_desc* d, simt_stream_t stream);
 
+/* ---- exponential moving average of the weights (simt_amd/ema.py): e <- e + omd * (w - e) over a segment table, ONE launch ------
+ * The shadow model of a trainer: every floating tensor of `params` (weights, biases, BatchNorm affine and running statistics) has an fp32
+ * twin `e`; one launch per optimiser step moves all of them towards the live tensors.  One workgroup of 256 lanes per chunk, like
+ * simt_sgd_multi; 16-byte loads and stores where w and e are both 16-byte aligned at the chunk's start, dwords otherwise and for the tail.
+ * ARITHMETIC CONTRACT (the kernel is held to it bit for bit; tests/_ema_ref.py is its numpy restatement):
+ *   - every operation is IEEE binary32, rounded to nearest even on its own, gradual underflow honoured; nothing is contracted into an FMA;
+ *   - omd == 1.0f:  e[i] = w[i] as a 32-bit word copy (NaN payloads and -0.0 survive);
+ *   - otherwise:    t = w[i] - e[i];  u = omd * t;  e[i] = e[i] + u.
+ *     Where w[i] == e[i] the VALUE of e[i] does not move (t = +0, u = +0, e + 0 = e) -- tensors no optimiser touches stay equal to the live
+ *     ones as numbers, no tensor needs a mode of its own.  One bit pattern does change there: e = -0.0 with w = +-0.0 becomes +0.0
+ *     (-0 + +0 = +0 under round to nearest); the restatement does the same;
+ *   - w is never written.
+ * Refused with SIMT_ERR_INVALID and no launch: omd outside (0, 1] or NaN, NULL segs or chunks, nchunks <= 0, chunk <= 0. */
+typedef struct {
+  const void* segs;        /* device array of {const float* w; float* e; int64_t n}  (24 bytes each) */
+  const int32_t* chunks;   /* device [nchunks][2] = (segment, chunk index), as simt_sgd_desc */
+  int32_t nchunks, chunk;  /* elements per chunk */
+  float omd;               /* 1 - decay of THIS update, rounded once from float64 by the host; in (0, 1] */
+  const uint64_t* skip_if; /* optional: the launch changes nothing while *skip_if != 0 (the fused-BatchNorm error word) */
+} simt_ema_desc;
+int simt_ema_multi(const simt_ema_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

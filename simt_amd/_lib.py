@@ -159,6 +159,11 @@ class PhotometricDesc(C.Structure):
                 ("jit", C.c_uint8 * PHOTOMETRIC_MAX), ("blur", C.c_uint8 * PHOTOMETRIC_MAX)]
 
 
+class EmaDesc(C.Structure):
+    """simt_ema_desc (include/simt_hip.h): one weight-EMA update over a segment table, e <- e + omd * (w - e)."""
+    _fields_ = [("segs", c_p), ("chunks", c_p), ("nchunks", i32), ("chunk", i32), ("omd", f32), ("skip_if", c_p)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -267,6 +272,7 @@ SIGNATURES = {
     "simt_class_mix": (_I, [C.POINTER(ClassMixDesc), c_p]),
     "simt_grey_mean_parts": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
+    "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),
 }
 
 _lib = None

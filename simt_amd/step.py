@@ -24,6 +24,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import trace
+from .ema import EmaMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
 from .train_state import TrainStateMixin, state_sha256
 
@@ -64,9 +65,9 @@ def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer
     return g0, g1
 
 
-class SimTTrainer(TrainStateMixin):
+class SimTTrainer(TrainStateMixin, EmaMixin):
     def __init__(self, state, fixed_state, ntm1, ntm2, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 openset=True, process_group=None, w_init=None, layers=None):
+                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None):
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -163,6 +164,7 @@ class SimTTrainer(TrainStateMixin):
         # ---- SGD segments (duplicate listings replayed in registers)
         self._build_sgd()
         self.it_done = 0
+        self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
         # ---- early optimiser step: the gradients SGD applies (layer3, layer4, heads) are final long before the backward has walked
         # through layer2 / layer1 / the stem (whose gradients this stage computes but never applies), so SGD and the re-pack of the
         # updated weights run on the side stream from that point on instead of after the backward (0.7 ms of exclusive tail).
@@ -345,6 +347,10 @@ class SimTTrainer(TrainStateMixin):
             ops.adam_step(self.ntm[k], self.ntm_grad[k], self.ntm_m[k], self.ntm_v[k], lr=lr_T, step=self.it_done + 1, skip_if=self._skip_word)
         if not self._early_sgd:
             self.plan.repack()
+            if self.ema is not None:
+                # behind the re-pack on the main stream: in order after this step's forward (running statistics) and SGD launch, and in front
+                # of everything the next step enqueues (its side-stream work waits for an event the main stream records first: ev0)
+                self.ema.update(st)
         self.it_done += 1
         return self.lout
 
@@ -382,6 +388,11 @@ class SimTTrainer(TrainStateMixin):
                     red.finish()
                 self._sgd(lr, side.cuda_stream)
                 self._pack_applied.run()
+                if self.ema is not None:
+                    # behind the re-pack the next forward waits for.  The side stream waited for ev_main (the whole forward: this step's
+                    # running statistics) and has just run SGD; the backward list's final join makes the main stream wait for the side
+                    # stream, so the launch is complete before the next step writes a master
+                    self.ema.update(side.cuda_stream)
         self.plan.backward(hook=hook)
         assert done[0]
 
@@ -416,13 +427,13 @@ class SimTTrainer(TrainStateMixin):
         return dict(zip(keys, v))
 
 
-class WarmupTrainer(TrainStateMixin):
+class WarmupTrainer(TrainStateMixin, EmaMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
     Same engine as SimTTrainer: TrunkPlan forward/backward, the fused head kernels in mode 1, simt_sgd_multi."""
 
-    def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None):
+    def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None):
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -458,6 +469,7 @@ class WarmupTrainer(TrainStateMixin):
         self.head_desc = hd
         SimTTrainer._build_sgd(self, roots=("conv1", "layer1", "layer2", "layer3", "layer4"))
         self.it_done = 0
+        self._init_ema(ema_decay)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -509,6 +521,8 @@ class WarmupTrainer(TrainStateMixin):
         d.first_step = 1 if self.it_done == 0 else 0
         L.call("simt_sgd_multi", C.byref(d), st)
         self.plan.repack()
+        if self.ema is not None:
+            self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward
         self.it_done += 1
         return self.hout
 

@@ -25,14 +25,15 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .ema import EmaMixin
 from .engine import LaunchList, side_stream
 from .step import lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
 
-class SimTSingleTrainer(TrainStateMixin):
+class SimTSingleTrainer(TrainStateMixin, EmaMixin):
     def __init__(self, model, state, fixed_state, ntm, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 process_group=None, arch=None):
+                 process_group=None, arch=None, ema_decay=None):
         """model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
         DeeplabVGG(nc + openc)); fixed_state: the frozen model's (nc outputs).  arch: plan keyword arguments (reduced depths / widths
         for tests): v3 -> layers, width, assp_ch; vgg -> vgg_layers."""
@@ -130,6 +131,7 @@ class SimTSingleTrainer(TrainStateMixin):
         self.post_desc = npd
         self._build_sgd()
         self.it_done = 0
+        self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -224,6 +226,8 @@ class SimTSingleTrainer(TrainStateMixin):
         main.wait_event(ev_post)
         ops.adam_step(self.ntm, self.ntm_grad, self.ntm_m, self.ntm_v, lr=lr_T, step=self.it_done + 1, skip_if=self._skip_word)
         self.plan.repack()
+        if self.ema is not None:
+            self.ema.update(st)          # main stream, behind SGD and the re-pack; the next step's side-stream work waits for ev0 (main) first
         self.it_done += 1
         return self.lout
 
@@ -256,7 +260,7 @@ class SimTSingleTrainer(TrainStateMixin):
                 "vol_ok": v[9]}
 
 
-class WarmupSingleTrainer(TrainStateMixin):
+class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
     """The warm-up stage (tools/trainV1_warmup.py:156-256) over a ONE-OUTPUT model: DeepLabv3(nc) or DeeplabVGG(nc), trained by cross-entropy
     on the pseudo labels, loss = CE(interp_target(model(x)), label) with ignore_index 255 (:212-231 without the auxiliary head; for
     DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
@@ -264,7 +268,7 @@ class WarmupSingleTrainer(TrainStateMixin):
     Engine: the plans of SimTSingleTrainer, the fused head kernels in their one-head warm-up flavour (simt_head_desc single = 1, mode = 1),
     the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
 
-    def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None):
+    def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer."""
         assert model in ("v3", "vgg")
@@ -320,6 +324,7 @@ class WarmupSingleTrainer(TrainStateMixin):
         self.head_desc = hd
         SimTSingleTrainer._build_sgd(self)
         self.it_done = 0
+        self._init_ema(ema_decay)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -373,6 +378,8 @@ class WarmupSingleTrainer(TrainStateMixin):
         d.first_step = 1 if self.it_done == 0 else 0
         L.call("simt_sgd_multi", C.byref(d), st)
         self.plan.repack()
+        if self.ema is not None:
+            self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward
         self.it_done += 1
         return self.hout
 

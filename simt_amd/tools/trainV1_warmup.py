@@ -6,6 +6,8 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 is honoured) unless --from-scratch is given.
 --cache-dataset device [--cache-gb G], --scale-crop [S ...], --class-mix [P], --colour-jitter [S] and --gaussian-blur [P] as in trainV2_simt (both tools share its `batches`).
 --train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
+--ema [D] as in trainV2_simt: a weight EMA beside the trained model (simt_amd/ema.py), evaluated beside it, kept as
+GTA5_BAPA_warmup_ema_iter<i>_mIoU<m>.pth and written at the stop as GTA5_<stop>_ema.pth.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -24,8 +26,8 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
-from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
-                                          add_photometric_args, add_scale_crop_args, add_train_state_args, add_v3_layers, batches, restore, save_atomic, shutdown)
+from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
+                                          add_ema_args, add_photometric_args, add_scale_crop_args, add_train_state_args, add_v3_layers, batches, restore, save_atomic, shutdown)
 
 
 def get_arguments(argv=None):
@@ -83,6 +85,7 @@ def get_arguments(argv=None):
     add_class_mix_args(p)
     add_photometric_args(p)
     add_train_state_args(p)
+    add_ema_args(p)
     return p.parse_args(argv)
 
 
@@ -129,13 +132,14 @@ def main(argv=None):
                momentum=args.momentum, weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
     dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg)
+    tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
     resume = TrainStateFile(args, rank, world, cd)
+    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
     start = resume.resume(tr, keeper)
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
@@ -155,6 +159,7 @@ def main(argv=None):
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
             resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
@@ -164,14 +169,17 @@ def main(argv=None):
                 evaluator = Evaluator(tr.params, num_classes=C, open_classes=0, dtype=eval_dtype, device=dev)
             if rank == 0:
                 print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            mIoU = evaluate_warmup(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                   device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
+            score = lambda params: evaluate_warmup(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                                   device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
+            mIoU = score(tr.params)
             if rank == 0:
                 print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
                 keeper.best(tr.state_dict(), i_iter, mIoU)
+            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             # no validation set given (the reference hard-codes one, evaluate_cityscapes.py:26-28): a rolling periodic snapshot instead
             keeper.rolling(tr.state_dict(), i_iter)
+            ema_snap.rolling(i_iter)
         resume.after_iteration(i_iter, tr, keeper)
     shutdown(world)
 
@@ -208,7 +216,8 @@ def main_single(args):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
-    tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch)
+    tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
+                             ema_decay=args.ema)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
@@ -216,6 +225,7 @@ def main_single(args):
         os.makedirs(args.snapshot_dir, exist_ok=True)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
     resume = TrainStateFile(args, rank, world, cd)
+    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
     start = resume.resume(tr, keeper)
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
@@ -235,6 +245,7 @@ def main_single(args):
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
             resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
@@ -243,14 +254,17 @@ def main_single(args):
                 evaluator = Evaluator(tr.params, num_classes=C, open_classes=0, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
             if rank == 0:
                 print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            mIoU = evaluate_simt(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                 open_classes=0, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg,
-                                 model=model, layers=eval_layers)
+            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                                 open_classes=0, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
+                                                 process_group=pg, model=model, layers=eval_layers)
+            mIoU = score(tr.params)
             if rank == 0:
                 print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
                 keeper.best(tr.state_dict(), i_iter, mIoU)
+            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
+            ema_snap.rolling(i_iter)
         resume.after_iteration(i_iter, tr, keeper)
     shutdown(world)
 

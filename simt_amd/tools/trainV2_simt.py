@@ -27,9 +27,13 @@ with probability 0.8 brightness, contrast and saturation factors from [1 - S, 1 
 either flag alone is allowed),
 --train-state FILE [--train-state-every N]: resume from FILE if it exists and keep it current (simt_amd/train_state.py).  The snapshots hold
 the model only; FILE also holds the SGD momentum, both NTMs and W with their Adam moments, the iteration counter, the snapshot rotation's
-bookkeeping -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
+bookkeeping (with --ema: the shadow, its update count and the second rotation's too) -- the loader continues at the batch the stopped run would have drawn next, so stopping after step k and re-issuing the same
 command line (with a later --num-steps-stop) continues bit for bit as if nothing had happened.  --restore-from stays the same: the frozen
 model is not in FILE, its SHA-256 is.  Without the flag the tool writes and prints what it always did.
+--ema [D]: keep an exponential moving average of the weights beside the trained ones (simt_amd/ema.py: one launch per step; no value: D = 0.999;
+0 <= D < 1).  Training is bit for bit what it is without the flag.  Every evaluation also scores the averaged model (an `EMA mIoU` line) and
+a second rotation keeps its best snapshot `GTA5_ema_iter<i>_mIoU<m>.pth` (without a validation set: a rolling `GTA5_ema_iter<i>.pth`); the
+stop writes `GTA5_<stop>_ema.pth` beside `GTA5_<stop>.pth` -- same keys, loads wherever the other does.  Default: off.
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -109,6 +113,7 @@ def get_arguments(argv=None):
     add_class_mix_args(p)
     add_photometric_args(p)
     add_train_state_args(p)
+    add_ema_args(p)
     return p.parse_args(argv)
 
 
@@ -196,6 +201,22 @@ def add_train_state_args(p):
                         "Re-issue the same command line until the run is finished")
     p.add_argument("--train-state-every", type=int, default=None, metavar="N",
                    help="write --train-state every N iterations instead of at the snapshot cadence")
+
+
+def _ema_decay(text):
+    from simt_amd.ema import check_decay
+    try:
+        return check_decay(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def add_ema_args(p):
+    p.add_argument("--ema", type=_ema_decay, nargs="?", const=0.999, default=None, metavar="D",
+                   help="keep an exponential moving average of the weights (simt_amd/ema.py): one launch per optimiser step, decay "
+                        "min(D, 1 - 1 / (t + 1)) at update t (no value: D = 0.999; 0 <= D < 1).  The trained model is unchanged; the averaged one is "
+                        "evaluated beside it (`EMA mIoU`), kept by a rotation of its own (`..._ema_iter...`) and written at the stop as "
+                        "GTA5_<stop>_ema.pth.  Default: off")
 
 
 def add_v3_layers(p):
@@ -325,6 +346,37 @@ class SnapshotKeeper:
         self.best_mIoU, self.best_iter, self.rolling_iter = st["best_mIoU"], st["best_iter"], st["rolling_iter"]
 
 
+class EmaSnapshots:
+    """--ema: the averaged model's half of every snapshot decision of the training loops -- a second SnapshotKeeper whose stem is the live
+    one's with `ema_` in front of `iter` (GTA5_ema_iter..., GTA5_BAPA_warmup_ema_iter...), the `EMA mIoU` line and GTA5_<stop>_ema.pth.  Its
+    bookkeeping travels in --train-state (TrainStateFile.ema_keeper).  A trainer without an EMA: every method does nothing."""
+
+    def __init__(self, tr, keeper, resume, rank):
+        self.tr, self.rank = tr, rank
+        self.keeper = None
+        if getattr(tr, "ema", None) is not None:
+            assert keeper.stem.endswith("iter")
+            self.keeper = SnapshotKeeper(keeper.dir, keeper.stem[:-len("iter")] + "ema_iter")
+        resume.ema_keeper = self.keeper
+
+    def final(self, snapshot_dir, stop):
+        if self.keeper is not None and self.rank == 0:
+            save_atomic(self.tr.ema_state_dict(), osp.join(snapshot_dir, "GTA5_" + str(stop) + "_ema.pth"))
+
+    def evaluated(self, score, i_iter):
+        """score(params) -> mIoU: the loop's evaluation call (every rank runs it, as for the live model)."""
+        if self.keeper is None:
+            return
+        mIoU = score(self.tr.ema_params)
+        if self.rank == 0:
+            print("EMA mIoU: ", mIoU)
+            self.keeper.best(self.tr.ema_state_dict(), i_iter, mIoU)
+
+    def rolling(self, i_iter):
+        if self.keeper is not None and self.rank == 0:
+            self.keeper.rolling(self.tr.ema_state_dict(), i_iter)
+
+
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
@@ -358,6 +410,7 @@ class TrainStateFile:
         self.path, self.every = getattr(args, "train_state", None), getattr(args, "train_state_every", None)
         self.run = run_identity(args, class_dist) if self.path and class_dist is not None else {}
         self.save_pred_every, self.rank, self.world = args.save_pred_every, rank, world
+        self.ema_keeper = None                     # --ema: the second rotation (EmaSnapshots sets it); its bookkeeping travels in the file's loop part
         if self.every is not None and self.every < 1:
             raise SystemExit(f"--train-state-every {self.every}: expected a positive number of iterations")
         if self.every is not None and not self.path:
@@ -386,6 +439,8 @@ class TrainStateFile:
             raise SystemExit(f"--train-state {self.path!r}: {e}")
         if ks is not None:
             keeper.load_state(ks)
+        if self.ema_keeper is not None and ls.get("ema_keeper") is not None:
+            self.ema_keeper.load_state(ls["ema_keeper"])
         if self.rank == 0:
             print(f"resumed {type(tr).__name__} from {self.path} at iteration {tr.it_done}")
         return tr.it_done
@@ -393,7 +448,10 @@ class TrainStateFile:
     def write(self, tr, keeper):
         if self.path and self.rank == 0:
             from simt_amd import train_state
-            train_state.save(self.path, tr.training_state(), keeper.state(), {"world": self.world, "run": self.run})
+            loop = {"world": self.world, "run": self.run}
+            if self.ema_keeper is not None:
+                loop["ema_keeper"] = self.ema_keeper.state()
+            train_state.save(self.path, tr.training_state(), keeper.state(), loop)
 
     def after_iteration(self, i_iter, tr, keeper):
         if self.every is not None:
@@ -412,6 +470,9 @@ class TrainStateFile:
             print(f"the run is complete: {start} of {stop} iterations done" + ("" if osp.exists(final) else f"; writing {final}"))
             if not osp.exists(final):
                 save_atomic(tr.state_dict(), final)
+            final_ema = final[:-len(".pth")] + "_ema.pth"
+            if getattr(tr, "ema", None) is not None and not osp.exists(final_ema):
+                save_atomic(tr.ema_state_dict(), final_ema)
         return True
 
 
@@ -505,13 +566,14 @@ def main(argv=None):
     dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
-                     args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg)
+                     args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema)
     if rank == 0:
         print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
     resume = TrainStateFile(args, rank, world, cd)
+    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
     start = resume.resume(tr, keeper)
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
@@ -533,6 +595,7 @@ def main(argv=None):
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))   # :447-450
+            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
             resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
@@ -542,15 +605,19 @@ def main(argv=None):
                 evaluator = Evaluator(tr.params, num_classes=C, open_classes=K, dtype=eval_dtype, device=dev)
             if rank == 0:
                 print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            mIoU = evaluate_simt(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
+            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
+                                                 process_group=pg)
+            mIoU = score(tr.params)
             if rank == 0:
                 print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
                 keeper.best(tr.state_dict(), i_iter, mIoU)
+            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             # no validation set given (the reference hard-codes one, :452-464): without an evaluation there is no best-mIoU snapshot,
             # so keep a rolling periodic one -- a crash must not lose the run
             keeper.rolling(tr.state_dict(), i_iter)
+            ema_snap.rolling(i_iter)
         resume.after_iteration(i_iter, tr, keeper)
     shutdown(world)
 
@@ -592,13 +659,14 @@ def main_single(args):
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
     tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
-                           device=dev, process_group=pg, arch=arch)
+                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema)
     if rank == 0:
         print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
     resume = TrainStateFile(args, rank, world, cd)
+    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
     start = resume.resume(tr, keeper)
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
@@ -619,6 +687,7 @@ def main_single(args):
             if rank == 0:
                 print("save model ...")
                 save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
+            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
             resume.write(tr, keeper)
             break
         if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
@@ -627,13 +696,17 @@ def main_single(args):
                 evaluator = Evaluator(tr.params, num_classes=C, open_classes=K, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
             if rank == 0:
                 print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            mIoU = evaluate_simt(tr.params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
+            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
+                                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
+                                                 process_group=pg)
+            mIoU = score(tr.params)
             if rank == 0:
                 print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
                 keeper.best(tr.state_dict(), i_iter, mIoU)
+            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
         elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
             keeper.rolling(tr.state_dict(), i_iter)
+            ema_snap.rolling(i_iter)
         resume.after_iteration(i_iter, tr, keeper)
     shutdown(world)
 

@@ -124,7 +124,8 @@ class TrainStateMixin:
         """Everything the next `step()` depends on, as a plain dict of host tensors and Python scalars: `model` (= state_dict()),
         `momentum`, the NTM / W tensors with their Adam moments (SimT trainers), `it_done`, the device-side accumulators that outlive a step
         and reach `losses()` (the scalars of the last step with the cumulative bad-label count, and its host twin `bad_reported`), `hyper`
-        and (SimT trainers) `frozen_sha256`.  Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
+        and (SimT trainers) `frozen_sha256`; with a weight EMA (`ema_decay`, simt_amd/ema.py) also `ema` = {decay, updates, shadow} -- the key is
+        absent without one, and `load_training_state` refuses a state whose `ema` does not fit the trainer's.  Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
         run -- RuntimeError (`TrunkPlan.raise_on_fbn_error`), no dict, and a file written earlier stays the last good state.  Data parallel: every rank holds the same parameters, momentum and NTM state after the exchange, so rank 0's dict is THE
@@ -142,6 +143,8 @@ class TrainStateMixin:
             ts["accumulators"] = {"lout": self.lout.detach().cpu()}
         else:      # the warm-up trainers: the head's scalars (overwritten by every launch) and the bad-label accumulator beside them
             ts["accumulators"] = {"hout": self.hout[:16].detach().cpu(), "bad_labels": self.bad_labels.detach().cpu()}
+        if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
+            ts["ema"] = self.ema.state()
         return ts
 
     def load_training_state(self, ts):
@@ -159,6 +162,10 @@ class TrainStateMixin:
         if hasattr(self, "frozen_sha256") and ts.get("frozen_sha256") != self.frozen_sha256:
             raise ValueError(f"frozen_sha256 differs: the train state was written beside another frozen model (state: {ts.get('frozen_sha256')}, "
                              f"this trainer: {self.frozen_sha256}); give the resumed run the same --restore-from")
+        from .ema import state_mismatch
+        why = state_mismatch(getattr(self, "ema", None), ts.get("ema"))
+        if why:
+            raise ValueError(why)
         problems = []
         for what, theirs, mine in (("momentum", ts["momentum"], self.mom), ("model", ts["model"], self.params)):
             for n in mine:
@@ -198,6 +205,8 @@ class TrainStateMixin:
             self.hout[:16].copy_(acc["hout"])
             self.bad_labels.copy_(acc["bad_labels"])
         self._bad_reported = int(ts["bad_reported"])
+        if getattr(self, "ema", None) is not None:
+            self.ema.load_state(ts["ema"])
         self.plan.repack()
         torch.cuda.synchronize(self.dev)
 
