@@ -81,9 +81,9 @@ typedef struct {
   const void* w_frag;  /* optional (may be NULL): the SAME weights as `w` in MFMA-fragment order (simt_pack_weight with
                         * SIMT_PACK_FRAG(Npad / 16) in `mode`): [K / 64][Npad / 16][2][64 lanes][8] bf16, i.e. element (row, kcol) of the
                         * K-contiguous matrix sits at ((((kcol / 64) * (Npad / 16) + row / 16) * 2 + (kcol / 32) % 2) * 64 +
-                        * (row % 16) + 16 * ((kcol / 8) % 4)) * 8 + kcol % 8.  When present and simt_conv_wants_frag(d) != 0 the wide
-                        * bf16 kernel loads its weight operand straight into registers (1 KB contiguous per wave-instruction)
-                        * instead of staging it through LDS; results are bit-identical either way */
+                        * (row % 16) + 16 * ((kcol / 8) % 4)) * 8 + kcol % 8.  No kernel of the library reads it: the form of the wide
+                        * bf16 kernel that loaded its weight operand straight into registers instead of staging it through LDS was
+                        * measured slower and removed (simt_conv_wants_frag is always 0); the field stays for the layout */
   const struct simt_fbn_desc* fbn;   /* optional (may be NULL): the train-mode BatchNorm behind this conv fused into the launch, below */
   int32_t cu_budget;   /* ABI 2.  Compute units this launch may plan for; 0 = all of the device (256); -1: A/B only, rounds 1-5 tile choice.  Data-parallel plans pass 256 minus the
                         * CUs the collective's persistent kernels hold (NCCL_MAX_NCHANNELS): the one-workgroup-per-CU tile lists of the wide convs
@@ -147,7 +147,7 @@ int simt_conv_pair_fused(const simt_conv_desc* d0, const simt_conv_desc* d1);
  * the current device (tiles <= compute units); d->fbn itself need not be set yet */
 int simt_conv_fbn_ok(const simt_conv_desc* d);
 long simt_conv_fbn_words(const simt_conv_desc* d);      /* uint64 words simt_fbn_desc.work needs for d (0 if !simt_conv_fbn_ok) */
-/* 1 if the launch for d would use d->w_frag when given (conv_igemm2_kernel<256, *, 3>: Npad tiles of 256, long reductions) */
+/* 1 if the launch for d would use d->w_frag when given.  Always 0: the weights-direct form was measured slower and removed */
 int simt_conv_wants_frag(const simt_conv_desc* d);
 /* `mode` of simt_pack_weight / PackJob: low byte = layout mode 0 / 1 / 2 below; SIMT_PACK_FRAG(nt16) additionally stores the
  * destination in MFMA-fragment order (see simt_conv_desc.w_frag) with nt16 = Npad / 16 row blocks */

@@ -7,7 +7,7 @@ Per production shape of the DeepLab-v2 trunk at BASELINE configs[1] (B = 4, 768 
 model/deeplab_multi.py:62,68,73) it times, on ONE box, in ONE process, under the same protocol:
   own     simt_conv_fprop of the shipped library, the tile the production plan picks, bias + ReLU epilogue (the frozen net's flavour)
   vendor  torch.matmul (hipBLASLt / rocBLAS) on [M, K] x [K, N] for the 1x1 shapes; F.conv2d (MIOpen) on channels_last bf16 for the 3x3 shapes
-Protocol (as profiles/tools/conv_modes.py / one_conv.py): 6 rotating operand sets (each launch's operands come from HBM, not from the previous launch's
+Protocol (as profiles/tools/one_conv.py): 6 rotating operand sets (each launch's operands come from HBM, not from the previous launch's
 cache state), 3 untimed rounds (clocks and MIOpen's find step warm), then `rounds` x 6 launches back to back between two HIP events -> us per launch;
 the median of 5 such measurements, own and vendor interleaved.  `--step` adds one eager PyTorch-ROCm training step of a torch.nn restatement of the
 two-head DeepLab-v2 ResNet-101 at configs[1] (frozen eval forward + train-mode forward + backward of a plain cross-entropy + SGD; bf16 channels_last):

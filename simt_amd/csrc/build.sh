@@ -6,11 +6,8 @@ OUT=../libsimt_hip.so
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 # -packed-fp32-ops: v_pk_*_f32 cannot issue in the shadow of an MFMA (profiles/microbench/mixbench2.hip: one per MFMA costs +77 %), plain VALU can
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Xclang -target-feature -Xclang -packed-fp32-ops"
-# ABLATION=1: also compile the timing-ablation instantiations and csrc/experiments/*.hip (round-3 experiments on the conv kernel: loader
-# waves, weights-direct, role-split conv_igemm3; outputs of the timing modes are meaningless; never shipped).  OUT=path BUILD=dir: where to.
 SRCS=(*.hip)
 BUILD=${BUILD:-../_build}
-if [ "${ABLATION:-0}" = "1" ]; then FLAGS="${FLAGS/-std=c++17/-std=c++20} -DSIMT_ABLATION"; SRCS+=(experiments/*.hip); BUILD=${BUILD}_abl; OUT=${OUT_ABL:-../libsimt_hip_abl.so}; fi
 mkdir -p $BUILD
 objs=()
 pids=()

@@ -19,13 +19,6 @@
 #include "conv2_common.h"
 #include <type_traits>
 
-// Compile-time timing ablations (scratch builds only; outputs meaningless): 1 = no fragment reads / MFMA, 2 = no global stores,
-// 4 = no LDS-DMA loads, 8 = store waves idle (barriers only), 64 = no epilogue in the compute waves, 128 = no fragment reads, 256 = no statistics,
-// 512 = the store waves' global operands (residual, BatchNorm-backward y) from an L2-resident window
-#ifndef SIMT_ROWS_ABL
-#define SIMT_ROWS_ABL 0
-#endif
-
 #ifndef SIMT_ROWS_PF1
 #define SIMT_ROWS_PF1 6
 #endif
@@ -128,7 +121,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
   const bool has_rbits = GEN ? (AUX && a.res_bits != nullptr) : FL == FL_BNR;
   const bool has_bnr = GEN ? (AUX && a.bnr_mode != 0) : FL == FL_BNR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (SIMT_ROWS_ABL & 16) return;
 #ifdef SIMT_ROWS_STAGGER
   { const int ph = (blockIdx.x >> 3) & 3; for (int i = 0; i < ph * SIMT_ROWS_STAGGER; ++i) __builtin_amdgcn_s_sleep(1); }
 #endif
@@ -174,7 +166,7 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       for (int q = 0; q < g::PT; ++q) {
         const unsigned off = ibase + pconst[q];
         const char* src = off <= pmax[q] ? a.x + off : a.zero + pzero[q];
-        if (!(SIMT_ROWS_ABL & 4)) __builtin_amdgcn_global_load_lds(GPTR(src), LPTR(sb + (q * NC + wave * 64) * 16), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(GPTR(src), LPTR(sb + (q * NC + wave * 64) * 16), 16, 0, 0);
       }
       ibase += stage_step;
       if (++is == g::SPT) { is = 0; ++ii; tile_base += tile_step; ibase = tile_base; }
@@ -192,10 +184,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
 #pragma unroll
       for (int e = 0; e < 4; ++e) { cs1[j][e] = 0.f; cs2[j][e] = 0.f; }
     int c_is = 0, c_ci = 0;                                    // cursor of the stage whose epilogue runs: stage inside the tile, tile
-#ifdef SIMT_ABLATION
-    unsigned long long t_wait = 0, t_bar = 0, t_work = 0;
-    const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-#endif
     // The epilogue of stage g - 1 (round to bf16, write the slab, statistics) is DEFERRED into the MFMA loop of stage g, two VALU
     // operations behind every MFMA: a wave issues in order, so its own VALU work only overlaps its MFMAs if it sits between them (measured,
     // profiles/microbench/mixbench2.hip: up to two plain VALU per MFMA are free with two waves per SIMD; v_pk_*_f32 never is -- the library is built
@@ -215,7 +203,7 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       // must assume the store aliases an LDS-DMA in flight -- also with separate static LDS arrays), and around C++ LDS loads it waits
       // lgkmcnt(0) right after requesting the next fragments
       asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(sbase), "v"(pk), "n"(i * 16 * CP + j * 32));
-      if (CSTAT && !(SIMT_ROWS_ABL & 256)) {                   // statistics of the values as stored (bf16); rows past the end are exact zeros
+      if (CSTAT) {                   // statistics of the values as stored (bf16); rows past the end are exact zeros
         const float v0 = __uint_as_float(pk.x << 16), v1 = __uint_as_float(pk.x & 0xffff0000u);
         const float v2 = __uint_as_float(pk.y << 16), v3 = __uint_as_float(pk.y & 0xffff0000u);
         cs1[j][0] += v0; cs1[j][1] += v1; cs1[j][2] += v2; cs1[j][3] += v3;
@@ -251,7 +239,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int i = 0; i < TM; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      constexpr int KSN = (SIMT_ROWS_ABL & 1) ? 0 : KS;
       // pixel fragments: requested PF k-steps ahead into PF + 1 rotating register sets (an LDS round trip under load is longer than the
       // 4 MFMAs of one k-step)
       constexpr int PF = TM == 2 ? 2 : TM == 1 ? SIMT_ROWS_PF1 : 1;     // (TM = 1, Cin = 1024: one MFMA per k-step -- a deeper fragment queue)
@@ -260,10 +247,8 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       const unsigned ad01[2] = {st_addr + (unsigned)(((0 + kq) ^ sw) << 4), st_addr + (unsigned)(((4 + kq) ^ sw) << 4)};   // even / odd k-steps
       auto frags = [&](int ks, bf16x8* f) {                    // request the pixel fragments of k-step ks (TM x ds_read_b128, immediate offsets)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          if (SIMT_ROWS_ABL & 128) asm volatile("" : "=v"(f[i]) : "v"(ad01[ks & 1]));
-          else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[i]) : "v"(ad01[ks & 1]), "n"((ks >> 1) * (g::RS * 128) + i * 16 * 128));
-        }
+        for (int i = 0; i < TM; ++i)
+          asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[i]) : "v"(ad01[ks & 1]), "n"((ks >> 1) * (g::RS * 128) + i * 16 * 128));
       };
       auto landed = [&](bf16x8* f, int younger) {              // f is complete: everything but the `younger` most recent LDS operations has returned
         static_assert(TM == 1 || TM == 2 || TM == 4, "fragment blocks");
@@ -275,13 +260,13 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       };
       if (MMA) {
 #pragma unroll
-        for (int k0 = 0; k0 < PF && k0 < KSN; ++k0) frags(k0, xf[k0 % (PF + 1)]);
+        for (int k0 = 0; k0 < PF && k0 < KS; ++k0) frags(k0, xf[k0 % (PF + 1)]);
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        if (MMA && ks + PF < KSN) frags(ks + PF, xf[(ks + PF) % (PF + 1)]);
-        if (MMA && ks < KSN) {
-          const int ahead = (KSN - 1 - ks) < PF ? (KSN - 1 - ks) : PF;      // k-steps requested after this one
+        if (MMA && ks + PF < KS) frags(ks + PF, xf[(ks + PF) % (PF + 1)]);
+        if (MMA) {
+          const int ahead = (KS - 1 - ks) < PF ? (KS - 1 - ks) : PF;      // k-steps requested after this one
           landed(xf[ks % (PF + 1)], ahead * TM);
 #pragma unroll
           for (int j = 0; j < TN; ++j)
@@ -290,12 +275,12 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
         }
         if (EPI) {                                             // the quads of the previous stage, spread evenly over the k-steps
 #pragma unroll
-          for (int qd = 0; qd < NQ; ++qd) if (!(SIMT_ROWS_ABL & 64) && qd * KS / NQ == ks) epi_quad(qd, sbase);
+          for (int qd = 0; qd < NQ; ++qd) if (qd * KS / NQ == ks) epi_quad(qd, sbase);
         }
       }
       if (MMA && EPI) {                                        // 1 MFMA, then at most 2 VALU, ... (whatever is left follows the last MFMA)
 #pragma unroll
-        for (int n = 0; n < KSN * NQ; ++n) {
+        for (int n = 0; n < KS * NQ; ++n) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
         }
@@ -313,42 +298,18 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
       asm volatile("" ::: "memory");
     }
     for (int gi = 0; gi <= S_total; ++gi) {
-#ifdef SIMT_ABLATION
-      const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
       // stage gi landed (this wave's pieces); INBN: stage gi + 1 -- the store waves normalise it during period gi
       if (INBN) { if (gi + D - 2 < S_total) wait_vmcnt<g::PT * (D - 3)>(); else wait_vmcnt<0>(); }
       else if (gi + D - 2 < S_total) wait_vmcnt<g::PT * (D - 2)>(); else wait_vmcnt<0>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                  // this wave's slab writes (stage gi - 2)
-#ifdef SIMT_ABLATION
-      const unsigned long long tw1 = __builtin_amdgcn_s_memtime();
-#endif
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-#ifdef SIMT_ABLATION
-      const unsigned long long tw2 = __builtin_amdgcn_s_memtime();
-      t_wait += tw1 - tw0; t_bar += tw2 - tw1;
-#endif
       if (gi + D - 1 < S_total) issue(slot_i);                 // into the slot every wave finished reading in stage gi - 1
       if (++slot_i == D) slot_i = 0;
       if (gi == 0) body(std::true_type{}, std::false_type{}, gi);
       else if (gi < S_total) body(std::true_type{}, std::true_type{}, gi);
       else body(std::false_type{}, std::true_type{}, gi);
-#ifdef SIMT_ABLATION
-      asm volatile("s_nop 0" ::: "memory");
-      t_work += __builtin_amdgcn_s_memtime() - tw2;
-#endif
     }
-#ifdef SIMT_ABLATION
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {
-      unsigned long long* o = g_stamps + blockIdx.x * 8;
-      o[0] = t_wait; o[1] = t_bar; o[2] = t_work; o[3] = __builtin_amdgcn_s_memtime() - t_begin; o[4] = (unsigned long long)S_total;
-    }
-    if (lane == 0 && blockIdx.x < 256) {                       // per compute wave: work / barrier ticks (second half of the stamp array)
-      unsigned long long* o = g_stamps + 4096 * 8 + (blockIdx.x * 8 + wave) * 2;
-      o[0] = t_work; o[1] = t_bar;
-    }
-#endif
     // drain: the store waves run one (two: pipelined path) slabs behind the last slab write, then the last tile's sums go through sR
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -408,14 +369,12 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
     if (!has_bnr) { d.by = make_uint4(0u, 0u, 0u, 0u); d.ybits = 0xffu; }
     if (has_res && !has_rbits) d.rbits = 0xffu;
     if (has_res) {
-      unsigned o = (unsigned)(slab_row0 + p * RGS) * r_pitch + r_c;
-      if (SIMT_ROWS_ABL & 512) o = (o & 0x3ff0u) + blockIdx.x * 0x4000u;     // ablation: the operands come from 16 KB per workgroup (L2-resident)
+      const unsigned o = (unsigned)(slab_row0 + p * RGS) * r_pitch + r_c;
       d.res = *(const uint4*)(resb + o);
       if (has_rbits) d.rbits = a.res_bits[o >> 4];
     }
     if (has_bnr) {
-      unsigned o = (unsigned)(slab_row0 + p * RGS) * b_pitch + b_c;
-      if (SIMT_ROWS_ABL & 512) o = (o & 0x3ff0u) + blockIdx.x * 0x4000u;
+      const unsigned o = (unsigned)(slab_row0 + p * RGS) * b_pitch + b_c;
       d.by = *(const uint4*)(byb + o);
       d.ybits = a.bnr_bits[o >> 4];
     }
@@ -454,9 +413,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
     }
   };
 
-#ifdef SIMT_ABLATION
-  unsigned long long ts_bar = 0, ts_work = 0, ts_prev = 0, ts_lds = 0;
-#endif
   // MSTAT: this wave's channel blocks (16 channels each): running ones x Y and Y^T x Y of the tile in progress
   constexpr int MBLK = BN / 16 / NSW;
   f32x4 m1[MBLK], m2[MBLK];
@@ -534,20 +490,9 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
   in_bn(1);                                                    // period 0 (stage 1 landed before barrier 0)
   for (int gi = 0; gi <= LAST; ++gi) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // slab reads / sR writes of the previous iteration
-#ifdef SIMT_ABLATION
-    const unsigned long long tb0 = __builtin_amdgcn_s_memtime();
-#endif
     __builtin_amdgcn_s_barrier();
-#ifdef SIMT_ABLATION
-    const unsigned long long tb1 = __builtin_amdgcn_s_memtime();
-    ts_bar += tb1 - tb0;
-    if (gi > 0) ts_work += tb0 - ts_prev;
-#endif                              // barrier gi: slab gi - 1 is complete; slab gi - 2 may be overwritten
     if (stats_pending) { sums_out(pend_mt); stats_pending = false; }
-#ifdef SIMT_ABLATION
-    ts_prev = tb1;
-#endif
-    if (gi == 0 || (SIMT_ROWS_ABL & 8)) { in_bn(gi + 2); continue; }
+    if (gi == 0) { in_bn(gi + 2); continue; }
     const char* sl = slab + ((gi - 1) & 1) * g::SLAB;
     if (PIPE) {
       const bool guard_cur = !(all_cols && row0 + g::RS <= a.M);
@@ -563,15 +508,10 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
             for (int e = 0; e < 8; ++e) { v[e] += bias8[e]; if (has_relu) v[e] = v[e] > 0.f ? v[e] : 0.f; }
             o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]); o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
           }
-          unsigned yo = (unsigned)(row0 + p * RGS) * y_pitch + y_c;
-          if (SIMT_ROWS_ABL & 32) yo = (yo & 0x3fffu) + blockIdx.x * 0x4000u;
-          if (!(SIMT_ROWS_ABL & 2) || o.x == 0x12345678u) st_out16(const_cast<char*>(yb) + yo, o);
+          const unsigned yo = (unsigned)(row0 + p * RGS) * y_pitch + y_c;
+          st_out16(const_cast<char*>(yb) + yo, o);
         }
       }
-#ifdef SIMT_ABLATION
-      asm volatile("s_nop 0" ::: "memory");
-      ts_lds += __builtin_amdgcn_s_memtime() - tb1;            // (PIPE: barrier -> stores issued)
-#endif
       uint4 nv[g::PASSES];
       if (gi <= S_total) {                                     // slab gi - 1: LDS -> registers (in flight during the statistics below)
 #pragma unroll
@@ -650,10 +590,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
     // several, the compiler sinks them into a shared tail of a 4-byte and a 12-byte store)
 #pragma unroll
     for (int p = 0; p < g::PASSES; ++p) if (!AUX) ov[p] = *(const uint4*)(sl + (rg + p * RGS) * CP + vcol * 2);
-#ifdef SIMT_ABLATION
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    ts_lds += __builtin_amdgcn_s_memtime() - tb1;
-#endif
     // full slabs of full-width tiles take the branch-free path (uniform test); only the last tile / a narrow last column tile is guarded
     const bool guard_cur = !(all_cols && row0 + g::RS <= a.M);
     const bool guard_next = !(all_cols && nrow0 + g::RS <= a.M);        // uniform
@@ -678,7 +614,7 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
             float rv[8];
             unpack8(cur.res, rv);
             // bit e of the mask as an all-ones / all-zeros word (one v_bfe_i32) ANDed onto the value: 2 vector instructions per element where
-            // test + compare + select take 3 -- these store waves are bound by their vector work (profiles/tools/stamps3.py)
+            // test + compare + select take 3 -- these store waves are bound by their vector work (profiles/r06_rows_aux.txt)
 #pragma unroll
             for (int e = 0; e < 8; ++e)
               v[e] += has_rbits ? __uint_as_float(__float_as_uint(rv[e]) & (unsigned)__builtin_amdgcn_sbfe((int)cur.rbits, e, 1)) : rv[e];
@@ -700,9 +636,8 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
           for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * (yv[e] - bmu[e]); }
         }
       }
-      unsigned yo = (unsigned)(row0 + p * RGS) * y_pitch + y_c;
-      if (SIMT_ROWS_ABL & 32) yo = (yo & 0x3fffu) + blockIdx.x * 0x4000u;        // ablation: every store hits the same 16 KB per workgroup (L2-resident)
-      if (!(SIMT_ROWS_ABL & 2) || o.x == 0x12345678u) st_out16(const_cast<char*>(yb) + yo, o);
+      const unsigned yo = (unsigned)(row0 + p * RGS) * y_pitch + y_c;
+      st_out16(const_cast<char*>(yb) + yo, o);
     };
     if (guard_cur || FL == FL_GEN_AUX) {                       // (one copy of the pass code in the run-time-flag aux flavour: registers)
 #pragma unroll
@@ -731,9 +666,6 @@ __device__ __forceinline__ void conv1x1_rows_body(const Conv2KArgs& a, const int
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (stats_pending) sums_out(pend_mt);
-#ifdef SIMT_ABLATION
-  if (threadIdx.x == NC && blockIdx.x < 8192) { g_stamps[blockIdx.x * 8 + 5] = ts_bar; g_stamps[blockIdx.x * 8 + 6] = ts_work; g_stamps[blockIdx.x * 8 + 7] = ts_lds; }
-#endif
 }
 
 template <int KS, int TM, int D, int FL, int NSW, int NCW, int TN>
@@ -784,12 +716,6 @@ int launch_rows(Conv2KArgs k, int npad, hipStream_t st) {
 }
 
 }  // namespace
-
-#ifdef SIMT_ABLATION
-extern "C" int simt_debug_stamps_rows(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // Shapes this kernel takes over from conv_igemm2_kernel<128, *, 2> / conv1x1_stream_kernel (simt_conv_fprop_bf16_v2 fills the arguments).
 bool simt_conv_rows_eligible(const simt_conv_desc* d) {

@@ -19,12 +19,6 @@
 // waves in fixed order), + bias / ReLU.  Residual / bit-mask / fused BN-backward flavours stay on conv_igemm2_kernel.
 #include "conv2_common.h"
 
-// Compile-time timing ablations (scratch builds only; outputs meaningless): 1 = no fragment reads / MFMA, 2 = no global stores,
-// 4 = no LDS-DMA loads, 8 = store waves idle (barriers only), 16 = no statistics, 32 = no accumulator -> LDS writes, 64 = no LDS reads in row passes
-#ifndef SIMT_STREAM_ABL
-#define SIMT_STREAM_ABL 0
-#endif
-
 namespace {
 
 constexpr int NC = 512, NS = 512, NT = NC + NS;      // 8 compute waves (LDS-DMA loads + MFMA) + 8 store waves (deferred epilogue)
@@ -60,8 +54,6 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
   const int tstep = G >> 3;                                      // tile-id step per round: xcd_remap(b + i*G) = tile0 + i * G/8
   const int nt = tile0 % a.ntiles_n;                             // the same for every tile of this workgroup (host checks ntiles_n | G/8)
   const int n0 = nt * BN;
-  STAMP(1);
-
   if (wave < NC / 64) {
     // =============================== compute waves: stage stream + MFMA; they never store to global memory ===============================
     const int wm = wave / WN, wn = wave % WN;
@@ -93,7 +85,6 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
     tile_addr(0);
     auto issue = [&](int slot) {
       char* sbase = smem + slot * STAGE;
-#if !(SIMT_STREAM_ABL & 4)
 #pragma unroll
       for (int q = 0; q < A_IT; ++q) {
         const char* src = ia_ok[q] ? a.x + (unsigned)(ia_off[q] + (unsigned)(ikc * 128)) : zsrc;
@@ -102,7 +93,6 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
 #pragma unroll
       for (int q = 0; q < B_IT; ++q)
         __builtin_amdgcn_global_load_lds(GPTR(a.w + (b_off[q] + (unsigned)(ikc * 128))), LPTR(sbase + A_BYTES + (q * NC + wave * 64) * 16), 16, 0, 0);
-#endif
       if (++ikc == nk) {
         ikc = 0;
         if (++ii < my_n) tile_addr(ii);
@@ -137,47 +127,22 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
     if (S_total > 0) issue(0);
     if (S_total > 1) issue(1);
     int g = 0;
-#ifdef SIMT_ABLATION
-    unsigned long long t_wait = 0, t_bar = 0, t_work = 0, t_hand = 0;
-#endif
     for (int ci = 0; ci < my_n; ++ci) {
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int i = 0; i < TM; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       for (int kc = 0; kc < nk; ++kc, ++g) {
-#ifdef SIMT_ABLATION
-        const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
         if (g + 1 < S_total) wait_vmcnt<P>(); else wait_vmcnt<0>();        // stage g landed; stage g+1 may be in flight
-#ifdef SIMT_ABLATION
-        const unsigned long long tw1 = __builtin_amdgcn_s_memtime();
-#endif
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#ifdef SIMT_ABLATION
-        const unsigned long long tw2 = __builtin_amdgcn_s_memtime();
-        t_wait += tw1 - tw0; t_bar += tw2 - tw1;
-#endif
         const int slot = g % NST;
-#if !(SIMT_STREAM_ABL & 1)
         load_frags(slot);
-#endif
         if (g + 2 < S_total) issue((g + 2) % NST);
-#if !(SIMT_STREAM_ABL & 1)
         mma();
-#endif
-#ifdef SIMT_ABLATION
-        asm volatile("s_nop 0" ::: "memory");
-        t_work += __builtin_amdgcn_s_memtime() - tw2;
-#endif
       }
-#ifdef SIMT_ABLATION
-      const unsigned long long th0 = __builtin_amdgcn_s_memtime();
-#endif
       // hand-over: barrier A (the store waves are done with the previous tile in sC), accumulators -> sC, barrier B (sC visible)
       __builtin_amdgcn_s_barrier();
-#if !(SIMT_STREAM_ABL & 32)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -192,17 +157,9 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
           const unsigned addr = (unsigned)(size_t)LPTR(sC + r * CP + c * 2);
           asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(pk) : "memory");
         }
-#endif
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-#ifdef SIMT_ABLATION
-      t_hand += __builtin_amdgcn_s_memtime() - th0;
-#endif
     }
-    STAMP(3);
-#ifdef SIMT_ABLATION
-    if (threadIdx.x == 0 && blockIdx.x < 8192) { g_stamps[blockIdx.x * 8 + 4] = t_wait; g_stamps[blockIdx.x * 8 + 6] = t_bar; g_stamps[blockIdx.x * 8 + 7] = (unsigned long long)my_n; g_stamps[blockIdx.x * 8 + 0] = t_work; g_stamps[blockIdx.x * 8 + 2] = t_hand; }
-#endif
     // drain: the store waves finish the last tile behind three more barriers (A, B, and C for its statistics in sR)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_barrier();
@@ -223,9 +180,6 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
 #pragma unroll
   for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(bias8[e]));
   const bool plain = !a.bias && !a.relu;
-#if SIMT_STREAM_ABL & 16
-  a.stats = nullptr;
-#endif
   float s1[8], s2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
@@ -236,7 +190,7 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
   uint2 nlo = make_uint2(0u, 0u), nhi = make_uint2(0u, 0u);
   auto fetch_row = [&](int pass) {
     const int r = rg + pass * RPP;
-    if (!(SIMT_STREAM_ABL & 64) && pass < NIT && ncol_ok && prev_m0 + r < a.M) {
+    if (pass < NIT && ncol_ok && prev_m0 + r < a.M) {
       nlo = *(const uint2*)(sC + r * CP + vcol * 2);
       nhi = *(const uint2*)(sC + r * CP + vcol * 2 + 8);
     }
@@ -254,7 +208,7 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
         v[2] = __uint_as_float(o.y << 16); v[3] = __uint_as_float(o.y & 0xffff0000u);
         v[4] = __uint_as_float(o.z << 16); v[5] = __uint_as_float(o.z & 0xffff0000u);
         v[6] = __uint_as_float(o.w << 16); v[7] = __uint_as_float(o.w & 0xffff0000u);
-        if (!(SIMT_STREAM_ABL & 512) && a.stats) {
+        if (a.stats) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
         }
@@ -265,11 +219,7 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
           o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
         }
       }
-#if !(SIMT_STREAM_ABL & 2)
       st_out16(a.y + (long)m * a.ldy + n, o);
-#else
-      if (o.x == 0x12345678u && o.y == 0x9abcdef0u) *(uint4*)(a.y + (long)m * a.ldy + n) = o;
-#endif
     }
   };
   // statistics of the previous tile: the 4 row groups of a wave by lane swaps, then the store waves in fixed order through sR
@@ -279,13 +229,13 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
       // lanes l, l^16, l^32, l^48 hold the four row groups of a column: v_permlane16_swap / v_permlane32_swap (VALU; a
       // ds_bpermute shuffle here cost 13 us per launch: 256 LDS-crossbar instructions per tile inside the hand-over)
       const float t1 = quad_rows_sum(s1[e]), t2 = quad_rows_sum(s2[e]);
-      if (!(SIMT_STREAM_ABL & 256) && lane < 16) { sR[(swv * 2 + 0) * BN + vcol + e] = t1; sR[(swv * 2 + 1) * BN + vcol + e] = t2; }
+      if (lane < 16) { sR[(swv * 2 + 0) * BN + vcol + e] = t1; sR[(swv * 2 + 1) * BN + vcol + e] = t2; }
       s1[e] = 0.f; s2[e] = 0.f;
     }
   };
   auto stats_to_hbm = [&](int mt) {
     const int nn = n0 + st;
-    if (!(SIMT_STREAM_ABL & 128) && st < BN && nn < a.Cout) {
+    if (st < BN && nn < a.Cout) {
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll
       for (int q = 0; q < NSW; ++q) { t1 += sR[(q * 2 + 0) * BN + st]; t2 += sR[(q * 2 + 1) * BN + st]; }
@@ -299,19 +249,15 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
   for (int ci = 0; ci <= my_n; ++ci) {                 // iteration my_n is the drain of the last tile
     if (ci < my_n) {
       for (int kc = 0; kc < nk; ++kc) {
-#if !(SIMT_STREAM_ABL & 8)
         if (has_prev)
           for (int q = 0; q < passes_per_stage && rows_done < NIT; ++q) row_pass();
-#endif
         if (stats_pending) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                  // the compute waves' stage barrier
         if (stats_pending) { stats_to_hbm(prev_stats_mt); stats_pending = false; }
       }
     }
-#if !(SIMT_STREAM_ABL & 8)
     if (has_prev)
       while (rows_done < NIT) row_pass();
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                      // barrier A: sC may be overwritten
     if (stats_pending) { stats_to_hbm(prev_stats_mt); stats_pending = false; }      // drain iteration only (no stage barrier came by)
@@ -328,18 +274,9 @@ __global__ __launch_bounds__(NT, 4) void conv1x1_stream_kernel(Conv2KArgs a, int
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                        // drain barrier C
   if (stats_pending) stats_to_hbm(prev_stats_mt);
-#ifdef SIMT_ABLATION
-  if (threadIdx.x == NC && blockIdx.x < 8192) { g_stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memtime(); }
-#endif
 }
 
 }  // namespace
-
-#ifdef SIMT_ABLATION
-extern "C" int simt_debug_stamps_stream(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // Shapes this kernel takes over from conv_igemm2_kernel<128, *, 2> (called by simt_conv_fprop_bf16_v2 with the filled arguments).
 bool simt_conv_stream_eligible(const simt_conv_desc* d) {

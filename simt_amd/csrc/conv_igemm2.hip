@@ -29,18 +29,9 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifdef SIMT_ABLATION       // in-kernel s_memtime stamps of THIS kernel (diagnostic builds only; conv2_common.h STAMP)
-extern "C" int simt_debug_stamps(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-extern "C" int simt_debug_stamps_rt(unsigned long long* out, int n) {      // s_memrealtime ticks (100 MHz) between stamps 0 and 6, one per workgroup
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_rt), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
-
-// Round-3 experiments on this kernel (timing-ablation MODEs, loader waves LW = 4 / 8, weights straight into registers WD = 1, and the
-// role-split conv_igemm3) live in csrc/experiments/ and are compiled only into -DSIMT_ABLATION builds (csrc/build.sh ABLATION=1);
-// what they measured is in DESIGN.md section 9 and profiles/r03_conv_experiments.txt.  This file is the product kernel only.
+// The round-3 / round-5 experiments on this kernel (timing ablations, loader waves, weights straight into registers, the role-split
+// conv_igemm3, the half split) were measured slower or neutral and removed; what they measured is in DESIGN.md section 9,
+// profiles/r03_conv_experiments.txt and profiles/r05_conv_attribution.txt.
 // FBN = 1: the same kernel with the fused train-mode BatchNorm tail compiled in (conv2_epilogue.h; a.fbn_mode selects forward / backward).
 // A separate instantiation so that the plain kernels keep their code (the main loop is sensitive to what surrounds it).
 // EPI: compile-time epilogue flavour (conv2_epilogue.h): 0 generic, 1 statistics, 2 BatchNorm-backward reduce, 3 bias + ReLU, 4-8 the dgrad forms.
@@ -62,8 +53,6 @@ __device__ __forceinline__ void conv_igemm2_body(const Conv2KArgs& a, const int 
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-
-  STAMP(0);
   const int nwg = a.ntiles_m * a.ntiles_n;
   const int tile = xcd_remap(bid, nwg);
   const int mt = tile / a.ntiles_n, nt = tile - mt * a.ntiles_n;
@@ -195,7 +184,6 @@ __device__ __forceinline__ void conv_igemm2_body(const Conv2KArgs& a, const int 
         for (int i = 0; i < TM; ++i)
           acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][j], xf[s][i], acc[j][i], 0, 0, 0);
   };
-  STAMP(1);
   issue(0, false);                               // (its weight pieces are already in flight)
   if (NST == 3 && nk > 1) issue(1);
   int buf = 0;
@@ -205,7 +193,6 @@ __device__ __forceinline__ void conv_igemm2_body(const Conv2KArgs& a, const int 
       wait_stage(kt + 1 < nk);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (kt == 0) STAMP(2);
       load_frags(buf);
       if (kt + NST - 1 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);     // stage kt+NST-1 -> buffer (buf-1) mod NST
       mma();
@@ -225,8 +212,6 @@ __device__ __forceinline__ void conv_igemm2_body(const Conv2KArgs& a, const int 
     }
     mma();
   }
-
-  STAMP(3);
   conv2_epilogue<BN, BM, NT, TN, TM, FBN, EPI>(a, smem, acc, true, wm, wn, tid, lane, m0, n0, m_end, mt, tile);
 }
 
@@ -250,15 +235,6 @@ __global__ __launch_bounds__(512, (NSTP == 2 ? 4 : 2)) void conv_igemm2_pair_ker
   else if ((int)blockIdx.x >= base1) conv_igemm2_body<BN, TMP, NSTP, 0, EPI1>(a1, (int)blockIdx.x - base1);
 }
 
-#ifdef SIMT_ABLATION
-// csrc/experiments/conv_igemm2_abl.hip: returns true when an experiment build (SIMT_CONV2_MODE / SIMT_CONV2_LW / SIMT_WDIRECT / SIMT_IGEMM3)
-// took the launch; *rc is its result
-bool simt_conv2_abl_launch(const Conv2KArgs& k, int bn, int tm, int nst, hipStream_t st, int* rc);
-int simt_conv2_abl_wants_frag(const simt_conv_desc* d);
-#endif
-#ifdef SIMT_ABLATION
-bool simt_conv2_roles_launch(const Conv2KArgs& k, int tm, int epi, size_t lds, hipStream_t st, int* rc); bool simt_conv2_half_launch(const Conv2KArgs& k, int tm, int epi, size_t lds, hipStream_t st, int* rc);      // round-5 experiments, ablation builds only
-#endif
 template <int BN, int TM, int NST = 3, int FBN = 0, int EPI = 0>
 static int launch_conv2e(const Conv2KArgs& k, hipStream_t st) {
   constexpr int WM = (BN == 64) ? 4 : 2;
@@ -266,12 +242,6 @@ static int launch_conv2e(const Conv2KArgs& k, hipStream_t st) {
   const size_t ring = NST * (size_t)(BM * 128 + BN * 128);
   const size_t epi = (size_t)BM * (BN * 2 + 8) + (size_t)(512 / (BN / 8)) * 2 * BN * 4 + (FBN ? 32 * 8 * 3 * sizeof(double) + 16 + 2 * BN * sizeof(float) : 0);
   const size_t lds = ring > epi ? ring : epi;
-#ifdef SIMT_ABLATION
-  if constexpr (NST == 3 && BN == 256 && FBN == 0 && (EPI == 1 || EPI == 2 || EPI == 3 || EPI == 5)) {
-    int rc;
-    if (simt_conv2_half_launch(k, TM, EPI, lds, st, &rc) || simt_conv2_roles_launch(k, TM, EPI, lds, st, &rc)) return rc;      // csrc/experiments/conv_igemm2_roles.hip (SIMT_CONV2_ROLES=1 | 2, SIMT_CONV2_INTER=1)
-  }
-#endif
   static SimtLdsAttrCache attr_cache;
   if (simt_lds_attr_needed(&attr_cache, lds))
     (void)hipFuncSetAttribute((const void*)conv_igemm2_kernel<BN, TM, NST, FBN, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -301,9 +271,6 @@ static int conv2_flavour(const Conv2KArgs& k) {
 
 template <int BN, int TM, int NST = 3>
 static int launch_conv2(const Conv2KArgs& k, hipStream_t st) {
-#ifdef SIMT_ABLATION
-  { int rc; if (!k.fbn_mode && simt_conv2_abl_launch(k, BN, TM, NST, st, &rc)) return rc; }
-#endif
   const int e = conv2_flavour(k);
   if constexpr (NST == 3) {
     if constexpr (BN == 256) {
@@ -352,14 +319,6 @@ static bool rows_enabled() {
   static const int off = getenv("SIMT_NO_ROWS") ? atoi(getenv("SIMT_NO_ROWS")) : 0;     // A/B switch
   return !off;
 }
-static bool stream_enabled() {
-#ifdef SIMT_ABLATION
-  static const int off = getenv("SIMT_NO_STREAM") ? atoi(getenv("SIMT_NO_STREAM")) : 0;
-  return !off;
-#else
-  return true;
-#endif
-}
 struct Conv2Variant { int tile_n, tm, nst, rows, ntiles_n; bool stream, rowsk; };
 static Conv2Variant pick_variant(const simt_conv_desc* d) {
   Conv2Variant v;
@@ -369,9 +328,6 @@ static Conv2Variant pick_variant(const simt_conv_desc* d) {
   v.tile_n = d->tile_n;
   const long Kt = (long)d->ntaps * d->Cin;
   const bool short_k = d->tile_n == 256 && d->dtype_out == SIMT_BF16 && ((Kt <= 512 && d->Cout >= 512) || (Kt <= 128 && d->Cout >= 256));
-#ifdef SIMT_ABLATION
-  { static const int no_short = getenv("SIMT_NO_SHORTK") ? atoi(getenv("SIMT_NO_SHORTK")) : 0; if (no_short) { Conv2Variant w; w.stream = false; w.rowsk = false; w.tile_n = d->tile_n; w.nst = 3; w.ntiles_n = d->Npad / w.tile_n; w.tm = 4; pick_rows(M, w.ntiles_n, w.tile_n != 64, &w.rows, &w.tm, d->cu_budget); if (w.tile_n == 64) w.tm = 2; return w; } }
-#endif
   // Round 4 experiment (SIMT_ROWS_1024=1; default OFF): the long-reduction 1x1 convs on dense rows (conv1 of layer 3 / 4: 1024 -> 256 / 512)
   // as whole 2-KB pixel rows streamed past register-resident weights (conv1x1_rows_kernel<32, 1, 4, ..., 1, 4, 1>: 128 weight registers per
   // wave leave room for 4 compute waves and 64-column workgroups only).  Parity green, and SLOWER: 45.6 us against 29.6-31.9 on
@@ -380,7 +336,7 @@ static Conv2Variant pick_variant(const simt_conv_desc* d) {
   const bool long_rows = rows1024 && d->ntaps == 1 && d->Cin == 1024 && d->Cout <= 512 && d->dtype_out == SIMT_BF16;
   v.rowsk = (short_k || long_rows) && rows_enabled() && simt_conv_rows_eligible(d);
   if (v.rowsk) { v.stream = false; v.tile_n = 256; v.nst = 6; v.ntiles_n = d->Npad / 256; v.tm = 2; v.rows = 128; return v; }
-  v.stream = short_k && stream_enabled() && simt_conv_stream_eligible(d);
+  v.stream = short_k && simt_conv_stream_eligible(d);
   if (v.stream) { v.tile_n = 128; v.nst = 3; v.ntiles_n = d->Npad / 128; v.tm = 4; v.rows = 128; return v; }
   if (short_k) v.tile_n = 128;
   v.nst = short_k ? 2 : 3;
@@ -402,16 +358,12 @@ extern "C" int simt_conv_variant(const simt_conv_desc* d, int* bn, int* tm, int*
   return v.rowsk ? 5 : v.stream ? 4 : 2;
 }
 
-// Does the launch for d take its weights from d->w_frag (the weights-direct experiment)?  The engine asks before it allocates / packs the
-// fragment-ordered copy.  Round 3 measured that form 15-40 % SLOWER than the LDS-staged one on every production shape (DESIGN.md
-// section 9): it exists only in -DSIMT_ABLATION builds (csrc/experiments/), behind SIMT_WDIRECT=1; the product library always answers 0.
+// Does the launch for d take its weights from d->w_frag?  Always 0: the weights-direct form (weight operand straight from a fragment-ordered
+// copy into registers) was measured 15-40 % SLOWER than the LDS-staged one on every production shape (round 3) and
+// removed.  The symbol stays for the ABI.
 extern "C" int simt_conv_wants_frag(const simt_conv_desc* d) {
-#ifdef SIMT_ABLATION
-  return simt_conv2_abl_wants_frag(d);
-#else
   (void)d;
   return 0;
-#endif
 }
 
 // Which compile-time epilogue flavour (conv2_epilogue.h EPI) the launch for d runs: 0 generic, 1 statistics, 2 BatchNorm-backward reduce,
@@ -475,7 +427,7 @@ extern "C" int simt_conv_mtiles(const simt_conv_desc* d) {
 
 // Kernel arguments of the bf16 v2 family for d (every generation: conv_igemm2 / rows / stream); *vout = the variant the launch takes.
 static int conv2_fill_args(const simt_conv_desc* d, Conv2KArgs& k, Conv2Variant* vout) {
-  k.wf = (d->w_frag && simt_conv_wants_frag(d)) ? (const char*)d->w_frag : nullptr; k.nt16 = d->Npad / 16;
+  k.wf = nullptr; k.nt16 = d->Npad / 16;
   k.x = (const char*)d->x; k.w = (const char*)d->w; k.y = (bf16_t*)d->y; k.bias = d->bias; k.res = (const bf16_t*)d->res;
   k.stats = d->stats; k.zero = (const char*)simt_zero_page();
   k.mask = (const bf16_t*)d->mask; k.ldm = d->ldm; k.res_bits = d->res_bits;

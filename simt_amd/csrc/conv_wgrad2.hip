@@ -30,7 +30,6 @@ template <int N> __device__ __forceinline__ void wg_wait_vmcnt() {
   else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
 }
 
-// MODE 0 = product; 1 = loads only, 2 = fragment reads + MFMA only (timing ablations, env SIMT_WGRAD2_MODE)
 // Round 1 measured 3x3 256<-256 83 us = loads-only 52 + MFMA-only 43 "with little overlap": a compiler-inserted s_waitcnt vmcnt(0) in
 // front of the ds_read_tr builtin drained the ring every stage.  Round 2 (profiles/tools/ab_wgrad.py): asm fragment reads 84 -> 70 us,
 // incremental pixel coordinates in the issue phase -> 57 us (loads-only 42, MFMA-only 43), XCD-aware block order: 1x1 1024<-256
@@ -38,7 +37,6 @@ template <int N> __device__ __forceinline__ void wg_wait_vmcnt() {
 // the 1x1 shapes slower (62-67 us): it doubles the line requests.
 // `a`: the problem (kernel argument, or one entry of a grouped launch's table in device memory -- uniform per workgroup either way);
 // (split, tix): the pixel split and the output tile of this workgroup.
-template <int MODE>
 __device__ __forceinline__ void conv_wgrad2_body(const Wgrad2KArgs& a, const int split, const int tix) {
   constexpr int NT = 512, NST = 3, BP = 64;
   constexpr int ROWB = 256;                  // bytes per LDS row (128 channels)
@@ -207,19 +205,17 @@ __device__ __forceinline__ void conv_wgrad2_body(const Wgrad2KArgs& a, const int
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks][j], af[ks][i], acc[i][j], 0, 0, 0);   // D = [k][co]
   };
 
-  if (MODE != 2) {
-    if (nk > 0) issue(0);
-    if (nk > 1) issue(1);
-  }
+  if (nk > 0) issue(0);
+  if (nk > 1) issue(1);
   int buf = 0;
   if (wave < 4) {
     for (int kt = 0; kt < nk; ++kt) {
       if (kt + 1 < nk) wg_wait_vmcnt<6>(); else wg_wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (MODE != 1) load_frags(buf);                     // fragment reads first: their latency gates the MFMAs
-      if (MODE != 2 && kt + 2 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
-      if (MODE != 1) { frags_landed(); mma(); }
+      load_frags(buf);                     // fragment reads first: their latency gates the MFMAs
+      if (kt + 2 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
+      frags_landed(); mma();
       buf = (buf + 1 == NST) ? 0 : buf + 1;
     }
   } else {
@@ -228,12 +224,12 @@ __device__ __forceinline__ void conv_wgrad2_body(const Wgrad2KArgs& a, const int
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (MODE != 1 && kt > 0) { frags_landed(); mma(); }
-      if (MODE != 2 && kt + 2 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
-      if (MODE != 1) load_frags(buf);
+      if (kt > 0) { frags_landed(); mma(); }
+      if (kt + 2 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
+      load_frags(buf);
       buf = (buf + 1 == NST) ? 0 : buf + 1;
     }
-    if (MODE != 1 && nk > 0) { frags_landed(); mma(); }
+    if (nk > 0) { frags_landed(); mma(); }
   }
 
   // slab[split][co][k]: the X columns are the MFMA's row operand, so every accumulator quad is 4 consecutive k of one dY
@@ -259,7 +255,6 @@ __device__ __forceinline__ void conv_wgrad2_body(const Wgrad2KArgs& a, const int
 // ring keeps three stages (96 KB) in flight.  Each wave owns 128 channels x 64 columns: 32 accumulator quads (128 VGPRs), 12
 // fragments per stage (8 dY + 4 X, one 32-pixel k-step).  Same swizzle, same transposed reads, same early / late wave stagger.
 // Needs Cd % 256 == 0 to pay (layer 3 / 4 of the ResNets); everything else stays on the 128-row tile.
-template <int MODE>
 __device__ __forceinline__ void conv_wgrad3_body(const Wgrad2KArgs& a, const int split, const int tix) {
   constexpr int NST = 4, BP = 32;
   constexpr int ROWB = 256;                  // bytes per LDS row (128 channels)
@@ -349,12 +344,10 @@ __device__ __forceinline__ void conv_wgrad3_body(const Wgrad2KArgs& a, const int
           srcx[s] = a.x + ((unsigned)((b * a.H + iy) * a.W + ix) * (unsigned)pix_bytes + (unsigned)(xoff[s] - (tdy[s] * a.W + tdx[s]) * pix_bytes));
       }
     }
-    if (MODE != 2) {
-      __builtin_amdgcn_global_load_lds(GPTR(srcd[0]), LPTR(sbase), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(GPTR(srcd[1]), LPTR(sbase + SUB), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(GPTR(srcx[0]), LPTR(sbase + 2 * SUB), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(GPTR(srcx[1]), LPTR(sbase + 3 * SUB), 16, 0, 0);
-    }
+    __builtin_amdgcn_global_load_lds(GPTR(srcd[0]), LPTR(sbase), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(srcd[1]), LPTR(sbase + SUB), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(srcx[0]), LPTR(sbase + 2 * SUB), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GPTR(srcx[1]), LPTR(sbase + 3 * SUB), 16, 0, 0);
     ld_m += BP;
   };
 
@@ -418,9 +411,9 @@ __device__ __forceinline__ void conv_wgrad3_body(const Wgrad2KArgs& a, const int
       wait_stage(kt);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (MODE != 1) load_frags(buf);
+      load_frags(buf);
       if (kt + NST - 1 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
-      if (MODE != 1) { frags_landed(); mma(); }
+      frags_landed(); mma();
       buf = (buf + 1 == NST) ? 0 : buf + 1;
     }
   } else {
@@ -429,12 +422,12 @@ __device__ __forceinline__ void conv_wgrad3_body(const Wgrad2KArgs& a, const int
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (MODE != 1 && kt > 0) { frags_landed(); mma(); }
+      if (kt > 0) { frags_landed(); mma(); }
       if (kt + NST - 1 < nk) issue(buf >= 1 ? buf - 1 : NST - 1);
-      if (MODE != 1) load_frags(buf);
+      load_frags(buf);
       buf = (buf + 1 == NST) ? 0 : buf + 1;
     }
-    if (MODE != 1 && nk > 0) { frags_landed(); mma(); }
+    if (nk > 0) { frags_landed(); mma(); }
   }
 
   float* out = a.slab + (long)split * a.Cd * a.Ktot;
@@ -448,12 +441,11 @@ __device__ __forceinline__ void conv_wgrad3_body(const Wgrad2KArgs& a, const int
     }
 }
 
-template <int MODE>
 __global__ __launch_bounds__(512, 2) void conv_wgrad2_kernel(Wgrad2KArgs a) {
   const int tiles = a.cotiles * a.ktiles;
   const int lin = xcd_remap(blockIdx.x, tiles * a.nsplit);
   const int split = lin / tiles;
-  conv_wgrad2_body<MODE>(a, split, lin - split * tiles);
+  conv_wgrad2_body(a, split, lin - split * tiles);
 }
 
 // Grouped launch: n problems (the convs of one Bottleneck: same pixels, same split count) as ONE tile list.  Per problem the output has
@@ -467,15 +459,14 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad2_multi_kernel(const Wgrad2K
   const int t = lin - split * tiles;
   int j = 0;
   for (int i = 1; i < njobs; ++i) if (t >= jobs[i].tile0) j = i;
-  conv_wgrad2_body<0>(jobs[j], split, t - jobs[j].tile0);
+  conv_wgrad2_body(jobs[j], split, t - jobs[j].tile0);
 }
 
-template <int MODE>
 __global__ __launch_bounds__(512, 2) void conv_wgrad3_kernel(Wgrad2KArgs a) {
   const int tiles = a.cotiles * a.ktiles;
   const int lin = xcd_remap(blockIdx.x, tiles * a.nsplit);
   const int split = lin / tiles;
-  conv_wgrad3_body<MODE>(a, split, lin - split * tiles);
+  conv_wgrad3_body(a, split, lin - split * tiles);
 }
 __global__ __launch_bounds__(512, 2) void conv_wgrad3_multi_kernel(const Wgrad2KArgs* __restrict__ jobs, int njobs, int tiles) {
   const int lin = xcd_remap(blockIdx.x, (int)gridDim.x);
@@ -483,7 +474,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad3_multi_kernel(const Wgrad2K
   const int t = lin - split * tiles;
   int j = 0;
   for (int i = 1; i < njobs; ++i) if (t >= jobs[i].tile0) j = i;
-  conv_wgrad3_body<0>(jobs[j], split, t - jobs[j].tile0);
+  conv_wgrad3_body(jobs[j], split, t - jobs[j].tile0);
 }
 
 // Rows of dY channels per output tile: 256 (conv_wgrad3_body) when the problem has whole 256-channel tiles, else 128.
@@ -570,41 +561,17 @@ int simt_conv_wgrad_bf16_v2(const simt_wgrad_desc* d, simt_stream_t stream) {
   if (tco == 256) {
     static SimtLdsAttrCache attr_cache3;
     if (simt_lds_attr_needed(&attr_cache3, WGRAD3_LDS))
-      (void)hipFuncSetAttribute((const void*)conv_wgrad3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WGRAD3_LDS);
-#ifdef SIMT_ABLATION     // timing ablations (loads only / fragment reads + MFMA only: MEANINGLESS outputs), never in the product library
-    {
-      static const int mode3 = getenv("SIMT_WGRAD2_MODE") ? atoi(getenv("SIMT_WGRAD2_MODE")) : 0;
-      if (mode3 == 1 || mode3 == 2) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WGRAD3_LDS);
-        (void)hipFuncSetAttribute((const void*)conv_wgrad3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WGRAD3_LDS);
-        if (mode3 == 1) hipLaunchKernelGGL(conv_wgrad3_kernel<1>, dim3(k.cotiles * k.ktiles * k.nsplit), dim3(512), WGRAD3_LDS, (hipStream_t)stream, k);
-        else hipLaunchKernelGGL(conv_wgrad3_kernel<2>, dim3(k.cotiles * k.ktiles * k.nsplit), dim3(512), WGRAD3_LDS, (hipStream_t)stream, k);
-        SIMT_LAUNCH_CHECK();
-        return SIMT_OK;
-      }
-    }
-#endif
-    hipLaunchKernelGGL(conv_wgrad3_kernel<0>, dim3(k.cotiles * k.ktiles * k.nsplit), dim3(512), WGRAD3_LDS, (hipStream_t)stream, k);
+      (void)hipFuncSetAttribute((const void*)conv_wgrad3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WGRAD3_LDS);
+    hipLaunchKernelGGL(conv_wgrad3_kernel, dim3(k.cotiles * k.ktiles * k.nsplit), dim3(512), WGRAD3_LDS, (hipStream_t)stream, k);
     SIMT_LAUNCH_CHECK();
     return SIMT_OK;
   }
   const int lds = WGRAD2_LDS;
   static SimtLdsAttrCache attr_cache;
   if (simt_lds_attr_needed(&attr_cache, lds))
-    (void)hipFuncSetAttribute((const void*)conv_wgrad2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)conv_wgrad2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const int grid = k.cotiles * k.ktiles * k.nsplit;
-#ifdef SIMT_ABLATION     // timing ablations (loads only / MFMA only: MEANINGLESS outputs), never in the product library
-  static const int mode = getenv("SIMT_WGRAD2_MODE") ? atoi(getenv("SIMT_WGRAD2_MODE")) : 0;
-  if (mode == 1 || mode == 2) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (mode == 1) hipLaunchKernelGGL(conv_wgrad2_kernel<1>, dim3(grid), dim3(512), lds, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL(conv_wgrad2_kernel<2>, dim3(grid), dim3(512), lds, (hipStream_t)stream, k);
-    SIMT_LAUNCH_CHECK();
-    return SIMT_OK;
-  }
-#endif
-  hipLaunchKernelGGL(conv_wgrad2_kernel<0>, dim3(grid), dim3(512), lds, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(conv_wgrad2_kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, k);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }

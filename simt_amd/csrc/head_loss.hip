@@ -20,10 +20,6 @@
 #include <math.h>
 
 #define QMAX 40
-#ifndef SIMT_HEAD_ABL
-#define SIMT_HEAD_ABL 0      // timing ablations (results meaningless): 1 no dT partials, 2 no anchors, 4 no x-reduction, 8 no gradient terms,
-                             // 16 no run sums, 32 no gradient staging
-#endif
 #define NSCAL 13
 #define XR_MAX 287   // low-res columns one 256-pixel chunk may touch on the run-based x-reduction of pass 2 (more: the scanning form)
 
@@ -442,7 +438,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head
     // dL_y/dT partials: per wave, one label value at a time (labels are spatially coherent -> few rounds)
     // (tried and measured slower, round 2: staging q / r per wave as [pixel][j] and letting lane j walk the pixels -- with a register
     // run sum and scalar branches at label changes 455 us against 330, with one LDS float add per pixel 755: ds_add_f32 is slow)
-    if (!(SIMT_HEAD_ABL & 1)) {
+    {
       unsigned long long todo = __ballot(lab_ok);
       const float ir1 = lab_ok ? 1.0f / r1 : 0.f, ir2 = lab_ok ? 1.0f / r2 : 0.f;
       while (todo) {
@@ -465,7 +461,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head
       }
     }
     // ---- anchors: arg-max over all pixels of each channel's upsampled logit (first index), Exist masks (:375-384)
-    if (a.mode == 0 && !(SIMT_HEAD_ABL & 2)) {
+    if (a.mode == 0) {
       unsigned long long ex1 = live ? (1ull << e1.arg) : 0ull, ex2 = live ? (1ull << e2.arg) : 0ull;
       ex1 = wave_or_u64(ex1);
       ex2 = wave_or_u64(ex2);
@@ -629,7 +625,6 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(HeadArgs a, int nblk
 // use.  mode 0: right-tap weights l1;  1: left-tap weights 1 - l1;  2: last column, whose right tap is the column itself.
 template <int NB>
 __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL1, int lo, int hi, int mode, float s) {
-  if (SIMT_HEAD_ABL & 16) return s;
   float wv[NB * 4], gv[NB * 4];
 #pragma unroll
   for (int u = 0; u < NB * 4; ++u) {
@@ -803,7 +798,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
         if (j < Q) {
           float q1 = exp_le0(v1[j] - e1.vmax) * inv1, q2 = exp_le0(v2[j] - e2.vmax) * inv2;
           float G1 = 0.f, G2 = 0.f;
-          if (live && !(SIMT_HEAD_ABL & 8)) {
+          if (live) {
             if (conf != 255) {
               float oh = (j == conf) ? 1.f : 0.f;
               G1 += gp1 * (q1 - oh);
@@ -822,10 +817,8 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
               G2 += gy2 * (q2 - q2 * sT[QC + j * C + labi] * ir2);
             }
           }
-          if (!(SIMT_HEAD_ABL & 32)) {
           sG[(0 * 256 + tid) * GP + j] = G1;
           sG[(1 * 256 + tid) * GP + j] = G2;
-          } else { asm volatile("" :: "v"(G1), "v"(G2)); }
         }
       }
     }
@@ -836,8 +829,7 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
     const int xl_lo = max(0, (int)src_coord(g.half, g.sx, x0) - 1);
     const int xl_hi = min(g.w - 1, (int)src_coord(g.half, g.sx, xend - 1) + 2);
     const int nxl = xl_hi - xl_lo + 1;
-    if (SIMT_HEAD_ABL & 4) {
-    } else if (nxl <= XR_MAX) {
+    if (nxl <= XR_MAX) {
       // Pixels whose left tap is column xl form one run of the chunk ([sStart[xr], sStart[xr+1])), the ones whose right tap is xl the
       // run before it: two short weighted sums instead of a scan over every pixel that could touch the column.  A wave takes one
       // column, its lanes the (head, channel) pairs: run bounds, clamps and masks are wave-uniform (scalar unit), the weights broadcast

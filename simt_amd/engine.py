@@ -451,25 +451,6 @@ class TrunkPlan:
                            ops.dt_code(self.dtype))
         return wt, tile, npad, ck
 
-    def _frag_twin(self, wp, npad):
-        """Fragment-ordered copy of the packed operand `wp` (simt_conv_desc.w_frag), kept fresh by twin pack jobs: every
-        simt_pack_weight entry that writes `wp` gets a second entry with the same source and SIMT_PACK_FRAG in `mode`."""
-        if not hasattr(self, "_frag"):
-            self._frag = {}
-        key = wp.data_ptr()
-        if key not in self._frag:
-            lib = L.load()
-            wf = self.new(*wp.shape, zero=True)
-            jobs = [it for it in self.pack_list.items if it.fn is lib.simt_pack_weight and it.args[1] == key]
-            assert jobs, "a conv asked for fragment-ordered weights before its pack job was planned"
-            for it in jobs:
-                a = list(it.args)
-                a[1] = wf.data_ptr()
-                a[9] = a[9] | ops.PACK_FRAG(npad)
-                self.pack_list.add("simt_pack_weight", *a)
-            self._frag[key] = wf
-        return self._frag[key]
-
     def repack(self):
         """Refresh every packed operand from the fp32 master weights (after an optimiser step / load_state_dict)."""
         self.pack_list.run()
@@ -533,13 +514,8 @@ class TrunkPlan:
             d.fbn = C.addressof(fd)
             d._fbn_keep = fd                       # the descriptor is read at every launch
             fb = 1
-        wd = 0
-        if gen == 2 and ops.conv_wants_frag(d):
-            # -DSIMT_ABLATION builds with SIMT_WDIRECT=1 only: weight operand from a fragment-ordered copy (csrc/experiments/conv_igemm2_abl.hip)
-            d.w_frag = self._frag_twin(wp, npad).data_ptr()
-            wd = 1
         epi = L.load().simt_conv_epilogue_flavour(C.byref(d)) if gen == 2 else 0
-        tag = (f"conv_igemm2_kernel<{bn_.value}, {tm_.value}, {nst_.value}, {fb}, {epi}>{' [weights-direct experiment]' if wd else ''}" if gen == 2 else
+        tag = (f"conv_igemm2_kernel<{bn_.value}, {tm_.value}, {nst_.value}, {fb}, {epi}>" if gen == 2 else
                "conv1x1_stream_kernel" if gen == 4 else "conv1x1_rows_kernel" if gen == 5 else
                f"conv_igemm_kernel<{tn[x.dtype]}, {tn[y.dtype]}, {tile}>")
         nbytes = (Bn * Hi * Wi * Cin + npad * len(taps) * Cin) * x.element_size() + M * Cout * y.element_size()
