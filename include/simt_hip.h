@@ -691,6 +691,37 @@ typedef struct {
 } simt_ema_desc;
 int simt_ema_multi(const simt_ema_desc* d, simt_stream_t stream);
 
+/* ---- every eval-mode BatchNorm fold of a plan in ONE launch (simt_amd/ema_teacher.py) --------------------------------------------
+ * The table-driven form of simt_bn_fold: a frozen plan whose weights move (the EMA teacher) re-derives the (scale, shift) pair of every
+ * BatchNorm at each refresh -- 104 launches of at most 2 048 lanes for a ResNet-101, one launch here.  One workgroup of 256 lanes per chunk of
+ * `chunk` channels of one segment; plain loads, plain stores, no LDS, no atomics, no scratch.
+ * CONTRACT: for every segment and every c < C, scale[c] and shift[c] are, bit for bit, what simt_bn_fold writes for the same six pointers,
+ * eps and C:   sc = gamma[c] / sqrtf(rv[c] + eps);  scale[c] = sc;  shift[c] = beta[c] - rm[c] * sc
+ * -- the same source expression compiled under the same floating-point contraction setting as bn_fold_kernel (csrc/build.sh: one set of flags,
+ * no pragma in either file), so the multiply-subtract of `shift` is fused, or not, exactly as it is there.  The yardstick is that kernel on
+ * the GPU (tests/test_gpu_ema_teacher.py), not a host restatement.  Nothing but scale[0, C) and shift[0, C) of each segment is written.
+ * The segment table exists twice: `segs` on the device for the kernel, `segs_host` in host memory for the checks below (the same `nsegs`
+ * records; the caller keeps both alive and identical).
+ * Refused with SIMT_ERR_INVALID and no launch: NULL d, segs, segs_host or chunks; nsegs <= 0, nchunks <= 0, chunk <= 0; a segment with
+ * C <= 0 or a NULL pointer among its six. */
+typedef struct {
+  const float* gamma;        /* BatchNorm weight        [C] */
+  const float* beta;         /* BatchNorm bias          [C] */
+  const float* running_mean; /*                         [C] */
+  const float* running_var;  /*                         [C] */
+  float* scale;              /* out                     [C] */
+  float* shift;              /* out                     [C] */
+  int32_t C, reserved_;
+} simt_bn_fold_seg;          /* 56 bytes */
+typedef struct {
+  const simt_bn_fold_seg* segs;      /* device array [nsegs] */
+  const simt_bn_fold_seg* segs_host; /* host copy of the same records: what the refusals are decided on */
+  const int32_t* chunks;             /* device [nchunks][2] = (segment, chunk index): channels [index * chunk, (index + 1) * chunk) of it */
+  int32_t nsegs, nchunks, chunk;
+  float eps;
+} simt_bn_fold_desc;
+int simt_bn_fold_multi(const simt_bn_fold_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

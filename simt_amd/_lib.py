@@ -164,6 +164,19 @@ class EmaDesc(C.Structure):
     _fields_ = [("segs", c_p), ("chunks", c_p), ("nchunks", i32), ("chunk", i32), ("omd", f32), ("skip_if", c_p)]
 
 
+class BnFoldSeg(C.Structure):
+    """simt_bn_fold_seg (include/simt_hip.h): one BatchNorm of a simt_bn_fold_multi launch."""
+    _fields_ = [("gamma", c_p), ("beta", c_p), ("running_mean", c_p), ("running_var", c_p), ("scale", c_p), ("shift", c_p),
+                ("C", i32), ("reserved_", i32)]
+
+
+class BnFoldDesc(C.Structure):
+    """simt_bn_fold_desc (include/simt_hip.h): every eval-mode BatchNorm fold of a plan in one launch; `segs` on the device, `segs_host` the
+    same records in host memory (the refusals are decided on them)."""
+    _fields_ = [("segs", c_p), ("segs_host", C.POINTER(BnFoldSeg)), ("chunks", c_p), ("nsegs", i32), ("nchunks", i32), ("chunk", i32),
+                ("eps", f32)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -273,6 +286,7 @@ SIGNATURES = {
     "simt_grey_mean_parts": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),
+    "simt_bn_fold_multi": (_I, [C.POINTER(BnFoldDesc), c_p]),
 }
 
 _lib = None

@@ -25,6 +25,7 @@ from . import _lib as L
 from . import ops
 from . import trace
 from .ema import EmaMixin
+from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
 from .train_state import TrainStateMixin, state_sha256
 
@@ -65,9 +66,9 @@ def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer
     return g0, g1
 
 
-class SimTTrainer(TrainStateMixin, EmaMixin):
+class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
     def __init__(self, state, fixed_state, ntm1, ntm2, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None):
+                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None, ema_teacher_every=None):
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -165,6 +166,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin):
         self._build_sgd()
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
+        self._init_teacher(ema_teacher_every)      # None: the frozen model never moves (simt_amd/ema_teacher.py)
         # ---- early optimiser step: the gradients SGD applies (layer3, layer4, heads) are final long before the backward has walked
         # through layer2 / layer1 / the stem (whose gradients this stage computes but never applies), so SGD and the re-pack of the
         # updated weights run on the side stream from that point on instead of after the backward (0.7 ms of exclusive tail).
@@ -351,6 +353,12 @@ class SimTTrainer(TrainStateMixin, EmaMixin):
                 # behind the re-pack on the main stream: in order after this step's forward (running statistics) and SGD launch, and in front
                 # of everything the next step enqueues (its side-stream work waits for an event the main stream records first: ev0)
                 self.ema.update(st)
+                # the EMA teacher's refresh (simt_amd/ema_teacher.py), if this update made one due, directly behind it on the main stream:
+                #   behind this step's frozen forward and softmax_rows (side stream): the main stream waited for ev_fix in front of the head;
+                #   in front of the next step's stem launch (main stream, reads the frozen plan's w7 and bn1 shift): stream order;
+                #   in front of the next step's frozen forward (side stream): it waits for ev0 / ev_in, which the main stream records first.
+                # Once per optimiser step: this point is behind the last micro-batch.
+                self._teacher_follows(st)
         self.it_done += 1
         return self.lout
 
@@ -393,6 +401,14 @@ class SimTTrainer(TrainStateMixin, EmaMixin):
                     # running statistics) and has just run SGD; the backward list's final join makes the main stream wait for the side
                     # stream, so the launch is complete before the next step writes a master
                     self.ema.update(side.cuda_stream)
+                    # the EMA teacher's refresh, if due, directly behind it on the SIDE stream:
+                    #   behind this step's frozen forward and softmax_rows: they ran on this stream earlier in the step (stream order);
+                    #   behind this step's stem launch, the one main-stream reader of the frozen plan's operands: the side stream waited
+                    #   for ev_main, recorded on the main stream after it;
+                    #   in front of the next step's frozen forward: stream order;
+                    #   in front of the next step's stem launch (main stream): the backward list's final join makes the main stream wait
+                    #   for the side stream after this hook has enqueued.
+                    self._teacher_follows(side.cuda_stream)
         self.plan.backward(hook=hook)
         assert done[0]
 

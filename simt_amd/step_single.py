@@ -26,14 +26,15 @@ import torch
 from . import _lib as L
 from . import ops
 from .ema import EmaMixin
+from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
 from .step import lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
 
-class SimTSingleTrainer(TrainStateMixin, EmaMixin):
+class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
     def __init__(self, model, state, fixed_state, ntm, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 process_group=None, arch=None, ema_decay=None):
+                 process_group=None, arch=None, ema_decay=None, ema_teacher_every=None):
         """model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
         DeeplabVGG(nc + openc)); fixed_state: the frozen model's (nc outputs).  arch: plan keyword arguments (reduced depths / widths
         for tests): v3 -> layers, width, assp_ch; vgg -> vgg_layers."""
@@ -132,6 +133,9 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin):
         self._build_sgd()
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
+        # None: the frozen model never moves (simt_amd/ema_teacher.py).  DeeplabVGG has ONE classifier of Cn + K rows: the frozen model's Cn rows
+        # follow the leading Cn rows of its shadow
+        self._init_teacher(ema_teacher_every, prefix_rows=K if model == "vgg" else 0)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -228,6 +232,10 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin):
         self.plan.repack()
         if self.ema is not None:
             self.ema.update(st)          # main stream, behind SGD and the re-pack; the next step's side-stream work waits for ev0 (main) first
+            # the EMA teacher's refresh, if due, directly behind it on the main stream: behind this step's frozen forward (side stream; the main
+            # stream waited for ev_fix in front of the head) and in front of the next one (the side stream waits for ev0, recorded on the main
+            # stream at the start of the next step); no main-stream launch reads the frozen plan's operands
+            self._teacher_follows(st)
         self.it_done += 1
         return self.lout
 

@@ -34,6 +34,12 @@ model is not in FILE, its SHA-256 is.  Without the flag the tool writes and prin
 0 <= D < 1).  Training is bit for bit what it is without the flag.  Every evaluation also scores the averaged model (an `EMA mIoU` line) and
 a second rotation keeps its best snapshot `GTA5_ema_iter<i>_mIoU<m>.pth` (without a validation set: a rolling `GTA5_ema_iter<i>.pth`); the
 stop writes `GTA5_<stop>_ema.pth` beside `GTA5_<stop>.pth` -- same keys, loads wherever the other does.  Default: off.
+--ema-teacher [N]: with --ema, the frozen model FOLLOWS the averaged one (simt_amd/ema_teacher.py): behind every N-th EMA update (no value:
+N = 1) its weights, BatchNorm affine and running statistics become copies of their shadows and its packed operands are rebuilt -- three to
+five launches on the stream of the EMA update, no synchronisation.  Until the first refresh the run is bit for bit the one without the flag;
+from then on the confidence labels come from a moving teacher.  --restore-from still names the model the run STARTS beside (its SHA-256 is
+what --train-state checks); the state file carries the teacher as it is, N and the refresh count, and refuses a command line that drops the
+flag, adds it or changes N.  All three --model values.  Default: off.
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -114,7 +120,11 @@ def get_arguments(argv=None):
     add_photometric_args(p)
     add_train_state_args(p)
     add_ema_args(p)
-    return p.parse_args(argv)
+    add_ema_teacher_args(p)
+    args = p.parse_args(argv)
+    if args.ema_teacher is not None and args.ema is None:
+        p.error("--ema-teacher needs --ema: the frozen model follows the weight EMA")
+    return args
 
 
 MODELS = ("DeepLab", "DeepLabv3", "DeepLabVGG")
@@ -217,6 +227,22 @@ def add_ema_args(p):
                         "min(D, 1 - 1 / (t + 1)) at update t (no value: D = 0.999; 0 <= D < 1).  The trained model is unchanged; the averaged one is "
                         "evaluated beside it (`EMA mIoU`), kept by a rotation of its own (`..._ema_iter...`) and written at the stop as "
                         "GTA5_<stop>_ema.pth.  Default: off")
+
+
+def _teacher_every(text):
+    from simt_amd.ema_teacher import check_every
+    try:
+        return check_every(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected an integer >= 1 ({e})")
+
+
+def add_ema_teacher_args(p):
+    p.add_argument("--ema-teacher", type=_teacher_every, nargs="?", const=1, default=None, metavar="N",
+                   help="the frozen model follows the weight EMA (simt_amd/ema_teacher.py; needs --ema): behind every N-th EMA update (no value: "
+                        "N = 1; an integer >= 1) its tensors become copies of their shadows and its packed operands are rebuilt, on the stream of "
+                        "the update.  Bit for bit the run without the flag until the first refresh.  --train-state carries the teacher and refuses "
+                        "a run that drops the flag, adds it or changes N.  Default: off")
 
 
 def add_v3_layers(p):
@@ -476,6 +502,12 @@ class TrainStateFile:
         return True
 
 
+def teacher_line(args):
+    if args.ema_teacher is not None:
+        print(f"EMA teacher: the frozen model follows the weight EMA (decay {args.ema}), refreshed behind every "
+              f"{'update' if args.ema_teacher == 1 else str(args.ema_teacher) + ' updates'} (N = {args.ema_teacher})")
+
+
 def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
     resumed run: iterations done x iter_size)."""
@@ -566,8 +598,10 @@ def main(argv=None):
     dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
-                     args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema)
+                     args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
+                     ema_teacher_every=args.ema_teacher)
     if rank == 0:
+        teacher_line(args)
         print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -659,8 +693,9 @@ def main_single(args):
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
     tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
-                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema)
+                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema, ema_teacher_every=args.ema_teacher)
     if rank == 0:
+        teacher_line(args)
         print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)

@@ -9,7 +9,8 @@ steps == n steps (tests/test_gpu_resume.py).
 
 Stored: what is not derived from something else in the dict.  NOT stored: T (the inner loop rewrites it every step), every packed operand
 (`plan.repack()` rebuilds them from the masters on load) and the frozen model -- a resumed run is given the same --restore-from and the
-SHA-256 of the frozen tensors is compared instead, which keeps the file at weights + momentum.
+SHA-256 of the frozen tensors is compared instead, which keeps the file at weights + momentum.  (With the EMA teacher the frozen model moves: the
+file then carries it as it is, beside the unchanged SHA-256 of the model the run started beside.)
 """
 import hashlib
 import os
@@ -125,7 +126,10 @@ class TrainStateMixin:
         `momentum`, the NTM / W tensors with their Adam moments (SimT trainers), `it_done`, the device-side accumulators that outlive a step
         and reach `losses()` (the scalars of the last step with the cumulative bad-label count, and its host twin `bad_reported`), `hyper`
         and (SimT trainers) `frozen_sha256`; with a weight EMA (`ema_decay`, simt_amd/ema.py) also `ema` = {decay, updates, shadow} -- the key is
-        absent without one, and `load_training_state` refuses a state whose `ema` does not fit the trainer's.  Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
+        absent without one, and `load_training_state` refuses a state whose `ema` does not fit the trainer's; with the EMA teacher
+        (`ema_teacher_every`, simt_amd/ema_teacher.py) also `teacher` = {every, refreshes, params}: the frozen model as the last refresh left it
+        (`frozen_sha256` stays the hash of the model the run started beside), refused likewise when the keyword is dropped, added or N differs.
+        Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
         run -- RuntimeError (`TrunkPlan.raise_on_fbn_error`), no dict, and a file written earlier stays the last good state.  Data parallel: every rank holds the same parameters, momentum and NTM state after the exchange, so rank 0's dict is THE
@@ -145,6 +149,8 @@ class TrainStateMixin:
             ts["accumulators"] = {"hout": self.hout[:16].detach().cpu(), "bad_labels": self.bad_labels.detach().cpu()}
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
             ts["ema"] = self.ema.state()
+        if getattr(self, "teacher", None) is not None:      # the EMA teacher (simt_amd/ema_teacher.py): every, refresh count, the frozen model as it is now
+            ts["teacher"] = self.teacher.state()
         return ts
 
     def load_training_state(self, ts):
@@ -164,6 +170,10 @@ class TrainStateMixin:
                              f"this trainer: {self.frozen_sha256}); give the resumed run the same --restore-from")
         from .ema import state_mismatch
         why = state_mismatch(getattr(self, "ema", None), ts.get("ema"))
+        if why:
+            raise ValueError(why)
+        from .ema_teacher import state_mismatch as teacher_mismatch
+        why = teacher_mismatch(getattr(self, "teacher", None), ts.get("teacher"))
         if why:
             raise ValueError(why)
         problems = []
@@ -207,6 +217,8 @@ class TrainStateMixin:
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "ema", None) is not None:
             self.ema.load_state(ts["ema"])
+        if getattr(self, "teacher", None) is not None:      # the frozen model as the saved run's last refresh left it; its plan is re-packed
+            self.teacher.load_state(ts["teacher"])
         self.plan.repack()
         torch.cuda.synchronize(self.dev)
 
