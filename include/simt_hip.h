@@ -355,6 +355,12 @@ int simt_head_keys_count(void);
 int simt_softmax_rows(const float* in, int ldi, float* out, int ldo, long M, int C, simt_stream_t stream);
 int simt_head_loss(const simt_head_desc* d, simt_stream_t stream);
 int simt_head_grad(const simt_head_desc* d, simt_stream_t stream);
+/* Two views (the weak-view teacher): the frozen operand of pixel p = (b, y, x) is read from item fb = min(fix_item[p], B - 1)
+ * of fixp instead of item b -- the confidence label of pass 1, of pass 2 when it decides the labels again, and the anchor rows of hout.
+ * pred1 / pred2 / label stay at item b.  fix_item: [B][H][W] bytes (the item map of simt_class_mix_items);  NULL: simt_head_loss /
+ * simt_head_grad, launch for launch.  mode 1 has no frozen operand: a map with it is refused. */
+int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream);
+int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream);
 
 /* ---- NTM micro-solver (model/deeplab_multi.py:244-286, tools/trainV2_simt.py:326-339,412-424,435-436) ---- */
 typedef struct {
@@ -613,6 +619,10 @@ typedef struct {
 } simt_class_mix_desc;
 int simt_label_presence(const long long* lab, int B, long hw, int n_classes, uint32_t* part, simt_stream_t stream);
 int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream);
+/* simt_class_mix, and the item every pixel came from: item_out[i][p] = m ? partner[i] : i with the m above (apply[i] == 0: i everywhere).
+ * item_out: [B][h][w] bytes at a 4-byte aligned base (a quad's four bytes leave as one dword when h * w % 4 == 0); NULL is refused.
+ * x_out and lab_out are simt_class_mix's, bit for bit: same grid, same paste mask. */
+int simt_class_mix_items(const simt_class_mix_desc* d, uint8_t* item_out, simt_stream_t stream);
 
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------

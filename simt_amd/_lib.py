@@ -244,6 +244,8 @@ SIGNATURES = {
     "simt_softmax_rows": (_I, [c_p, _I, c_p, _I, _L, _I, c_p]),
     "simt_head_loss": (_I, [C.POINTER(HeadDesc), c_p]),
     "simt_head_grad": (_I, [C.POINTER(HeadDesc), c_p]),
+    "simt_head_loss_views": (_I, [C.POINTER(HeadDesc), c_p, c_p]),
+    "simt_head_grad_views": (_I, [C.POINTER(HeadDesc), c_p, c_p]),
     "simt_ntm_inner_loop": (_I, [C.POINTER(NtmInnerDesc), c_p]),
     "simt_ntm_post": (_I, [C.POINTER(NtmPostDesc), c_p]),
     "simt_sig_ntm": (_I, [c_p, c_p, c_p, c_p, c_p, _I, _I, c_p]),
@@ -283,6 +285,7 @@ SIGNATURES = {
     "simt_scale_crop": (_I, [C.POINTER(ScaleCropDesc), c_p]),
     "simt_label_presence": (_I, [c_p, _I, _L, _I, c_p, c_p]),
     "simt_class_mix": (_I, [C.POINTER(ClassMixDesc), c_p]),
+    "simt_class_mix_items": (_I, [C.POINTER(ClassMixDesc), c_p, c_p]),
     "simt_grey_mean_parts": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),

@@ -88,8 +88,12 @@ __device__ __forceinline__ bool pasted(long long l, int C, uint32_t mask) { retu
 
 // One lane: pixels p .. p+3 of item i = blockIdx.y.  lab[j] is read always (when apply[i]); a quad whose four decisions agree reads one
 // source only, a mixed quad reads both and selects.  Values travel as integer words.
-template <bool VEC>
-__global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_desc d) {
+// ITEMS_: empty for simt_class_mix (name and code as before the flavour existed); {true} for simt_class_mix_items, which also writes the item
+// each pixel came from, item_out[i][p] = m ? j : i -- one byte per pixel on top of the 40-48: a quad's four bytes leave as one dword when
+// VEC (h*w % 4 == 0 and a 4-byte aligned base: every item's row then starts on a dword), as bytes in the unaligned flavour and the tail.
+template <bool VEC, bool... ITEMS_>
+__global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_desc d, uint8_t* __restrict__ item_out) {
+  constexpr bool ITEMS = (false || ... || ITEMS_);
   const int i = blockIdx.y;
   const int apply = d.apply[i];
   const int j = d.partner[i];
@@ -100,6 +104,7 @@ __global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_des
   const long long* __restrict__ li = d.lab + (long)i * HW;
   uint32_t* __restrict__ xo = (uint32_t*)d.x_out + (long)i * 3 * HW;
   long long* __restrict__ lo = d.lab_out + (long)i * HW;
+  uint8_t* __restrict__ io = ITEMS ? item_out + (long)i * HW : nullptr;
   const long q = (long)blockIdx.x * 256 + threadIdx.x;
   if (!apply) {                                          // a straight copy of item i (wave-uniform branch): the partner is not read
     if (q < nquad) {
@@ -109,18 +114,21 @@ __global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_des
         *(i64x2*)(lo + p + 2) = *(const i64x2*)(li + p + 2);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) *(uint4*)(xo + ch * HW + p) = *(const uint4*)(xi + ch * HW + p);
+        if (ITEMS) *(uint32_t*)(io + p) = (uint32_t)i * 0x01010101u;
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           lo[p + e] = li[p + e];
 #pragma unroll
           for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p + e] = xi[ch * HW + p + e];
+          if (ITEMS) io[p + e] = (uint8_t)i;
         }
       }
     } else if (q == nquad) {
       for (long p = nquad << 2; p < HW; ++p) {
         lo[p] = li[p];
         for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = xi[ch * HW + p];
+        if (ITEMS) io[p] = (uint8_t)i;
       }
     }
     return;
@@ -156,6 +164,14 @@ __global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_des
     } else {
       lo[p] = a[0]; lo[p + 1] = a[1]; lo[p + 2] = a[2]; lo[p + 3] = a[3];
     }
+    if (ITEMS) {
+      const uint32_t b0 = m0 ? j : i, b1 = m1 ? j : i, b2 = m2 ? j : i, b3 = m3 ? j : i;
+      if (VEC) {
+        *(uint32_t*)(io + p) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+      } else {
+        io[p] = (uint8_t)b0; io[p + 1] = (uint8_t)b1; io[p + 2] = (uint8_t)b2; io[p + 3] = (uint8_t)b3;
+      }
+    }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const long o = ch * HW + p;
@@ -184,12 +200,14 @@ __global__ __launch_bounds__(256) void class_mix_kernel(const simt_class_mix_des
       const bool m = pasted(l, C, mask);
       lo[p] = m ? l : li[p];
       for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = m ? xj[ch * HW + p] : xi[ch * HW + p];
+      if (ITEMS) io[p] = (uint8_t)(m ? j : i);
     }
   }
 }
 
-extern "C" int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream) {
+static int class_mix_launch(const simt_class_mix_desc* d, uint8_t* item_out, bool items, simt_stream_t stream) {
   SIMT_CHECK(d && d->x && d->lab && d->x_out && d->lab_out && d->part);
+  SIMT_CHECK(!items || (item_out && ((uintptr_t)item_out & 3) == 0));
   SIMT_CHECK(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->lab & 15) == 0 && ((uintptr_t)d->x_out & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0);
   SIMT_CHECK(((uintptr_t)d->part & 3) == 0 && (const void*)d->x != (const void*)d->x_out && (const void*)d->lab != (const void*)d->lab_out);
   SIMT_CHECK(d->B > 0 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0);
@@ -202,10 +220,22 @@ extern "C" int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream
   }
   const long lanes = (HW >> 2) + ((HW & 3) ? 1 : 0);
   const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)d->B);
-  if ((HW & 3) == 0)
-    hipLaunchKernelGGL((class_mix_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  const bool vec = (HW & 3) == 0;
+  if (vec && !items)
+    hipLaunchKernelGGL((class_mix_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d, (uint8_t*)nullptr);
+  else if (!items)
+    hipLaunchKernelGGL((class_mix_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d, (uint8_t*)nullptr);
+  else if (vec)
+    hipLaunchKernelGGL((class_mix_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
   else
-    hipLaunchKernelGGL((class_mix_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL((class_mix_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
+}
+
+extern "C" int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream) { return class_mix_launch(d, nullptr, false, stream); }
+
+// simt_class_mix plus the item map (the weak-view teacher gathers its predictions through it): x_out / lab_out bit for bit as above.
+extern "C" int simt_class_mix_items(const simt_class_mix_desc* d, uint8_t* item_out, simt_stream_t stream) {
+  return class_mix_launch(d, item_out, true, stream);
 }

@@ -234,7 +234,20 @@ struct HeadArgs {
   int mode;                    // 0 = SimT loss block; 1 = warm-up stage: plain CE of both heads against `label`
   unsigned char* conf_out;     // optional [B][H][W]: the confidence label decided per pixel (255 = none)
   unsigned char* label_ws;     // optional [B][H][W]: the checked noisy label (255 = ignored / invalid / warm-up mode), pass 1 -> pass 2
+  const unsigned char* fix_item;  // optional [B][H][W] (simt_head_*_views): the item of fixp a pixel reads its frozen operand from
 };
+
+// The flavour pack of the two pass kernels: <> the SimT / DeepLab-v2 warm-up code (names as before any flavour existed), <true> ONE,
+// <false, true> VIEWS.
+template <bool... F_>
+constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false}; return v[i]; }
+
+// VIEWS: the frozen operand of pixel pix of item b comes from item fb = min(fix_item[pix], B - 1).  The taps index pixels from fixp's base
+// and differ from the pixel's own by a constant: one byte load and one pointer offset, no second make_taps.
+__device__ __forceinline__ const float* fixp_of_item(const HeadArgs& a, const HeadGeom& g, int b, long pix) {
+  const int fb = min((int)a.fix_item[pix], g.B - 1);
+  return a.fixp + (long)(fb - b) * g.h * g.w * g.ldf;
+}
 
 // Full-wave sum with DPP row operations (no LDS crossbar): result valid in lane 63.
 __device__ __forceinline__ float wave_sum_dpp63(float v) {
@@ -284,9 +297,11 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
 #endif
 // ONE_: empty for every SimT / DeepLab-v2 warm-up flavour (names and code as before the flag existed); {true} for the warm-up stage of a
 // one-output model (single = 1, mode = 1): one head per pixel and only its cross-entropy against the label, run-time channel counts.
+// {false, true}: VIEWS, mode 0 with an item map (a.fix_item): a compile-time flavour, so the map-less launches keep their code and registers.
+// (Its QM = 40 fall-back asks for one wave per SIMD: at two, the extra address pair spilled where the map-less fall-back already does.)
 template <int QM, int QT, int CT, bool... ONE_>
-__global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head_pass1_kernel(HeadArgs a) {
-  constexpr bool ONE = (false || ... || ONE_);
+__global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass1_kernel(HeadArgs a) {
+  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time");
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C;
@@ -351,7 +366,9 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : 2)) void head
     // ---- fixed-model posterior -> confidence label (reference :354-361)
     float fm = 0.f;
     int fa = 0;
-    if (a.mode == 0) fixed_posterior<CM>(g, C, a.fixp, tp, fm, fa);
+    const float* fixp = a.fixp;
+    if constexpr (VIEWS) { if (live) fixp = fixp_of_item(a, g, b, p); }
+    if (a.mode == 0) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
     asm volatile("" ::: "memory");   // keep the next gathers from being hoisted above (register pressure)
     int conf = (fm > a.th_high) ? fa : 255;
     if (fm < a.th_low) conf = C;
@@ -563,6 +580,52 @@ __device__ __forceinline__ double* head_sums(float* hout, int Q, int C) {
   return (double*)(hout + ((16 + 4 * Q * C + 4 * QMAX + 1) & ~1));
 }
 
+// The anchor rows of hout: the frozen posterior at each channel's anchor pixel -- with a map (a.fix_item) the posterior of the item that
+// pixel's map byte names.  Both forms must give the same rows bit for bit (a constant map per item == the map-less launch on the gathered
+// operand), and two separately compiled copies of the softmax below fused different products on gfx950 (last-bit differences in ~6 % of the
+// rows' words), so the softmax exists ONCE: the general loop tests the pointer at run time.  SHORT is the loop of a launch without a map
+// whose fixp holds probabilities (fix_logits = 0: DeepLab-v2, DeepLab-VGG16) -- one interpolation per word and nothing else, where the
+// run-time test and the select on the operand's base cost 3.6 us at Q = 34 (profiles/weak_teacher.txt); it shares no arithmetic with the
+// general loop but that one lerp4, whose rows tests/test_gpu_weak_teacher.py holds equal bit for bit.
+template <bool SHORT>
+__device__ __forceinline__ void head_anchor_rows(const HeadArgs& a, const HeadGeom& g, float* o, int tid, int C, int QC) {
+  for (int i = tid; i < 2 * QC; i += 256) {
+    if (a.mode != 0) { o[16 + i] = 0.f; continue; }
+    int hd = i / QC, r = i % QC, j = r / C, c = r % C;
+    unsigned long long key = a.keys[hd * QMAX + j];
+    long p = (long)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull));
+    int x = (int)(p % g.W);
+    long t = p / g.W;
+    int y = (int)(t % g.H);
+    int b = (int)(t / g.H);
+    if (b >= g.B) { b = 0; y = 0; x = 0; }
+    Taps tp = make_taps(g, b, y, x);
+    const float* f = a.fixp;
+    if constexpr (!SHORT) { if (a.fix_item) f = fixp_of_item(a, g, b, ((long)b * g.H + y) * g.W + x); }   // (the anchor pixel's view)
+    float vc;
+    if constexpr (SHORT) {
+      vc = lerp4(tp, f[(long)tp.o00 * g.ldf + c], f[(long)tp.o01 * g.ldf + c], f[(long)tp.o10 * g.ldf + c], f[(long)tp.o11 * g.ldf + c]);
+    } else {
+      // lerp4 with its products fused as the kernel has always fused them for this word (wx0 * v00 rounded, wx1 * v01 fused onto it; wy1 *
+      // bottom rounded, wy0 * top fused onto it) -- spelt out, because beside the select above the compiler fuses the other product of each
+      // pair: the rows of a launch without a map would move in the last bit
+      const float top = __fmaf_rn(tp.wx1, f[(long)tp.o01 * g.ldf + c], __fmul_rn(tp.wx0, f[(long)tp.o00 * g.ldf + c]));
+      const float bot = __fmaf_rn(tp.wx1, f[(long)tp.o11 * g.ldf + c], __fmul_rn(tp.wx0, f[(long)tp.o10 * g.ldf + c]));
+      vc = __fmaf_rn(tp.wy0, top, __fmul_rn(tp.wy1, bot));
+    }
+    if (SHORT || !g.fix_logits) { o[16 + i] = vc; continue; }
+    float mx = -INFINITY;                 // softmax of the interpolated logits at the anchor pixel (same order as fixed_posterior)
+    for (int cc = 0; cc < C; ++cc)
+      mx = fmaxf(mx, lerp4(tp, f[(long)tp.o00 * g.ldf + cc], f[(long)tp.o01 * g.ldf + cc], f[(long)tp.o10 * g.ldf + cc],
+                           f[(long)tp.o11 * g.ldf + cc]));
+    float sum = 0.f;
+    for (int cc = 0; cc < C; ++cc)
+      sum += expf(lerp4(tp, f[(long)tp.o00 * g.ldf + cc], f[(long)tp.o01 * g.ldf + cc], f[(long)tp.o10 * g.ldf + cc],
+                        f[(long)tp.o11 * g.ldf + cc]) - mx);
+    o[16 + i] = expf(vc - mx) / sum;
+  }
+}
+
 __global__ __launch_bounds__(256) void head_finalize_kernel(HeadArgs a, int nblk) {
   const HeadGeom g = a.g;
   const int Q = g.Q, C = g.C, QC = Q * C;
@@ -594,31 +657,8 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(HeadArgs a, int nblk
     int pidx = (j < Q) ? (int)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull)) : 0;
     ai[tid] = __int_as_float(pidx);
   }
-  for (int i = tid; i < 2 * QC; i += 256) {
-    if (a.mode != 0) { o[16 + i] = 0.f; continue; }
-    int hd = i / QC, r = i % QC, j = r / C, c = r % C;
-    unsigned long long key = a.keys[hd * QMAX + j];
-    long p = (long)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull));
-    int x = (int)(p % g.W);
-    long t = p / g.W;
-    int y = (int)(t % g.H);
-    int b = (int)(t / g.H);
-    if (b >= g.B) { b = 0; y = 0; x = 0; }
-    Taps tp = make_taps(g, b, y, x);
-    const float* f = a.fixp;
-    const float vc = lerp4(tp, f[(long)tp.o00 * g.ldf + c], f[(long)tp.o01 * g.ldf + c], f[(long)tp.o10 * g.ldf + c],
-                           f[(long)tp.o11 * g.ldf + c]);
-    if (!g.fix_logits) { o[16 + i] = vc; continue; }
-    float mx = -INFINITY;                 // softmax of the interpolated logits at the anchor pixel (same order as fixed_posterior)
-    for (int cc = 0; cc < C; ++cc)
-      mx = fmaxf(mx, lerp4(tp, f[(long)tp.o00 * g.ldf + cc], f[(long)tp.o01 * g.ldf + cc], f[(long)tp.o10 * g.ldf + cc],
-                           f[(long)tp.o11 * g.ldf + cc]));
-    float sum = 0.f;
-    for (int cc = 0; cc < C; ++cc)
-      sum += expf(lerp4(tp, f[(long)tp.o00 * g.ldf + cc], f[(long)tp.o01 * g.ldf + cc], f[(long)tp.o10 * g.ldf + cc],
-                        f[(long)tp.o11 * g.ldf + cc]) - mx);
-    o[16 + i] = expf(vc - mx) / sum;
-  }
+  if (!g.fix_logits && !a.fix_item) head_anchor_rows<true>(a, g, o, tid, C, QC);      // (uniform)
+  else head_anchor_rows<false>(a, g, o, tid, C, QC);
 }
 
 // Weighted sum of up to 4*NB terms of one run [lo, hi) of a chunk's pixels, in pixel order, every LDS read requested before the first
@@ -655,8 +695,8 @@ __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL
 // ONE_: as in head_pass1_kernel.  The one-head flavour evaluates the model's head once per pixel and fills, reduces and writes only the
 // head-2 rows of sG / sAcc / g1 (head_yreduce_kernel skips head 1 of a single-head descriptor).
 template <int QM, int QT, int CT, bool... ONE_>
-__global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
-  constexpr bool ONE = (false || ... || ONE_);
+__global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass2_kernel(HeadArgs a) {
+  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time (rows = 1)");
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C, QP = a.QP;
@@ -747,7 +787,9 @@ __global__ __launch_bounds__(256, 2) void head_pass2_kernel(HeadArgs a) {
       } else {
       float fm = 0.f;
       int fa = 0;
-      if (a.mode == 0 && !from_p1) fixed_posterior<CM>(g, C, a.fixp, tp, fm, fa);
+      const float* fixp = a.fixp;
+      if constexpr (VIEWS) { if (live && !from_p1) fixp = fixp_of_item(a, g, b, pix); }
+      if (a.mode == 0 && !from_p1) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
       asm volatile("" ::: "memory");
       int conf = (fm > a.th_high) ? fa : 255;
       if (fm < a.th_low) conf = C;
@@ -987,7 +1029,7 @@ static int head_rows_per_block(const simt_head_desc* d, float sy) {
   return 1;
 }
 
-static int fill_args(const simt_head_desc* d, HeadArgs& a) {
+static int fill_args(const simt_head_desc* d, const uint8_t* fix_item, HeadArgs& a) {
   SIMT_CHECK(d && d->pred2 && d->label && d->part && d->keys && d->hout);
   SIMT_CHECK(d->single || d->pred1 != nullptr);
   SIMT_CHECK(d->mode == 1 || (d->fixp && d->T2 && (d->single || d->T1)));
@@ -1013,7 +1055,9 @@ static int fill_args(const simt_head_desc* d, HeadArgs& a) {
   a.mode = d->mode;
   a.conf_out = d->conf_out;
   a.label_ws = d->label_ws;
+  a.fix_item = fix_item;
   SIMT_CHECK(d->mode == 0 || d->mode == 1);
+  SIMT_CHECK(!fix_item || d->mode == 0);      // the warm-up stage has no frozen operand to move
   return SIMT_OK;
 }
 
@@ -1030,9 +1074,9 @@ extern "C" int simt_head_hout_floats(int Q, int C) {
 extern "C" int simt_head_keys_count(void) { return 2 * QMAX + 2; }
 
 // losses (pass 1 + finalize).  keys must be zeroed by this call: done here with a memset node on the stream.
-extern "C" int simt_head_loss(const simt_head_desc* d, simt_stream_t stream) {
+extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
   HeadArgs a;
-  int rc = fill_args(d, a);
+  int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nblk = simt_head_nblk(d->B, d->H, d->W);
@@ -1043,12 +1087,17 @@ extern "C" int simt_head_loss(const simt_head_desc* d, simt_stream_t stream) {
   if (simt_lds_attr_needed(&lds1_cache, lds1)) {
 #define P1ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass1_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)
     P1ATTR(24, 22, 19); P1ATTR(28, 25, 19); P1ATTR(24, 0, 0); P1ATTR(QMAX, 0, 0); P1ATTR(24, 0, 0, true); P1ATTR(QMAX, 0, 0, true);
+    P1ATTR(24, 22, 19, false, true); P1ATTR(28, 25, 19, false, true); P1ATTR(24, 0, 0, false, true); P1ATTR(QMAX, 0, 0, false, true);
 #undef P1ATTR
   }
 #define P1(...) hipLaunchKernelGGL((head_pass1_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), lds1, st, a)
   const bool one = d->single && d->mode == 1;            // warm-up stage of a one-output model: one head, plain CE
   if (one && d->Q <= 24) P1(24, 0, 0, true);
   else if (one) P1(QMAX, 0, 0, true);
+  else if (fix_item && d->Q == 22 && d->C == 19) P1(24, 22, 19, false, true);
+  else if (fix_item && d->Q == 25 && d->C == 19) P1(28, 25, 19, false, true);
+  else if (fix_item && d->Q <= 24) P1(24, 0, 0, false, true);
+  else if (fix_item) P1(QMAX, 0, 0, false, true);
   else if (d->Q == 22 && d->C == 19) P1(24, 22, 19);     // Cityscapes, K = 3 open classes (BASELINE configs[0..2], [4])
   else if (d->Q == 25 && d->C == 19) P1(28, 25, 19);     // K = 6 (configs[3])
   else if (d->Q <= 24) P1(24, 0, 0);
@@ -1067,9 +1116,9 @@ extern "C" int simt_head_loss(const simt_head_desc* d, simt_stream_t stream) {
 }
 
 // gradients w.r.t. the low-res logits (pass 2 + y reduction); needs hout from simt_head_loss of the same inputs.
-extern "C" int simt_head_grad(const simt_head_desc* d, simt_stream_t stream) {
+extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
   HeadArgs a;
-  int rc = fill_args(d, a);
+  int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
   SIMT_CHECK(d->g1 && d->QP >= d->Q);
   hipStream_t st = (hipStream_t)stream;
@@ -1079,12 +1128,17 @@ extern "C" int simt_head_grad(const simt_head_desc* d, simt_stream_t stream) {
   if (simt_lds_attr_needed(&lds2_cache, lds2)) {
 #define P2ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass2_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)
     P2ATTR(24, 22, 19); P2ATTR(28, 25, 19); P2ATTR(24, 0, 0); P2ATTR(QMAX, 0, 0); P2ATTR(24, 0, 0, true); P2ATTR(QMAX, 0, 0, true);
+    P2ATTR(24, 22, 19, false, true); P2ATTR(28, 25, 19, false, true); P2ATTR(24, 0, 0, false, true); P2ATTR(QMAX, 0, 0, false, true);
 #undef P2ATTR
   }
 #define P2(...) hipLaunchKernelGGL((head_pass2_kernel<__VA_ARGS__>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
   const bool one = d->single && d->mode == 1;            // (fill_args: a.rows = 1)
   if (one && d->Q <= 24) P2(24, 0, 0, true);
   else if (one) P2(QMAX, 0, 0, true);
+  else if (fix_item && d->Q == 22 && d->C == 19) P2(24, 22, 19, false, true);
+  else if (fix_item && d->Q == 25 && d->C == 19) P2(28, 25, 19, false, true);
+  else if (fix_item && d->Q <= 24) P2(24, 0, 0, false, true);
+  else if (fix_item) P2(QMAX, 0, 0, false, true);
   else if (d->Q == 22 && d->C == 19) P2(24, 22, 19);
   else if (d->Q == 25 && d->C == 19) P2(28, 25, 19);
   else if (d->Q <= 24) P2(24, 0, 0);
@@ -1102,3 +1156,7 @@ extern "C" int simt_head_grad(const simt_head_desc* d, simt_stream_t stream) {
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }
+
+// the one-view forms: the NULL case of the same code
+extern "C" int simt_head_loss(const simt_head_desc* d, simt_stream_t stream) { return simt_head_loss_views(d, nullptr, stream); }
+extern "C" int simt_head_grad(const simt_head_desc* d, simt_stream_t stream) { return simt_head_grad_views(d, nullptr, stream); }

@@ -184,10 +184,11 @@ class InputPrep:
             d.mean[0], d.mean[1], d.mean[2] = self.mean
             L.call("simt_scale_crop", C.byref(d), stream)
 
-    def class_mix_batch(self, x, lab, draws, x_out, lab_out, stream):
+    def class_mix_batch(self, x, lab, draws, x_out, lab_out, stream, item_out=None):
         """ClassMix of a finished batch: x [B,3,h,w] f32 / lab [B,h,w] i64 -> x_out / lab_out (other buffers: item i reads item
         (i + 1) % B while another workgroup writes it).  draws = (apply [B] bool, rank [B, n_classes] permutations)
-        (class_mix.draw_batch).  Two launches on `stream`: simt_label_presence, then simt_class_mix."""
+        (class_mix.draw_batch).  Two launches on `stream`: simt_label_presence, then simt_class_mix -- or, with item_out ([B,h,w] u8),
+        simt_class_mix_items, which also writes the item each pixel came from (i or its partner)."""
         assert self.cm is not None, "built without class_mix"
         n_classes = self.cm[0]
         for t, o in ((x, x_out), (lab, lab_out)):
@@ -204,7 +205,11 @@ class InputPrep:
             d.partner[i], d.apply[i] = (i + 1) % self.B, 1 if apply[i] else 0
             C.memmove(d.rank[i], rank[i].ctypes.data, n_classes)
         L.call("simt_label_presence", lab.data_ptr(), self.B, self.h * self.w, n_classes, self.part.data_ptr(), stream)
-        L.call("simt_class_mix", C.byref(d), stream)
+        if item_out is None:
+            L.call("simt_class_mix", C.byref(d), stream)
+        else:
+            assert item_out.dtype == torch.uint8 and tuple(item_out.shape) == (self.B, self.h, self.w) and item_out.is_contiguous()
+            L.call("simt_class_mix_items", C.byref(d), item_out.data_ptr(), stream)
 
     def photometric_batch(self, x, draws, x_out, stream):
         """Colour jitter + Gaussian blur of a finished batch: x [B,3,h,w] f32 -> x_out (another buffer: a blurred pixel reads its
@@ -237,7 +242,9 @@ class DevicePrefetcher:
 
     source: iterator of (rgb u8 [B,Hs,Ws,3], label u8 [B,Hs,Ws] or None, meta) host arrays / tensors (numpy or torch; pinned
     tensors are uploaded in place, anything else is staged through this object's pinned buffers).
-    Each __next__ returns (image f32 [B,3,h,w], label i64 [B,h,w] | None, meta) resident in HBM.
+    Each __next__ returns (image f32 [B,3,h,w], label i64 [B,h,w] | None, meta) resident in HBM -- with teacher_view (the weak-view teacher:
+    it needs mix_fn or photo_fn) two more: the slot's batch BEFORE the mix and the photometric launches (the loader's batch without
+    either, bit for bit) and the item map of the mix ([B,h,w] u8: the item each pixel was taken from; None without mix_fn); same life time.
 
     Slot life time: the consumer may HOLD `hold` batches at once (gradient accumulation pulls `iter_size` micro-batches before the step
     that reads them is enqueued: tools/trainV2_simt.py `mb = [next(data) for _ in range(iter_size)]`).  The tensors returned by call k
@@ -245,7 +252,8 @@ class DevicePrefetcher:
     that stream up to that point -- the step that consumed batch k included -- precedes the refill), and the copy stream waits for
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
-    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None, photo_fn=None):
+    def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None, photo_fn=None,
+                 teacher_view=False):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
         assert (draw_fn is not None) == (prep.sc is not None)
@@ -253,6 +261,8 @@ class DevicePrefetcher:
         assert (mix_fn is not None) == (prep.cm is not None)
         self.photo_fn = photo_fn        # photometric mode (prep.ph): B -> draws; the finished (mixed) batch is jittered and blurred into xp
         assert (photo_fn is not None) == (prep.ph is not None)
+        self.teacher_view = bool(teacher_view)
+        assert not self.teacher_view or mix_fn is not None or photo_fn is not None, "teacher_view: without a mix or a photometric step the views are one"
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -270,6 +280,8 @@ class DevicePrefetcher:
                 s["lab"] = torch.empty(B, prep.h, prep.w, dtype=torch.int64, device=dev)
             if mix_fn is not None:                     # what __next__ hands out in class-mix mode: same life time as x / lab
                 s["xm"], s["labm"] = torch.empty_like(s["x"]), torch.empty_like(s["lab"])
+                if self.teacher_view:
+                    s["item"] = torch.empty(B, prep.h, prep.w, dtype=torch.uint8, device=dev)
             if photo_fn is not None:                   # what __next__ hands out in photometric mode: same life time as x
                 s["xp"] = torch.empty_like(s["x"])
             if cache is not None:                      # transient slots for the items the cache has no room for
@@ -336,7 +348,7 @@ class DevicePrefetcher:
             return
         if not has_lab:
             raise ValueError("--class-mix: a batch without labels cannot be mixed")
-        self.prep.class_mix_batch(s["x"], s["lab"], self.mix_fn(self.prep.B), s["xm"], s["labm"], cs.cuda_stream)
+        self.prep.class_mix_batch(s["x"], s["lab"], self.mix_fn(self.prep.B), s["xm"], s["labm"], cs.cuda_stream, item_out=s.get("item"))
 
     def _photo(self, s, cs):
         """Photometric mode: the slot's finished batch -- xm when it was mixed, else x -> xp, on the copy stream, behind `_mix`."""
@@ -412,6 +424,8 @@ class DevicePrefetcher:
             out = (s["x"], s["lab"] if s["has_lab"] else None, s["meta"])
         if self.photo_fn is not None:      # the label that would have been handed out anyway
             out = (s["xp"], out[1], out[2])
+        if self.teacher_view:              # the weak view: what this slot would have handed out without the mix and the photometric step
+            out = out + (s["x"], s.get("item"))
         self.filled -= 1
         self.calls += 1
         self.head = (i + 1) % len(self.slots)
@@ -484,7 +498,11 @@ class GpuLoader:
     jitter and Gaussian blur (simt_amd/data/photometric.py): the finished batch -- after the mix, when there is one -- is jittered and
     blurred on the copy stream into a buffer of its own; labels are not touched (a dataset without labels works).  Its draws come from
     photometric.generator(seed, rank): the batch underneath is the batch of the loader without the flags, bit for bit, and start_batch
-    skips these draws too."""
+    skips these draws too.
+
+    dataset.teacher_view = True (--weak-teacher) needs one of the two above and hands out both views: (strong image, labels, sizes, names,
+    weak image, item map | None) -- the weak image is the batch of the loader without class-mix and photometric, bit for bit, the item
+    map ([B,h,w] u8, None without class-mix) names the item each pixel of the strong view was taken from.  Not one draw changes."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -508,6 +526,10 @@ class GpuLoader:
             if self.photometric is None:
                 raise ValueError("dataset.photometric is (None, None): pass None for no photometric augmentation")
             self._photo_rng = ph.skip_draws(ph.generator(seed, rank), batch_size, int(start_batch))
+        self.teacher_view = bool(getattr(dataset, "teacher_view", False))
+        if self.teacher_view and self.class_mix is None and self.photometric is None:
+            raise ValueError("dataset.teacher_view needs dataset.class_mix or dataset.photometric (--weak-teacher needs --class-mix, "
+                             "--colour-jitter or --gaussian-blur): without them the two views are the same batch")
         self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
         if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
@@ -634,5 +656,7 @@ class GpuLoader:
         if self.photometric is not None:
             photo_fn = lambda n: ph.draw_batch(self._photo_rng, n, self.photometric)
         pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn,
-                              photo_fn=photo_fn)
+                              photo_fn=photo_fn, teacher_view=self.teacher_view)
+        if self.teacher_view:
+            return ((x, lab, meta[0], meta[1], xw, item) for (x, lab, meta, xw, item) in pf)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

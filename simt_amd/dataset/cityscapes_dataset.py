@@ -76,7 +76,7 @@ class cityscapesPseudo(_Base):
     """Image + pseudo-label PNG (the SimT stage's training set): dataset/cityscapes_dataset.py:66-120."""
 
     def __init__(self, root, list_path, max_iters=None, crop_size=(321, 321), mean=(128, 128, 128), scale=True, mirror=False,
-                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None):
+                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None, teacher_view=False):
         super().__init__(root, list_path, max_iters, crop_size, mean, scale, mirror, ignore_label)
         # decimal scale choices or None: GpuLoader's random scale + crop (simt_amd/data/scale_crop.py).  `scale` stays what the reference
         # makes of it: stored and never read
@@ -85,6 +85,8 @@ class cityscapesPseudo(_Base):
         self.class_mix = None if class_mix is None else (int(class_mix[0]), float(class_mix[1]))
         # (S | None, P | None) or None: GpuLoader's colour jitter and Gaussian blur of every batch (simt_amd/data/photometric.py)
         self.photometric = None if photometric is None else tuple(None if v is None else float(v) for v in photometric)
+        # GpuLoader also hands out the batch before class_mix / photometric and the mix's item map (the weak-view teacher; needs one of the two)
+        self.teacher_view = bool(teacher_view)
         self.img_ids = self._repeat([i_id.strip().split() for i_id in open(list_path)], max_iters)
         for image_path, label_path in self.img_ids:
             self.files.append({"img": osp.join(self.root, image_path), "label": osp.join(self.root, label_path),

@@ -66,10 +66,36 @@ def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer
     return g0, g1
 
 
+def check_views(tr, teacher_image, fix_item, n):
+    """The weak-view arguments of a SimT trainer's step() as two lists of n = iter_size entries (None where absent); ValueError when they do
+    not fit the trainer's `teacher_view`."""
+    if not tr.teacher_view:
+        if teacher_image is not None or fix_item is not None:
+            raise ValueError("step(): teacher_image / fix_item need a trainer built with teacher_view=True")
+        return [None] * n, [None] * n
+    if teacher_image is None:
+        raise ValueError("step(): this trainer was built with teacher_view=True and needs teacher_image (the frozen model's view)")
+    teachers = list(teacher_image) if isinstance(teacher_image, (list, tuple)) else [teacher_image]
+    maps = list(fix_item) if isinstance(fix_item, (list, tuple)) else [fix_item] * (n if fix_item is None else 1)
+    if len(teachers) != n or len(maps) != n:
+        raise ValueError(f"step() needs {n} teacher_image(s) and fix_item(s) (hp.iter_size), got {len(teachers)} and {len(maps)}")
+    for t in teachers:
+        if tuple(t.shape) != (tr.B, 3, tr.H, tr.W):
+            raise ValueError(f"teacher_image of shape {tuple(t.shape)}, expected {(tr.B, 3, tr.H, tr.W)}")
+    for m in maps:
+        if m is not None and (tuple(m.shape) != (tr.B, tr.H, tr.W) or m.dtype != torch.uint8):
+            raise ValueError(f"fix_item of shape {tuple(m.shape)} and dtype {m.dtype}, expected {(tr.B, tr.H, tr.W)} uint8")
+    return teachers, maps
+
+
 class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
     def __init__(self, state, fixed_state, ntm1, ntm2, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None, ema_teacher_every=None):
+                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None, ema_teacher_every=None, teacher_view=False):
+        """teacher_view=True (the weak-view teacher): the frozen model reads an image of its own -- `step(..., teacher_image=...)`,
+        the weak view -- through its own one-set stem launch, and the head reads each pixel's frozen operand from the item `fix_item` names
+        (simt_head_loss_views / simt_head_grad_views).  False: one image for both networks, as the reference feeds them."""
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
+        self.teacher_view = bool(teacher_view)
         dev = self.dev = torch.device(device)
         self.pg = process_group
         Cn, K = hp.num_classes, hp.open_classes
@@ -84,11 +110,15 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                               grads_from_layer=3 if getattr(hp, "skip_unapplied_grads", False) else 0,
                               data_parallel=process_group is not None, **kw)
         # the frozen model sees the same image: it reuses the trainable plan's stem im2col matrix (one im2col per micro-batch)
+        # (teacher_view: it sees another one -- no stem_from: its own x_in and its own stem launch, the first of its forward, on the side stream)
         self.fixed = TrunkPlan(self.fixed_params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=False,
-                               stem_from=self.plan, data_parallel=process_group is not None, **kw)      # (same CU budget = same tile lists as the trainable plan)
+                               stem_from=None if self.teacher_view else self.plan,
+                               data_parallel=process_group is not None, **kw)      # (same CU budget = same tile lists as the trainable plan)
         # item 0 of the trainable forward feeds BOTH nets: the direct stem launch with the frozen net as its second weight set (bf16), or the im2col
+        # (teacher_view: the trainable net alone, one weight set)
         assert self.plan.fwd_list.items[0].tag in ("simt_stem7_fwd", "simt_im2col_stem")
-        assert self.plan.fwd_list.items[0].tag == "simt_im2col_stem" or self.plan.stem_desc.nsets == 2
+        assert self.plan.fwd_list.items[0].tag == "simt_im2col_stem" or self.plan.stem_desc.nsets == (1 if self.teacher_view else 2)
+        assert not self.teacher_view or self.fixed.fwd_list.items[0].tag == self.plan.fwd_list.items[0].tag
         self._fwd_rest = LaunchList()
         self._fwd_rest.items = self.plan.fwd_list.items[1:]
         h, w = self.plan.heads[1].h, self.plan.heads[1].w
@@ -142,6 +172,9 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         self._label_ws = torch.full((B, H, W), 255, device=dev, dtype=torch.uint8)          # checked noisy labels, loss pass -> gradient pass
         hd.label_ws = self._label_ws.data_ptr()
         self.head_desc = hd
+        # teacher_view: the item of the frozen map each pixel reads (simt_class_mix_items' map), resident; a step without a map reads no map
+        self.fix_item = torch.zeros(B, H, W, device=dev, dtype=torch.uint8) if self.teacher_view else None
+        self._fix_item_ptr = None
         # ---- NTM descriptors
         ni = L.NtmInnerDesc()
         for k in range(2):
@@ -241,10 +274,16 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         self.sgd_desc = d
 
     # ------------------------------------------------------------------ one iteration
-    def _micro_batch(self, image, label, st):
+    def _micro_batch(self, image, label, st, teacher_image=None, fix_item=None):
         """Steps 2-5 of the iteration for one micro-batch: both forwards, fused head, NTM terms, backward."""
         self.plan.x_in.copy_(image, non_blocking=True)
         self.label.copy_(label, non_blocking=True)
+        if self.teacher_view:      # the weak view and its map: main stream, in front of ev_in (the frozen forward waits for it)
+            self.fixed.x_in.copy_(teacher_image, non_blocking=True)
+            self._fix_item_ptr = None
+            if fix_item is not None:
+                self.fix_item.copy_(fix_item, non_blocking=True)
+                self._fix_item_ptr = self.fix_item.data_ptr()
         # the stem launch (first launch of the trainable forward: direct conv of both nets, or the im2col they share) feeds BOTH nets: run it before forking
         head = self.plan.fwd_list.items[0]
         rc = head.fn(*head.args, st)
@@ -275,7 +314,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         if self._ev_post is not None:
             main.wait_event(self._ev_post)     # an earlier micro-batch's regularisers still read the head's outputs
         with trace.range("head"):
-            L.call("simt_head_loss", C.byref(self.head_desc), st)
+            L.call("simt_head_loss_views", C.byref(self.head_desc), self._fix_item_ptr, st)
             ev_loss = torch.cuda.Event()
             ev_loss.record(main)
             with torch.cuda.stream(side):
@@ -283,13 +322,16 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                 L.call("simt_ntm_post", C.byref(self.post_desc), side.cuda_stream)
                 self._ev_post = torch.cuda.Event()
                 self._ev_post.record(side)
-            L.call("simt_head_grad", C.byref(self.head_desc), st)
+            L.call("simt_head_grad_views", C.byref(self.head_desc), self._fix_item_ptr, st)
 
-    def step(self, image, label, it=None):
+    def step(self, image, label, it=None, teacher_image=None, fix_item=None):
         """image [B,3,H,W] fp32 (device or host), label [B,H,W] int64 -- or, with hp.iter_size > 1 (gradient accumulation,
         trainV2_simt.py:341-432), sequences of iter_size micro-batches.  Returns the device tensor `lout`
-        (total, loss_p1, loss_p2, loss_y1, loss_y2, Place, Convex, Volume, Anchor, vol_ok, ...) of the last micro-batch."""
+        (total, loss_p1, loss_p2, loss_y1, loss_y2, Place, Convex, Volume, Anchor, vol_ok, ...) of the last micro-batch.
+        teacher_view=True: teacher_image (required) is the frozen model's image, fix_item ([B,H,W] uint8 or None) the item of the frozen
+        map each pixel reads; sequences like image when hp.iter_size > 1."""
         hp = self.hp
+        teachers, maps = check_views(self, teacher_image, fix_item, hp.iter_size)
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         lr_T = lr_poly(hp.lr_T, it, hp.num_steps, hp.power)
@@ -313,7 +355,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         flat = self.plan.flat_grad
         for mi, (img, lab) in enumerate(zip(images, labels)):
             last = mi == hp.iter_size - 1
-            self._micro_batch(img, lab, st)
+            self._micro_batch(img, lab, st, teachers[mi], maps[mi])
             # 5. trunk backward (+ 6. data-parallel mean of the gradients, bucket by bucket, on a side stream)
             if self._early_sgd:            # (with a reducer: the exchange completes on the side stream too, ahead of its SGD)
                 with trace.range("backward (+ exchange + early optimiser step)"):

@@ -28,18 +28,20 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .step import lr_poly
+from .step import check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
 
 class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
     def __init__(self, model, state, fixed_state, ntm, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 process_group=None, arch=None, ema_decay=None, ema_teacher_every=None):
+                 process_group=None, arch=None, ema_decay=None, ema_teacher_every=None, teacher_view=False):
         """model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
         DeeplabVGG(nc + openc)); fixed_state: the frozen model's (nc outputs).  arch: plan keyword arguments (reduced depths / widths
-        for tests): v3 -> layers, width, assp_ch; vgg -> vgg_layers."""
+        for tests): v3 -> layers, width, assp_ch; vgg -> vgg_layers.  teacher_view: as for SimTTrainer (the frozen plan has an input of its
+        own here already: the weak view is copied into it instead of the trainable plan's image)."""
         assert model in ("v3", "vgg")
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
+        self.teacher_view = bool(teacher_view)
         dev = self.dev = torch.device(device)
         self.pg = process_group
         Cn, K = hp.num_classes, hp.open_classes
@@ -113,6 +115,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         self._label_ws = torch.full((B, H, W), 255, device=dev, dtype=torch.uint8)          # checked noisy labels, loss pass -> gradient pass
         hd.label_ws = self._label_ws.data_ptr()
         self.head_desc = hd
+        self.fix_item = torch.zeros(B, H, W, device=dev, dtype=torch.uint8) if self.teacher_view else None      # (step.SimTTrainer)
         ni = L.NtmInnerDesc()
         ni.ntm[1], ni.w[1], ni.ntm_grad[1] = self.ntm.data_ptr(), self.wraw.data_ptr(), self.ntm_grad.data_ptr()
         ni.w_m[1], ni.w_v[1], ni.T_out[1] = self.w_m.data_ptr(), self.w_v.data_ptr(), self.T.data_ptr()
@@ -177,9 +180,10 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         self.sgd_desc = d
 
     # ------------------------------------------------------------------ one iteration
-    def step(self, image, label, it=None):
+    def step(self, image, label, it=None, teacher_image=None, fix_item=None):
         hp = self.hp
         assert hp.iter_size == 1, "gradient accumulation is implemented for the DeepLab-v2 trainer only"
+        (teacher_image,), (fix_item,) = check_views(self, teacher_image, fix_item, 1)
         it = self.it_done if it is None else it
         lr, lr_T = lr_poly(hp.lr, it, hp.num_steps, hp.power), lr_poly(hp.lr_T, it, hp.num_steps, hp.power)
         st = ops.stream_ptr()
@@ -188,6 +192,12 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         ev0.record(main)
         self.plan.x_in.copy_(image, non_blocking=True)
         self.label.copy_(label, non_blocking=True)
+        item_ptr = None
+        if self.teacher_view:      # the weak view and its map: main stream, in front of ev_in
+            self.fixed.x_in.copy_(teacher_image, non_blocking=True)
+            if fix_item is not None:
+                self.fix_item.copy_(fix_item, non_blocking=True)
+                item_ptr = self.fix_item.data_ptr()
         ev_in = torch.cuda.Event()
         ev_in.record(main)
         with torch.cuda.stream(side):
@@ -198,7 +208,8 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
             ni.step0, ni.lr = self.inner_steps * self.it_done, lr_T
             L.call("simt_ntm_inner_loop", C.byref(ni), side.cuda_stream)
             side.wait_event(ev_in)
-            self.fixed.x_in.copy_(self.plan.x_in, non_blocking=True)
+            if not self.teacher_view:
+                self.fixed.x_in.copy_(self.plan.x_in, non_blocking=True)
             self._fix_fwd.run()
             if not self.head_desc.fix_logits:
                 ops.softmax_rows(self.fix_logits_t, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
@@ -206,7 +217,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
             ev_fix.record(side)
         self._fwd.run()
         main.wait_event(ev_fix)
-        L.call("simt_head_loss", C.byref(self.head_desc), st)
+        L.call("simt_head_loss_views", C.byref(self.head_desc), item_ptr, st)
         ev_loss = torch.cuda.Event()
         ev_loss.record(main)
         with torch.cuda.stream(side):          # the regularisers only feed Adam and the loss read-out: beside the head's gradient pass
@@ -214,7 +225,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
             L.call("simt_ntm_post", C.byref(self.post_desc), side.cuda_stream)
             ev_post = torch.cuda.Event()
             ev_post.record(side)
-        L.call("simt_head_grad", C.byref(self.head_desc), st)
+        L.call("simt_head_grad_views", C.byref(self.head_desc), item_ptr, st)
         if self.reducer is not None:
             self.reducer.start()
             self._bwd.run()

@@ -40,6 +40,12 @@ five launches on the stream of the EMA update, no synchronisation.  Until the fi
 from then on the confidence labels come from a moving teacher.  --restore-from still names the model the run STARTS beside (its SHA-256 is
 what --train-state checks); the state file carries the teacher as it is, N and the refresh count, and refuses a command line that drops the
 flag, adds it or changes N.  All three --model values.  Default: off.
+--weak-teacher: the frozen model labels the WEAK view.  Needs --class-mix, --colour-jitter or --gaussian-blur (and not
+--synthetic, where they do nothing): the loader then also hands out the batch as it was before the mix and the photometric step, the frozen
+model's forward runs on that one, and the fused head reads every pixel's frozen posterior from the item the pixel was pasted from (the mix's
+item map), so the teacher's predictions are mixed with the same mask as the pixels and the labels.  The student still trains on the strong
+view.  Not one loader draw changes; without the flag nothing does.  --train-state refuses a resume with the flag added or dropped.  All
+three --model values.  Default: off.
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -121,9 +127,15 @@ def get_arguments(argv=None):
     add_train_state_args(p)
     add_ema_args(p)
     add_ema_teacher_args(p)
+    p.add_argument("--weak-teacher", action="store_true",
+                   help="the frozen model sees the batch before --class-mix / --colour-jitter / --gaussian-blur (needs one of them) and its "
+                        "predictions are mixed with the pixels' mask; the student trains on the augmented batch.  Default: off")
     args = p.parse_args(argv)
     if args.ema_teacher is not None and args.ema is None:
         p.error("--ema-teacher needs --ema: the frozen model follows the weight EMA")
+    if args.weak_teacher and (args.synthetic or (args.class_mix is None and args.colour_jitter is None and args.gaussian_blur is None)):
+        p.error("--weak-teacher needs --class-mix, --colour-jitter or --gaussian-blur on real data (with --synthetic they do nothing): "
+                "without an augmentation the two views are the same batch")
     return args
 
 
@@ -403,7 +415,7 @@ class EmaSnapshots:
             self.keeper.rolling(self.tr.ema_state_dict(), i_iter)
 
 
-RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False}      # run_identity keys that are absent when their flag is off: what absence means
+RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -423,6 +435,8 @@ def run_identity(args, class_dist):
     photo = None if args.synthetic else photometric_setting(args)
     if photo is not None:
         ident["photometric"] = list(photo)          # [colour-jitter S | None, gaussian-blur P | None]
+    if getattr(args, "weak_teacher", False):
+        ident["weak_teacher"] = True
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -508,9 +522,17 @@ def teacher_line(args):
               f"{'update' if args.ema_teacher == 1 else str(args.ema_teacher) + ' updates'} (N = {args.ema_teacher})")
 
 
+def weak_teacher_line(args):
+    if getattr(args, "weak_teacher", False):
+        on = [f for f, v in (("--class-mix", args.class_mix), ("--colour-jitter", args.colour_jitter), ("--gaussian-blur", args.gaussian_blur))
+              if v is not None]
+        print(f"weak-view teacher: the frozen model sees the batch before {', '.join(on)}; its predictions follow the "
+              f"{'mix mask' if args.class_mix is not None else 'pixels (no mix: no item map)'}")
+
+
 def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
-    resumed run: iterations done x iter_size)."""
+    resumed run: iterations done x iter_size); with --weak-teacher of (image, label, weak image, item map [B,H,W] u8 | None)."""
     choices = scale_crop_choices(args)
     mix = class_mix_setting(args)
     photo = photometric_setting(args)
@@ -533,7 +555,7 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
-                          scale_crop=choices, class_mix=mix, photometric=photo)
+                          scale_crop=choices, class_mix=mix, photometric=photo, teacher_view=bool(getattr(args, "weak_teacher", False)))
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
@@ -553,6 +575,8 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=args.random_seed, rank=rank, world=world,
                        hold=max(1, getattr(args, "iter_size", 1)),     # the loop keeps iter_size micro-batches alive per step
                        cache=cache, on_epoch=on_epoch, start_batch=start_batch)
+    if ds.teacher_view:
+        return ((img, lab, weak, item) for (img, lab, _sizes, _names, weak, item) in loader)
     return ((img, lab) for (img, lab, _sizes, _names) in loader)
 
 
@@ -599,9 +623,10 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
                      args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
-                     ema_teacher_every=args.ema_teacher)
+                     ema_teacher_every=args.ema_teacher, teacher_view=args.weak_teacher)
     if rank == 0:
         teacher_line(args)
+        weak_teacher_line(args)
         print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -615,8 +640,12 @@ def main(argv=None):
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]           # gradient accumulation: iter_size micro-batches per step
-        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
-        tr.step(img, lab, i_iter)
+        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0][:2]
+        if args.weak_teacher:
+            weak, item = ([m[2] for m in mb], [m[3] for m in mb]) if args.iter_size > 1 else mb[0][2:]
+            tr.step(img, lab, i_iter, teacher_image=weak, fix_item=item)
+        else:
+            tr.step(img, lab, i_iter)
         if i_iter % args.print_every == 0:
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
@@ -693,9 +722,11 @@ def main_single(args):
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
     tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
-                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema, ema_teacher_every=args.ema_teacher)
+                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema, ema_teacher_every=args.ema_teacher,
+                           teacher_view=args.weak_teacher)
     if rank == 0:
         teacher_line(args)
+        weak_teacher_line(args)
         print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -708,8 +739,12 @@ def main_single(args):
     data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
-        img, lab = next(data)
-        tr.step(img, lab, i_iter)
+        if args.weak_teacher:
+            img, lab, weak, item = next(data)
+            tr.step(img, lab, i_iter, teacher_image=weak, fix_item=item)
+        else:
+            img, lab = next(data)
+            tr.step(img, lab, i_iter)
         if i_iter % args.print_every == 0:
             l = tr.losses()
             if rank == 0:

@@ -24,6 +24,9 @@ FORMAT_VERSION = 1
 TRAJECTORY_FIELDS = ("lr", "lr_T", "momentum", "weight_decay", "power", "num_steps", "lambda_seg", "lambda_place", "lambda_convex",
                      "lambda_volume", "lambda_anchor", "th_high", "th_low", "num_classes", "open_classes", "iter_size")
 CHECKED_FIELDS = TRAJECTORY_FIELDS + ("B", "H", "W", "dtype", "trainer", "model", "arch", "format_version")
+# Checked too, but ABSENT = False: keywords added after format_version 1 that a trainer writes into `hyper` only when they are on, so that the
+# states of runs without them stay what they were (teacher_view: the weak-view teacher of the SimT trainers)
+SWITCH_FIELDS = ("teacher_view",)
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -54,6 +57,11 @@ def hyper_mismatches(saved, current, fields=CHECKED_FIELDS):
     """Names of the checked fields in which two `hyper` dicts differ, in the order of `fields`.  Fields outside `fields` are ignored."""
     missing = object()
     return [f for f in fields if _norm(saved.get(f, missing)) != _norm(current.get(f, missing))]
+
+
+def switch_mismatches(saved, current, fields=SWITCH_FIELDS):
+    """Names of the switches (absent = off) in which two `hyper` dicts differ."""
+    return [f for f in fields if bool(saved.get(f, False)) != bool(current.get(f, False))]
 
 
 def save_atomic(obj, path):
@@ -112,6 +120,8 @@ class TrainStateMixin:
         hy = {k: v for k, v in self.hp.__dict__.items() if isinstance(v, (bool, int, float, str))}
         hy.update(B=self.B, H=self.H, W=self.W, dtype={torch.bfloat16: "bf16", torch.float32: "f32"}[self.dtype],
                   trainer=type(self).__name__, model=getattr(self, "model", "v2"), arch=_arch(self), format_version=FORMAT_VERSION)
+        if getattr(self, "teacher_view", False):      # (absent = False: a state from before the keyword loads into a trainer without it)
+            hy["teacher_view"] = True
         return hy
 
     def _nbt_steps(self, key):
@@ -160,7 +170,7 @@ class TrainStateMixin:
         naming what differs, otherwise; nothing has been changed then.  Every packed operand is rebuilt from the loaded masters
         (`plan.repack()`).  `state_dict()` afterwards reports the `num_batches_tracked` an uninterrupted run reports (the steps taken are
         counted once).  Data parallel: every rank loads the same dict (see training_state)."""
-        bad = hyper_mismatches(ts["hyper"], self._hyper_state())
+        bad = hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state())
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
