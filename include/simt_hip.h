@@ -732,6 +732,34 @@ typedef struct {
 } simt_bn_fold_desc;
 int simt_bn_fold_multi(const simt_bn_fold_desc* d, simt_stream_t stream);
 
+/* ---- MIC patch masking of a finished batch (simt_amd/data/patch_mask.py; csrc/patch_mask.hip) ------------------------------------
+ * Masked Image Consistency (Hoyer et al., CVPR'23): square patches of the student's view are blanked.  x [B][3][h][w] fp32 is a finished
+ * batch, every plane colour - mean, so a blanked pixel is +0.0f: the mean colour.  One launch.
+ * CONTRACT (the kernel is held to it bit for bit; tests/_patch_mask_ref.py is its numpy restatement).  gh = ceil(h / patch),
+ * gw = ceil(w / patch).  For every item i < B, plane p < 3 and pixel (y, x):
+ *     m = (rows[i][y / patch] >> (x / patch)) & 1;     x_out[i][p][y][x] = m ? +0.0f : x[i][p][y][x]
+ *   - a blanked word is the bit pattern 0x00000000; a kept word is a 32-bit word copy: NaN payloads, -0.0, infinities and denormals survive;
+ *   - the three planes of an item share its mask; edge patches are partial when patch does not divide h or w;
+ *   - bits at column >= gw of a row word and the words of rows >= gh are ignored;
+ *   - out of place (x_out != x): x is never written, every word of x_out[0, B) is written, the blanked patches of x are not read;
+ *   - in place (x_out == x): only the blanked words are stored, kept words are neither read nor written -- a sparse zero fill that moves the
+ *     blanked share R of the batch's bytes (out of place: 2 - R of them).
+ * Refused with SIMT_ERR_INVALID and no launch: a NULL d, x or x_out; B outside [1, SIMT_PATCH_MASK_MAX]; h < 1, w < 1 or patch < 1; gh or gw
+ * above SIMT_PATCH_MASK_GRID; h * w >= 2^31; a base that is not 16-byte aligned; x_out overlapping x without being equal to it.
+ * Items are independent: the caller splits a larger batch.  The descriptor is read on the host during the call and travels as kernel
+ * arguments, like simt_class_mix_desc: no table is uploaded and nothing synchronises.  A wave owns one pixel row of an item (all three
+ * planes) and takes the row's mask word from the kernel arguments as a wave-uniform value.  16-byte loads and stores when w % 4 == 0 and
+ * patch % 4 == 0 (every row then starts on a 16-byte boundary and no quad straddles a patch), dwords otherwise.  No LDS, no atomics. */
+#define SIMT_PATCH_MASK_MAX  16     /* items per launch */
+#define SIMT_PATCH_MASK_GRID 32     /* patch rows and patch columns per item, at most */
+typedef struct {
+  const float* x;       /* [B][3][h][w] fp32 */
+  float* x_out;         /* [B][3][h][w] fp32; x_out == x is allowed (in place) */
+  int32_t B, h, w, patch;
+  uint32_t rows[SIMT_PATCH_MASK_MAX][SIMT_PATCH_MASK_GRID];   /* bit c of rows[i][r]: patch (r, c) of item i is blanked */
+} simt_patch_mask_desc;
+int simt_patch_mask(const simt_patch_mask_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,16 @@ class PhotometricDesc(C.Structure):
                 ("jit", C.c_uint8 * PHOTOMETRIC_MAX), ("blur", C.c_uint8 * PHOTOMETRIC_MAX)]
 
 
+PATCH_MASK_MAX = 16      # include/simt_hip.h SIMT_PATCH_MASK_MAX
+PATCH_MASK_GRID = 32     # SIMT_PATCH_MASK_GRID
+
+
+class PatchMaskDesc(C.Structure):
+    """simt_patch_mask_desc (include/simt_hip.h): one finished batch -> the batch with the patches its row words name blanked."""
+    _fields_ = [("x", c_p), ("x_out", c_p), ("B", i32), ("h", i32), ("w", i32), ("patch", i32),
+                ("rows", (C.c_uint32 * PATCH_MASK_GRID) * PATCH_MASK_MAX)]
+
+
 class EmaDesc(C.Structure):
     """simt_ema_desc (include/simt_hip.h): one weight-EMA update over a segment table, e <- e + omd * (w - e)."""
     _fields_ = [("segs", c_p), ("chunks", c_p), ("nchunks", i32), ("chunk", i32), ("omd", f32), ("skip_if", c_p)]
@@ -290,6 +300,7 @@ SIGNATURES = {
     "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),
     "simt_bn_fold_multi": (_I, [C.POINTER(BnFoldDesc), c_p]),
+    "simt_patch_mask": (_I, [C.POINTER(PatchMaskDesc), c_p]),
 }
 
 _lib = None

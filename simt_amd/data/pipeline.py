@@ -18,6 +18,7 @@ import torch
 from .. import _lib as L
 from . import resample as rs
 from . import class_mix as cm
+from . import patch_mask as pm
 from . import photometric as ph
 from . import scale_crop as sc
 
@@ -32,7 +33,8 @@ class InputPrep:
     """Device transform of a batch of decoded frames of ONE source geometry: [B, Hs, Ws, 3] u8 RGB (+ [B, Hs, Ws] u8 labels) ->
     [B, 3, h, w] fp32 (BGR - mean) (+ [B, h, w] int64).  crop = (w, h) like the reference's `crop_size` / --input-size-target."""
 
-    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None, class_mix=None, photometric=None):
+    def __init__(self, B, src_hw, crop_wh, device, mean=IMG_MEAN, with_label=True, scale_crop=None, class_mix=None, photometric=None,
+                 patch_mask=None):
         self.B, (self.Hs, self.Ws), (self.w, self.h) = B, src_hw, crop_wh
         self.dev = torch.device(device)
         self.mean = tuple(_f32(m) for m in mean)
@@ -48,6 +50,9 @@ class InputPrep:
         if photometric is not None:         # (S | None, P | None): `photometric_batch` jitters and blurs a finished batch (simt_amd/data/photometric.py)
             self.ph = tuple(photometric)
             self.grey_part = torch.empty(B * L.PHOTOMETRIC_PARTS, dtype=torch.int64, device=dev)      # simt_grey_mean_parts' words
+        self.pm = None
+        if patch_mask is not None:          # (patch, ratio): `patch_mask_batch` blanks patches of a finished batch (simt_amd/data/patch_mask.py)
+            self.pm = pm.parse(patch_mask[1], patch_mask[0], crop_wh)
         self.sc = None
         if scale_crop is not None:          # the scale-crop mode (simt_amd/data/scale_crop.py): `scale_crop_batch` is the only entry point
             self.sc = sc.Tables(src_hw, crop_wh, scale_crop)
@@ -237,14 +242,37 @@ class InputPrep:
             L.call("simt_photometric", C.byref(d), stream)
 
 
+    def patch_mask_batch(self, x, words, x_out, stream):
+        """MIC patch masking of a finished batch: x [B,3,h,w] f32 -> x_out, which may BE x (in place: only the blanked words are stored).
+        words = patch_mask.draw_batch's [B, 32] uint32 row words.  One simt_patch_mask launch on `stream` per SIMT_PATCH_MASK_MAX items
+        (items are independent, so a larger batch is split)."""
+        assert self.pm is not None, "built without patch_mask"
+        assert x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.h, self.w) and x.is_contiguous()
+        assert x_out.dtype == torch.float32 and x_out.shape == x.shape and x_out.is_contiguous()
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        assert words.shape == (self.B, L.PATCH_MASK_GRID)
+        for b0 in range(0, self.B, L.PATCH_MASK_MAX):
+            n = min(L.PATCH_MASK_MAX, self.B - b0)
+            d = L.PatchMaskDesc()
+            d.x, d.x_out = x[b0].data_ptr(), x_out[b0].data_ptr()
+            d.B, d.h, d.w, d.patch = n, self.h, self.w, self.pm[0]
+            C.memmove(d.rows, words[b0:b0 + n].ctypes.data, n * L.PATCH_MASK_GRID * 4)
+            L.call("simt_patch_mask", C.byref(d), stream)
+
+
 class DevicePrefetcher:
     """Pinned double-buffered upload + device transform, one batch ahead of the consumer.
 
     source: iterator of (rgb u8 [B,Hs,Ws,3], label u8 [B,Hs,Ws] or None, meta) host arrays / tensors (numpy or torch; pinned
     tensors are uploaded in place, anything else is staged through this object's pinned buffers).
     Each __next__ returns (image f32 [B,3,h,w], label i64 [B,h,w] | None, meta) resident in HBM -- with teacher_view (the weak-view teacher:
-    it needs mix_fn or photo_fn) two more: the slot's batch BEFORE the mix and the photometric launches (the loader's batch without
-    either, bit for bit) and the item map of the mix ([B,h,w] u8: the item each pixel was taken from; None without mix_fn); same life time.
+    it needs mix_fn, photo_fn or mask_fn) two more: the slot's batch BEFORE the mix, the photometric and the mask launches (the loader's
+    batch without any of them, bit for bit) and the item map of the mix ([B,h,w] u8: the item each pixel was taken from; None without
+    mix_fn); same life time.
+    mask_fn (MIC patch masking, prep.pm): a fourth stage behind the mix and the photometric step on the copy stream, ONE launch per 16
+    items.  It blanks patches in place in the buffer that is about to be handed out (xp with a photometric step, else xm with a mix, else
+    x); only where that buffer is also the weak view (teacher_view with neither mix nor photometric step) does it write a masked copy into
+    a per-slot buffer xk of its own and leave x whole.
 
     Slot life time: the consumer may HOLD `hold` batches at once (gradient accumulation pulls `iter_size` micro-batches before the step
     that reads them is enqueued: tools/trainV2_simt.py `mb = [next(data) for _ in range(iter_size)]`).  The tensors returned by call k
@@ -253,7 +281,7 @@ class DevicePrefetcher:
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
     def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None, photo_fn=None,
-                 teacher_view=False):
+                 teacher_view=False, mask_fn=None):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
         assert (draw_fn is not None) == (prep.sc is not None)
@@ -261,8 +289,13 @@ class DevicePrefetcher:
         assert (mix_fn is not None) == (prep.cm is not None)
         self.photo_fn = photo_fn        # photometric mode (prep.ph): B -> draws; the finished (mixed) batch is jittered and blurred into xp
         assert (photo_fn is not None) == (prep.ph is not None)
+        self.mask_fn = mask_fn          # patch-mask mode (prep.pm): B -> row words; the batch about to be handed out gets its patches blanked
+        assert (mask_fn is not None) == (prep.pm is not None)
         self.teacher_view = bool(teacher_view)
-        assert not self.teacher_view or mix_fn is not None or photo_fn is not None, "teacher_view: without a mix or a photometric step the views are one"
+        assert not self.teacher_view or mix_fn is not None or photo_fn is not None or mask_fn is not None, \
+            "teacher_view: without a mix, a photometric step or a patch mask the views are one"
+        # the mask runs IN PLACE in the buffer that is handed out (xp, else xm, else x) -- unless that buffer is also the weak view
+        self.mask_out_of_place = mask_fn is not None and self.teacher_view and mix_fn is None and photo_fn is None
         self.hold = max(1, int(hold))
         depth = 2 * self.hold if depth is None else depth
         assert depth > self.hold, "the consumer holds `hold` slots: at least one more is needed to hand out"
@@ -284,6 +317,8 @@ class DevicePrefetcher:
                     s["item"] = torch.empty(B, prep.h, prep.w, dtype=torch.uint8, device=dev)
             if photo_fn is not None:                   # what __next__ hands out in photometric mode: same life time as x
                 s["xp"] = torch.empty_like(s["x"])
+            if self.mask_out_of_place:                 # the masked copy of x, which stays whole as the weak view: same life time as x
+                s["xk"] = torch.empty_like(s["x"])
             if cache is not None:                      # transient slots for the items the cache has no room for
                 s["sp_img"] = torch.empty(B * cache.img_stride, dtype=torch.uint8, device=dev)
                 s["sp_lab"] = torch.empty(B * cache.lab_stride, dtype=torch.uint8, device=dev) if prep.with_label else None
@@ -338,6 +373,7 @@ class DevicePrefetcher:
                               mirror=mirror, stream=cs.cuda_stream)
             self._mix(s, lab is not None, cs)
             self._photo(s, cs)
+            self._mask(s, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
         self.filled += 1
@@ -356,6 +392,15 @@ class DevicePrefetcher:
             return
         src = s["xm"] if self.mix_fn is not None else s["x"]
         self.prep.photometric_batch(src, self.photo_fn(self.prep.B), s["xp"], cs.cuda_stream)
+
+    def _mask(self, s, cs):
+        """Patch-mask mode: the buffer about to be handed out -- xp, else xm, else x -- gets its patches blanked in place, on the copy stream,
+        behind `_photo` (MIC masks the augmented image).  Where that buffer is also the weak view (teacher_view with neither mix nor
+        photometric step) x stays whole and the masked copy goes to xk."""
+        if self.mask_fn is None:
+            return
+        src = s["xp"] if self.photo_fn is not None else s["xm"] if self.mix_fn is not None else s["x"]
+        self.prep.patch_mask_batch(src, self.mask_fn(self.prep.B), s["xk"] if self.mask_out_of_place else src, cs.cuda_stream)
 
     def _fill_cached(self, s, rgb, lab, meta):
         """With a cache the source yields only the batch's MISSES: rgb [M,Hs,Ws,3] (None when M = 0), lab likewise, and
@@ -404,6 +449,7 @@ class DevicePrefetcher:
                 prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
             self._mix(s, has_lab, cs)
             self._photo(s, cs)
+            self._mask(s, cs)
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, has_lab, True
         self.filled += 1
@@ -424,7 +470,9 @@ class DevicePrefetcher:
             out = (s["x"], s["lab"] if s["has_lab"] else None, s["meta"])
         if self.photo_fn is not None:      # the label that would have been handed out anyway
             out = (s["xp"], out[1], out[2])
-        if self.teacher_view:              # the weak view: what this slot would have handed out without the mix and the photometric step
+        if self.mask_out_of_place:         # (every other mask ran in place in the buffer `out` names)
+            out = (s["xk"], out[1], out[2])
+        if self.teacher_view:              # the weak view: what this slot would have handed out without the mix, the photometric step and the mask
             out = out + (s["x"], s.get("item"))
         self.filled -= 1
         self.calls += 1
@@ -500,9 +548,15 @@ class GpuLoader:
     photometric.generator(seed, rank): the batch underneath is the batch of the loader without the flags, bit for bit, and start_batch
     skips these draws too.
 
-    dataset.teacher_view = True (--weak-teacher) needs one of the two above and hands out both views: (strong image, labels, sizes, names,
-    weak image, item map | None) -- the weak image is the batch of the loader without class-mix and photometric, bit for bit, the item
-    map ([B,h,w] u8, None without class-mix) names the item each pixel of the strong view was taken from.  Not one draw changes."""
+    dataset.patch_mask = (patch, ratio) (cityscapesPseudo(patch_mask=...), --mask-patches / --mask-patch-size) turns on MIC patch masking
+    (simt_amd/data/patch_mask.py): the batch about to be handed out -- after the mix and the photometric step, when there are any -- has
+    every patch of its patch x patch grid blanked to +0.0f (the mean colour) with probability `ratio`, by one launch per 16 items on the
+    copy stream; labels are not touched.  Its draws come from patch_mask.generator(seed, rank): the batch underneath is the batch of the
+    loader without the flag, bit for bit, and start_batch skips these draws too.
+
+    dataset.teacher_view = True (--weak-teacher) needs one of the three above and hands out both views: (strong image, labels, sizes,
+    names, weak image, item map | None) -- the weak image is the batch of the loader without class-mix, photometric and patch mask, bit for
+    bit, the item map ([B,h,w] u8, None without class-mix) names the item each pixel of the strong view was taken from.  Not one draw changes."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -526,10 +580,15 @@ class GpuLoader:
             if self.photometric is None:
                 raise ValueError("dataset.photometric is (None, None): pass None for no photometric augmentation")
             self._photo_rng = ph.skip_draws(ph.generator(seed, rank), batch_size, int(start_batch))
+        self.patch_mask = getattr(dataset, "patch_mask", None)
+        self._mask_rng = None
+        if self.patch_mask is not None:
+            self.patch_mask = pm.parse(self.patch_mask[1], self.patch_mask[0], tuple(dataset.crop_size))      # (patch, ratio, gh, gw)
+            self._mask_rng = pm.skip_draws(pm.generator(seed, rank), batch_size, int(start_batch), *self.patch_mask[2:])
         self.teacher_view = bool(getattr(dataset, "teacher_view", False))
-        if self.teacher_view and self.class_mix is None and self.photometric is None:
-            raise ValueError("dataset.teacher_view needs dataset.class_mix or dataset.photometric (--weak-teacher needs --class-mix, "
-                             "--colour-jitter or --gaussian-blur): without them the two views are the same batch")
+        if self.teacher_view and self.class_mix is None and self.photometric is None and self.patch_mask is None:
+            raise ValueError("dataset.teacher_view needs dataset.class_mix, dataset.photometric or dataset.patch_mask (--weak-teacher needs "
+                             "--class-mix, --colour-jitter or --gaussian-blur, or --mask-patches): without them the two views are the same batch")
         self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
         if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
@@ -636,7 +695,8 @@ class GpuLoader:
         if self.class_mix is not None and first[1] is None:
             raise ValueError("--class-mix: the dataset yields no labels, and the classes to paste are read from the partner's label")
         self._prep = InputPrep(self.B, (Hs, Ws), tuple(self.ds.crop_size), self.dev, mean=self.ds.mean, with_label=first[1] is not None,
-                               scale_crop=self.scale_crop, class_mix=self.class_mix, photometric=self.photometric)
+                               scale_crop=self.scale_crop, class_mix=self.class_mix, photometric=self.photometric,
+                               patch_mask=None if self.patch_mask is None else self.patch_mask[:2])
         if self.scale_crop is not None and self.cache is not None:
             assert (self.cache.w, self.cache.h) == (Ws, Hs), "with scale-crop the cache holds the ORIGINAL frames: DatasetCache((Ws, Hs))"
 
@@ -655,8 +715,11 @@ class GpuLoader:
         photo_fn = None
         if self.photometric is not None:
             photo_fn = lambda n: ph.draw_batch(self._photo_rng, n, self.photometric)
+        mask_fn = None
+        if self.patch_mask is not None:
+            mask_fn = lambda n: pm.draw_batch(self._mask_rng, n, self.patch_mask[2], self.patch_mask[3], self.patch_mask[1])
         pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn,
-                              photo_fn=photo_fn, teacher_view=self.teacher_view)
+                              photo_fn=photo_fn, teacher_view=self.teacher_view, mask_fn=mask_fn)
         if self.teacher_view:
             return ((x, lab, meta[0], meta[1], xw, item) for (x, lab, meta, xw, item) in pf)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)

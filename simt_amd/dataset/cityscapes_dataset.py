@@ -55,9 +55,11 @@ class cityscapesDataSet(_Base):
     """Images only (evaluation / target-domain images): dataset/cityscapes_dataset.py:21-63."""
 
     def __init__(self, root, list_path, max_iters=None, crop_size=(321, 321), mean=(128, 128, 128), scale=True, mirror=True,
-                 ignore_label=255, set="val"):
+                 ignore_label=255, set="val", patch_mask=None):
         super().__init__(root, list_path, max_iters, crop_size, mean, scale, mirror, ignore_label)
         self.set = set
+        # (patch, ratio) or None: GpuLoader's MIC patch masking of every batch (simt_amd/data/patch_mask.py)
+        self.patch_mask = None if patch_mask is None else (int(patch_mask[0]), float(patch_mask[1]))
         self.img_ids = self._repeat([i_id.strip() for i_id in open(list_path)], max_iters)
         for name in self.img_ids:
             self.files.append({"img": osp.join(self.root, "%s/%s" % (self.set, name)), "name": name})
@@ -76,7 +78,7 @@ class cityscapesPseudo(_Base):
     """Image + pseudo-label PNG (the SimT stage's training set): dataset/cityscapes_dataset.py:66-120."""
 
     def __init__(self, root, list_path, max_iters=None, crop_size=(321, 321), mean=(128, 128, 128), scale=True, mirror=False,
-                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None, teacher_view=False):
+                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None, teacher_view=False, patch_mask=None):
         super().__init__(root, list_path, max_iters, crop_size, mean, scale, mirror, ignore_label)
         # decimal scale choices or None: GpuLoader's random scale + crop (simt_amd/data/scale_crop.py).  `scale` stays what the reference
         # makes of it: stored and never read
@@ -85,7 +87,9 @@ class cityscapesPseudo(_Base):
         self.class_mix = None if class_mix is None else (int(class_mix[0]), float(class_mix[1]))
         # (S | None, P | None) or None: GpuLoader's colour jitter and Gaussian blur of every batch (simt_amd/data/photometric.py)
         self.photometric = None if photometric is None else tuple(None if v is None else float(v) for v in photometric)
-        # GpuLoader also hands out the batch before class_mix / photometric and the mix's item map (the weak-view teacher; needs one of the two)
+        # (patch, ratio) or None: GpuLoader's MIC patch masking of every batch, behind the two above (simt_amd/data/patch_mask.py)
+        self.patch_mask = None if patch_mask is None else (int(patch_mask[0]), float(patch_mask[1]))
+        # GpuLoader also hands out the batch before class_mix / photometric / patch_mask and the mix's item map (the weak-view teacher; needs one of the three)
         self.teacher_view = bool(teacher_view)
         self.img_ids = self._repeat([i_id.strip().split() for i_id in open(list_path)], max_iters)
         for image_path, label_path in self.img_ids:

@@ -4,7 +4,8 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 `evaluate_warmup` + best-mIoU snapshot rotation of :241-256 keeps the reference's file names; data: `cityscapesPseudo` through the device input pipeline (simt_amd/data/pipeline.py) or, with
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
---cache-dataset device [--cache-gb G], --scale-crop [S ...], --class-mix [P], --colour-jitter [S] and --gaussian-blur [P] as in trainV2_simt (both tools share its `batches`).
+--cache-dataset device [--cache-gb G], --scale-crop [S ...], --class-mix [P], --colour-jitter [S], --gaussian-blur [P] and
+--mask-patches [R] [--mask-patch-size P] as in trainV2_simt (both tools share its `batches`).
 --train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
 --ema [D] as in trainV2_simt: a weight EMA beside the trained model (simt_amd/ema.py), evaluated beside it, kept as
 GTA5_BAPA_warmup_ema_iter<i>_mIoU<m>.pth and written at the stop as GTA5_<stop>_ema.pth.
@@ -27,7 +28,8 @@ import torch
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
 from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
-                                          add_ema_args, add_photometric_args, add_scale_crop_args, add_train_state_args, add_v3_layers, batches, restore, save_atomic, shutdown)
+                                          add_ema_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args, add_train_state_args,
+                                          add_v3_layers, batches, check_patch_mask_args, patch_mask_line, restore, save_atomic, shutdown)
 
 
 def get_arguments(argv=None):
@@ -84,9 +86,12 @@ def get_arguments(argv=None):
     add_scale_crop_args(p)
     add_class_mix_args(p)
     add_photometric_args(p)
+    add_patch_mask_args(p)
     add_train_state_args(p)
     add_ema_args(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    check_patch_mask_args(p, args)
+    return args
 
 
 def check_model(args):
@@ -135,6 +140,7 @@ def main(argv=None):
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        patch_mask_line(args, frozen=False)
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
     evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
@@ -220,6 +226,7 @@ def main_single(args):
                              ema_decay=args.ema)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        patch_mask_line(args, frozen=False)
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)

@@ -46,6 +46,12 @@ model's forward runs on that one, and the fused head reads every pixel's frozen 
 item map), so the teacher's predictions are mixed with the same mask as the pixels and the labels.  The student still trains on the strong
 view.  Not one loader draw changes; without the flag nothing does.  --train-state refuses a resume with the flag added or dropped.  All
 three --model values.  Default: off.
+--mask-patches [R] [--mask-patch-size P]: MIC patch masking (Hoyer et al., CVPR'23) -- every P x P patch (default 64) of the
+student's image is blanked to the mean colour with probability R (no value: 0.7; 0 < R < 1), behind --class-mix, --colour-jitter and
+--gaussian-blur, by one launch per 16 items on the copy stream (simt_amd/data/patch_mask.py); labels stay.  --input-size-target may need at
+most 32 x 32 patches.  It satisfies --weak-teacher on its own: the frozen model then labels the whole image and the student predicts those
+labels for the blanked regions from their context; without --weak-teacher both models see the masked image (one start-up line says so).
+Draws of its own generator: not one other draw changes; --train-state refuses a resume with the flag added, dropped or changed.  Default: off.
 
 --model: DeepLab (the reference's DeeplabMulti, `SimTTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or
 DeepLabVGG (model/deeplab_vgg.py); the last two run `SimTSingleTrainer` (simt_amd/step_single.py), the reference's loop with the
@@ -124,18 +130,21 @@ def get_arguments(argv=None):
     add_scale_crop_args(p)
     add_class_mix_args(p)
     add_photometric_args(p)
+    add_patch_mask_args(p)
     add_train_state_args(p)
     add_ema_args(p)
     add_ema_teacher_args(p)
     p.add_argument("--weak-teacher", action="store_true",
-                   help="the frozen model sees the batch before --class-mix / --colour-jitter / --gaussian-blur (needs one of them) and its "
-                        "predictions are mixed with the pixels' mask; the student trains on the augmented batch.  Default: off")
+                   help="the frozen model sees the batch before --class-mix / --colour-jitter / --gaussian-blur / --mask-patches (needs one of "
+                        "them) and its predictions are mixed with the pixels' mask; the student trains on the augmented batch.  Default: off")
     args = p.parse_args(argv)
+    check_patch_mask_args(p, args)
     if args.ema_teacher is not None and args.ema is None:
         p.error("--ema-teacher needs --ema: the frozen model follows the weight EMA")
-    if args.weak_teacher and (args.synthetic or (args.class_mix is None and args.colour_jitter is None and args.gaussian_blur is None)):
-        p.error("--weak-teacher needs --class-mix, --colour-jitter or --gaussian-blur on real data (with --synthetic they do nothing): "
-                "without an augmentation the two views are the same batch")
+    if args.weak_teacher and (args.synthetic or (args.class_mix is None and args.colour_jitter is None and args.gaussian_blur is None
+                                                 and args.mask_patches is None)):
+        p.error("--weak-teacher needs --class-mix, --colour-jitter or --gaussian-blur, or --mask-patches, on real data (with --synthetic "
+                "they do nothing): without an augmentation the two views are the same batch")
     return args
 
 
@@ -212,6 +221,45 @@ def photometric_setting(args):
     from simt_amd.data.photometric import parse
     try:
         return parse(jitter, blur)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+def add_patch_mask_args(p):
+    from simt_amd.data.patch_mask import DEFAULT_PATCH, DEFAULT_RATIO
+    p.add_argument("--mask-patches", type=str, nargs="?", const=DEFAULT_RATIO, default=None, metavar="R",
+                   help="MIC patch masking on the device (simt_amd/data/patch_mask.py): every patch of the student's image is blanked to the "
+                        f"mean colour with probability R (no value: {DEFAULT_RATIO}; 0 < R < 1), after --class-mix, --colour-jitter and "
+                        "--gaussian-blur; one launch per 16 items on the copy stream; labels are not touched.  With --weak-teacher the frozen "
+                        "model sees the whole image.  Default: off.  Ignored with --synthetic")
+    p.add_argument("--mask-patch-size", type=str, default=None, metavar="P",
+                   help=f"side of the square patches of --mask-patches in pixels (default: {DEFAULT_PATCH}); --input-size-target may need at "
+                        "most 32 patch rows and 32 patch columns")
+
+
+def check_patch_mask_args(p, args):
+    """Both flags against --input-size-target, in get_arguments of both tools: a bad R, P or a crop of more than 32 x 32 patches is
+    argparse's error (exit status 2) naming it, and so is --mask-patch-size without --mask-patches."""
+    if args.mask_patches is None:
+        if args.mask_patch_size is not None:
+            p.error("--mask-patch-size needs --mask-patches: it is the patch size of that mask")
+        return
+    try:
+        patch_mask_setting(args)
+    except SystemExit as e:
+        p.error(str(e))
+
+
+def patch_mask_setting(args):
+    """--mask-patches / --mask-patch-size -> (P, R), or None when the flag is off (a bad value is a SystemExit naming it)."""
+    ratio = getattr(args, "mask_patches", None)
+    if ratio is None:
+        return None
+    from simt_amd.data.patch_mask import DEFAULT_PATCH, parse
+    patch = getattr(args, "mask_patch_size", None)
+    try:
+        w, h = map(int, args.input_size_target.split(","))
+        return parse(ratio, DEFAULT_PATCH if patch is None else patch, (w, h))[:2]
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -415,12 +463,12 @@ class EmaSnapshots:
             self.keeper.rolling(self.tr.ema_state_dict(), i_iter)
 
 
-RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False}      # run_identity keys that are absent when their flag is off: what absence means
+RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
     """What the LOOP feeds the trainer and no trainer can check: the seed (loader order, mirror and scale-crop draws, synthetic batches), the
-    mirror switch, the scale-crop choices, the class-mix probability and the photometric pair [S, P] (RUN_DEFAULTS: a key is absent when its flag is off, and absent means
+    mirror switch, the scale-crop choices, the class-mix probability, the photometric pair [S, P] and the patch-mask pair [P, R] (RUN_DEFAULTS: a key is absent when its flag is off, and absent means
     False -- the state files of runs from before a flag existed are those of runs without it; with --synthetic the flags do nothing), where the data comes from
     (the list file's SHA-256) and the class prior (it enters T and the synthetic labels)."""
     import hashlib
@@ -435,6 +483,9 @@ def run_identity(args, class_dist):
     photo = None if args.synthetic else photometric_setting(args)
     if photo is not None:
         ident["photometric"] = list(photo)          # [colour-jitter S | None, gaussian-blur P | None]
+    mask = None if args.synthetic else patch_mask_setting(args)
+    if mask is not None:
+        ident["patch_mask"] = list(mask)            # [mask-patch-size P, mask-patches R]
     if getattr(args, "weak_teacher", False):
         ident["weak_teacher"] = True
     if not args.synthetic and osp.isfile(args.data_list_target):
@@ -524,10 +575,18 @@ def teacher_line(args):
 
 def weak_teacher_line(args):
     if getattr(args, "weak_teacher", False):
-        on = [f for f, v in (("--class-mix", args.class_mix), ("--colour-jitter", args.colour_jitter), ("--gaussian-blur", args.gaussian_blur))
-              if v is not None]
+        on = [f for f, v in (("--class-mix", args.class_mix), ("--colour-jitter", args.colour_jitter), ("--gaussian-blur", args.gaussian_blur),
+                             ("--mask-patches", getattr(args, "mask_patches", None))) if v is not None]
         print(f"weak-view teacher: the frozen model sees the batch before {', '.join(on)}; its predictions follow the "
               f"{'mix mask' if args.class_mix is not None else 'pixels (no mix: no item map)'}")
+
+
+def patch_mask_line(args, frozen=True):
+    """--mask-patches without --weak-teacher: say once who sees the masked image (frozen=False: the warm-up tool, which has one model)."""
+    mask = None if args.synthetic else patch_mask_setting(args)
+    if mask is not None and not getattr(args, "weak_teacher", False):
+        print(f"patch mask: {mask[0]} x {mask[0]} patches blanked with probability {mask[1]}; " +
+              ("without --weak-teacher both models see the masked image" if frozen else "the model trains on the masked image"))
 
 
 def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
@@ -536,7 +595,10 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     choices = scale_crop_choices(args)
     mix = class_mix_setting(args)
     photo = photometric_setting(args)
+    mask = patch_mask_setting(args)
     if args.synthetic:
+        if mask is not None and rank == 0:
+            print("--mask-patches does nothing with --synthetic: the synthetic batches are not masked")
         if choices is not None and rank == 0:
             print("--scale-crop does nothing with --synthetic: the synthetic batches are made at the crop's size")
         if mix is not None and rank == 0:
@@ -555,7 +617,8 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
-                          scale_crop=choices, class_mix=mix, photometric=photo, teacher_view=bool(getattr(args, "weak_teacher", False)))
+                          scale_crop=choices, class_mix=mix, photometric=photo, teacher_view=bool(getattr(args, "weak_teacher", False)),
+                          patch_mask=mask)
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
@@ -627,6 +690,7 @@ def main(argv=None):
     if rank == 0:
         teacher_line(args)
         weak_teacher_line(args)
+        patch_mask_line(args)
         print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -727,6 +791,7 @@ def main_single(args):
     if rank == 0:
         teacher_line(args)
         weak_teacher_line(args)
+        patch_mask_line(args)
         print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}, K={K}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
