@@ -453,6 +453,21 @@ int simt_pseudo_label_u8(const float* la, int ha, int wa, int lda, const float* 
 int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, const float* lb, int hb, int wb, int ldb,
                           int hib, int wib, int B, int H, int W, int C, int mode, float threshold, uint8_t* out, int64_t* counts,
                           simt_stream_t stream);
+/* online labels (the warm-up trainers' teacher): the confidence rule of mode 1 above, written as the int64 label the head
+ * kernels read.  label[b][y][x] = arg where conf > threshold (strictly), 255 elsewhere; a NaN confidence or threshold gives 255.
+ * family 0 (DeepLab-v2, VGG): (arg, conf) of simt_pseudo_label_u8 mode 1 (fix = low-res PROBABILITIES, align_corners=True), bit for bit;
+ * family 1 (DeepLabv3): those of simt_pseudo_label2_u8 mode 1 called with hia = H, wia = W (fix = low-res LOGITS; softmax of their
+ *   half-pixel resample to (H, W)), bit for bit; B*h*w*ld < 2^31.
+ * Refused (SIMT_ERR_INVALID, nothing launched): a NULL pointer, a size <= 0, C > ld, C > 255, another family, label not 8-byte aligned,
+ * the 2^31 limit of family 1.  The descriptor travels as kernel arguments: no device copy, no synchronisation. */
+typedef struct {
+  const float* fix;        /* [B*h*w][ld] fp32, first C channels.  family 0: probabilities (simt_softmax_rows); family 1: logits */
+  int64_t* label;          /* out [B][H][W]: class index, 255 = ignore; every 8-byte word is written in full */
+  int64_t* counts;         /* [C+1], accumulated across calls: classes 0..C-1, then the 255s (as simt_pseudo_label_u8) */
+  int32_t B, h, w, ld, H, W, C, family;
+  float threshold;
+} simt_online_label_desc;
+int simt_online_label(const simt_online_label_desc* d, simt_stream_t stream);
 /* class-balanced pseudo labels (CBST / BDL: per-class confidence thresholds).  (arg, conf) of a pixel are the arg-max and the maximum
  * of mode 1 above, bit for bit: simt_pseudo_conf_u8 over the geometry of simt_pseudo_label_u8 (la = low-res PROBABILITIES),
  * simt_pseudo_conf2_u8 over that of simt_pseudo_label2_u8 (la = LOGITS), one scale.

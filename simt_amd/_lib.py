@@ -187,6 +187,12 @@ class BnFoldDesc(C.Structure):
                 ("eps", f32)]
 
 
+class OnlineLabelDesc(C.Structure):
+    """simt_online_label_desc (include/simt_hip.h): a teacher's low-res map -> the int64 labels the head kernels read, and their counts."""
+    _fields_ = [("fix", c_p), ("label", c_p), ("counts", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32), ("H", i32), ("W", i32),
+                ("C", i32), ("family", i32), ("threshold", f32)]
+
+
 TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
 
 
@@ -278,6 +284,7 @@ SIGNATURES = {
     "simt_pseudo_label2_u8": (_I, [c_p, _I, _I, _I, _I, _I, c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, f32, c_p, c_p, c_p]),
     "simt_pseudo_conf_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
     "simt_pseudo_conf2_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
+    "simt_online_label": (_I, [C.POINTER(OnlineLabelDesc), c_p]),
     "simt_tta_label": (_I, [C.POINTER(TtaDesc), c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),

@@ -141,6 +141,18 @@ __device__ __forceinline__ void pl_hist_init(unsigned int* sh, int nbins) {
   for (int i = threadIdx.x; i < nbins; i += BLOCK) sh[i] = 0u;
   __syncthreads();
 }
+// the first n labels packed in `word` (one per byte) into the LDS histogram: runs of equal labels are added once
+__device__ __forceinline__ void pl_count(unsigned int word, int n, int C, unsigned int* sh) {
+  int run_bin = 0, run_n = 0;
+  for (int i = 0; i < n; ++i) {
+    const unsigned int l = (word >> (8 * i)) & 255u;
+    const int bin = l == 255u ? C : (int)l;
+    if (bin != run_bin && run_n) { atomicAdd(&sh[run_bin], (unsigned int)run_n); run_n = 0; }
+    run_bin = bin;
+    ++run_n;
+  }
+  atomicAdd(&sh[run_bin], (unsigned int)run_n);
+}
 __device__ __forceinline__ void pl_store(unsigned int lab, long p, long P, int C, unsigned char* out, unsigned int* sh) {
   const bool leader = (threadIdx.x & 3) == 0;
   unsigned int word = lab | (__shfl_down(lab, 1, 4) << 8);
@@ -152,15 +164,7 @@ __device__ __forceinline__ void pl_store(unsigned int lab, long p, long P, int C
     } else {
       for (int i = 0; i < n; ++i) out[p + i] = (unsigned char)(word >> (8 * i));
     }
-    int run_bin = 0, run_n = 0;
-    for (int i = 0; i < n; ++i) {
-      const unsigned int l = (word >> (8 * i)) & 255u;
-      const int bin = l == 255u ? C : (int)l;
-      if (bin != run_bin && run_n) { atomicAdd(&sh[run_bin], (unsigned int)run_n); run_n = 0; }
-      run_bin = bin;
-      ++run_n;
-    }
-    atomicAdd(&sh[run_bin], (unsigned int)run_n);
+    pl_count(word, n, C, sh);
   }
 }
 template <int BLOCK>
@@ -748,6 +752,99 @@ extern "C" int simt_pseudo_label2_u8(const float* la, int ha, int wa, int lda, i
     hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 4>), g, blk, 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((pseudo_label2_u8_kernel<1, 1>), g, blk, 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+// ---- online labels: the warm-up trainers' teacher labels every batch on the device.  The label rule of the export kernels'
+// confidence mode, through the SAME device functions (pseudo_pixel<1> / up2_confident: (arg, conf) are theirs bit for bit), written as the
+// int64 label the head kernels read -- no uint8 map, no widening copy.  FAM 0: pseudo_label_u8_kernel<1>.  FAM 1: pseudo_label2_u8_kernel<1>
+// with a virtual map of the label's own size (hia = H, wia = W): its outer taps then have weights exactly 1 and 0, but a one-sample
+// shortcut is NOT bit-equal (0 * NaN of a neighbouring sample is NaN there, and H == 1 gives scale 0), so the four-sample function is called
+// as it is.  One pixel per lane, as above: a wave's 64 labels are one contiguous 512-byte store.  Counts: the quad shuffle of pl_store packs
+// 4 labels into the quad leader, which adds runs of equal labels to the LDS histogram once (pl_count); pl_hist_flush as above.
+struct Online2Args {
+  Up2Scale s;
+  int B, H, W, C;
+  float threshold;
+};
+
+__device__ __forceinline__ void ol_store(unsigned int lab, long p, long P, int C, long long* label, unsigned int* sh) {
+  unsigned int word = lab | (__shfl_down(lab, 1, 4) << 8);
+  word |= __shfl_down(word, 2, 4) << 16;
+  if (p < P) {
+    label[p] = (long long)lab;
+    if ((threadIdx.x & 3) == 0) pl_count(word, P - p < 4 ? (int)(P - p) : 4, C, sh);
+  }
+}
+
+__global__ __launch_bounds__(PL_BLOCK) void online_label_kernel(PseudoArgs a, long long* label) {
+  __shared__ unsigned int sh[256];
+  pl_hist_init<PL_BLOCK>(sh, a.C + 1);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL_BLOCK; base < P; base += (long)gridDim.x * PL_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      const ArgConf r = pseudo_pixel<1>(a, (int)(t / a.H), (int)(t % a.H), x);
+      lab = (unsigned int)(!(r.conf > a.threshold) ? 255 : r.arg);   // strictly greater (:359); a NaN on either side: 255
+    }
+    ol_store(lab, p, P, a.C, label, sh);
+  }
+  pl_hist_flush<PL_BLOCK>(sh, a.C + 1, a.counts);
+}
+
+template <int V>
+__global__ __launch_bounds__(PL2_BLOCK) void online_label2_kernel(Online2Args a, long long* label, unsigned long long* counts) {
+  __shared__ unsigned int sh[256];
+  pl_hist_init<PL2_BLOCK>(sh, a.C + 1);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL2_BLOCK; base < P; base += (long)gridDim.x * PL2_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      lab = (unsigned int)up2_confident<V>(a.s, a.C, a.threshold, (int)(t / a.H), (int)(t % a.H), x);
+    }
+    ol_store(lab, p, P, a.C, label, sh);
+  }
+  pl_hist_flush<PL2_BLOCK>(sh, a.C + 1, counts);
+}
+
+extern "C" int simt_online_label(const simt_online_label_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->fix && d->label && d->counts);
+  SIMT_CHECK(d->B > 0 && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->C <= 255 && d->C <= d->ld);
+  SIMT_CHECK(d->family == 0 || d->family == 1);
+  SIMT_CHECK(((uintptr_t)d->label & 7) == 0);
+  const int B = d->B, h = d->h, w = d->w, ld = d->ld, H = d->H, W = d->W;
+  const long P = (long)B * H * W;
+  if (d->family == 0) {
+    PseudoArgs a;
+    a.la = d->fix; a.lb = nullptr; a.out = nullptr; a.counts = (unsigned long long*)d->counts;
+    a.B = B; a.ha = h; a.wa = w; a.lda = ld; a.hb = 0; a.wb = 0; a.ldb = 0; a.H = H; a.W = W; a.C = d->C;
+    a.sya = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    a.sxa = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    a.syb = 0.f; a.sxb = 0.f;
+    a.threshold = d->threshold;
+    long grid = (P + PL_BLOCK - 1) / PL_BLOCK;
+    if (grid > PL_MAX_GRID) grid = PL_MAX_GRID;
+    hipLaunchKernelGGL(online_label_kernel, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a, (long long*)d->label);
+  } else {
+    SIMT_CHECK((long)B * h * w * ld < 2147483647L);          // the taps' element offsets are 32-bit (Up2Taps)
+    Online2Args a;
+    fill_up2(a.s, d->fix, h, w, ld, H, W, H, W);
+    a.B = B; a.H = H; a.W = W; a.C = d->C; a.threshold = d->threshold;
+    long grid = (P + PL2_BLOCK - 1) / PL2_BLOCK;
+    if (grid > PL2_MAX_GRID) grid = PL2_MAX_GRID;
+    const dim3 g((unsigned)grid), blk(PL2_BLOCK);
+    if (ld % 4 == 0 && ((uintptr_t)d->fix & 15) == 0)
+      hipLaunchKernelGGL(online_label2_kernel<4>, g, blk, 0, (hipStream_t)stream, a, (long long*)d->label, (unsigned long long*)d->counts);
+    else
+      hipLaunchKernelGGL(online_label2_kernel<1>, g, blk, 0, (hipStream_t)stream, a, (long long*)d->label, (unsigned long long*)d->counts);
+  }
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }

@@ -75,10 +75,12 @@ class cityscapesDataSet(_Base):
 
 
 class cityscapesPseudo(_Base):
-    """Image + pseudo-label PNG (the SimT stage's training set): dataset/cityscapes_dataset.py:66-120."""
+    """Image + pseudo-label PNG (the SimT stage's training set): dataset/cityscapes_dataset.py:66-120.
+    labels=False (online labels, DESIGN 7.16: a teacher labels the batch on the device): a list line has one column or two, a second column
+    is never opened, `decode` returns (rgb, None, name) with the name taken from the image path, and `cache_key` is the image alone."""
 
     def __init__(self, root, list_path, max_iters=None, crop_size=(321, 321), mean=(128, 128, 128), scale=True, mirror=False,
-                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None, teacher_view=False, patch_mask=None):
+                 ignore_label=255, scale_crop=None, class_mix=None, photometric=None, teacher_view=False, patch_mask=None, labels=True):
         super().__init__(root, list_path, max_iters, crop_size, mean, scale, mirror, ignore_label)
         # decimal scale choices or None: GpuLoader's random scale + crop (simt_amd/data/scale_crop.py).  `scale` stays what the reference
         # makes of it: stored and never read
@@ -91,14 +93,28 @@ class cityscapesPseudo(_Base):
         self.patch_mask = None if patch_mask is None else (int(patch_mask[0]), float(patch_mask[1]))
         # GpuLoader also hands out the batch before class_mix / photometric / patch_mask and the mix's item map (the weak-view teacher; needs one of the three)
         self.teacher_view = bool(teacher_view)
-        self.img_ids = self._repeat([i_id.strip().split() for i_id in open(list_path)], max_iters)
-        for image_path, label_path in self.img_ids:
-            self.files.append({"img": osp.join(self.root, image_path), "label": osp.join(self.root, label_path),
-                               "name": osp.splitext(osp.basename(label_path))[0]})
+        self.labels = bool(labels)
+        if self.labels:
+            self.img_ids = self._repeat([i_id.strip().split() for i_id in open(list_path)], max_iters)
+            for image_path, label_path in self.img_ids:
+                self.files.append({"img": osp.join(self.root, image_path), "label": osp.join(self.root, label_path),
+                                   "name": osp.splitext(osp.basename(label_path))[0]})
+            return
+        if self.class_mix is not None:
+            raise ValueError("cityscapesPseudo(labels=False, class_mix=...): the mix reads the classes to paste from the partner's label")
+        lines = [(n, ln.split()) for n, ln in enumerate(open(list_path), 1) if ln.strip()]
+        for n, cols in lines:
+            if len(cols) not in (1, 2):
+                raise ValueError(f"{list_path}:{n}: expected an image path, or an image path and a label path, got {len(cols)} columns")
+        self.img_ids = self._repeat([cols for _n, cols in lines], max_iters)
+        for cols in self.img_ids:
+            self.files.append({"img": osp.join(self.root, cols[0]), "name": osp.splitext(osp.basename(cols[0]))[0]})
 
     def decode(self, index):
         from PIL import Image
         f = self.files[index]
+        if not self.labels:
+            return self._open_rgb(f["img"]), None, f["name"]
         lab = np.asarray(Image.open(f["label"]))
         if lab.ndim != 2 or lab.dtype != np.uint8:
             raise ValueError(f"{f['label']}: expected an 8-bit single-channel label image, got {lab.dtype} {lab.shape}")
@@ -106,5 +122,5 @@ class cityscapesPseudo(_Base):
 
     def __getitem__(self, index):
         rgb, lab, name = self.decode(index)
-        image, label = self._device_item(rgb, lab)
+        image, label = self._device_item(rgb, lab)          # (labels=False: label is None)
         return image, label, np.array((self.crop_size[1], self.crop_size[0], 3)), name

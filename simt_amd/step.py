@@ -27,6 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
+from .online_labels import OnlineLabelMixin, check_settings
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -485,13 +486,18 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         return dict(zip(keys, v))
 
 
-class WarmupTrainer(TrainStateMixin, EmaMixin):
+class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
     Same engine as SimTTrainer: TrunkPlan forward/backward, the fused head kernels in mode 1, simt_sgd_multi."""
 
-    def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None):
+    def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
+                 online_labels=None, online_labels_every=None):
+        """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
+        closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
+        online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was."""
+        tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -501,7 +507,13 @@ class WarmupTrainer(TrainStateMixin, EmaMixin):
         kw = {"layers": layers} if layers is not None else {}
         self.plan = TrunkPlan(self.params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=True,
                               data_parallel=process_group is not None, **kw)
-        h, w = self.plan.heads[1].h, self.plan.heads[1].w
+        h, w = self.h, self.w = self.plan.heads[1].h, self.plan.heads[1].w
+        if tau is not None:      # the teacher: the frozen plan of SimTTrainer(teacher_view=True) -- stem_from=None: its own x_in and stem launch
+            self.fixed_params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
+            self.frozen_sha256 = state_sha256(self.fixed_params)      # a train state is refused beside another start model (train_state.py)
+            self.fixed = TrunkPlan(self.fixed_params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=False, stem_from=None,
+                                   data_parallel=process_group is not None, **kw)
+            self._fix_fwd = self.fixed.fwd_list
         lib = L.load()
         self.part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Cn, Cn), device=dev)
         self.keys = torch.zeros(lib.simt_head_keys_count(), device=dev, dtype=torch.int64)
@@ -528,6 +540,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin):
         SimTTrainer._build_sgd(self, roots=("conv1", "layer1", "layer2", "layer3", "layer4"))
         self.it_done = 0
         self._init_ema(ema_decay)
+        fix = (self.fixed.out["x2"], self.fixed.ldp["x2"]) if tau is not None else (None, 0)
+        self._init_online(tau, every, *fix, 0)      # (family 0: the posterior is resampled align_corners=True)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -536,22 +550,28 @@ class WarmupTrainer(TrainStateMixin, EmaMixin):
             self.reducer = BucketReducer(self.plan.flat_grad, buckets, group=self.pg, extra=[self.bad_labels])
         self._grad_acc = None
 
-    def step(self, image, label, it=None):
+    def step(self, image, label=None, it=None, teacher_image=None):
         """One micro-batch, or sequences of hp.iter_size micro-batches (trainV1_warmup.py:212-231: loss / iter_size,
-        gradients accumulated, one optimiser step)."""
+        gradients accumulated, one optimiser step).  Built with online_labels: `label` must be None (the labels come from the teacher),
+        teacher_image is the teacher's view (None: it sees `image`); sequences like image when hp.iter_size > 1."""
         hp = self.hp
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
-        labels = list(label) if isinstance(label, (list, tuple)) else [label]
+        labels, teachers = self._views(label, teacher_image, hp.iter_size)
         if len(images) != hp.iter_size or len(labels) != hp.iter_size:
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
         flat = self.plan.flat_grad
         for mi, (img, lab) in enumerate(zip(images, labels)):
             self.plan.x_in.copy_(img, non_blocking=True)
-            self.label.copy_(lab, non_blocking=True)
-            self.plan.forward()
+            if self.online_labels is None:
+                self.label.copy_(lab, non_blocking=True)
+                self.plan.forward()
+            else:          # the teacher writes self.label on the side stream, beside the student's forward; the main stream waits for it here
+                ev_in = self._teacher_input(img, teachers[mi])
+                self.plan.forward()
+                self._teacher_labels(ev_in)
             L.call("simt_head_loss", C.byref(self.head_desc), st)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
             L.call("simt_head_grad", C.byref(self.head_desc), st)
@@ -581,6 +601,13 @@ class WarmupTrainer(TrainStateMixin, EmaMixin):
         self.plan.repack()
         if self.ema is not None:
             self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward
+            # online_labels_every: the teacher's refresh, if this update made one due, directly behind it on the main stream:
+            #   behind this step's teacher forward, softmax_rows and label launch (side stream): the main stream waited for their event in
+            #   front of simt_head_loss (_teacher_labels);
+            #   in front of the next step's teacher forward (side stream): it waits for ev_in, which the main stream records behind this point
+            #   (_teacher_input); no main-stream launch reads the teacher plan's operands.
+            # Once per optimiser step: this point is behind the last micro-batch.
+            self._teacher_follows(st)
         self.it_done += 1
         return self.hout
 
@@ -601,4 +628,4 @@ class WarmupTrainer(TrainStateMixin, EmaMixin):
         if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like SimTTrainer's
-        return {"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]}
+        return self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]})

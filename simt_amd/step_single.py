@@ -28,6 +28,7 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
+from .online_labels import OnlineLabelMixin, check_settings
 from .step import check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
@@ -279,7 +280,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                 "vol_ok": v[9]}
 
 
-class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
+class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     """The warm-up stage (tools/trainV1_warmup.py:156-256) over a ONE-OUTPUT model: DeepLabv3(nc) or DeeplabVGG(nc), trained by cross-entropy
     on the pseudo labels, loss = CE(interp_target(model(x)), label) with ignore_index 255 (:212-231 without the auxiliary head; for
     DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
@@ -287,10 +288,13 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
     Engine: the plans of SimTSingleTrainer, the fused head kernels in their one-head warm-up flavour (simt_head_desc single = 1, mode = 1),
     the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
 
-    def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None):
+    def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
+                 online_labels=None, online_labels_every=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
-        keyword arguments, as for SimTSingleTrainer."""
+        keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every: as for step.WarmupTrainer; the
+        teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample)."""
         assert model in ("v3", "vgg")
+        tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -319,6 +323,20 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
             self.pred, self.ldp = self.plan.out["x"], self.plan.ldp["x"]
             half = 0
         self.h, self.w = h, w
+        fix_out, ldf = None, 0
+        if tau is not None:      # the teacher: a second plan over a copy of the start state, as SimTSingleTrainer builds its frozen one
+            self.fixed_params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
+            self.frozen_sha256 = state_sha256(self.fixed_params)      # a train state is refused beside another start model (train_state.py)
+            if model == "v3":
+                self.fixed = V3Plan(self.fixed_params, B, H, W, Cn, 0, False, dtype=dtype, train=False, **arch)
+                assert self.fixed.fwd_list.items[-1].tag == "simt_upsample_nchw"      # the label kernel resamples the low-res logits itself
+                self._fix_fwd = LaunchList()
+                self._fix_fwd.items = self.fixed.fwd_list.items[:-1]
+                fix_out, ldf = self.fixed.logits, self.fixed.ldq
+            else:
+                self.fixed = VggPlan(self.fixed_params, B, H, W, Cn, dtype=dtype, train=False, **arch)
+                self._fix_fwd = self.fixed.fwd_list
+                fix_out, ldf = self.fixed.out["x"], self.fixed.ldp["x"]
         dl = self.plan.dlogits["x"]
         lib = L.load()
         self.part = torch.zeros(lib.simt_head_nblk(B, H, W), lib.simt_head_part_floats(Cn, Cn), device=dev)
@@ -344,6 +362,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
         SimTSingleTrainer._build_sgd(self)
         self.it_done = 0
         self._init_ema(ema_decay)
+        self._init_online(tau, every, fix_out, ldf, half)      # (family 1 = the half-pixel model, DeepLabv3)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -354,22 +373,28 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
 
     optim_groups = SimTSingleTrainer.optim_groups
 
-    def step(self, image, label, it=None):
+    def step(self, image, label=None, it=None, teacher_image=None):
         """One micro-batch, or sequences of hp.iter_size micro-batches (trainV1_warmup.py:212-231: loss / iter_size, gradients accumulated,
-        one optimiser step; under data parallelism one exchange of the accumulated gradient)."""
+        one optimiser step; under data parallelism one exchange of the accumulated gradient).  Built with online_labels: `label` must be
+        None, teacher_image is the teacher's view (None: it sees `image`), as for step.WarmupTrainer."""
         hp = self.hp
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
-        labels = list(label) if isinstance(label, (list, tuple)) else [label]
+        labels, teachers = self._views(label, teacher_image, hp.iter_size)
         if len(images) != hp.iter_size or len(labels) != hp.iter_size:
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
         flat = self.plan.flat_grad
         for mi, (img, lab) in enumerate(zip(images, labels)):
             self.plan.x_in.copy_(img, non_blocking=True)
-            self.label.copy_(lab, non_blocking=True)
-            self._fwd.run()
+            if self.online_labels is None:
+                self.label.copy_(lab, non_blocking=True)
+                self._fwd.run()
+            else:          # the teacher writes self.label on the side stream, beside the student's forward; the main stream waits for it here
+                ev_in = self._teacher_input(img, teachers[mi])
+                self._fwd.run()
+                self._teacher_labels(ev_in)
             L.call("simt_head_loss", C.byref(self.head_desc), st)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
             L.call("simt_head_grad", C.byref(self.head_desc), st)
@@ -399,6 +424,10 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
         self.plan.repack()
         if self.ema is not None:
             self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward
+            # online_labels_every: the teacher's refresh, if due, directly behind it on the main stream: behind this step's teacher forward and
+            # label launch (side stream; the main stream waited for their event in front of simt_head_loss) and in front of the next ones
+            # (the side stream waits for ev_in, recorded on the main stream behind this point); as in step.WarmupTrainer
+            self._teacher_follows(st)
         self.it_done += 1
         return self.hout
 
@@ -426,4 +455,4 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin):
         if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like WarmupTrainer's
-        return {"total": v[14] / self.hp.iter_size, "loss_seg": v[1]}
+        return self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg": v[1]})

@@ -9,6 +9,14 @@ is honoured) unless --from-scratch is given.
 --train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
 --ema [D] as in trainV2_simt: a weight EMA beside the trained model (simt_amd/ema.py), evaluated beside it, kept as
 GTA5_BAPA_warmup_ema_iter<i>_mIoU<m>.pth and written at the stop as GTA5_<stop>_ema.pth.
+--online-labels [T] [--online-labels-every N]: self-training from a list of images alone (simt_amd/online_labels.py) -- a frozen
+copy of the start model, the teacher, labels every batch on the device (one launch per micro-batch, beside the student's forward), pixels whose
+confidence is not above T (no value: 0.968; 0 <= T < 1) are ignored and the model trains on those labels by the same cross-entropy.
+--data-list-target may then have one column; no label file is opened.  With --colour-jitter, --gaussian-blur or --mask-patches the teacher
+labels the batch BEFORE them and the student sees it after (FixMatch / MIC consistency); --class-mix is refused (it needs the labels in the
+loader).  With --ema and --online-labels-every N the teacher follows the weight EMA behind every N-th update (the mean teacher); without N it
+stays at the start weights.  The loss line gains ` labelled = <share of pixels that received a label>`; --train-state carries the teacher and
+the counts and refuses a resume with either flag added, dropped or changed.  With --synthetic the labels are ignored too.  Default: off.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -28,8 +36,9 @@ import torch
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer, lr_poly
 from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
-                                          add_ema_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args, add_train_state_args,
-                                          add_v3_layers, batches, check_patch_mask_args, patch_mask_line, restore, save_atomic, shutdown)
+                                          add_ema_args, add_online_label_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args,
+                                          add_train_state_args, add_v3_layers, batches, check_online_label_args, check_patch_mask_args,
+                                          online_label_line, patch_mask_line, restore, save_atomic, shutdown)
 
 
 def get_arguments(argv=None):
@@ -89,9 +98,28 @@ def get_arguments(argv=None):
     add_patch_mask_args(p)
     add_train_state_args(p)
     add_ema_args(p)
+    add_online_label_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
+    check_online_label_args(p, args)
     return args
+
+
+def step_args(args, mb):
+    """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
+    (image, None) and the keyword teacher_image where the loader made a weak view."""
+    one = args.iter_size == 1
+    img = mb[0][0] if one else [m[0] for m in mb]
+    if args.online_labels is None:
+        return (img, mb[0][1] if one else [m[1] for m in mb]), {}
+    if mb[0][2] is None:
+        return (img, None), {}
+    return (img, None), {"teacher_image": mb[0][2] if one else [m[2] for m in mb]}
+
+
+def labelled_text(args, l):
+    """` labelled = 0.xxx` of the loss line: only with --online-labels."""
+    return " labelled = {0:.3f}".format(l["labelled"]) if args.online_labels is not None else ""
 
 
 def check_model(args):
@@ -137,9 +165,11 @@ def main(argv=None):
                momentum=args.momentum, weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
     dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema)
+    tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
+                       online_labels=args.online_labels, online_labels_every=args.online_labels_every)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        online_label_line(args)
         patch_mask_line(args, frozen=False)
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
@@ -153,14 +183,14 @@ def main(argv=None):
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
-        tr.step(img, lab, i_iter)
+        a, kw = step_args(args, mb)
+        tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:              # :231-234 (every 100 iterations there)
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}  lr = {4:.2e}  ({5:.1f} img/s)".format(
+                print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -223,9 +253,10 @@ def main_single(args):
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
     tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
-                             ema_decay=args.ema)
+                             ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        online_label_line(args)
         patch_mask_line(args, frozen=False)
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}")
@@ -240,14 +271,14 @@ def main_single(args):
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0]
-        tr.step(img, lab, i_iter)
+        a, kw = step_args(args, mb)
+        tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}  lr = {3:.2e}  ({4:.1f} img/s)".format(
+                print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

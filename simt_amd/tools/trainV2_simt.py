@@ -305,6 +305,68 @@ def add_ema_teacher_args(p):
                         "a run that drops the flag, adds it or changes N.  Default: off")
 
 
+def _online_threshold(text):
+    from simt_amd.online_labels import check_threshold
+    try:
+        return check_threshold(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _online_every(text):
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected an integer >= 1")
+    return n
+
+
+def add_online_label_args(p):
+    """--online-labels / --online-labels-every of trainV1_warmup; `check_online_label_args` holds their refusals."""
+    from simt_amd.online_labels import DEFAULT_THRESHOLD
+    p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
+                   help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
+                        "labels every batch on the device, pixels whose confidence is not above T are ignored (no value: T = "
+                        f"{DEFAULT_THRESHOLD}; 0 <= T < 1).  --data-list-target may then list images alone; with --colour-jitter, "
+                        "--gaussian-blur or --mask-patches the teacher labels the batch before them.  Not with --class-mix.  Default: off")
+    p.add_argument("--online-labels-every", type=_online_every, default=None, metavar="N",
+                   help="with --online-labels and --ema: the teacher follows the weight EMA, refreshed behind every N-th update (an integer "
+                        ">= 1; simt_amd/ema_teacher.py).  Default: the teacher stays at the start weights")
+
+
+def check_online_label_args(p, args):
+    """argparse's error (exit status 2) naming the flag: --online-labels-every without --online-labels or without --ema, and --online-labels
+    with --class-mix (the mix reads the classes to paste from the partner's LABEL, which the teacher has not made yet)."""
+    if args.online_labels_every is not None and args.online_labels is None:
+        p.error("--online-labels-every needs --online-labels: it moves the teacher that makes the labels")
+    if args.online_labels_every is not None and args.ema is None:
+        p.error("--online-labels-every needs --ema: the teacher follows the weight EMA")
+    if args.online_labels is not None and args.class_mix is not None:
+        p.error("--online-labels cannot be combined with --class-mix: the mix reads the classes to paste from the partner's label, and "
+                "the teacher makes the labels behind the loader")
+
+
+def online_label_line(args):
+    """One start-up line: who labels, the threshold, which view the teacher sees."""
+    if getattr(args, "online_labels", None) is None:
+        return
+    n = args.online_labels_every
+    who = "a fixed teacher (the start weights)" if n is None else f"a teacher that follows the weight EMA (decay {args.ema}), refreshed every {n} update(s)"
+    weak = online_weak_view(args)
+    print(f"online labels: {who} labels every batch, kept where its confidence is > {args.online_labels}; the teacher sees "
+          f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}")
+
+
+def online_weak_view(args):
+    """The flags that give --online-labels a weak view of its own (none with --synthetic, where they do nothing)."""
+    if getattr(args, "online_labels", None) is None or args.synthetic:
+        return []
+    return [f for f, v in (("--colour-jitter", args.colour_jitter), ("--gaussian-blur", args.gaussian_blur),
+                           ("--mask-patches", getattr(args, "mask_patches", None))) if v is not None]
+
+
 def add_v3_layers(p):
     p.add_argument("--v3-layers", type=int, nargs=3, default=[3, 4, 6], metavar=("L1", "L2", "L3"),
                    help="DeepLabv3 trunk: Bottlenecks of layer1..layer3 (3 4 6: model/deeplabv3.py as written, ResNet-50; "
@@ -463,7 +525,8 @@ class EmaSnapshots:
             self.keeper.rolling(self.tr.ema_state_dict(), i_iter)
 
 
-RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False}      # run_identity keys that are absent when their flag is off: what absence means
+RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
+                "online_labels": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -488,6 +551,8 @@ def run_identity(args, class_dist):
         ident["patch_mask"] = list(mask)            # [mask-patch-size P, mask-patches R]
     if getattr(args, "weak_teacher", False):
         ident["weak_teacher"] = True
+    if getattr(args, "online_labels", None) is not None:
+        ident["online_labels"] = [float(args.online_labels), args.online_labels_every]      # [T, N | None]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -591,7 +656,10 @@ def patch_mask_line(args, frozen=True):
 
 def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """-> iterator of (image f32 [B,3,H,W], label i64 [B,H,W]) resident on the device, from this rank's batch number `start_batch` on (a
-    resumed run: iterations done x iter_size); with --weak-teacher of (image, label, weak image, item map [B,H,W] u8 | None)."""
+    resumed run: iterations done x iter_size); with --weak-teacher of (image, label, weak image, item map [B,H,W] u8 | None); with
+    --online-labels (trainV1_warmup) of (image, None, weak image | None): the list needs no label column and no label file is opened, the weak
+    image is there exactly when --colour-jitter, --gaussian-blur or --mask-patches is on."""
+    online = getattr(args, "online_labels", None) is not None
     choices = scale_crop_choices(args)
     mix = class_mix_setting(args)
     photo = photometric_setting(args)
@@ -611,14 +679,17 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
             while True:                                     # one global sequence of seeds, dealt round-robin to the ranks
                 yield ms.synthetic_batch(B, H, W, cd, seed=args.random_seed + it * world + rank, device=dev)
                 it += 1
+        if online:                                          # the synthetic labels are ignored; the teacher sees the same batch
+            return ((img, None, None) for (img, _lab) in synth())
         return synth()
     if not args.data_dir_target or not osp.isdir(args.data_dir_target):
         raise SystemExit(f"--data-dir-target {args.data_dir_target!r} is not a directory; pass --synthetic for synthetic batches")
     from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
     from simt_amd.dataset.cityscapes_dataset import cityscapesPseudo
     ds = cityscapesPseudo(args.data_dir_target, args.data_list_target, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
-                          scale_crop=choices, class_mix=mix, photometric=photo, teacher_view=bool(getattr(args, "weak_teacher", False)),
-                          patch_mask=mask)
+                          scale_crop=choices, class_mix=mix, photometric=photo,
+                          teacher_view=bool(getattr(args, "weak_teacher", False)) or bool(online_weak_view(args)),
+                          patch_mask=mask, labels=not online)
     cache, on_epoch = None, None
     if getattr(args, "cache_dataset", "off") == "device":
         from simt_amd.data.cache import DatasetCache, default_budget_bytes
@@ -630,7 +701,7 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
             with Image.open(ds.files[0]["img"]) as im:
                 held = im.size
         budget = default_budget_bytes(n_distinct, held) if gb is None else int(gb * 1e9)
-        cache = DatasetCache(held, with_label=True, budget_bytes=budget, device=dev)
+        cache = DatasetCache(held, with_label=not online, budget_bytes=budget, device=dev)
 
         def on_epoch(epoch, hits, misses, nbytes):
             print(f"dataset cache: rank {rank} epoch {epoch}: {hits} hits, {misses} misses, {nbytes / 1e9:.3f} GB of {budget / 1e9:.3f} GB "
@@ -638,6 +709,10 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=args.random_seed, rank=rank, world=world,
                        hold=max(1, getattr(args, "iter_size", 1)),     # the loop keeps iter_size micro-batches alive per step
                        cache=cache, on_epoch=on_epoch, start_batch=start_batch)
+    if online:
+        if ds.teacher_view:
+            return ((img, None, weak) for (img, _lab, _sizes, _names, weak, _item) in loader)
+        return ((img, None, None) for (img, _lab, _sizes, _names) in loader)
     if ds.teacher_view:
         return ((img, lab, weak, item) for (img, lab, _sizes, _names, weak, item) in loader)
     return ((img, lab) for (img, lab, _sizes, _names) in loader)

@@ -27,6 +27,9 @@ CHECKED_FIELDS = TRAJECTORY_FIELDS + ("B", "H", "W", "dtype", "trainer", "model"
 # Checked too, but ABSENT = False: keywords added after format_version 1 that a trainer writes into `hyper` only when they are on, so that the
 # states of runs without them stay what they were (teacher_view: the weak-view teacher of the SimT trainers)
 SWITCH_FIELDS = ("teacher_view",)
+# The same, with VALUES: absent = off, present = the keyword's value, compared as it is (online_labels = tau, online_labels_every = N: the
+# warm-up trainers' teacher)
+VALUE_FIELDS = ("online_labels", "online_labels_every")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -62,6 +65,11 @@ def hyper_mismatches(saved, current, fields=CHECKED_FIELDS):
 def switch_mismatches(saved, current, fields=SWITCH_FIELDS):
     """Names of the switches (absent = off) in which two `hyper` dicts differ."""
     return [f for f in fields if bool(saved.get(f, False)) != bool(current.get(f, False))]
+
+
+def value_mismatches(saved, current, fields=VALUE_FIELDS):
+    """Names of the valued keywords (absent = off) in which two `hyper` dicts differ: added, dropped, or another value."""
+    return [f for f in fields if _norm(saved.get(f)) != _norm(current.get(f))]
 
 
 def save_atomic(obj, path):
@@ -122,6 +130,10 @@ class TrainStateMixin:
                   trainer=type(self).__name__, model=getattr(self, "model", "v2"), arch=_arch(self), format_version=FORMAT_VERSION)
         if getattr(self, "teacher_view", False):      # (absent = False: a state from before the keyword loads into a trainer without it)
             hy["teacher_view"] = True
+        if getattr(self, "online_labels", None) is not None:      # (absent = off: the states of trainers without the keyword stay what they were)
+            hy["online_labels"] = float(self.online_labels)
+            if self.teacher is not None:
+                hy["online_labels_every"] = int(self.teacher.every)
         return hy
 
     def _nbt_steps(self, key):
@@ -139,6 +151,9 @@ class TrainStateMixin:
         absent without one, and `load_training_state` refuses a state whose `ema` does not fit the trainer's; with the EMA teacher
         (`ema_teacher_every`, simt_amd/ema_teacher.py) also `teacher` = {every, refreshes, params}: the frozen model as the last refresh left it
         (`frozen_sha256` stays the hash of the model the run started beside), refused likewise when the keyword is dropped, added or N differs.
+        The warm-up trainers' online labels (`online_labels`, simt_amd/online_labels.py): `hyper` carries tau and N only when on, `frozen_sha256`
+        is that of the start model, a moving teacher travels as the same `teacher` entry, and `accumulators` gains the cumulative label counts
+        with their host twin; without the keyword the dict is what it was.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -157,6 +172,8 @@ class TrainStateMixin:
             ts["accumulators"] = {"lout": self.lout.detach().cpu()}
         else:      # the warm-up trainers: the head's scalars (overwritten by every launch) and the bad-label accumulator beside them
             ts["accumulators"] = {"hout": self.hout[:16].detach().cpu(), "bad_labels": self.bad_labels.detach().cpu()}
+            if getattr(self, "online_labels", None) is not None:      # the cumulative label counts and their host twin: `labelled` resumes exactly
+                ts["accumulators"].update(label_counts=self.label_counts.detach().cpu(), counts_reported=[int(c) for c in self._counts_reported])
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
             ts["ema"] = self.ema.state()
         if getattr(self, "teacher", None) is not None:      # the EMA teacher (simt_amd/ema_teacher.py): every, refresh count, the frozen model as it is now
@@ -170,7 +187,8 @@ class TrainStateMixin:
         naming what differs, otherwise; nothing has been changed then.  Every packed operand is rebuilt from the loaded masters
         (`plan.repack()`).  `state_dict()` afterwards reports the `num_batches_tracked` an uninterrupted run reports (the steps taken are
         counted once).  Data parallel: every rank loads the same dict (see training_state)."""
-        bad = hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state())
+        bad = (hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state()) +
+               value_mismatches(ts["hyper"], self._hyper_state()))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -224,6 +242,9 @@ class TrainStateMixin:
         else:
             self.hout[:16].copy_(acc["hout"])
             self.bad_labels.copy_(acc["bad_labels"])
+            if getattr(self, "online_labels", None) is not None:
+                self.label_counts.copy_(acc["label_counts"])
+                self._counts_reported = [int(c) for c in acc["counts_reported"]]
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "ema", None) is not None:
             self.ema.load_state(ts["ema"])
