@@ -481,6 +481,46 @@ int simt_pseudo_conf_u8(const float* la, int ha, int wa, int lda, int B, int H, 
                         int64_t* counts, int64_t* hist, simt_stream_t stream);
 int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, int hia, int wia, int B, int H, int W, int C, const float* thr,
                          uint8_t* out, int64_t* counts, int64_t* hist, simt_stream_t stream);
+/* class-balanced online labels: one threshold per class, kept on the DEVICE and moved by every micro-batch.
+ * State: thr[C], fp32, initialised by the caller (the warm-up trainers: to T for every class).  Per micro-batch, two launches:
+ *
+ * simt_online_label_cb -- label with the thresholds as they stand, and count in the same pass.  (arg, conf) of a pixel are those of
+ *   simt_online_label (family 0: simt_pseudo_conf_u8's; family 1: simt_pseudo_conf2_u8's called with hia = H, wia = W), bit for bit.
+ *   label[b][y][x] = arg where conf >= thr[arg], 255 elsewhere (a NaN confidence or threshold gives 255): the rule of simt_pseudo_conf*_u8;
+ *   counts[C+1] as simt_online_label; hist[arg][bin] += 1 for EVERY pixel, bin as simt_pseudo_conf_u8 defines it (SIMT_CONF_BINS bins).
+ *   thr is read from device memory when the kernel runs (into LDS at block start): no host copy, no synchronisation.
+ *   Refused (SIMT_ERR_INVALID, nothing launched): a NULL pointer, a size <= 0, C > ld, C > 64 (the LDS histogram), another family, label or
+ *   hist not 8-byte aligned, thr not 4-byte aligned, the 2^31 limit of family 1.
+ *
+ * simt_class_thresholds -- derive the batch thresholds from hist, fold them into thr, zero hist.  One small launch, no global atomics.
+ *   Per class c, with n = the sum of hist[c][:] (exact 64-bit integers):
+ *     n == 0: thr[c] stays, t = 0;
+ *     else  k = min((int64)rint((double)n * drop), n - 1)          (drop = 1 - P formed by the caller in double; rint: half to even)
+ *           b = the smallest bin whose inclusive cumulative count exceeds k
+ *           t = fminf((float)b / SIMT_CONF_BINS, cap)
+ *           thr[c] = thr[c] + omd * (t - thr[c])                    (fp32; subtract, multiply, add each rounded on its own: no FMA)
+ *   t_out (optional) receives t; hist is zero afterwards (plain stores).  This is class_thresholds() of tools/make_pseudo_labels.py with
+ *   cap, followed by the arithmetic form of simt_ema_desc.
+ *   Refused: NULL hist / thr, C outside 1..64, hist not 8-byte aligned, thr / t_out not 4-byte aligned, drop outside [0, 1), omd outside
+ *   (0, 1], a NaN cap. */
+typedef struct {
+  const float* fix;        /* as simt_online_label_desc */
+  int64_t* label;          /* out [B][H][W] */
+  int64_t* counts;         /* [C+1], accumulated */
+  int64_t* hist;           /* [C][SIMT_CONF_BINS], accumulated */
+  const float* thr;        /* [C] fp32 in DEVICE memory */
+  int32_t B, h, w, ld, H, W, C, family;
+} simt_online_label_cb_desc;
+int simt_online_label_cb(const simt_online_label_cb_desc* d, simt_stream_t stream);
+typedef struct {
+  int64_t* hist;           /* [C][SIMT_CONF_BINS]: read, then zeroed */
+  float* thr;              /* [C] in / out */
+  float* t_out;            /* [C] out: the batch thresholds (0 for a class without pixels), or NULL */
+  double drop;             /* 1 - P */
+  int32_t C;
+  float cap, omd;          /* omd = (float)(1 - M) */
+} simt_class_thresholds_desc;
+int simt_class_thresholds(const simt_class_thresholds_desc* d, simt_stream_t stream);
 /* test-time augmentation (mirror / multi-scale): the label of n <= SIMT_TTA_MAX maps ("terms", one forward each), any of which may belong
  * to the horizontally mirrored frame.  Value of term t, channel c, at label pixel (b, y, x), fp32:
  *   one-resample family (hi == wi == 0): the value simt_upsample_sum_argmax forms for that map (align_corners=True, ATen's association);

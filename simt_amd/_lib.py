@@ -193,7 +193,19 @@ class OnlineLabelDesc(C.Structure):
                 ("C", i32), ("family", i32), ("threshold", f32)]
 
 
-TTA_MAX = 8              # include/simt_hip.h SIMT_TTA_MAX
+class OnlineLabelCbDesc(C.Structure):
+    """simt_online_label_cb_desc (include/simt_hip.h): simt_online_label with per-class thresholds read from device memory, and the
+    confidence histogram of the same pass."""
+    _fields_ = [("fix", c_p), ("label", c_p), ("counts", c_p), ("hist", c_p), ("thr", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32),
+                ("H", i32), ("W", i32), ("C", i32), ("family", i32)]
+
+
+class ClassThresholdsDesc(C.Structure):
+    """simt_class_thresholds_desc (include/simt_hip.h): the histogram -> the batch thresholds, folded into the device thresholds; hist zeroed."""
+    _fields_ = [("hist", c_p), ("thr", c_p), ("t_out", c_p), ("drop", C.c_double), ("C", i32), ("cap", f32), ("omd", f32)]
+
+
+TTA_MAX = 8             # include/simt_hip.h SIMT_TTA_MAX
 
 
 class TtaTerm(C.Structure):
@@ -285,6 +297,8 @@ SIGNATURES = {
     "simt_pseudo_conf_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
     "simt_pseudo_conf2_u8": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p, c_p, c_p, c_p]),
     "simt_online_label": (_I, [C.POINTER(OnlineLabelDesc), c_p]),
+    "simt_online_label_cb": (_I, [C.POINTER(OnlineLabelCbDesc), c_p]),
+    "simt_class_thresholds": (_I, [C.POINTER(ClassThresholdsDesc), c_p]),
     "simt_tta_label": (_I, [C.POINTER(TtaDesc), c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),

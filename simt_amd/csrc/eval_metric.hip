@@ -907,6 +907,169 @@ extern "C" int simt_pseudo_conf2_u8(const float* la, int ha, int wa, int lda, in
   return SIMT_OK;
 }
 
+// ---- class-balanced online labels: the combined kernels above (STATS and LABELS) with the output side of the online-label
+// kernels -- int64 labels through ol_store -- and the thresholds read from DEVICE memory into ConfShared::thr at block start, so that the
+// launch behind this one (class_thresholds_kernel) can move them without the host.  Every device function is the export kernels' own:
+// (arg, conf), the bin, the rule (kept iff conf >= thr[arg]), the in-wave key aggregation and the flushes are theirs bit for bit.  Families, block
+// sizes and grid caps: those of simt_online_label.
+struct OnlineCbOut {
+  long long* label;             // [B][H][W]
+  unsigned long long* counts;   // [C+1], accumulated
+  unsigned long long* hist;     // [C][CONF_BINS], accumulated
+  const float* thr;             // [C], device memory
+};
+
+template <int BLOCK>
+__device__ __forceinline__ void ol_cb_init(ConfShared<true>& sh, const OnlineCbOut& o, int C) {
+  for (int i = threadIdx.x; i < C; i += BLOCK) sh.thr[i] = o.thr[i];
+  for (int i = threadIdx.x; i < C * CONF_BINS; i += BLOCK) sh.hist[i] = 0u;
+  pl_hist_init<BLOCK>(sh.counts, C + 1);
+}
+template <int BLOCK>
+__device__ __forceinline__ void ol_cb_flush(const ConfShared<true>& sh, const OnlineCbOut& o, int C) {
+  pl_hist_flush<BLOCK>(sh.counts, C + 1, o.counts);
+  pl_hist_flush<BLOCK>(sh.hist, C * CONF_BINS, o.hist);
+}
+
+__global__ __launch_bounds__(PL_BLOCK) void online_label_cb_kernel(PseudoArgs a, OnlineCbOut o) {
+  __shared__ ConfShared<true> sh;
+  ol_cb_init<PL_BLOCK>(sh, o, a.C);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL_BLOCK; base < P; base += (long)gridDim.x * PL_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int key = 0u, lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      conf_pixel<true, true>(sh, pseudo_pixel<1>(a, (int)(t / a.H), (int)(t % a.H), x), key, lab);
+    }
+    conf_hist_add(p < P, key, sh.hist);
+    ol_store(lab, p, P, a.C, o.label, sh.counts);
+  }
+  ol_cb_flush<PL_BLOCK>(sh, o, a.C);
+}
+
+template <int V>
+__global__ __launch_bounds__(PL2_BLOCK) void online_label2_cb_kernel(Online2Args a, OnlineCbOut o) {
+  __shared__ ConfShared<true> sh;
+  ol_cb_init<PL2_BLOCK>(sh, o, a.C);
+  const long P = (long)a.B * a.H * a.W;
+  for (long base = (long)blockIdx.x * PL2_BLOCK; base < P; base += (long)gridDim.x * PL2_BLOCK) {
+    const long p = base + threadIdx.x;
+    unsigned int key = 0u, lab = 0u;
+    if (p < P) {
+      const int x = (int)(p % a.W);
+      const long t = p / a.W;
+      conf_pixel<true, true>(sh, up2_confident<V, true>(a.s, a.C, 0.f, (int)(t / a.H), (int)(t % a.H), x), key, lab);
+    }
+    conf_hist_add(p < P, key, sh.hist);
+    ol_store(lab, p, P, a.C, o.label, sh.counts);
+  }
+  ol_cb_flush<PL2_BLOCK>(sh, o, a.C);
+}
+
+extern "C" int simt_online_label_cb(const simt_online_label_cb_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->fix && d->label && d->counts && d->hist && d->thr);
+  SIMT_CHECK(d->B > 0 && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->C <= CONF_MAX_C && d->C <= d->ld);
+  SIMT_CHECK(d->family == 0 || d->family == 1);
+  SIMT_CHECK(((uintptr_t)d->label & 7) == 0 && ((uintptr_t)d->hist & 7) == 0 && ((uintptr_t)d->thr & 3) == 0);
+  const int B = d->B, h = d->h, w = d->w, ld = d->ld, H = d->H, W = d->W;
+  const long P = (long)B * H * W;
+  OnlineCbOut o;
+  o.label = (long long*)d->label; o.counts = (unsigned long long*)d->counts; o.hist = (unsigned long long*)d->hist; o.thr = d->thr;
+  if (d->family == 0) {
+    PseudoArgs a;
+    a.la = d->fix; a.lb = nullptr; a.out = nullptr; a.counts = nullptr;
+    a.B = B; a.ha = h; a.wa = w; a.lda = ld; a.hb = 0; a.wb = 0; a.ldb = 0; a.H = H; a.W = W; a.C = d->C;
+    a.sya = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    a.sxa = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    a.syb = 0.f; a.sxb = 0.f; a.threshold = 0.f;
+    long grid = (P + PL_BLOCK - 1) / PL_BLOCK;
+    if (grid > PL_MAX_GRID) grid = PL_MAX_GRID;
+    hipLaunchKernelGGL(online_label_cb_kernel, dim3((unsigned)grid), dim3(PL_BLOCK), 0, (hipStream_t)stream, a, o);
+  } else {
+    SIMT_CHECK((long)B * h * w * ld < 2147483647L);          // the taps' element offsets are 32-bit (Up2Taps)
+    Online2Args a;
+    fill_up2(a.s, d->fix, h, w, ld, H, W, H, W);
+    a.B = B; a.H = H; a.W = W; a.C = d->C; a.threshold = 0.f;
+    long grid = (P + PL2_BLOCK - 1) / PL2_BLOCK;
+    if (grid > PL2_MAX_GRID) grid = PL2_MAX_GRID;
+    const dim3 g((unsigned)grid), blk(PL2_BLOCK);
+    if (ld % 4 == 0 && ((uintptr_t)d->fix & 15) == 0)
+      hipLaunchKernelGGL(online_label2_cb_kernel<4>, g, blk, 0, (hipStream_t)stream, a, o);
+    else
+      hipLaunchKernelGGL(online_label2_cb_kernel<1>, g, blk, 0, (hipStream_t)stream, a, o);
+  }
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+// The thresholds' side: class_thresholds() of tools/make_pseudo_labels.py on the device, the fold into thr, and the histogram's reset.  ONE
+// workgroup of CT_BLOCK / 64 waves; wave v takes classes v, v + CT_BLOCK / 64, ...  Lane l holds bins 4l .. 4l+3 of the class's row (the
+// row is 64 lanes x 4 bins = CONF_BINS), an inclusive prefix sum of the lanes' 64-bit totals runs over the wave (6 shuffle steps), the
+// first lane whose inclusive sum exceeds k is found with one ballot, and that lane walks its 4 bins.  Integer arithmetic throughout; the
+// only floating point is (double)n * drop (n < 2^53: exact conversion, one rounding, then rint: half to even -- np.round of the same
+// product) and the three fp32 operations of the fold.  The lane then zeroes its 4 bins.  No LDS, no atomics.
+constexpr int CT_BLOCK = 256;
+static_assert(CONF_BINS == 64 * 4, "class_thresholds_kernel: one wave holds one row, four bins per lane");
+
+struct ClassThrArgs {
+  unsigned long long* hist;
+  float* thr;
+  float* t_out;
+  double drop;
+  int C;
+  float cap, omd;
+};
+
+__global__ __launch_bounds__(CT_BLOCK) void class_thresholds_kernel(ClassThrArgs a) {
+#pragma clang fp contract(off)
+  const int lane = (int)(threadIdx.x & 63);
+  for (int c = (int)(threadIdx.x >> 6); c < a.C; c += CT_BLOCK / 64) {      // uniform over the wave
+    unsigned long long* row = a.hist + (long)c * CONF_BINS + 4 * lane;
+    const unsigned long long h0 = row[0], h1 = row[1], h2 = row[2], h3 = row[3];
+    const unsigned long long mine = (h0 + h1) + (h2 + h3);
+    unsigned long long incl = mine;
+    for (int s = 1; s < 64; s <<= 1) {
+      const unsigned long long up = __shfl_up(incl, s, 64);
+      if (lane >= s) incl += up;
+    }
+    const long long n = (long long)__shfl(incl, 63, 64);
+    row[0] = 0ull; row[1] = 0ull; row[2] = 0ull; row[3] = 0ull;
+    float t = 0.f;
+    if (n > 0) {
+      long long k = (long long)rint((double)n * a.drop);
+      if (k > n - 1) k = n - 1;
+      const unsigned long long over = __ballot(incl > (unsigned long long)k);      // never empty: lane 63 holds n > k
+      const int first = __ffsll(over) - 1;
+      const unsigned long long before = incl - mine;      // the exclusive prefix
+      const int j = before + h0 > (unsigned long long)k ? 0 : before + h0 + h1 > (unsigned long long)k ? 1 :
+                    before + h0 + h1 + h2 > (unsigned long long)k ? 2 : 3;
+      const int b = __shfl(4 * lane + j, first, 64);
+      t = fminf((float)b / (float)CONF_BINS, a.cap);
+      if (lane == 0) {
+        const float old = a.thr[c];
+        const float diff = t - old;
+        const float step = a.omd * diff;
+        a.thr[c] = old + step;
+      }
+    }
+    if (lane == 0 && a.t_out) a.t_out[c] = t;
+  }
+}
+
+extern "C" int simt_class_thresholds(const simt_class_thresholds_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->hist && d->thr && d->C > 0 && d->C <= CONF_MAX_C);
+  SIMT_CHECK(((uintptr_t)d->hist & 7) == 0 && ((uintptr_t)d->thr & 3) == 0 && ((uintptr_t)d->t_out & 3) == 0);
+  SIMT_CHECK(d->drop >= 0.0 && d->drop < 1.0 && d->omd > 0.0f && d->omd <= 1.0f && d->cap == d->cap);      // (a NaN fails every comparison)
+  ClassThrArgs a;
+  a.hist = (unsigned long long*)d->hist; a.thr = d->thr; a.t_out = d->t_out;
+  a.drop = d->drop; a.C = d->C; a.cap = d->cap; a.omd = d->omd;
+  hipLaunchKernelGGL(class_thresholds_kernel, dim3(1), dim3(CT_BLOCK), 0, (hipStream_t)stream, a);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
 // ---- test-time augmentation: the label of up to SIMT_TTA_MAX maps, each of which may belong to the horizontally mirrored frame (the
 // reference's offline tools import ttach, compute_ClassDistribution.py:6, compute_ConfusionMatrix.py:6, and never use it).  A term is one
 // forward's low-res map; its value at a label pixel is the old kernels' value -- bil_taps + ATen's association for the one-resample

@@ -18,9 +18,18 @@ simt_amd/ema_teacher.py as they are, directly behind `ema.update()`; without N i
 
 `losses()` gains `labelled`: the share of pixels that received a label since the previous call -- the host diffs the cumulative device counts,
 as it does for the bad-label counter.  Rank-local under data parallelism.
+
+Class-balanced (keywords `online_labels_balanced=P` / `online_labels_momentum=M`, flags --online-labels-balanced /
+--online-labels-momentum): one threshold PER CLASS, kept on the device.  `label_thr[C]` starts at tau; step 3 becomes `simt_online_label_cb`
+(label = arg where conf >= thr[arg], and the [C][256] histogram of the confidences in the same pass) followed by `simt_class_thresholds` on the
+same stream: per class the threshold that keeps the share P of THIS batch's pixels (`class_thresholds` of tools/make_pseudo_labels.py, capped
+at tau), folded into the state with momentum M, and the histogram zeroed.  A batch is therefore labelled with the thresholds of the batches
+before it (IAST's ordering), and nothing waits for the host.  `balanced_update` below restates the second launch in numpy.  `losses()` gains
+`label_thresholds`.  Rank-local, as `labelled` is.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -29,6 +38,9 @@ from .ema_teacher import TeacherMixin, check_every
 from .engine import side_stream
 
 DEFAULT_THRESHOLD = 0.968      # DACS / DAFormer
+DEFAULT_PORTION = 0.5          # BDL's label generator keeps the more confident half of every class
+DEFAULT_MOMENTUM = 0.9         # IAST's exponential average of the per-class thresholds
+MAX_BALANCED_CLASSES = 64      # CONF_MAX_C of csrc/eval_metric.hip: the confidence histogram lives in LDS
 
 
 def check_threshold(tau):
@@ -58,6 +70,53 @@ def check_settings(online_labels, online_labels_every, ema_decay):
     return tau, every
 
 
+def check_balanced(online_labels_balanced, online_labels_momentum, tau, num_classes):
+    """The two keywords of the class-balanced thresholds -> (P | None, M | None); `tau` is check_settings' first value.  ValueError that
+    starts with the keyword that does not fit."""
+    if online_labels_balanced is None:
+        if online_labels_momentum is not None:
+            raise ValueError("online_labels_momentum needs online_labels_balanced: it averages the per-class thresholds, and this trainer keeps none")
+        return None, None
+    what = "expected the share of every class's pixels to keep, 0 < P <= 1"
+    try:
+        p = float(online_labels_balanced)
+    except (TypeError, ValueError):
+        raise ValueError(f"online_labels_balanced {online_labels_balanced!r}: {what}") from None
+    if isinstance(online_labels_balanced, bool) or not (0.0 < p <= 1.0):
+        raise ValueError(f"online_labels_balanced {online_labels_balanced!r}: {what}")
+    if tau is None:
+        raise ValueError("online_labels_balanced needs online_labels: it balances the teacher's labels, and this trainer has no teacher")
+    if num_classes > MAX_BALANCED_CLASSES:
+        raise ValueError(f"online_labels_balanced with num_classes = {num_classes}: the confidence histogram holds at most {MAX_BALANCED_CLASSES} classes")
+    if online_labels_momentum is None:
+        return p, DEFAULT_MOMENTUM
+    what = "expected the thresholds' momentum, 0 <= M < 1"
+    try:
+        m = float(online_labels_momentum)
+    except (TypeError, ValueError):
+        raise ValueError(f"online_labels_momentum {online_labels_momentum!r}: {what}") from None
+    if isinstance(online_labels_momentum, bool) or not (0.0 <= m < 1.0):
+        raise ValueError(f"online_labels_momentum {online_labels_momentum!r}: {what}")
+    return p, m
+
+
+def balanced_update(thr, hist, P, T, M):
+    """`simt_class_thresholds` in numpy (steps 3 and 4 of DESIGN 7.17) -> (the new thresholds, the batch thresholds t), float32 [C] each.
+
+    t = class_thresholds(hist, P, cap=T); for every class with a pixel in `hist`: thr + omd * (t - thr) with omd = float32(1 - M), each of
+    the three float32 operations rounded on its own (the form csrc/ema.hip pins); a class without pixels keeps its threshold."""
+    from .tools.make_pseudo_labels import class_thresholds
+    hist = np.asarray(hist)
+    thr = np.asarray(thr, dtype=np.float32)
+    t = class_thresholds(hist, P, cap=T)
+    omd = np.float32(1.0 - M)
+    diff = (t - thr).astype(np.float32)
+    step = (omd * diff).astype(np.float32)
+    moved = (thr + step).astype(np.float32)
+    seen = hist.astype(np.int64).sum(axis=1) > 0
+    return np.where(seen, moved, thr).astype(np.float32), t
+
+
 def labelled_share(counts, reported):
     """counts: the cumulative [C+1] label counts (classes, then the 255s); reported: [labelled, pixels] already handed out.  -> (share of the
     pixels counted since that received a label -- 0.0 when none were counted --, the new `reported`)."""
@@ -70,10 +129,11 @@ class OnlineLabelMixin(TeacherMixin):
     """The teacher's side of WarmupTrainer and WarmupSingleTrainer.  The trainer builds `fixed_params`, `fixed` (the eval-mode plan), `_fix_fwd`
     (its forward launches) and names the teacher's low-res output; this class owns the per-step launches, the counts and the read-out."""
 
-    def _init_online(self, tau, every, fix_out, ldf, family):
-        """tau / every: check_settings' pair (tau None: off -- no buffer, no launch).  fix_out: the teacher's low-res logits [B*h*w][ldf];
+    def _init_online(self, tau, every, fix_out, ldf, family, balanced=(None, None)):
+        """tau / every: check_settings' pair (tau None: off -- no buffer, no launch).  balanced: check_balanced's pair (P None: one threshold).  fix_out: the teacher's low-res logits [B*h*w][ldf];
         family: 0 = probabilities resampled align_corners=True (DeepLab-v2, VGG16), 1 = logits resampled half-pixel (DeepLabv3)."""
         self.online_labels, self.teacher = tau, None
+        self.online_labels_balanced, self.online_labels_momentum = balanced
         if tau is None:
             return
         dev = self.dev
@@ -86,7 +146,23 @@ class OnlineLabelMixin(TeacherMixin):
         d.fix, d.label, d.counts = self.fixp.data_ptr(), self.label.data_ptr(), self.label_counts.data_ptr()
         d.B, d.h, d.w, d.ld, d.H, d.W, d.C, d.family, d.threshold = self.B, self.h, self.w, ldf, self.H, self.W, self.C, family, tau
         self.online_desc = d
+        if self.online_labels_balanced is not None:
+            self._init_balanced(d)
         self._init_teacher(every)          # None: the teacher stays at the start weights (simt_amd/ema_teacher.py)
+
+    def _init_balanced(self, one):
+        """The per-class thresholds (start: tau everywhere), the histogram the two launches share (zero between micro-batches) and their
+        descriptors; `one` is the descriptor of simt_online_label, whose geometry they take."""
+        P, M, dev = self.online_labels_balanced, self.online_labels_momentum, self.dev
+        self.label_thr = torch.full((self.C,), self.online_labels, device=dev, dtype=torch.float32)
+        self.label_hist = torch.zeros(self.C, L.CONF_BINS, device=dev, dtype=torch.int64)
+        d = L.OnlineLabelCbDesc()
+        d.fix, d.label, d.counts, d.hist, d.thr = one.fix, one.label, one.counts, self.label_hist.data_ptr(), self.label_thr.data_ptr()
+        d.B, d.h, d.w, d.ld, d.H, d.W, d.C, d.family = one.B, one.h, one.w, one.ld, one.H, one.W, one.C, one.family
+        t = L.ClassThresholdsDesc()
+        t.hist, t.thr, t.t_out = self.label_hist.data_ptr(), self.label_thr.data_ptr(), None
+        t.drop, t.C, t.cap, t.omd = 1.0 - P, self.C, self.online_labels, 1.0 - M      # (ctypes rounds cap and omd to float32)
+        self.online_cb_desc, self.thresholds_desc = d, t
 
     def _views(self, label, teacher_image, n):
         """step()'s `label` / `teacher_image` as lists of n = iter_size entries; ValueError when they do not fit the trainer."""
@@ -125,7 +201,11 @@ class OnlineLabelMixin(TeacherMixin):
             self._fix_fwd.run()
             if not self._family:
                 ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
-            L.call("simt_online_label", C.byref(self.online_desc), side.cuda_stream)
+            if self.online_labels_balanced is None:
+                L.call("simt_online_label", C.byref(self.online_desc), side.cuda_stream)
+            else:          # label with the thresholds as they stand and count; then move them and zero the histogram
+                L.call("simt_online_label_cb", C.byref(self.online_cb_desc), side.cuda_stream)
+                L.call("simt_class_thresholds", C.byref(self.thresholds_desc), side.cuda_stream)
             ev_lab = torch.cuda.Event()
             ev_lab.record(side)
         main.wait_event(ev_lab)
@@ -134,4 +214,6 @@ class OnlineLabelMixin(TeacherMixin):
         """losses(): adds `labelled` to `out` (one more device-to-host copy: int64 counts do not ride in the float scalars)."""
         if self.online_labels is not None:
             out["labelled"], self._counts_reported = labelled_share(self.label_counts.cpu().tolist(), self._counts_reported)
+            if getattr(self, "online_labels_balanced", None) is not None:
+                out["label_thresholds"] = self.label_thr.cpu().tolist()
         return out

@@ -27,7 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
-from .online_labels import OnlineLabelMixin, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_settings
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -493,11 +493,15 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     Same engine as SimTTrainer: TrunkPlan forward/backward, the fused head kernels in mode 1, simt_sgd_multi."""
 
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
-                 online_labels=None, online_labels_every=None):
+                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None):
         """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
-        online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was."""
+        online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
+        online_labels_balanced=P in (0, 1] (needs online_labels): one threshold per class, kept on the device -- it starts at tau and
+        every micro-batch moves it towards the value that keeps the share P of that class's pixels, never above tau, with momentum
+        online_labels_momentum=M in [0, 1) (default 0.9).  None: the one threshold tau."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
+        balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -541,7 +545,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self.it_done = 0
         self._init_ema(ema_decay)
         fix = (self.fixed.out["x2"], self.fixed.ldp["x2"]) if tau is not None else (None, 0)
-        self._init_online(tau, every, *fix, 0)      # (family 0: the posterior is resampled align_corners=True)
+        self._init_online(tau, every, *fix, 0, balanced)      # (family 0: the posterior is resampled align_corners=True)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets

@@ -28,7 +28,7 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .online_labels import OnlineLabelMixin, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_settings
 from .step import check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
@@ -289,12 +289,14 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
-                 online_labels=None, online_labels_every=None):
+                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
-        keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every: as for step.WarmupTrainer; the
+        keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
+        online_labels_momentum: as for step.WarmupTrainer; the
         teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample)."""
         assert model in ("v3", "vgg")
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
+        balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -362,7 +364,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         SimTSingleTrainer._build_sgd(self)
         self.it_done = 0
         self._init_ema(ema_decay)
-        self._init_online(tau, every, fix_out, ldf, half)      # (family 1 = the half-pixel model, DeepLabv3)
+        self._init_online(tau, every, fix_out, ldf, half, balanced)      # (family 1 = the half-pixel model, DeepLabv3)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets

@@ -122,6 +122,18 @@ def labelled_text(args, l):
     return " labelled = {0:.3f}".format(l["labelled"]) if args.online_labels is not None else ""
 
 
+def thresholds_text(args, l):
+    """` thr = <min>..<max>` of the loss line, the lowest and the highest per-class threshold: only with --online-labels-balanced."""
+    if getattr(args, "online_labels_balanced", None) is None:
+        return ""
+    return " thr = {0:.3f}..{1:.3f}".format(min(l["label_thresholds"]), max(l["label_thresholds"]))
+
+
+def balanced_kwargs(args):
+    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum."""
+    return {"online_labels_balanced": args.online_labels_balanced, "online_labels_momentum": args.online_labels_momentum}
+
+
 def check_model(args):
     """--model names one of trainV2_simt.MODELS (as trainV2_simt.check_model_args checks it); --iter-size works for all three."""
     if args.model not in MODELS:
@@ -166,7 +178,8 @@ def main(argv=None):
     dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
-                       online_labels=args.online_labels, online_labels_every=args.online_labels_every)
+                       online_labels=args.online_labels, online_labels_every=args.online_labels_every,
+                       **balanced_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         online_label_line(args)
@@ -190,7 +203,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -253,7 +266,8 @@ def main_single(args):
     arch = {"layers": layers} if model == "v3" else None
     eval_layers = layers if model == "v3" else None
     tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
-                             ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every)
+                             ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every,
+                             **balanced_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         online_label_line(args)
@@ -278,7 +292,7 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

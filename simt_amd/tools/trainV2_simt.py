@@ -323,9 +323,30 @@ def _online_every(text):
     return n
 
 
+def _online_portion(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 < v <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected the share of every class's pixels to keep, 0 < P <= 1")
+    return v
+
+
+def _online_momentum(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected the thresholds' momentum, 0 <= M < 1")
+    return v
+
+
 def add_online_label_args(p):
-    """--online-labels / --online-labels-every of trainV1_warmup; `check_online_label_args` holds their refusals."""
-    from simt_amd.online_labels import DEFAULT_THRESHOLD
+    """--online-labels / --online-labels-every (DESIGN 7.16) and --online-labels-balanced / --online-labels-momentum (7.17) of trainV1_warmup;
+    `check_online_label_args` holds their refusals."""
+    from simt_amd.online_labels import DEFAULT_PORTION, DEFAULT_THRESHOLD
     p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
                    help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
                         "labels every batch on the device, pixels whose confidence is not above T are ignored (no value: T = "
@@ -334,6 +355,13 @@ def add_online_label_args(p):
     p.add_argument("--online-labels-every", type=_online_every, default=None, metavar="N",
                    help="with --online-labels and --ema: the teacher follows the weight EMA, refreshed behind every N-th update (an integer "
                         ">= 1; simt_amd/ema_teacher.py).  Default: the teacher stays at the start weights")
+    p.add_argument("--online-labels-balanced", type=_online_portion, nargs="?", const=DEFAULT_PORTION, default=None, metavar="P",
+                   help="with --online-labels: one confidence threshold per class, kept on the device (CBST / IAST).  Each starts at T; every batch "
+                        "moves it towards the value that keeps the share P of that class's pixels, never above T (no value: P = "
+                        f"{DEFAULT_PORTION}; 0 < P <= 1).  A batch is labelled with the thresholds of the batches before it.  At most 64 classes.  "
+                        "Default: the one threshold T")
+    p.add_argument("--online-labels-momentum", type=_online_momentum, default=None, metavar="M",
+                   help="with --online-labels-balanced: thr <- M * thr + (1 - M) * the batch's threshold (0 <= M < 1).  Default: 0.9")
 
 
 def check_online_label_args(p, args):
@@ -343,6 +371,12 @@ def check_online_label_args(p, args):
         p.error("--online-labels-every needs --online-labels: it moves the teacher that makes the labels")
     if args.online_labels_every is not None and args.ema is None:
         p.error("--online-labels-every needs --ema: the teacher follows the weight EMA")
+    if args.online_labels_balanced is not None and args.online_labels is None:
+        p.error("--online-labels-balanced needs --online-labels: it balances the teacher's labels")
+    if args.online_labels_momentum is not None and args.online_labels_balanced is None:
+        p.error("--online-labels-momentum needs --online-labels-balanced: it averages the per-class thresholds")
+    if args.online_labels_balanced is not None and args.num_classes > 64:
+        p.error(f"--online-labels-balanced with --num-classes {args.num_classes}: the confidence histogram holds at most 64 classes")
     if args.online_labels is not None and args.class_mix is not None:
         p.error("--online-labels cannot be combined with --class-mix: the mix reads the classes to paste from the partner's label, and "
                 "the teacher makes the labels behind the loader")
@@ -356,7 +390,25 @@ def online_label_line(args):
     who = "a fixed teacher (the start weights)" if n is None else f"a teacher that follows the weight EMA (decay {args.ema}), refreshed every {n} update(s)"
     weak = online_weak_view(args)
     print(f"online labels: {who} labels every batch, kept where its confidence is > {args.online_labels}; the teacher sees "
-          f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}")
+          f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}" + balanced_clause(args))
+
+
+def online_balanced(args):
+    """-> [P, M] of --online-labels-balanced / --online-labels-momentum (M: the default where the flag is absent), or None when off."""
+    if getattr(args, "online_labels", None) is None or getattr(args, "online_labels_balanced", None) is None:
+        return None
+    from simt_amd.online_labels import DEFAULT_MOMENTUM
+    m = args.online_labels_momentum
+    return [float(args.online_labels_balanced), float(DEFAULT_MOMENTUM if m is None else m)]
+
+
+def balanced_clause(args):
+    """What --online-labels-balanced adds to the start-up line ("" without it)."""
+    pm = online_balanced(args)
+    if pm is None:
+        return ""
+    return (f"; class-balanced: one threshold per class, from {args.online_labels} towards the value that keeps the share {pm[0]} of the class's "
+            f"pixels in a batch (momentum {pm[1]}), never above {args.online_labels}")
 
 
 def online_weak_view(args):
@@ -526,7 +578,7 @@ class EmaSnapshots:
 
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
-                "online_labels": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_labels": False, "online_labels_balanced": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -553,6 +605,8 @@ def run_identity(args, class_dist):
         ident["weak_teacher"] = True
     if getattr(args, "online_labels", None) is not None:
         ident["online_labels"] = [float(args.online_labels), args.online_labels_every]      # [T, N | None]
+        if online_balanced(args) is not None:
+            ident["online_labels_balanced"] = online_balanced(args)      # [P, M]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

@@ -30,6 +30,9 @@ SWITCH_FIELDS = ("teacher_view",)
 # The same, with VALUES: absent = off, present = the keyword's value, compared as it is (online_labels = tau, online_labels_every = N: the
 # warm-up trainers' teacher)
 VALUE_FIELDS = ("online_labels", "online_labels_every")
+# and the class-balanced thresholds of that teacher's labels (online_labels_balanced = P, online_labels_momentum = M: DESIGN 7.17), compared
+# through value_mismatches(..., fields=BALANCE_FIELDS)
+BALANCE_FIELDS = ("online_labels_balanced", "online_labels_momentum")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -134,6 +137,9 @@ class TrainStateMixin:
             hy["online_labels"] = float(self.online_labels)
             if self.teacher is not None:
                 hy["online_labels_every"] = int(self.teacher.every)
+            if getattr(self, "online_labels_balanced", None) is not None:
+                hy["online_labels_balanced"] = float(self.online_labels_balanced)
+                hy["online_labels_momentum"] = float(self.online_labels_momentum)
         return hy
 
     def _nbt_steps(self, key):
@@ -153,7 +159,8 @@ class TrainStateMixin:
         (`frozen_sha256` stays the hash of the model the run started beside), refused likewise when the keyword is dropped, added or N differs.
         The warm-up trainers' online labels (`online_labels`, simt_amd/online_labels.py): `hyper` carries tau and N only when on, `frozen_sha256`
         is that of the start model, a moving teacher travels as the same `teacher` entry, and `accumulators` gains the cumulative label counts
-        with their host twin; without the keyword the dict is what it was.
+        with their host twin; without the keyword the dict is what it was.  With `online_labels_balanced` `hyper` also carries P and M
+        and `accumulators` the per-class thresholds (`label_thresholds`); their histogram is zero between steps and is not stored.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -174,6 +181,8 @@ class TrainStateMixin:
             ts["accumulators"] = {"hout": self.hout[:16].detach().cpu(), "bad_labels": self.bad_labels.detach().cpu()}
             if getattr(self, "online_labels", None) is not None:      # the cumulative label counts and their host twin: `labelled` resumes exactly
                 ts["accumulators"].update(label_counts=self.label_counts.detach().cpu(), counts_reported=[int(c) for c in self._counts_reported])
+                if getattr(self, "online_labels_balanced", None) is not None:
+                    ts["accumulators"]["label_thresholds"] = self.label_thr.detach().cpu()
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
             ts["ema"] = self.ema.state()
         if getattr(self, "teacher", None) is not None:      # the EMA teacher (simt_amd/ema_teacher.py): every, refresh count, the frozen model as it is now
@@ -188,7 +197,7 @@ class TrainStateMixin:
         (`plan.repack()`).  `state_dict()` afterwards reports the `num_batches_tracked` an uninterrupted run reports (the steps taken are
         counted once).  Data parallel: every rank loads the same dict (see training_state)."""
         bad = (hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state()) +
-               value_mismatches(ts["hyper"], self._hyper_state()))
+               value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -245,6 +254,8 @@ class TrainStateMixin:
             if getattr(self, "online_labels", None) is not None:
                 self.label_counts.copy_(acc["label_counts"])
                 self._counts_reported = [int(c) for c in acc["counts_reported"]]
+                if getattr(self, "online_labels_balanced", None) is not None:
+                    self.label_thr.copy_(acc["label_thresholds"])
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "ema", None) is not None:
             self.ema.load_state(ts["ema"])
