@@ -15,7 +15,7 @@ for f in "${SRCS[@]}"; do
   b=$(basename "$f")
   o=$BUILD/${b%.hip}.o
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ conv2_common.h -nt "$o" ] || [ conv2_epilogue.h -nt "$o" ] || [ ../../include/simt_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ conv2_common.h -nt "$o" ] || [ conv2_epilogue.h -nt "$o" ] || [ bilinear_taps.h -nt "$o" ] || [ ../../include/simt_hip.h -nt "$o" ]; then
     $HIPCC $FLAGS -c "$f" -o "$o" &
     pids+=($!)
   fi

@@ -7,9 +7,9 @@ and every micro-batch
 
   1. the teacher's forward runs on the side stream beside the student's (the event pattern of SimTTrainer._micro_batch),
   2. family 0 (DeepLab-v2, VGG16): `simt_softmax_rows` of its low-res logits,
-  3. ONE `simt_online_label` launch (csrc/eval_metric.hip) writes the int64 labels straight into `trainer.label`, the buffer the head
-     descriptor already points at -- arg-max where the resampled posterior's maximum is > tau, 255 elsewhere; the label rule and the device
-     functions of the export kernels' confidence mode -- and adds the labels' counts to `label_counts`,
+  3. ONE `simt_online_label` launch (csrc/label_sweep.hip) writes the int64 labels straight into `trainer.label`, the buffer the head
+     descriptor already points at -- arg-max where the resampled posterior's maximum is > tau, 255 elsewhere; the label rule and the
+     source of the export's confidence mode -- and adds the labels' counts to `label_counts`,
   4. the main stream waits for that launch in front of `simt_head_loss`; everything behind it is the step without the keyword.
 
 There is no host label and no widening copy.  The teacher sees `teacher_image` (the weak view) when one is passed, else the student's image.
@@ -40,7 +40,7 @@ from .engine import side_stream
 DEFAULT_THRESHOLD = 0.968      # DACS / DAFormer
 DEFAULT_PORTION = 0.5          # BDL's label generator keeps the more confident half of every class
 DEFAULT_MOMENTUM = 0.9         # IAST's exponential average of the per-class thresholds
-MAX_BALANCED_CLASSES = 64      # CONF_MAX_C of csrc/eval_metric.hip: the confidence histogram lives in LDS
+MAX_BALANCED_CLASSES = 64      # CONF_MAX_C of csrc/label_sweep.hip: the confidence histogram lives in LDS
 
 
 def check_threshold(tau):

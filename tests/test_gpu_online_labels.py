@@ -1,4 +1,4 @@
-"""Online labels on the GPU (simt_amd/online_labels.py, simt_online_label in csrc/eval_metric.hip).  Every comparison is between two
+"""Online labels on the GPU (simt_amd/online_labels.py, simt_online_label in csrc/label_sweep.hip).  Every comparison is between two
 executions of the same arithmetic and therefore BITWISE.
 
   (a) the kernel against the export kernels it shares its device functions with: `label` == their uint8 output widened to int64, `counts`

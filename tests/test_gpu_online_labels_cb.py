@@ -1,4 +1,4 @@
-"""Class-balanced online labels on the GPU (simt_online_label_cb / simt_class_thresholds in csrc/eval_metric.hip, simt_amd/online_labels.py,
+"""Class-balanced online labels on the GPU (simt_online_label_cb / simt_class_thresholds in csrc/label_sweep.hip, simt_amd/online_labels.py,
 DESIGN 7.17).  Every comparison is between two executions of the same arithmetic, or between integers, and therefore BITWISE.
 
   (a) the label kernel against the composition of existing launches: simt_pseudo_conf_u8 / simt_pseudo_conf2_u8 (hia = H, wia = W) with out +

@@ -1,4 +1,4 @@
-"""GPU parity of the pseudo-label export (simt_amd.tools.make_pseudo_labels, csrc/eval_metric.hip simt_pseudo_label_u8):
+"""GPU parity of the pseudo-label export (simt_amd.tools.make_pseudo_labels, csrc/label_sweep.hip simt_pseudo_label_u8):
 arg-max mode bitwise against simt_upsample_sum_argmax (the evaluation kernel, which tests/test_gpu_eval.py pins to the reference),
 confidence mode against the oracle's confidence_labels (trainV2_simt.py:353-359), the exported files against Evaluator.predict,
 cityscapesPseudo and compute_ClassDistribution, the single-head model against the fp32 oracle, and the command line at full depth."""

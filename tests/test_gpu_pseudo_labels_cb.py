@@ -1,4 +1,4 @@
-"""GPU tests of the class-balanced pseudo labels (csrc/eval_metric.hip simt_pseudo_conf_u8 / simt_pseudo_conf2_u8, make_pseudo_labels
+"""GPU tests of the class-balanced pseudo labels (csrc/label_sweep.hip simt_pseudo_conf_u8 / simt_pseudo_conf2_u8, make_pseudo_labels
 --class-balanced).  Every comparison is exact (integers or bytes): the histogram against NumPy where the resample is the identity, the
 histogram and the labels against the existing confidence-mode kernels (whose (arg, conf) the new kernels share) where it interpolates,
 and the exported files against compositions of single-threshold confidence-mode runs."""

@@ -1,4 +1,4 @@
-"""GPU parity of the pseudo-label export for DeepLabv3 and DeepLab-VGG16 (make_pseudo_labels --arch v3 | vgg; csrc/eval_metric.hip
+"""GPU parity of the pseudo-label export for DeepLabv3 and DeepLab-VGG16 (make_pseudo_labels --arch v3 | vgg; csrc/label_sweep.hip
 simt_pseudo_label2_u8): arg-max mode bitwise against simt_upsample2_sum_argmax (the evaluator's kernel), confidence mode against the
 oracle's confidence_labels of the model's input-size output, PseudoLabeller against Evaluator.predict and the fp32 oracle forwards,
 the command line end to end (PNGs, list, prior, the SimT trainer reading the prior), and one DeepLabv3 R-50 run at full size."""

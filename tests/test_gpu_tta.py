@@ -1,4 +1,4 @@
-"""GPU tests of test-time augmentation: simt_tta_label (csrc/eval_metric.hip) -- up to 8 low-res maps, any of them of the mirrored frame,
+"""GPU tests of test-time augmentation: simt_tta_label (csrc/label_sweep.hip) -- up to 8 low-res maps, any of them of the mirrored frame,
 combined into one label map -- and its plumbing through Evaluator, PseudoLabeller and the export.  The yardstick is the float64
 restatement tests/_tta_ref.py (itself checked in tests/test_tta_cpu.py); the reference has no test-time augmentation.
 
