@@ -679,6 +679,65 @@ int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream);
  * x_out and lab_out are simt_class_mix's, bit for bit: same grid, same paste mask. */
 int simt_class_mix_items(const simt_class_mix_desc* d, uint8_t* item_out, simt_stream_t stream);
 
+/* ---- ClassMix behind a teacher (the warm-up trainers' online_mix; csrc/label_sweep.hip, csrc/class_mix.hip) -----------
+ * The mix of a batch whose labels a teacher has just made on the device: two launches on one stream, the label a byte in between.
+ *
+ * simt_online_label_u8 / simt_online_label_cb_u8 -- simt_online_label / simt_online_label_cb with two differences.  Sources, label rule,
+ *   counts (and hist, thr) are the parents', bit for bit.
+ *   lab8: the labels leave as uint8 [B][H][W] -- byte for byte those of simt_pseudo_label_u8 / simt_pseudo_label2_u8 (hia = H, wia = W)
+ *     mode 1, and the low byte of simt_online_label_cb's int64 word.
+ *   part: [B][rows] words, rows = simt_online_label_parts(d) (the launch's workgroups; at most SIMT_ONLINE_LABEL_MAX_PARTS).
+ *     part[b][g] = OR of 1u << l over the labels l < C of item b that workgroup g wrote; a 255 sets no bit; 0 where it saw none of the
+ *     item.  EVERY word is written by a plain store on every call: no atomics on global memory, nothing to zero, no launch that folds.
+ *     The OR of row b is item b's class presence, exactly (simt_label_presence's words for the widened labels).  Item-major, so that
+ *     simt_class_mix_u8 reads an item's words as one contiguous run.
+ *   Refused (SIMT_ERR_INVALID, nothing launched): what the parents refuse, C > SIMT_CLASS_MIX_CLASSES, B > SIMT_CLASS_MIX_MAX,
+ *   H * W >= 2^31, lab8 not 16-byte aligned, counts (hist) not 8-byte aligned, part (thr) NULL or not 4-byte aligned.
+ *   simt_online_label_parts reads B, H, W and family only (the cb launch of the same geometry writes the same rows); < 0: invalid.
+ *
+ * simt_class_mix_u8 -- simt_class_mix's selection over those bytes, into the buffers the next launches read.  With j = partner[i] and
+ *   P_j = the classes whose bit is set in the OR of part[j][0 .. rows-1], below n_classes: S_j and m exactly as above (k = (n + 1) / 2
+ *   classes of smallest rank[i]; a 255 is never pasted);
+ *     lab_out[i][p] = (int64)(m ? lab8[j][p] : lab8[i][p]);   x_out[i][ch][p] = m ? x[j][ch][p] : x[i][ch][p]   (no bit changes).
+ *   apply[i] == 0: x_out[i] = x[i], lab_out[i] = lab8[i] widened; the partner is not read.
+ *   Refused: a NULL pointer; x, lab8, x_out or lab_out not 16-byte aligned, part not 4-byte aligned; B outside 2 .. SIMT_CLASS_MIX_MAX;
+ *   n_classes outside 1 .. SIMT_CLASS_MIX_CLASSES; h, w <= 0 or h * w >= 2^31; rows outside 1 .. SIMT_ONLINE_LABEL_MAX_PARTS; x_out
+ *   overlapping x; a partner >= B; a rank >= n_classes.  Any h, w otherwise (h * w % 4 != 0 takes the scalar flavour).
+ * All descriptors travel as kernel arguments: no device copy, no synchronisation. */
+#define SIMT_ONLINE_LABEL_MAX_PARTS 1024
+typedef struct {
+  const float* fix;        /* as simt_online_label_desc */
+  uint8_t* lab8;           /* out [B][H][W] bytes: class index, 255 = ignore; 16-byte aligned */
+  int64_t* counts;         /* [C+1], accumulated, as simt_online_label */
+  uint32_t* part;          /* out [B][simt_online_label_parts()] */
+  int32_t B, h, w, ld, H, W, C, family;
+  float threshold;
+} simt_online_label_u8_desc;
+typedef struct {
+  const float* fix;        /* as simt_online_label_cb_desc */
+  uint8_t* lab8;           /* out [B][H][W] bytes; 16-byte aligned */
+  int64_t* counts;         /* [C+1], accumulated */
+  int64_t* hist;           /* [C][SIMT_CONF_BINS], accumulated */
+  const float* thr;        /* [C] fp32 in DEVICE memory */
+  uint32_t* part;          /* out [B][rows] */
+  int32_t B, h, w, ld, H, W, C, family;
+} simt_online_label_cb_u8_desc;
+typedef struct {
+  const float* x;            /* [B][3][h][w] fp32 */
+  const uint8_t* lab8;       /* [B][h][w] bytes */
+  float* x_out;              /* [B][3][h][w] fp32 */
+  long long* lab_out;        /* [B][h][w] int64 */
+  const uint32_t* part;      /* [B][rows]: the label launch's words for `lab8` */
+  int32_t B, h, w, n_classes, rows;
+  uint8_t partner[SIMT_CLASS_MIX_MAX];
+  uint8_t apply[SIMT_CLASS_MIX_MAX];
+  uint8_t rank[SIMT_CLASS_MIX_MAX][SIMT_CLASS_MIX_CLASSES];
+} simt_class_mix_u8_desc;
+int simt_online_label_parts(const simt_online_label_u8_desc* d);
+int simt_online_label_u8(const simt_online_label_u8_desc* d, simt_stream_t stream);
+int simt_online_label_cb_u8(const simt_online_label_cb_u8_desc* d, simt_stream_t stream);
+int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t stream);
+
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
  * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another

@@ -146,6 +146,17 @@ class ClassMixDesc(C.Structure):
                 ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
 
 
+ONLINE_LABEL_MAX_PARTS = 1024      # include/simt_hip.h SIMT_ONLINE_LABEL_MAX_PARTS
+
+
+class ClassMixU8Desc(C.Structure):
+    """simt_class_mix_u8_desc (include/simt_hip.h): a batch, its byte labels and their presence words -> the mixed batch and int64 labels."""
+    _fields_ = [("x", c_p), ("lab8", c_p), ("x_out", c_p), ("lab_out", c_p), ("part", c_p),
+                ("B", i32), ("h", i32), ("w", i32), ("n_classes", i32), ("rows", i32),
+                ("partner", C.c_uint8 * CLASS_MIX_MAX), ("apply", C.c_uint8 * CLASS_MIX_MAX),
+                ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
+
+
 PHOTOMETRIC_MAX = 32     # include/simt_hip.h SIMT_PHOTOMETRIC_MAX
 PHOTOMETRIC_PARTS = 64   # SIMT_PHOTOMETRIC_PARTS
 
@@ -198,6 +209,18 @@ class OnlineLabelCbDesc(C.Structure):
     confidence histogram of the same pass."""
     _fields_ = [("fix", c_p), ("label", c_p), ("counts", c_p), ("hist", c_p), ("thr", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32),
                 ("H", i32), ("W", i32), ("C", i32), ("family", i32)]
+
+
+class OnlineLabelU8Desc(C.Structure):
+    """simt_online_label_u8_desc (include/simt_hip.h): simt_online_label with byte labels and the per-item class-presence words."""
+    _fields_ = [("fix", c_p), ("lab8", c_p), ("counts", c_p), ("part", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32), ("H", i32),
+                ("W", i32), ("C", i32), ("family", i32), ("threshold", f32)]
+
+
+class OnlineLabelCbU8Desc(C.Structure):
+    """simt_online_label_cb_u8_desc (include/simt_hip.h): simt_online_label_cb with byte labels and the presence words."""
+    _fields_ = [("fix", c_p), ("lab8", c_p), ("counts", c_p), ("hist", c_p), ("thr", c_p), ("part", c_p), ("B", i32), ("h", i32), ("w", i32),
+                ("ld", i32), ("H", i32), ("W", i32), ("C", i32), ("family", i32)]
 
 
 class ClassThresholdsDesc(C.Structure):
@@ -299,6 +322,9 @@ SIGNATURES = {
     "simt_online_label": (_I, [C.POINTER(OnlineLabelDesc), c_p]),
     "simt_online_label_cb": (_I, [C.POINTER(OnlineLabelCbDesc), c_p]),
     "simt_class_thresholds": (_I, [C.POINTER(ClassThresholdsDesc), c_p]),
+    "simt_online_label_parts": (_I, [C.POINTER(OnlineLabelU8Desc)]),
+    "simt_online_label_u8": (_I, [C.POINTER(OnlineLabelU8Desc), c_p]),
+    "simt_online_label_cb_u8": (_I, [C.POINTER(OnlineLabelCbU8Desc), c_p]),
     "simt_tta_label": (_I, [C.POINTER(TtaDesc), c_p]),
     "simt_upsample_nchw": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, c_p]),
     "simt_upsample_nchw_bwd": (_I, [c_p, _I, _I, _I, _I, _I, _I, _I, _I, c_p, _I, c_p, c_p]),
@@ -317,6 +343,7 @@ SIGNATURES = {
     "simt_label_presence": (_I, [c_p, _I, _L, _I, c_p, c_p]),
     "simt_class_mix": (_I, [C.POINTER(ClassMixDesc), c_p]),
     "simt_class_mix_items": (_I, [C.POINTER(ClassMixDesc), c_p, c_p]),
+    "simt_class_mix_u8": (_I, [C.POINTER(ClassMixU8Desc), c_p]),
     "simt_grey_mean_parts": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_photometric": (_I, [C.POINTER(PhotometricDesc), c_p]),
     "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),

@@ -62,16 +62,15 @@ extern "C" int simt_label_presence(const long long* lab, int B, long hw, int n_c
 // The paste mask of item i, the same word in every lane.  Lane r < C plays RANK r: a wave-uniform walk over the classes (rank[i][c] is a
 // scalar load from the kernel arguments) tells it which class holds its rank; the ballot of "my class is present" then is the present
 // classes in rank order, and the class of rank r is chosen when fewer than k present ones rank below it.
-__device__ __forceinline__ uint32_t paste_mask(const simt_class_mix_desc& d, int i, int j) {
+// `present`: this lane's share of the partner's presence words (the OR over the wave is the partner's classes); `row`: rank[i], 32 bytes
+// at a 4-byte boundary of the descriptor: 8 scalar dwords.
+__device__ __forceinline__ uint32_t paste_mask_of(uint32_t present, const uint32_t* row, int C) {
   const int lane = threadIdx.x & 63;
-  const int C = d.n_classes;
-  uint32_t present = d.part[j * SIMT_CLASS_MIX_PARTS + lane];           // PARTS = 64 = one word per lane
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) present |= (uint32_t)__shfl_xor((int)present, o, 64);
   present &= C >= 32 ? 0xffffffffu : ((1u << C) - 1u);
   const int k = (__popc(present) + 1) >> 1;
   int cls = -1;
-  const uint32_t* row = (const uint32_t*)d.rank[i];                      // 32 bytes at a 4-byte boundary of the descriptor: 8 scalar dwords
 #pragma unroll
   for (int c = 0; c < SIMT_CLASS_MIX_CLASSES; ++c)
     if (c < C && (int)((row[c >> 2] >> (8 * (c & 3))) & 255u) == lane) cls = c;
@@ -82,6 +81,10 @@ __device__ __forceinline__ uint32_t paste_mask(const simt_class_mix_desc& d, int
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mask |= (uint32_t)__shfl_xor((int)mask, o, 64);
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)mask);
+}
+
+__device__ __forceinline__ uint32_t paste_mask(const simt_class_mix_desc& d, int i, int j) {
+  return paste_mask_of(d.part[j * SIMT_CLASS_MIX_PARTS + (threadIdx.x & 63)], (const uint32_t*)d.rank[i], d.n_classes);   // PARTS = 64 = one word per lane
 }
 
 __device__ __forceinline__ bool pasted(long long l, int C, uint32_t mask) { return l >= 0 && l < C && ((mask >> (int)l) & 1u); }
@@ -238,4 +241,123 @@ extern "C" int simt_class_mix(const simt_class_mix_desc* d, simt_stream_t stream
 // simt_class_mix plus the item map (the weak-view teacher gathers its predictions through it): x_out / lab_out bit for bit as above.
 extern "C" int simt_class_mix_items(const simt_class_mix_desc* d, uint8_t* item_out, simt_stream_t stream) {
   return class_mix_launch(d, item_out, true, stream);
+}
+
+// ---- simt_class_mix_u8: the mix BEHIND a teacher, inside the warm-up trainers.  simt_class_mix's selection over BYTE
+// labels (simt_online_label_u8's lab8) and that launch's presence words (part[b][g], `rows` of them per item), written straight into the
+// buffers the student's forward and the head kernels read: x_out fp32, lab_out int64.  Byte floor per pixel: 12 + 8 written, 12 + 1-2
+// read = 33-34, against 40-48 of simt_class_mix, 8 of simt_label_presence and 24 + 16 of the copies into the trainer's buffers.
+// A lane takes MIX8_QPT quads, 256 * 4 pixels apart (every access of a wave stays one contiguous run), so the wave's paste mask -- the OR
+// of the partner's row of `part`, rows / 64 contiguous loads per lane from L2, then paste_mask_of: no LDS, no barrier -- is paid once per
+// 512 pixels.  Measured on MI355X (profiles/online_mix.txt): 2 quads per lane over item-major words 17.8 / 16.7 us (B = 4 768 x 768 / B = 8
+// 512 x 512); 1 quad 21.8 / 16.6; 4 quads 20.4 / 19.4 (too few waves); the words workgroup-major ([g][b]: a wave's loads B * 4 bytes apart)
+// 20.4 / 19.6 at 4 quads, 22.0 / 19.9 at 1.  The quad's four labels are ONE dword when h * w % 4 == 0; a quad whose four decisions agree
+// reads one image source.
+constexpr int MIX8_QPT = 2;
+
+__device__ __forceinline__ bool pasted8(uint32_t l, int C, uint32_t mask) { return l < (uint32_t)C && ((mask >> (l & 31u)) & 1u); }
+
+template <bool VEC>
+__device__ __forceinline__ uint32_t load_labels4(const uint8_t* __restrict__ l, long p) {
+  if (VEC) return *(const uint32_t*)(l + p);
+  return (uint32_t)l[p] | ((uint32_t)l[p + 1] << 8) | ((uint32_t)l[p + 2] << 16) | ((uint32_t)l[p + 3] << 24);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_u8_desc d) {
+  const int i = blockIdx.y;
+  const int apply = d.apply[i];
+  const int C = d.n_classes;
+  const long HW = (long)d.h * d.w;
+  const long nquad = HW >> 2;
+  const uint32_t* __restrict__ xi = (const uint32_t*)d.x + (long)i * 3 * HW;
+  const uint8_t* __restrict__ li = d.lab8 + (long)i * HW;
+  uint32_t* __restrict__ xo = (uint32_t*)d.x_out + (long)i * 3 * HW;
+  long long* __restrict__ lo = d.lab_out + (long)i * HW;
+  // apply[i] == 0 (wave-uniform): mask 0 over the item's own labels -- an image copy and a widening copy, the partner is not read
+  const uint32_t* __restrict__ xj = xi;
+  const uint8_t* __restrict__ lj = li;
+  uint32_t mask = 0u;
+  if (apply) {
+    const int j = d.partner[i];
+    uint32_t present = 0u;
+    for (int g = threadIdx.x & 63; g < d.rows; g += 64) present |= d.part[(long)j * d.rows + g];
+    mask = paste_mask_of(present, (const uint32_t*)d.rank[i], C);
+    xj = (const uint32_t*)d.x + (long)j * 3 * HW;
+    lj = d.lab8 + (long)j * HW;
+  }
+  for (int r = 0; r < MIX8_QPT; ++r) {
+    const long q = ((long)blockIdx.x * MIX8_QPT + r) * 256 + threadIdx.x;
+    if (q < nquad) {
+      const long p = q << 2;
+      uint32_t a = load_labels4<VEC>(lj, p);             // the partner's four labels, then the output's
+      const bool m0 = pasted8(a & 255u, C, mask), m1 = pasted8((a >> 8) & 255u, C, mask), m2 = pasted8((a >> 16) & 255u, C, mask),
+                 m3 = pasted8(a >> 24, C, mask);
+      const bool all = m0 && m1 && m2 && m3, none = !(m0 || m1 || m2 || m3);
+      if (apply && !all) {
+        const uint32_t sel = (m0 ? 0xffu : 0u) | (m1 ? 0xff00u : 0u) | (m2 ? 0xff0000u : 0u) | (m3 ? 0xff000000u : 0u);
+        a = (a & sel) | (load_labels4<VEC>(li, p) & ~sel);
+      }
+      if (VEC) {
+        const i64x2 u = {(long long)(a & 255u), (long long)((a >> 8) & 255u)}, v = {(long long)((a >> 16) & 255u), (long long)(a >> 24)};
+        *(i64x2*)(lo + p) = u;
+        *(i64x2*)(lo + p + 2) = v;
+      } else {
+        lo[p] = (long long)(a & 255u); lo[p + 1] = (long long)((a >> 8) & 255u);
+        lo[p + 2] = (long long)((a >> 16) & 255u); lo[p + 3] = (long long)(a >> 24);
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const long o = ch * HW + p;
+        if (VEC) {
+          uint4 v;
+          if (all) {
+            v = *(const uint4*)(xj + o);
+          } else if (none) {
+            v = *(const uint4*)(xi + o);
+          } else {
+            const uint4 s = *(const uint4*)(xj + o), t = *(const uint4*)(xi + o);
+            v = make_uint4(m0 ? s.x : t.x, m1 ? s.y : t.y, m2 ? s.z : t.z, m3 ? s.w : t.w);
+          }
+          *(uint4*)(xo + o) = v;
+        } else {
+          const uint32_t v0 = m0 ? xj[o] : xi[o], v1 = m1 ? xj[o + 1] : xi[o + 1], v2 = m2 ? xj[o + 2] : xi[o + 2],
+                         v3 = m3 ? xj[o + 3] : xi[o + 3];
+          xo[o] = v0; xo[o + 1] = v1; xo[o + 2] = v2; xo[o + 3] = v3;
+        }
+      }
+    } else if (q == nquad) {                             // scalar tail: h*w % 4 pixels
+      for (long p = nquad << 2; p < HW; ++p) {
+        const uint32_t l = lj[p];
+        const bool m = pasted8(l, C, mask);
+        lo[p] = (long long)(m ? l : (uint32_t)li[p]);
+        for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = m ? xj[ch * HW + p] : xi[ch * HW + p];
+      }
+    }
+  }
+}
+
+extern "C" int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->x && d->lab8 && d->x_out && d->lab_out && d->part);
+  SIMT_CHECK(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->lab8 & 15) == 0 && ((uintptr_t)d->x_out & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0);
+  SIMT_CHECK(((uintptr_t)d->part & 3) == 0);
+  SIMT_CHECK(d->B >= 2 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0);
+  SIMT_CHECK(d->n_classes >= 1 && d->n_classes <= SIMT_CLASS_MIX_CLASSES);
+  SIMT_CHECK(d->rows >= 1 && d->rows <= SIMT_ONLINE_LABEL_MAX_PARTS);
+  const long HW = (long)d->h * d->w;
+  SIMT_CHECK(HW < (1L << 31));
+  const uintptr_t x0 = (uintptr_t)d->x, y0 = (uintptr_t)d->x_out, xbytes = (uintptr_t)d->B * 3 * HW * sizeof(float);
+  SIMT_CHECK(x0 + xbytes <= y0 || y0 + xbytes <= x0);    // x_out does not overlap x: item i reads its partner's image
+  for (int b = 0; b < d->B; ++b) {
+    SIMT_CHECK(d->partner[b] < d->B);
+    for (int c = 0; c < d->n_classes; ++c) SIMT_CHECK(d->rank[b][c] < d->n_classes);
+  }
+  const long lanes = (HW >> 2) + ((HW & 3) ? 1 : 0);
+  const dim3 grid((unsigned)((lanes + 256 * MIX8_QPT - 1) / (256 * MIX8_QPT)), (unsigned)d->B);
+  if ((HW & 3) == 0)
+    hipLaunchKernelGGL((class_mix_u8_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else
+    hipLaunchKernelGGL((class_mix_u8_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
 }

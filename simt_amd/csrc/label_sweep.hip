@@ -472,6 +472,7 @@ struct CountSink {
   int C;
   template <int BLOCK> __device__ __forceinline__ void init(Shared& sh) const { pl_hist_init<BLOCK>(sh, C + 1); }
   __device__ __forceinline__ Item item(const Shared&, ArgConf r) const { return rule(r, nullptr); }
+  static __device__ __forceinline__ unsigned int label(Item lab) { return lab; }
   __device__ __forceinline__ void emit(Shared& sh, Item lab, long p, long P) const { o.store(lab, p, P, C, sh); }
   template <int BLOCK> __device__ __forceinline__ void flush(Shared& sh) const { pl_hist_flush<BLOCK>(sh, C + 1, o.counts); }
 };
@@ -551,6 +552,7 @@ struct ConfSink {
     if (LABELS) it.lab = rule(r, sh.thr);
     return it;
   }
+  static __device__ __forceinline__ unsigned int label(const Item& it) { return it.lab; }
   __device__ __forceinline__ void emit(Shared& sh, Item it, long p, long P) const {
     if (STATS) conf_hist_add(p < P, it.key, sh.hist);
     if (LABELS) o.store(it.lab, p, P, C, sh.counts);
@@ -598,6 +600,58 @@ struct TtaArgmaxSink {
   template <int BLOCK> __device__ __forceinline__ void flush(Shared& sh) const {
     if (o.out) pl_hist_flush<BLOCK>(sh.counts, C + 1, o.counts);
   }
+};
+
+// ---- class presence (ClassMix behind the teacher): a DECORATOR over a label sink.  Item, label rule, stores, counts and
+// histogram are the inner sink's, untouched; on top, the sweep leaves the words simt_class_mix_u8 builds its paste mask from:
+// part[b][g] = OR of 1u << l over the labels l < C of item b that workgroup g emitted (a 255 sets no bit; item-major, so that the mix reads
+// an item's words as one contiguous run).  The sweep is flat over B*H*W and strides by the grid, so a workgroup meets several items: one
+// LDS word per item (B <= SIMT_CLASS_MIX_MAX), OR-ed with LDS atomics -- once per wave where its 64 pixels lie in one item (an xor-shuffle
+// OR first; every wave but the few that straddle an item's edge), once per lane with a bit otherwise.  The flush stores the workgroup's
+// word of EVERY item, zeros included: every word of `part` is written by plain stores on every call -- no global atomics, nothing to
+// zero, simt_label_presence's contract.  An OR: exact and order independent.  Nothing lives across the sweep's bounds check but the inner
+// sink's Item.
+template <class Inner>
+struct PresenceSink {
+  struct Shared {
+    typename Inner::Shared in;
+    unsigned int pres[SIMT_CLASS_MIX_MAX];
+  };
+  typedef typename Inner::Item Item;
+  Inner in;
+  unsigned int* part;  // [B][gridDim.x]
+  int B;
+  long HW;             // H * W: pixel p belongs to item p / HW
+  template <int BLOCK> __device__ __forceinline__ void init(Shared& sh) const {
+    if (threadIdx.x < SIMT_CLASS_MIX_MAX) sh.pres[threadIdx.x] = 0u;
+    in.template init<BLOCK>(sh.in);                      // (ends with the barrier that also covers pres)
+  }
+  __device__ __forceinline__ Item item(const Shared& sh, ArgConf r) const { return in.item(sh.in, r); }
+  __device__ __forceinline__ void emit(Shared& sh, Item it, long p, long P) const {
+    in.emit(sh.in, it, p, P);
+    const unsigned int lab = Inner::label(it);
+    unsigned int bits = (p < P && lab < (unsigned int)in.C) ? 1u << lab : 0u;
+    const int b = (int)((p < P ? p : P - 1) / HW);       // lanes past the end: the last item, and no bit
+    const int b_first = __builtin_amdgcn_readfirstlane(b), b_last = __builtin_amdgcn_readlane(b, 63);
+    if (b_first == b_last) {                             // wave-uniform: the 64 lanes' pixels are consecutive
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) bits |= (unsigned int)__shfl_xor((int)bits, o, 64);
+      if ((threadIdx.x & 63) == 0 && bits) atomicOr(&sh.pres[b_first], bits);
+    } else if (bits) {
+      atomicOr(&sh.pres[b], bits);
+    }
+  }
+  template <int BLOCK> __device__ __forceinline__ void flush(Shared& sh) const {
+    in.template flush<BLOCK>(sh.in);
+    __syncthreads();
+    if ((int)threadIdx.x < B) part[(long)threadIdx.x * gridDim.x + blockIdx.x] = sh.pres[threadIdx.x];
+  }
+};
+
+// class-balanced online labels as bytes: OnlineCbOut over the uint8 output
+struct OnlineCbOut8 : U8Out {
+  unsigned long long* hist;     // [C][CONF_BINS], accumulated
+  const float* thr;             // [C], device memory
 };
 
 // ============================================================== entry points ===============================================================
@@ -722,6 +776,44 @@ extern "C" int simt_online_label_cb(const simt_online_label_cb_desc* d, simt_str
   OnlineCbOut o;
   o.label = (long long*)d->label; o.counts = (unsigned long long*)d->counts; o.hist = (unsigned long long*)d->hist; o.thr = d->thr;
   const ConfSink<true, true, OnlineCbOut> sink{o, {}, d->C};
+  return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
+}
+
+// ---- online labels for the mix behind the teacher: the two launches above with the label as a BYTE (U8Out: the export's
+// store) and the presence words on top (PresenceSink).  Sources, rule, counts, hist and thr are the parents'.
+template <class D>
+static int online_u8_checks(const D* d) {
+  SIMT_CHECK(d && d->fix && d->lab8 && d->counts && d->part);
+  SIMT_CHECK(d->B > 0 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0);
+  SIMT_CHECK(d->C > 0 && d->C <= SIMT_CLASS_MIX_CLASSES && d->C <= d->ld);
+  SIMT_CHECK(d->family == 0 || d->family == 1);
+  SIMT_CHECK((long)d->H * d->W < (1L << 31));
+  SIMT_CHECK(((uintptr_t)d->lab8 & 15) == 0 && ((uintptr_t)d->counts & 7) == 0 && ((uintptr_t)d->part & 3) == 0);
+  return SIMT_OK;
+}
+
+extern "C" int simt_online_label_parts(const simt_online_label_u8_desc* d) {
+  if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || (d->family != 0 && d->family != 1)) return -1;
+  const long P = (long)d->B * d->H * d->W;
+  const long block = d->family ? PL2_BLOCK : PL_BLOCK, max_grid = d->family ? PL2_MAX_GRID : PL_MAX_GRID;      // launch_sweep's clamp
+  const long grid = (P + block - 1) / block;
+  return (int)(grid > max_grid ? max_grid : grid);
+}
+
+extern "C" int simt_online_label_u8(const simt_online_label_u8_desc* d, simt_stream_t stream) {
+  if (int rc = online_u8_checks(d)) return rc;
+  const CountSink<U8Out, Strict> inner{{d->lab8, (unsigned long long*)d->counts}, {d->threshold}, d->C};
+  const PresenceSink<CountSink<U8Out, Strict>> sink{inner, d->part, d->B, (long)d->H * d->W};
+  return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
+}
+
+extern "C" int simt_online_label_cb_u8(const simt_online_label_cb_u8_desc* d, simt_stream_t stream) {
+  if (int rc = online_u8_checks(d)) return rc;
+  SIMT_CHECK(d->hist && d->thr && ((uintptr_t)d->hist & 7) == 0 && ((uintptr_t)d->thr & 3) == 0);
+  OnlineCbOut8 o;
+  o.out = d->lab8; o.counts = (unsigned long long*)d->counts; o.hist = (unsigned long long*)d->hist; o.thr = d->thr;
+  const ConfSink<true, true, OnlineCbOut8> inner{o, {}, d->C};
+  const PresenceSink<ConfSink<true, true, OnlineCbOut8>> sink{inner, d->part, d->B, (long)d->H * d->W};
   return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
 }
 

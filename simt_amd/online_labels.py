@@ -26,6 +26,13 @@ same stream: per class the threshold that keeps the share P of THIS batch's pixe
 at tau), folded into the state with momentum M, and the histogram zeroed.  A batch is therefore labelled with the thresholds of the batches
 before it (IAST's ordering), and nothing waits for the host.  `balanced_update` below restates the second launch in numpy.  `losses()` gains
 `label_thresholds`.  Rank-local, as `labelled` is.
+
+ClassMix behind the teacher (keywords `online_mix=P` / `online_mix_seed=S`, flag --online-mix): the student's forward then depends
+on the labels, so the whole micro-batch runs on the main stream (`_mixed_batch`): teacher forward, step 2, the `_u8` flavour of step 3's launch --
+the labels as BYTES plus the per-item class-presence words of the same pass -- and `simt_class_mix_u8`, which selects from the caller's image
+and those bytes straight into the student's input and `trainer.label` (int64); there is no input copy and no staging pair.  The draws are the
+loader's (`simt_amd.data.class_mix`: `generator(S, rank)`, one `draw_batch` per micro-batch).  `labelled` and `label_thresholds` stay statistics
+of the teacher's labels BEFORE the mix.
 """
 import ctypes as C
 
@@ -34,6 +41,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .data import class_mix
 from .ema_teacher import TeacherMixin, check_every
 from .engine import side_stream
 
@@ -100,6 +108,32 @@ def check_balanced(online_labels_balanced, online_labels_momentum, tau, num_clas
     return p, m
 
 
+def check_mix(online_mix, online_mix_seed, tau, batch_size, num_classes):
+    """The two keywords of the mix behind the teacher -> (P | None, S); `tau` is check_settings' first value.  ValueError that
+    starts with the keyword that does not fit."""
+    seed = 0 if online_mix_seed is None else online_mix_seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError(f"online_mix_seed {online_mix_seed!r}: expected a non-negative integer (the seed of the mix's own generator)")
+    if online_mix is None:
+        if seed != 0:
+            raise ValueError("online_mix_seed needs online_mix: it seeds the mix's draws, and this trainer mixes nothing")
+        return None, 0
+    what = "expected the probability that an item receives its neighbour's classes, 0 < P <= 1"
+    try:
+        p = float(online_mix)
+    except (TypeError, ValueError):
+        raise ValueError(f"online_mix {online_mix!r}: {what}") from None
+    if isinstance(online_mix, bool) or not (0.0 < p <= 1.0):          # (a NaN fails both comparisons)
+        raise ValueError(f"online_mix {online_mix!r}: {what}")
+    if tau is None:
+        raise ValueError("online_mix needs online_labels: it mixes by the teacher's labels, and this trainer has no teacher")
+    if not 2 <= batch_size <= class_mix.MAX_ITEMS:
+        raise ValueError(f"online_mix with a batch of {batch_size}: items are mixed with their neighbour in the batch, 2 to {class_mix.MAX_ITEMS} of them")
+    if not 1 <= num_classes <= class_mix.MAX_CLASSES:
+        raise ValueError(f"online_mix with num_classes = {num_classes}: the presence word holds 1 to {class_mix.MAX_CLASSES} classes")
+    return p, int(seed)
+
+
 def balanced_update(thr, hist, P, T, M):
     """`simt_class_thresholds` in numpy (steps 3 and 4 of DESIGN 7.17) -> (the new thresholds, the batch thresholds t), float32 [C] each.
 
@@ -163,6 +197,85 @@ class OnlineLabelMixin(TeacherMixin):
         t.hist, t.thr, t.t_out = self.label_hist.data_ptr(), self.label_thr.data_ptr(), None
         t.drop, t.C, t.cap, t.omd = 1.0 - P, self.C, self.online_labels, 1.0 - M      # (ctypes rounds cap and omd to float32)
         self.online_cb_desc, self.thresholds_desc = d, t
+
+    def _init_mix(self, mix):
+        """mix: check_mix's pair (P None: off -- no buffer, no launch, no draw).  Behind _init_online.  The byte labels, the presence words
+        of the label launch, the `_u8` descriptors (the geometry of the int64 ones) and the mix's descriptor, whose outputs are the student
+        plan's input and `self.label`: the buffers the forward and the head kernels already read."""
+        self.online_mix, self.online_mix_seed = mix
+        if self.online_mix is None:
+            return
+        dev, one = self.dev, self.online_desc
+        rank = 0
+        if getattr(self, "pg", None) is not None:
+            import torch.distributed as dist
+            rank = dist.get_rank(self.pg)
+        self._mix_rng = class_mix.generator(self.online_mix_seed, rank)      # the loader's ClassMix contract: a generator of the mix's own
+        self.lab8 = torch.zeros(self.B, self.H, self.W, device=dev, dtype=torch.uint8)
+        d = L.OnlineLabelU8Desc()
+        d.fix, d.lab8, d.counts = one.fix, self.lab8.data_ptr(), one.counts
+        d.B, d.h, d.w, d.ld, d.H, d.W, d.C, d.family, d.threshold = one.B, one.h, one.w, one.ld, one.H, one.W, one.C, one.family, one.threshold
+        rows = L.load().simt_online_label_parts(C.byref(d))
+        if rows < 1:
+            raise L.SimtHipError(f"simt_online_label_parts: {rows} for B = {self.B}, {self.H} x {self.W}")
+        self.mix_part = torch.zeros(self.B, rows, device=dev, dtype=torch.int32)      # every word is written by every label launch
+        d.part = self.mix_part.data_ptr()
+        self.online_u8_desc = d
+        if self.online_labels_balanced is not None:
+            cb, e = self.online_cb_desc, L.OnlineLabelCbU8Desc()
+            e.fix, e.lab8, e.counts, e.hist, e.thr, e.part = cb.fix, d.lab8, cb.counts, cb.hist, cb.thr, d.part
+            e.B, e.h, e.w, e.ld, e.H, e.W, e.C, e.family = cb.B, cb.h, cb.w, cb.ld, cb.H, cb.W, cb.C, cb.family
+            self.online_cb_u8_desc = e
+        m = L.ClassMixU8Desc()
+        m.lab8, m.x_out, m.lab_out, m.part = d.lab8, self.plan.x_in.data_ptr(), self.label.data_ptr(), d.part
+        m.B, m.h, m.w, m.n_classes, m.rows = self.B, self.H, self.W, self.C, rows
+        for i in range(self.B):
+            m.partner[i] = (i + 1) % self.B
+        self.mix_desc = m
+        self._mix_stage = None             # for an image the launch cannot read where it lies; allocated on first need
+
+    def _mix_source(self, image):
+        """The student's image as simt_class_mix_u8 reads it: the caller's tensor where it is a contiguous fp32 tensor of this device at a
+        16-byte base (and not the plan's input itself, which the launch writes), else a copy in a staging buffer of the trainer's own."""
+        if tuple(image.shape) != (self.B, 3, self.H, self.W):
+            raise ValueError(f"image of shape {tuple(image.shape)}, expected {(self.B, 3, self.H, self.W)}")
+        if (image.device == self.plan.x_in.device and image.dtype == torch.float32 and image.is_contiguous() and image.data_ptr() % 16 == 0
+                and image.data_ptr() != self.plan.x_in.data_ptr()):
+            return image
+        if self._mix_stage is None:
+            self._mix_stage = torch.empty_like(self.plan.x_in)
+        self._mix_stage.copy_(image, non_blocking=True)
+        return self._mix_stage
+
+    def _mixed_batch(self, image, teacher_image):
+        """One micro-batch with online_mix, ALL on the main stream, in front of the student's forward, which now depends on
+        the labels: the teacher's input, its forward, the posterior (family 0), the `_u8` label launch (+ simt_class_thresholds when
+        balanced), then simt_class_mix_u8 from the caller's image into `plan.x_in` and `self.label`.  No host synchronisation; the draws
+        are host values in the descriptor.  Ordering, all by stream order:
+          the previous micro-batch's head kernels (they read `label`), stem weight gradient (it reads `plan.x_in`; the backward joins its
+          side stream before it returns) and optimiser come first -- the write-after-read ordering the input copy had;
+          an EMA-teacher refresh (`_teacher_follows`, main stream, behind the update) lies behind this step's teacher forward and in front
+          of the next one, which runs on the same stream."""
+        st = ops.stream_ptr()
+        x = self._mix_source(image)
+        self.fixed.x_in.copy_(image if teacher_image is None else teacher_image, non_blocking=True)
+        self._fix_fwd.run()
+        if not self._family:
+            ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
+        if self.online_labels_balanced is None:
+            L.call("simt_online_label_u8", C.byref(self.online_u8_desc), st)
+        else:
+            L.call("simt_online_label_cb_u8", C.byref(self.online_cb_u8_desc), st)
+            L.call("simt_class_thresholds", C.byref(self.thresholds_desc), st)
+        apply, rank = class_mix.draw_batch(self._mix_rng, self.B, self.C, self.online_mix)      # one call per micro-batch, in order
+        m = self.mix_desc
+        m.x = x.data_ptr()
+        table = np.zeros((L.CLASS_MIX_MAX, L.CLASS_MIX_CLASSES), dtype=np.uint8)
+        table[:self.B, :self.C] = rank
+        C.memmove(m.rank, table.ctypes.data, table.nbytes)
+        for i in range(self.B):
+            m.apply[i] = 1 if apply[i] else 0
+        L.call("simt_class_mix_u8", C.byref(m), st)
 
     def _views(self, label, teacher_image, n):
         """step()'s `label` / `teacher_image` as lists of n = iter_size entries; ValueError when they do not fit the trainer."""

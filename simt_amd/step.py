@@ -27,7 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -493,15 +493,22 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     Same engine as SimTTrainer: TrunkPlan forward/backward, the fused head kernels in mode 1, simt_sgd_multi."""
 
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
-                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None):
+                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
+                 online_mix=None, online_mix_seed=0):
         """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
         online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
         online_labels_balanced=P in (0, 1] (needs online_labels): one threshold per class, kept on the device -- it starts at tau and
         every micro-batch moves it towards the value that keeps the share P of that class's pixels, never above tau, with momentum
-        online_labels_momentum=M in [0, 1) (default 0.9).  None: the one threshold tau."""
+        online_labels_momentum=M in [0, 1) (default 0.9).  None: the one threshold tau.
+        online_mix=P in (0, 1] (needs online_labels, 2 <= B <= 32, num_classes <= 32): ClassMix by the teacher's labels, behind
+        the teacher and in front of the student's forward -- with probability P item i receives, image and label, the pixels of half of the
+        classes the teacher found in item (i + 1) % B.  The draws are those of simt_amd.data.class_mix (`generator(online_mix_seed, rank)`,
+        one `draw_batch` per micro-batch).  `labelled` and `label_thresholds` stay statistics of the teacher's labels BEFORE the mix, as the
+        label launch counts them.  None: the trainer it was -- no buffer, no launch, no draw."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
+        mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -546,6 +553,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self._init_ema(ema_decay)
         fix = (self.fixed.out["x2"], self.fixed.ldp["x2"]) if tau is not None else (None, 0)
         self._init_online(tau, every, *fix, 0, balanced)      # (family 0: the posterior is resampled align_corners=True)
+        self._init_mix(mix)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -568,11 +576,15 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
         flat = self.plan.flat_grad
         for mi, (img, lab) in enumerate(zip(images, labels)):
-            self.plan.x_in.copy_(img, non_blocking=True)
-            if self.online_labels is None:
+            if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
+                self._mixed_batch(img, teachers[mi])
+                self.plan.forward()
+            elif self.online_labels is None:
+                self.plan.x_in.copy_(img, non_blocking=True)
                 self.label.copy_(lab, non_blocking=True)
                 self.plan.forward()
             else:          # the teacher writes self.label on the side stream, beside the student's forward; the main stream waits for it here
+                self.plan.x_in.copy_(img, non_blocking=True)
                 ev_in = self._teacher_input(img, teachers[mi])
                 self.plan.forward()
                 self._teacher_labels(ev_in)
@@ -610,6 +622,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             #   front of simt_head_loss (_teacher_labels);
             #   in front of the next step's teacher forward (side stream): it waits for ev_in, which the main stream records behind this point
             #   (_teacher_input); no main-stream launch reads the teacher plan's operands.
+            #   With online_mix the teacher's forward, the label launch and the mix run on the MAIN stream (_mixed_batch): this step's lie in
+            #   front of this point and the next step's behind it by stream order alone.
             # Once per optimiser step: this point is behind the last micro-batch.
             self._teacher_follows(st)
         self.it_done += 1

@@ -28,7 +28,7 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings
 from .step import check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
@@ -289,14 +289,18 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
-                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None):
+                 online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
+                 online_mix=None, online_mix_seed=0):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
         online_labels_momentum: as for step.WarmupTrainer; the
-        teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample)."""
+        teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample).  online_mix /
+        online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
+        statistics of the teacher's labels before the mix."""
         assert model in ("v3", "vgg")
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
+        mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -365,6 +369,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self.it_done = 0
         self._init_ema(ema_decay)
         self._init_online(tau, every, fix_out, ldf, half, balanced)      # (family 1 = the half-pixel model, DeepLabv3)
+        self._init_mix(mix)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -389,11 +394,15 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
         flat = self.plan.flat_grad
         for mi, (img, lab) in enumerate(zip(images, labels)):
-            self.plan.x_in.copy_(img, non_blocking=True)
-            if self.online_labels is None:
+            if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
+                self._mixed_batch(img, teachers[mi])
+                self._fwd.run()
+            elif self.online_labels is None:
+                self.plan.x_in.copy_(img, non_blocking=True)
                 self.label.copy_(lab, non_blocking=True)
                 self._fwd.run()
             else:          # the teacher writes self.label on the side stream, beside the student's forward; the main stream waits for it here
+                self.plan.x_in.copy_(img, non_blocking=True)
                 ev_in = self._teacher_input(img, teachers[mi])
                 self._fwd.run()
                 self._teacher_labels(ev_in)
@@ -428,7 +437,8 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward
             # online_labels_every: the teacher's refresh, if due, directly behind it on the main stream: behind this step's teacher forward and
             # label launch (side stream; the main stream waited for their event in front of simt_head_loss) and in front of the next ones
-            # (the side stream waits for ev_in, recorded on the main stream behind this point); as in step.WarmupTrainer
+            # (the side stream waits for ev_in, recorded on the main stream behind this point); as in step.WarmupTrainer.  With online_mix
+            # the teacher's launches and the mix run on the main stream (_mixed_batch): stream order alone
             self._teacher_follows(st)
         self.it_done += 1
         return self.hout

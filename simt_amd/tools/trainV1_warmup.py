@@ -17,6 +17,12 @@ labels the batch BEFORE them and the student sees it after (FixMatch / MIC consi
 loader).  With --ema and --online-labels-every N the teacher follows the weight EMA behind every N-th update (the mean teacher); without N it
 stays at the start weights.  The loss line gains ` labelled = <share of pixels that received a label>`; --train-state carries the teacher and
 the counts and refuses a resume with either flag added, dropped or changed.  With --synthetic the labels are ignored too.  Default: off.
+--online-mix [P] (needs --online-labels, --batch-size 2 ... 32, --num-classes <= 32): ClassMix by the teacher's labels, inside the
+trainer -- behind the teacher's label launch and in front of the student's forward, with probability P (no value: 1) item i receives, image and
+label, the pixels of half of the classes the teacher found in item i+1 (one launch, simt_class_mix_u8; draws seeded by --random-seed).  With
+--colour-jitter, --gaussian-blur or --mask-patches the teacher labels the weak view and the mix selects from the students' strong views: a pasted
+region carries its partner's jitter, blur and blanked patches.  ` labelled` stays the share of the teacher's labels before the mix.  --train-state
+carries the draws' generator and refuses a resume with the flag added, dropped or changed.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -130,8 +136,11 @@ def thresholds_text(args, l):
 
 
 def balanced_kwargs(args):
-    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum."""
-    return {"online_labels_balanced": args.online_labels_balanced, "online_labels_momentum": args.online_labels_momentum}
+    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed) when on."""
+    kw = {"online_labels_balanced": args.online_labels_balanced, "online_labels_momentum": args.online_labels_momentum}
+    if args.online_mix is not None:
+        kw.update(online_mix=args.online_mix, online_mix_seed=args.random_seed)
+    return kw
 
 
 def check_model(args):

@@ -343,9 +343,19 @@ def _online_momentum(text):
     return v
 
 
+def _online_mix(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 < v <= 1.0:             # (a NaN fails both comparisons)
+        raise argparse.ArgumentTypeError(f"{text!r}: expected the probability that an item receives its neighbour's classes, 0 < P <= 1")
+    return v
+
+
 def add_online_label_args(p):
-    """--online-labels / --online-labels-every (DESIGN 7.16) and --online-labels-balanced / --online-labels-momentum (7.17) of trainV1_warmup;
-    `check_online_label_args` holds their refusals."""
+    """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17) and --online-mix (7.18)
+    of trainV1_warmup; `check_online_label_args` holds their refusals."""
     from simt_amd.online_labels import DEFAULT_PORTION, DEFAULT_THRESHOLD
     p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
                    help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
@@ -362,11 +372,18 @@ def add_online_label_args(p):
                         "Default: the one threshold T")
     p.add_argument("--online-labels-momentum", type=_online_momentum, default=None, metavar="M",
                    help="with --online-labels-balanced: thr <- M * thr + (1 - M) * the batch's threshold (0 <= M < 1).  Default: 0.9")
+    p.add_argument("--online-mix", type=_online_mix, nargs="?", const=1.0, default=None, metavar="P",
+                   help="with --online-labels: ClassMix by the teacher's labels, inside the trainer (simt_amd/online_labels.py; DESIGN 7.18) -- "
+                        "with probability P (no value: 1.0) item i of a batch receives, image and label, the pixels of half of the classes the "
+                        "teacher found in item i+1.  Needs --batch-size 2 ... 32 and --num-classes <= 32; the draws are seeded by --random-seed.  "
+                        "With --colour-jitter, --gaussian-blur or --mask-patches the teacher labels the weak view and the mix selects from the "
+                        "strong views.  Default: off")
 
 
 def check_online_label_args(p, args):
-    """argparse's error (exit status 2) naming the flag: --online-labels-every without --online-labels or without --ema, and --online-labels
-    with --class-mix (the mix reads the classes to paste from the partner's LABEL, which the teacher has not made yet)."""
+    """argparse's error (exit status 2) naming the flag: --online-labels-every without --online-labels or without --ema, --online-labels
+    with --class-mix (the loader's mix reads the classes to paste from the partner's LABEL, which the teacher has not made yet), and --online-mix
+    without --online-labels or outside the batch sizes and class counts the mix holds."""
     if args.online_labels_every is not None and args.online_labels is None:
         p.error("--online-labels-every needs --online-labels: it moves the teacher that makes the labels")
     if args.online_labels_every is not None and args.ema is None:
@@ -379,7 +396,15 @@ def check_online_label_args(p, args):
         p.error(f"--online-labels-balanced with --num-classes {args.num_classes}: the confidence histogram holds at most 64 classes")
     if args.online_labels is not None and args.class_mix is not None:
         p.error("--online-labels cannot be combined with --class-mix: the mix reads the classes to paste from the partner's label, and "
-                "the teacher makes the labels behind the loader")
+                "the teacher makes the labels behind the loader (--online-mix mixes behind the teacher)")
+    if getattr(args, "online_mix", None) is not None:
+        from simt_amd.data.class_mix import MAX_CLASSES, MAX_ITEMS
+        if args.online_labels is None:
+            p.error("--online-mix needs --online-labels: it mixes by the teacher's labels")
+        if not 2 <= args.batch_size <= MAX_ITEMS:
+            p.error(f"--online-mix with --batch-size {args.batch_size}: items are mixed with their neighbour in the batch, 2 to {MAX_ITEMS} of them")
+        if not 1 <= args.num_classes <= MAX_CLASSES:
+            p.error(f"--online-mix with --num-classes {args.num_classes}: the presence word holds 1 to {MAX_CLASSES} classes")
 
 
 def online_label_line(args):
@@ -390,7 +415,8 @@ def online_label_line(args):
     who = "a fixed teacher (the start weights)" if n is None else f"a teacher that follows the weight EMA (decay {args.ema}), refreshed every {n} update(s)"
     weak = online_weak_view(args)
     print(f"online labels: {who} labels every batch, kept where its confidence is > {args.online_labels}; the teacher sees "
-          f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}" + balanced_clause(args))
+          f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}" + balanced_clause(args) +
+          mix_clause(args, weak))
 
 
 def online_balanced(args):
@@ -409,6 +435,16 @@ def balanced_clause(args):
         return ""
     return (f"; class-balanced: one threshold per class, from {args.online_labels} towards the value that keeps the share {pm[0]} of the class's "
             f"pixels in a batch (momentum {pm[1]}), never above {args.online_labels}")
+
+
+def mix_clause(args, weak):
+    """What --online-mix adds to the start-up line ("" without it)."""
+    p = getattr(args, "online_mix", None)
+    if p is None:
+        return ""
+    views = (f"; the mix selects from the students' strong views: a pasted region carries its partner's {', '.join(weak)}" if weak else "")
+    return (f"; online mix: with probability {p} an item receives, image and label, half of the classes the teacher found in its neighbour, "
+            f"behind the teacher and in front of the student's forward" + views)
 
 
 def online_weak_view(args):
@@ -578,7 +614,7 @@ class EmaSnapshots:
 
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
-                "online_labels": False, "online_labels_balanced": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_labels": False, "online_labels_balanced": False, "online_mix": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -607,6 +643,8 @@ def run_identity(args, class_dist):
         ident["online_labels"] = [float(args.online_labels), args.online_labels_every]      # [T, N | None]
         if online_balanced(args) is not None:
             ident["online_labels_balanced"] = online_balanced(args)      # [P, M]
+        if getattr(args, "online_mix", None) is not None:
+            ident["online_mix"] = float(args.online_mix)                 # P (the seed is random_seed)
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

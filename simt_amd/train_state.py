@@ -33,6 +33,8 @@ VALUE_FIELDS = ("online_labels", "online_labels_every")
 # and the class-balanced thresholds of that teacher's labels (online_labels_balanced = P, online_labels_momentum = M: DESIGN 7.17), compared
 # through value_mismatches(..., fields=BALANCE_FIELDS)
 BALANCE_FIELDS = ("online_labels_balanced", "online_labels_momentum")
+# and the mix behind that teacher (online_mix = P, online_mix_seed = S: DESIGN 7.18), compared through value_mismatches(..., fields=MIX_FIELDS)
+MIX_FIELDS = ("online_mix", "online_mix_seed")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -140,6 +142,9 @@ class TrainStateMixin:
             if getattr(self, "online_labels_balanced", None) is not None:
                 hy["online_labels_balanced"] = float(self.online_labels_balanced)
                 hy["online_labels_momentum"] = float(self.online_labels_momentum)
+            if getattr(self, "online_mix", None) is not None:
+                hy["online_mix"] = float(self.online_mix)
+                hy["online_mix_seed"] = int(self.online_mix_seed)
         return hy
 
     def _nbt_steps(self, key):
@@ -160,7 +165,9 @@ class TrainStateMixin:
         The warm-up trainers' online labels (`online_labels`, simt_amd/online_labels.py): `hyper` carries tau and N only when on, `frozen_sha256`
         is that of the start model, a moving teacher travels as the same `teacher` entry, and `accumulators` gains the cumulative label counts
         with their host twin; without the keyword the dict is what it was.  With `online_labels_balanced` `hyper` also carries P and M
-        and `accumulators` the per-class thresholds (`label_thresholds`); their histogram is zero between steps and is not stored.
+        and `accumulators` the per-class thresholds (`label_thresholds`); their histogram is zero between steps and is not stored.  With
+        `online_mix` `hyper` also carries P and S and the dict gains `mix_rng`, the `bit_generator.state` of the mix's generator:
+        the resumed run draws what the uninterrupted one draws.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -183,6 +190,8 @@ class TrainStateMixin:
                 ts["accumulators"].update(label_counts=self.label_counts.detach().cpu(), counts_reported=[int(c) for c in self._counts_reported])
                 if getattr(self, "online_labels_balanced", None) is not None:
                     ts["accumulators"]["label_thresholds"] = self.label_thr.detach().cpu()
+        if getattr(self, "online_mix", None) is not None:      # the position of the mix's own generator (numpy's plain dict of Python ints)
+            ts["mix_rng"] = self._mix_rng.bit_generator.state
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
             ts["ema"] = self.ema.state()
         if getattr(self, "teacher", None) is not None:      # the EMA teacher (simt_amd/ema_teacher.py): every, refresh count, the frozen model as it is now
@@ -197,7 +206,8 @@ class TrainStateMixin:
         (`plan.repack()`).  `state_dict()` afterwards reports the `num_batches_tracked` an uninterrupted run reports (the steps taken are
         counted once).  Data parallel: every rank loads the same dict (see training_state)."""
         bad = (hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state()) +
-               value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -205,6 +215,8 @@ class TrainStateMixin:
         if hasattr(self, "frozen_sha256") and ts.get("frozen_sha256") != self.frozen_sha256:
             raise ValueError(f"frozen_sha256 differs: the train state was written beside another frozen model (state: {ts.get('frozen_sha256')}, "
                              f"this trainer: {self.frozen_sha256}); give the resumed run the same --restore-from")
+        if getattr(self, "online_mix", None) is not None and "mix_rng" not in ts:
+            raise ValueError("mix_rng: the train state carries no generator state for online_mix")
         from .ema import state_mismatch
         why = state_mismatch(getattr(self, "ema", None), ts.get("ema"))
         if why:
@@ -257,6 +269,8 @@ class TrainStateMixin:
                 if getattr(self, "online_labels_balanced", None) is not None:
                     self.label_thr.copy_(acc["label_thresholds"])
         self._bad_reported = int(ts["bad_reported"])
+        if getattr(self, "online_mix", None) is not None:
+            self._mix_rng.bit_generator.state = ts["mix_rng"]
         if getattr(self, "ema", None) is not None:
             self.ema.load_state(ts["ema"])
         if getattr(self, "teacher", None) is not None:      # the frozen model as the saved run's last refresh left it; its plan is re-packed
