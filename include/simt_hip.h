@@ -738,6 +738,70 @@ int simt_online_label_u8(const simt_online_label_u8_desc* d, simt_stream_t strea
 int simt_online_label_cb_u8(const simt_online_label_cb_u8_desc* d, simt_stream_t stream);
 int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t stream);
 
+/* ---- Quality-weighted online labels (the warm-up trainers' online_labels_weighted; csrc/label_sweep.hip, csrc/head_loss.hip,
+ * csrc/class_mix.hip) -----------------------------------------------------------------------------------------------------------------
+ * DACS / DAFormer / MIC: the threshold deletes no pixel.  The student trains on the teacher's arg-max everywhere and every pixel's
+ * cross-entropy is multiplied by a weight q, the share of pixels whose confidence is above the threshold.
+ *
+ * simt_online_label_w / simt_online_label_w_u8 -- simt_online_label / simt_online_label_u8 with three differences.  Sources and families
+ *   are the parents'.
+ *   label / lab8 (and part): those of the parent launch at threshold = -INFINITY, bit for bit: the arg-max wherever the confidence is not
+ *     NaN, 255 where it is.
+ *   counts[C+1], accumulated: bin arg takes a pixel with conf > threshold, bin C every other pixel -- the counts of the parent launch at
+ *     `threshold`, count for count.
+ *   conf_part: [B][rows] uint32 words, rows = simt_online_label_parts() of the same B, H, W, family.  conf_part[b][g] = the number of pixels
+ *     of item b with conf > threshold that workgroup g swept.  EVERY word is written by a plain store on every call: no global atomics,
+ *     nothing to zero.  The sum of row b is the number of non-255 labels the parent launch at `threshold` writes into item b, exactly.
+ *   Refused (SIMT_ERR_INVALID, nothing launched): what the parents refuse, B > SIMT_CLASS_MIX_MAX, H * W >= 2^31, conf_part NULL or not
+ *   4-byte aligned.
+ *
+ * simt_label_quality -- conf_part -> q[B] fp32, one small launch of one workgroup behind the label launch on the same stream.  With n_b =
+ *   the integer sum of row b and N = H * W:
+ *     mode 0 ("item"):  q[b] = (float)((double)n_b / (double)N)
+ *     mode 1 ("batch"): every q[b] = (float)((double)(n_0 + ... + n_{B-1}) / (double)(B * N))
+ *   Integer sums, one conversion, one division, one rounding: np.float32(np.float64(n) / np.float64(N)).
+ *   Refused: a NULL or misaligned pointer, B outside 1 .. SIMT_CLASS_MIX_MAX, rows outside 1 .. SIMT_ONLINE_LABEL_MAX_PARTS, H, W <= 0 or
+ *   H * W >= 2^31, another mode.
+ *
+ * simt_head_loss_weighted / simt_head_grad_weighted -- simt_head_loss / simt_head_grad of a mode-1 descriptor (the warm-up stage's plain
+ *   cross-entropy; two heads or single = 1) with a weight per pixel.  w: [B] fp32 in DEVICE memory.  Pixel p of item b has weight w[b]
+ *   when w_item is NULL, else w[min(w_item[p], B - 1)] with w_item [B][H][W] bytes (the item map of simt_class_mix_u8_items).
+ *     hout[0], hout[1] = sum_p w_p * CE_k(p) / N with N = hout[6] the number of labelled pixels, unchanged; hout[14] formed from them as
+ *     before; hout[15], conf_out and label_ws unchanged.  Gradient: gscale * w_p * (softmax - onehot) / N through the same x- and
+ *     y-reductions.  With w = 1 everywhere and no map both launches give what the unweighted ones give, bit for bit.
+ *   Refused: what simt_head_loss / simt_head_grad refuse, mode 0, a NULL or misaligned w.
+ *
+ * simt_class_mix_u8_items -- simt_class_mix_u8, and the item every pixel came from: item_out[i][p] = m ? partner[i] : i (apply[i] == 0: i
+ *   everywhere), [B][h][w] bytes, 4-byte aligned.  x_out and lab_out are simt_class_mix_u8's, bit for bit.  A NULL map is refused. */
+typedef struct {
+  const float* fix;        /* as simt_online_label_desc */
+  int64_t* label;          /* out [B][H][W]: the arg-max (255: a NaN confidence) */
+  int64_t* counts;         /* [C+1], accumulated: what simt_online_label at `threshold` accumulates */
+  uint32_t* conf_part;     /* out [B][simt_online_label_parts()] */
+  int32_t B, h, w, ld, H, W, C, family;
+  float threshold;
+} simt_online_label_w_desc;
+typedef struct {
+  const float* fix;        /* as simt_online_label_desc */
+  uint8_t* lab8;           /* out [B][H][W] bytes; 16-byte aligned */
+  int64_t* counts;         /* [C+1], accumulated */
+  uint32_t* part;          /* out [B][rows]: the presence words of lab8 */
+  uint32_t* conf_part;     /* out [B][rows] */
+  int32_t B, h, w, ld, H, W, C, family;
+  float threshold;
+} simt_online_label_w_u8_desc;
+typedef struct {
+  const uint32_t* conf_part;   /* [B][rows] */
+  float* q;                    /* out [B] */
+  int32_t B, rows, H, W, mode; /* mode 0: per item; 1: one value for the batch */
+} simt_label_quality_desc;
+int simt_online_label_w(const simt_online_label_w_desc* d, simt_stream_t stream);
+int simt_online_label_w_u8(const simt_online_label_w_u8_desc* d, simt_stream_t stream);
+int simt_label_quality(const simt_label_quality_desc* d, simt_stream_t stream);
+int simt_head_loss_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream);
+int simt_head_grad_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream);
+int simt_class_mix_u8_items(const simt_class_mix_u8_desc* d, uint8_t* item_out, simt_stream_t stream);
+
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
  * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another

@@ -223,6 +223,26 @@ class OnlineLabelCbU8Desc(C.Structure):
                 ("ld", i32), ("H", i32), ("W", i32), ("C", i32), ("family", i32)]
 
 
+class OnlineLabelWDesc(C.Structure):
+    """simt_online_label_w_desc (include/simt_hip.h): simt_online_label that keeps every arg-max and counts the confident pixels per item."""
+    _fields_ = [("fix", c_p), ("label", c_p), ("counts", c_p), ("conf_part", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32), ("H", i32),
+                ("W", i32), ("C", i32), ("family", i32), ("threshold", f32)]
+
+
+class OnlineLabelWU8Desc(C.Structure):
+    """simt_online_label_w_u8_desc (include/simt_hip.h): the same with byte labels and the presence words."""
+    _fields_ = [("fix", c_p), ("lab8", c_p), ("counts", c_p), ("part", c_p), ("conf_part", c_p), ("B", i32), ("h", i32), ("w", i32), ("ld", i32),
+                ("H", i32), ("W", i32), ("C", i32), ("family", i32), ("threshold", f32)]
+
+
+LABEL_QUALITY_MODES = {"item": 0, "batch": 1}      # simt_label_quality_desc.mode
+
+
+class LabelQualityDesc(C.Structure):
+    """simt_label_quality_desc (include/simt_hip.h): the per-item counts of confident pixels -> the weights q[B]."""
+    _fields_ = [("conf_part", c_p), ("q", c_p), ("B", i32), ("rows", i32), ("H", i32), ("W", i32), ("mode", i32)]
+
+
 class ClassThresholdsDesc(C.Structure):
     """simt_class_thresholds_desc (include/simt_hip.h): the histogram -> the batch thresholds, folded into the device thresholds; hist zeroed."""
     _fields_ = [("hist", c_p), ("thr", c_p), ("t_out", c_p), ("drop", C.c_double), ("C", i32), ("cap", f32), ("omd", f32)]
@@ -349,6 +369,12 @@ SIGNATURES = {
     "simt_ema_multi": (_I, [C.POINTER(EmaDesc), c_p]),
     "simt_bn_fold_multi": (_I, [C.POINTER(BnFoldDesc), c_p]),
     "simt_patch_mask": (_I, [C.POINTER(PatchMaskDesc), c_p]),
+    "simt_online_label_w": (_I, [C.POINTER(OnlineLabelWDesc), c_p]),
+    "simt_online_label_w_u8": (_I, [C.POINTER(OnlineLabelWU8Desc), c_p]),
+    "simt_label_quality": (_I, [C.POINTER(LabelQualityDesc), c_p]),
+    "simt_head_loss_weighted": (_I, [C.POINTER(HeadDesc), c_p, c_p, c_p]),
+    "simt_head_grad_weighted": (_I, [C.POINTER(HeadDesc), c_p, c_p, c_p]),
+    "simt_class_mix_u8_items": (_I, [C.POINTER(ClassMixU8Desc), c_p, c_p]),
 }
 
 _lib = None

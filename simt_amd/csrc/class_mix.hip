@@ -263,8 +263,14 @@ __device__ __forceinline__ uint32_t load_labels4(const uint8_t* __restrict__ l, 
   return (uint32_t)l[p] | ((uint32_t)l[p + 1] << 8) | ((uint32_t)l[p + 2] << 16) | ((uint32_t)l[p + 3] << 24);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_u8_desc d) {
+// ItemOut: empty for simt_class_mix_u8 (name, arguments and code as before the flavour existed); {uint8_t*} for simt_class_mix_u8_items,
+// which also writes the item each pixel came from (class_mix_kernel's item_out: one dword per quad when VEC, bytes otherwise and in the tail).
+__device__ __forceinline__ uint8_t* first_item_out() { return nullptr; }
+__device__ __forceinline__ uint8_t* first_item_out(uint8_t* p) { return p; }
+
+template <bool VEC, class... ItemOut>
+__global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_u8_desc d, ItemOut... item_out) {
+  constexpr bool ITEMS = sizeof...(ItemOut) > 0;
   const int i = blockIdx.y;
   const int apply = d.apply[i];
   const int C = d.n_classes;
@@ -278,6 +284,8 @@ __global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_
   const uint32_t* __restrict__ xj = xi;
   const uint8_t* __restrict__ lj = li;
   uint32_t mask = 0u;
+  uint8_t* __restrict__ io = ITEMS ? first_item_out(item_out...) + (long)i * HW : nullptr;
+  const uint32_t jj = apply ? d.partner[i] : (uint32_t)i;      // (ITEMS: the item a pasted pixel came from)
   if (apply) {
     const int j = d.partner[i];
     uint32_t present = 0u;
@@ -306,6 +314,14 @@ __global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_
         lo[p] = (long long)(a & 255u); lo[p + 1] = (long long)((a >> 8) & 255u);
         lo[p + 2] = (long long)((a >> 16) & 255u); lo[p + 3] = (long long)(a >> 24);
       }
+      if (ITEMS) {
+        const uint32_t b0 = m0 ? jj : (uint32_t)i, b1 = m1 ? jj : (uint32_t)i, b2 = m2 ? jj : (uint32_t)i, b3 = m3 ? jj : (uint32_t)i;
+        if (VEC) {
+          *(uint32_t*)(io + p) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        } else {
+          io[p] = (uint8_t)b0; io[p + 1] = (uint8_t)b1; io[p + 2] = (uint8_t)b2; io[p + 3] = (uint8_t)b3;
+        }
+      }
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
         const long o = ch * HW + p;
@@ -332,13 +348,15 @@ __global__ __launch_bounds__(256) void class_mix_u8_kernel(const simt_class_mix_
         const bool m = pasted8(l, C, mask);
         lo[p] = (long long)(m ? l : (uint32_t)li[p]);
         for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = m ? xj[ch * HW + p] : xi[ch * HW + p];
+        if (ITEMS) io[p] = (uint8_t)(m ? jj : (uint32_t)i);
       }
     }
   }
 }
 
-extern "C" int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t stream) {
+static int class_mix_u8_launch(const simt_class_mix_u8_desc* d, uint8_t* item_out, bool items, simt_stream_t stream) {
   SIMT_CHECK(d && d->x && d->lab8 && d->x_out && d->lab_out && d->part);
+  SIMT_CHECK(!items || (item_out && ((uintptr_t)item_out & 3) == 0));
   SIMT_CHECK(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->lab8 & 15) == 0 && ((uintptr_t)d->x_out & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0);
   SIMT_CHECK(((uintptr_t)d->part & 3) == 0);
   SIMT_CHECK(d->B >= 2 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0);
@@ -354,10 +372,23 @@ extern "C" int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t 
   }
   const long lanes = (HW >> 2) + ((HW & 3) ? 1 : 0);
   const dim3 grid((unsigned)((lanes + 256 * MIX8_QPT - 1) / (256 * MIX8_QPT)), (unsigned)d->B);
-  if ((HW & 3) == 0)
+  const bool vec = (HW & 3) == 0;
+  if (vec && !items)
     hipLaunchKernelGGL((class_mix_u8_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d);
-  else
+  else if (!items)
     hipLaunchKernelGGL((class_mix_u8_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else if (vec)
+    hipLaunchKernelGGL((class_mix_u8_kernel<true, uint8_t*>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
+  else
+    hipLaunchKernelGGL((class_mix_u8_kernel<false, uint8_t*>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
+}
+
+extern "C" int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t stream) { return class_mix_u8_launch(d, nullptr, false, stream); }
+
+// simt_class_mix_u8 plus the item map (the weighted head reads a pasted pixel's weight from its partner's entry): x_out /
+// lab_out bit for bit as above -- same grid, same paste mask.
+extern "C" int simt_class_mix_u8_items(const simt_class_mix_u8_desc* d, uint8_t* item_out, simt_stream_t stream) {
+  return class_mix_u8_launch(d, item_out, true, stream);
 }

@@ -235,18 +235,28 @@ struct HeadArgs {
   unsigned char* conf_out;     // optional [B][H][W]: the confidence label decided per pixel (255 = none)
   unsigned char* label_ws;     // optional [B][H][W]: the checked noisy label (255 = ignored / invalid / warm-up mode), pass 1 -> pass 2
   const unsigned char* fix_item;  // optional [B][H][W] (simt_head_*_views): the item of fixp a pixel reads its frozen operand from
+  const float* w;                 // simt_head_*_weighted: [B] per-item weights of the warm-up cross-entropy (device memory), else NULL
+  const unsigned char* w_item;    // optional [B][H][W] (simt_head_*_weighted): the item whose weight a pixel carries
 };
 
 // The flavour pack of the two pass kernels: <> the SimT / DeepLab-v2 warm-up code (names as before any flavour existed), <true> ONE,
-// <false, true> VIEWS.
+// <false, true> VIEWS, <ONE, false, true> WEIGHTED.
 template <bool... F_>
-constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false}; return v[i]; }
+constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false, false}; return v[i]; }
 
 // VIEWS: the frozen operand of pixel pix of item b comes from item fb = min(fix_item[pix], B - 1).  The taps index pixels from fixp's base
 // and differ from the pixel's own by a constant: one byte load and one pointer offset, no second make_taps.
 __device__ __forceinline__ const float* fixp_of_item(const HeadArgs& a, const HeadGeom& g, int b, long pix) {
   const int fb = min((int)a.fix_item[pix], g.B - 1);
   return a.fixp + (long)(fb - b) * g.h * g.w * g.ldf;
+}
+
+// WEIGHTED: pixel pix of item b carries the weight of item wb = min(w_item[pix], B - 1), or of its own item without a map --
+// fixp_of_item's lookup on the [B] table.  The map is tested at run time: the two forms are ONE kernel, so a constant map per item gives
+// what the map-less launch gives on the gathered table, bit for bit.
+__device__ __forceinline__ float weight_of_item(const HeadArgs& a, const HeadGeom& g, int b, long pix) {
+  const int wb = a.w_item ? min((int)a.w_item[pix], g.B - 1) : b;
+  return a.w[wb];
 }
 
 // Full-wave sum with DPP row operations (no LDS crossbar): result valid in lane 63.
@@ -299,10 +309,16 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
 // one-output model (single = 1, mode = 1): one head per pixel and only its cross-entropy against the label, run-time channel counts.
 // {false, true}: VIEWS, mode 0 with an item map (a.fix_item): a compile-time flavour, so the map-less launches keep their code and registers.
 // (Its QM = 40 fall-back asks for one wave per SIMD: at two, the extra address pair spilled where the map-less fall-back already does.)
+// {ONE, false, true}: WEIGHTED, mode 1 with a weight per pixel (a.w, a.w_item): in the run-time-count builds the mode is a compile-time 1,
+// so the SimT terms fold away and what is left is the warm-up cross-entropy of the flavour beside it with one multiplication per pixel and
+// head.  The compile-time-count builds keep the run-time mode: with the SimT terms gone the compiler fused the softmax's product into the
+// subtraction of the one-hot (a last-bit difference on ~0.05 % of the gradient's words), and w = 1 must give the unweighted launch bit for bit.
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass1_kernel(HeadArgs a) {
-  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1);
+  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time");
+  static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
+  const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C;
   constexpr int CM = CT ? (CT + 3) / 4 * 4 : QM;
@@ -315,7 +331,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
   float* sRed = (float*)(sEx + 2);                                 // [4][NSCAL]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < QC; i += 256) { sT[i] = a.mode == 0 ? a.T1[i] : 0.f; sT[QC + i] = a.mode == 0 ? a.T2[i] : 0.f; }
+  for (int i = tid; i < QC; i += 256) { sT[i] = mode == 0 ? a.T1[i] : 0.f; sT[QC + i] = mode == 0 ? a.T2[i] : 0.f; }
   for (int i = tid; i < 8 * QC; i += 256) sdT[i] = 0.f;
   if (tid < 2 * QMAX) sKey[tid] = 0ull;
   if (tid < 2) sEx[tid] = 0ull;
@@ -342,6 +358,8 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
       b = (int)(t / g.H);
     }
     Taps tp = make_taps(g, b, y, x);
+    float wp = 1.f;                                    // WEIGHTED: the pixel's weight
+    if constexpr (WEIGHTED) { if (live) wp = weight_of_item(a, g, b, p); }
     if constexpr (ONE) {
       // warm-up stage of a one-output model: CrossEntropyLoss(ignore_index=255) of its one head against the label (hout[1]); the
       // out-of-range count as in the other modes.  No frozen posterior, T, placeholder or anchor term.
@@ -357,6 +375,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
 #pragma unroll
         for (int j = 0; j < QM; ++j)
           if (j == (int)lab) l2 = e2.lse - v2[j];
+        if constexpr (WEIGHTED) l2 = wp * l2;
         acc[1] += l2; acc[8] += 1.f;
       }
       if (live && a.conf_out) a.conf_out[p] = lab_ok ? (unsigned char)lab : (unsigned char)255;
@@ -368,7 +387,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
     int fa = 0;
     const float* fixp = a.fixp;
     if constexpr (VIEWS) { if (live) fixp = fixp_of_item(a, g, b, p); }
-    if (a.mode == 0) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
+    if (mode == 0) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
     asm volatile("" ::: "memory");   // keep the next gathers from being hoisted above (register pressure)
     int conf = (fm > a.th_high) ? fa : 255;
     if (fm < a.th_low) conf = C;
@@ -392,7 +411,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
     // a label outside [0, C) that is not the ignore value: the reference's nll_loss / CrossEntropyLoss raise ("Target out of bounds");
     // a kernel cannot, so the pixel is skipped and COUNTED (hout[15]): the host side raises when it reads the losses
     if (live && !lab_ok && lab != 255) acc[12] += 1.f;
-    if (a.mode == 1) {
+    if (mode == 1) {
       // warm-up stage (tools/trainV1_warmup.py:217-224): CrossEntropyLoss(ignore_index=255) of both heads against the
       // label itself; no placeholder, noise-posterior or anchor terms
       conf = lab_ok ? labi : 255;
@@ -409,6 +428,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
 #pragma unroll
         for (int j = 0; j < QM; ++j)
           if (j == conf) { l1 = e1.lse - v1[j]; l2 = e2.lse - v2[j]; }
+        if constexpr (WEIGHTED) { l1 = wp * l1; l2 = wp * l2; }
         acc[0] += l1; acc[1] += l2; acc[8] += 1.f;
       }
       if (e1.pseudo1 != 255) {
@@ -478,7 +498,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
       }
     }
     // ---- anchors: arg-max over all pixels of each channel's upsampled logit (first index), Exist masks (:375-384)
-    if (a.mode == 0) {
+    if (mode == 0) {
       unsigned long long ex1 = live ? (1ull << e1.arg) : 0ull, ex2 = live ? (1ull << e2.arg) : 0ull;
       ex1 = wave_or_u64(ex1);
       ex2 = wave_or_u64(ex2);
@@ -696,8 +716,10 @@ __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL
 // head-2 rows of sG / sAcc / g1 (head_yreduce_kernel skips head 1 of a single-head descriptor).
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass2_kernel(HeadArgs a) {
-  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1);
+  constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time (rows = 1)");
+  static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
+  const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C, QP = a.QP;
   constexpr int CM = CT ? (CT + 3) / 4 * 4 : QM;
@@ -722,7 +744,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
   for (int k = 0; k < 3; ++k)
 #pragma unroll
     for (int i = 0; i < NACC; ++i) gacc[k][i] = 0.f;
-  for (int i = tid; i < QC; i += 256) { sT[i] = a.mode == 0 ? a.T1[i] : 0.f; sT[QC + i] = a.mode == 0 ? a.T2[i] : 0.f; }
+  for (int i = tid; i < QC; i += 256) { sT[i] = mode == 0 ? a.T1[i] : 0.f; sT[QC + i] = mode == 0 ? a.T2[i] : 0.f; }
   const float* o = a.hout;
   const float Np = o[6], Nk1 = o[7], Nk2 = o[8], Ny = o[9];
   const float gs = a.gscale;
@@ -762,6 +784,12 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
       // instead of the frozen posterior's 4 x C gathers + arg-max and the 8-byte label), else decided again
       const bool from_p1 = a.conf_out != nullptr && a.label_ws != nullptr;
       const long pix = ((long)b * g.H + y) * g.W + x;
+      // WEIGHTED: the pixel's two gradient factors carry its weight (gscale * w_p / N; head 1 also lambda_seg), formed once per pixel
+      float gw1 = gp1, gw2 = gp2;
+      if constexpr (WEIGHTED) {
+        const float wp = live ? weight_of_item(a, g, b, pix) : 0.f;
+        gw1 = gp1 * wp; gw2 = gp2 * wp;
+      }
       if constexpr (ONE) {
         // warm-up stage of a one-output model: gscale * (softmax - onehot(label)) / N_valid of the one head, staged in the head-2 rows
         float v2[QM];
@@ -781,7 +809,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
           if (j < Q) {
             const float q2 = exp_le0(v2[j] - e2.vmax) * inv2;
             float G2 = 0.f;
-            if (live && conf != 255) G2 += gp2 * (q2 - ((j == conf) ? 1.f : 0.f));
+            if (live && conf != 255) G2 += (WEIGHTED ? gw2 : gp2) * (q2 - ((j == conf) ? 1.f : 0.f));
             sG[(1 * 256 + tid) * GP + j] = G2;
           }
       } else {
@@ -789,7 +817,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
       int fa = 0;
       const float* fixp = a.fixp;
       if constexpr (VIEWS) { if (live && !from_p1) fixp = fixp_of_item(a, g, b, pix); }
-      if (a.mode == 0 && !from_p1) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
+      if (mode == 0 && !from_p1) fixed_posterior<CM>(g, C, fixp, tp, fm, fa);
       asm volatile("" ::: "memory");
       int conf = (fm > a.th_high) ? fa : 255;
       if (fm < a.th_low) conf = C;
@@ -817,7 +845,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
         lab_ok = live && lab >= 0 && lab != 255 && lab < C;
         labi = lab_ok ? (int)lab : 0;
       }
-      if (a.mode == 1) {
+      if (mode == 1) {
         if (!from_p1) conf = lab_ok ? labi : 255;
         e1.pseudo1 = 255;
         e2.pseudo1 = 255;
@@ -843,8 +871,8 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
           if (live) {
             if (conf != 255) {
               float oh = (j == conf) ? 1.f : 0.f;
-              G1 += gp1 * (q1 - oh);
-              G2 += gp2 * (q2 - oh);
+              G1 += (WEIGHTED ? gw1 : gp1) * (q1 - oh);
+              G2 += (WEIGHTED ? gw2 : gp2) * (q2 - oh);
             }
             if (e1.pseudo1 != 255) {
               G1 += gk1 * (q1 - ((j == e1.arg) ? 1.f : 0.f));
@@ -1056,6 +1084,7 @@ static int fill_args(const simt_head_desc* d, const uint8_t* fix_item, HeadArgs&
   a.conf_out = d->conf_out;
   a.label_ws = d->label_ws;
   a.fix_item = fix_item;
+  a.w = nullptr; a.w_item = nullptr;
   SIMT_CHECK(d->mode == 0 || d->mode == 1);
   SIMT_CHECK(!fix_item || d->mode == 0);      // the warm-up stage has no frozen operand to move
   return SIMT_OK;
@@ -1074,10 +1103,20 @@ extern "C" int simt_head_hout_floats(int Q, int C) {
 extern "C" int simt_head_keys_count(void) { return 2 * QMAX + 2; }
 
 // losses (pass 1 + finalize).  keys must be zeroed by this call: done here with a memset node on the stream.
-extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
+// the weighted launches' side of the arguments: mode 1 only, as a map is refused for mode 1 above
+static int fill_weights(const simt_head_desc* d, const float* w, const uint8_t* w_item, HeadArgs& a) {
+  SIMT_CHECK(w && ((uintptr_t)w & 3) == 0);
+  SIMT_CHECK(d->mode == 1);
+  a.w = w; a.w_item = w_item;
+  return SIMT_OK;
+}
+
+static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, const uint8_t* w_item,
+                            simt_stream_t stream) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
+  if (weighted) { if (int rw = fill_weights(d, w, w_item, a)) return rw; }
   hipStream_t st = (hipStream_t)stream;
   const int nblk = simt_head_nblk(d->B, d->H, d->W);
   (void)hipMemsetAsync(d->keys, 0, (2 * QMAX + 2) * sizeof(unsigned long long), st);
@@ -1088,11 +1127,21 @@ extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_
 #define P1ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass1_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)
     P1ATTR(24, 22, 19); P1ATTR(28, 25, 19); P1ATTR(24, 0, 0); P1ATTR(QMAX, 0, 0); P1ATTR(24, 0, 0, true); P1ATTR(QMAX, 0, 0, true);
     P1ATTR(24, 22, 19, false, true); P1ATTR(28, 25, 19, false, true); P1ATTR(24, 0, 0, false, true); P1ATTR(QMAX, 0, 0, false, true);
+    P1ATTR(24, 0, 0, true, false, true); P1ATTR(QMAX, 0, 0, true, false, true); P1ATTR(24, 22, 19, false, false, true);
+    P1ATTR(28, 25, 19, false, false, true); P1ATTR(24, 0, 0, false, false, true); P1ATTR(QMAX, 0, 0, false, false, true);
 #undef P1ATTR
   }
 #define P1(...) hipLaunchKernelGGL((head_pass1_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), lds1, st, a)
   const bool one = d->single && d->mode == 1;            // warm-up stage of a one-output model: one head, plain CE
-  if (one && d->Q <= 24) P1(24, 0, 0, true);
+  if (weighted) {                                        // the dispatch below, flavour for flavour (no map: mode 1)
+    if (one && d->Q <= 24) P1(24, 0, 0, true, false, true);
+    else if (one) P1(QMAX, 0, 0, true, false, true);
+    else if (d->Q == 22 && d->C == 19) P1(24, 22, 19, false, false, true);
+    else if (d->Q == 25 && d->C == 19) P1(28, 25, 19, false, false, true);
+    else if (d->Q <= 24) P1(24, 0, 0, false, false, true);
+    else P1(QMAX, 0, 0, false, false, true);
+  }
+  else if (one && d->Q <= 24) P1(24, 0, 0, true);
   else if (one) P1(QMAX, 0, 0, true);
   else if (fix_item && d->Q == 22 && d->C == 19) P1(24, 22, 19, false, true);
   else if (fix_item && d->Q == 25 && d->C == 19) P1(28, 25, 19, false, true);
@@ -1116,10 +1165,12 @@ extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_
 }
 
 // gradients w.r.t. the low-res logits (pass 2 + y reduction); needs hout from simt_head_loss of the same inputs.
-extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
+static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, const uint8_t* w_item,
+                            simt_stream_t stream) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
+  if (weighted) { if (int rw = fill_weights(d, w, w_item, a)) return rw; }
   SIMT_CHECK(d->g1 && d->QP >= d->Q);
   hipStream_t st = (hipStream_t)stream;
   size_t lds2 = pass2_lds(d->Q, d->C, d->w);
@@ -1129,11 +1180,21 @@ extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_
 #define P2ATTR(...) (void)hipFuncSetAttribute((const void*)head_pass2_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)
     P2ATTR(24, 22, 19); P2ATTR(28, 25, 19); P2ATTR(24, 0, 0); P2ATTR(QMAX, 0, 0); P2ATTR(24, 0, 0, true); P2ATTR(QMAX, 0, 0, true);
     P2ATTR(24, 22, 19, false, true); P2ATTR(28, 25, 19, false, true); P2ATTR(24, 0, 0, false, true); P2ATTR(QMAX, 0, 0, false, true);
+    P2ATTR(24, 0, 0, true, false, true); P2ATTR(QMAX, 0, 0, true, false, true); P2ATTR(24, 22, 19, false, false, true);
+    P2ATTR(28, 25, 19, false, false, true); P2ATTR(24, 0, 0, false, false, true); P2ATTR(QMAX, 0, 0, false, false, true);
 #undef P2ATTR
   }
 #define P2(...) hipLaunchKernelGGL((head_pass2_kernel<__VA_ARGS__>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
   const bool one = d->single && d->mode == 1;            // (fill_args: a.rows = 1)
-  if (one && d->Q <= 24) P2(24, 0, 0, true);
+  if (weighted) {
+    if (one && d->Q <= 24) P2(24, 0, 0, true, false, true);
+    else if (one) P2(QMAX, 0, 0, true, false, true);
+    else if (d->Q == 22 && d->C == 19) P2(24, 22, 19, false, false, true);
+    else if (d->Q == 25 && d->C == 19) P2(28, 25, 19, false, false, true);
+    else if (d->Q <= 24) P2(24, 0, 0, false, false, true);
+    else P2(QMAX, 0, 0, false, false, true);
+  }
+  else if (one && d->Q <= 24) P2(24, 0, 0, true);
   else if (one) P2(QMAX, 0, 0, true);
   else if (fix_item && d->Q == 22 && d->C == 19) P2(24, 22, 19, false, true);
   else if (fix_item && d->Q == 25 && d->C == 19) P2(28, 25, 19, false, true);
@@ -1155,6 +1216,21 @@ extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_
                        (float*)d->dpred1_t, (float*)d->dpred2_t, a.g, d->QP, d->ld_f32, d->ld_t, total, a.rows);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
+}
+
+extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
+  return head_loss_launch(d, fix_item, false, nullptr, nullptr, stream);
+}
+extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
+  return head_grad_launch(d, fix_item, false, nullptr, nullptr, stream);
+}
+
+// the weighted warm-up cross-entropy: mode 1 with a [B] weight table in device memory and an optional item map
+extern "C" int simt_head_loss_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream) {
+  return head_loss_launch(d, nullptr, true, w, w_item, stream);
+}
+extern "C" int simt_head_grad_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream) {
+  return head_grad_launch(d, nullptr, true, w, w_item, stream);
 }
 
 // the one-view forms: the NULL case of the same code

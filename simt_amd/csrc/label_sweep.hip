@@ -654,6 +654,93 @@ struct OnlineCbOut8 : U8Out {
   const float* thr;             // [C], device memory
 };
 
+// ---- quality-weighted labels: the threshold no longer deletes a pixel, it only decides which count the pixel lands in.  The
+// Item carries TWO labels: byte 0 the one that is written (Strict{-INFINITY}: the arg-max, 255 for a NaN confidence), byte 1 the one
+// simt_online_label at the threshold would have written (Strict{threshold}), which is what is COUNTED -- counts[] therefore stays what that
+// launch accumulates and `labelled` keeps its meaning.  pl_store / ol_store with the counted word packed beside the stored one.
+__device__ __forceinline__ unsigned int quad_pack(unsigned int v) {
+  unsigned int word = v | (__shfl_down(v, 1, 4) << 8);
+  word |= __shfl_down(word, 2, 4) << 16;
+  return word;
+}
+__device__ __forceinline__ void store_w(const U8Out& o, unsigned int lab, unsigned int key, long p, long P, int C, unsigned int* sh) {
+  const unsigned int word = quad_pack(lab), kword = quad_pack(key);
+  if ((threadIdx.x & 3) == 0 && p < P) {
+    const int n = P - p < 4 ? (int)(P - p) : 4;
+    if (n == 4) {
+      *reinterpret_cast<unsigned int*>(o.out + p) = word;
+    } else {
+      for (int i = 0; i < n; ++i) o.out[p + i] = (unsigned char)(word >> (8 * i));
+    }
+    pl_count(kword, n, C, sh);
+  }
+}
+__device__ __forceinline__ void store_w(const I64Out& o, unsigned int lab, unsigned int key, long p, long P, int C, unsigned int* sh) {
+  const unsigned int kword = quad_pack(key);
+  if (p < P) {
+    o.label[p] = (long long)lab;
+    if ((threadIdx.x & 3) == 0) pl_count(kword, P - p < 4 ? (int)(P - p) : 4, C, sh);
+  }
+}
+
+template <class Out>
+struct WeightedSink {
+  typedef unsigned int Shared[256];
+  typedef unsigned int Item;    // byte 0: the label written; byte 1: the label counted
+  Out o;
+  float threshold;
+  int C;
+  template <int BLOCK> __device__ __forceinline__ void init(Shared& sh) const { pl_hist_init<BLOCK>(sh, C + 1); }
+  __device__ __forceinline__ Item item(const Shared&, ArgConf r) const {
+    return Strict{-INFINITY}(r, nullptr) | (Strict{threshold}(r, nullptr) << 8);
+  }
+  static __device__ __forceinline__ unsigned int label(Item it) { return it & 255u; }
+  static __device__ __forceinline__ bool confident(Item it) { return ((it >> 8) & 255u) != 255u; }
+  __device__ __forceinline__ void emit(Shared& sh, Item it, long p, long P) const { store_w(o, it & 255u, (it >> 8) & 255u, p, P, C, sh); }
+  template <int BLOCK> __device__ __forceinline__ void flush(Shared& sh) const { pl_hist_flush<BLOCK>(sh, C + 1, o.counts); }
+};
+
+// the per-item count of confident pixels: a DECORATOR in PresenceSink's pattern -- one LDS word per item, added to once per wave where the
+// wave's 64 pixels lie in one item (a ballot's population count), once per confident lane otherwise; the flush stores the workgroup's word of
+// EVERY item with a plain store: conf_part[b][g] is written on every call, no global atomics, nothing to zero.  Integer counts: exact and order
+// independent.  It forwards label() and C, so that PresenceSink composes over it.
+template <class Inner>
+struct ConfPartSink {
+  struct Shared {
+    typename Inner::Shared in;
+    unsigned int n[SIMT_CLASS_MIX_MAX];
+  };
+  typedef typename Inner::Item Item;
+  Inner in;
+  unsigned int* conf_part;      // [B][gridDim.x]
+  int B;
+  long HW;
+  int C;
+  template <int BLOCK> __device__ __forceinline__ void init(Shared& sh) const {
+    if (threadIdx.x < SIMT_CLASS_MIX_MAX) sh.n[threadIdx.x] = 0u;
+    in.template init<BLOCK>(sh.in);                      // (ends with the barrier that also covers n)
+  }
+  __device__ __forceinline__ Item item(const Shared& sh, ArgConf r) const { return in.item(sh.in, r); }
+  static __device__ __forceinline__ unsigned int label(const Item& it) { return Inner::label(it); }
+  __device__ __forceinline__ void emit(Shared& sh, Item it, long p, long P) const {
+    in.emit(sh.in, it, p, P);
+    const bool ok = p < P && Inner::confident(it);
+    const int b = (int)((p < P ? p : P - 1) / HW);       // lanes past the end: the last item, and no count
+    const int b_first = __builtin_amdgcn_readfirstlane(b), b_last = __builtin_amdgcn_readlane(b, 63);
+    if (b_first == b_last) {
+      const unsigned long long m = __ballot(ok);
+      if ((threadIdx.x & 63) == 0 && m) atomicAdd(&sh.n[b_first], (unsigned int)__popcll(m));
+    } else if (ok) {
+      atomicAdd(&sh.n[b], 1u);
+    }
+  }
+  template <int BLOCK> __device__ __forceinline__ void flush(Shared& sh) const {
+    in.template flush<BLOCK>(sh.in);
+    __syncthreads();
+    if ((int)threadIdx.x < B) conf_part[(long)threadIdx.x * gridDim.x + blockIdx.x] = sh.n[threadIdx.x];
+  }
+};
+
 // ============================================================== entry points ===============================================================
 extern "C" int simt_upsample_sum_argmax(const float* la, int ha, int wa, int lda, const float* lb, int hb, int wb, int ldb,
                                         int B, int H, int W, int C, int32_t* pred, simt_stream_t stream) {
@@ -815,6 +902,77 @@ extern "C" int simt_online_label_cb_u8(const simt_online_label_cb_u8_desc* d, si
   const ConfSink<true, true, OnlineCbOut8> inner{o, {}, d->C};
   const PresenceSink<ConfSink<true, true, OnlineCbOut8>> sink{inner, d->part, d->B, (long)d->H * d->W};
   return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
+}
+
+// ---- quality-weighted online labels: every pixel keeps its arg-max, the threshold decides the counts and the per-item
+// number of confident pixels simt_label_quality turns into the weights.  Sources and families are launch_online's.
+template <class D>
+static int online_w_checks(const D* d, bool u8) {
+  SIMT_CHECK(d && d->fix && d->counts && d->conf_part);
+  SIMT_CHECK(d->B > 0 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0);
+  SIMT_CHECK(d->C > 0 && d->C <= (u8 ? SIMT_CLASS_MIX_CLASSES : 255) && d->C <= d->ld);
+  SIMT_CHECK(d->family == 0 || d->family == 1);
+  SIMT_CHECK((long)d->H * d->W < (1L << 31));
+  SIMT_CHECK(((uintptr_t)d->counts & 7) == 0 && ((uintptr_t)d->conf_part & 3) == 0);
+  return SIMT_OK;
+}
+
+extern "C" int simt_online_label_w(const simt_online_label_w_desc* d, simt_stream_t stream) {
+  if (int rc = online_w_checks(d, false)) return rc;
+  SIMT_CHECK(d->label && ((uintptr_t)d->label & 7) == 0);
+  const WeightedSink<I64Out> inner{{(long long*)d->label, (unsigned long long*)d->counts}, d->threshold, d->C};
+  const ConfPartSink<WeightedSink<I64Out>> sink{inner, d->conf_part, d->B, (long)d->H * d->W, d->C};
+  return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
+}
+
+extern "C" int simt_online_label_w_u8(const simt_online_label_w_u8_desc* d, simt_stream_t stream) {
+  if (int rc = online_w_checks(d, true)) return rc;
+  SIMT_CHECK(d->lab8 && d->part && ((uintptr_t)d->lab8 & 15) == 0 && ((uintptr_t)d->part & 3) == 0);
+  const WeightedSink<U8Out> inner{{d->lab8, (unsigned long long*)d->counts}, d->threshold, d->C};
+  const ConfPartSink<WeightedSink<U8Out>> mid{inner, d->conf_part, d->B, (long)d->H * d->W, d->C};
+  const PresenceSink<ConfPartSink<WeightedSink<U8Out>>> sink{mid, d->part, d->B, (long)d->H * d->W};
+  return launch_online(d->fix, d->B, d->h, d->w, d->ld, d->H, d->W, d->C, d->family, sink, stream);
+}
+
+// The weights: q[b] = the share of confident pixels, of item b (mode 0, "item") or of the whole micro-batch (mode 1, "batch": DACS's scalar,
+// written to every entry).  ONE workgroup; wave v sums the rows of items v, v + LQ_BLOCK / 64, ... as 64-bit integers (lanes stride the row,
+// six shuffle steps), the sums meet in LDS, and thread b forms its quotient: one conversion of each integer to double (exact below 2^53),
+// one division, one rounding to float -- np.float32(np.float64(n) / np.float64(N)).  No atomics.
+constexpr int LQ_BLOCK = 256;
+
+__global__ __launch_bounds__(LQ_BLOCK) void label_quality_kernel(const unsigned int* __restrict__ conf_part, float* __restrict__ q, int B,
+                                                                 int rows, long HW, int mode) {
+  __shared__ unsigned long long n[SIMT_CLASS_MIX_MAX];
+  const int lane = (int)(threadIdx.x & 63);
+  for (int b = (int)(threadIdx.x >> 6); b < B; b += LQ_BLOCK / 64) {          // uniform over the wave
+    unsigned long long s = 0ull;
+    for (int g = lane; g < rows; g += 64) s += (unsigned long long)conf_part[(long)b * rows + g];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) n[b] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < B) {
+    unsigned long long num = n[threadIdx.x];
+    long den = HW;
+    if (mode == 1) {
+      num = 0ull;
+      for (int b = 0; b < B; ++b) num += n[b];
+      den = (long)B * HW;
+    }
+    q[threadIdx.x] = (float)((double)num / (double)den);
+  }
+}
+
+extern "C" int simt_label_quality(const simt_label_quality_desc* d, simt_stream_t stream) {
+  SIMT_CHECK(d && d->conf_part && d->q && ((uintptr_t)d->conf_part & 3) == 0 && ((uintptr_t)d->q & 3) == 0);
+  SIMT_CHECK(d->B > 0 && d->B <= SIMT_CLASS_MIX_MAX && d->H > 0 && d->W > 0 && (long)d->H * d->W < (1L << 31));
+  SIMT_CHECK(d->rows >= 1 && d->rows <= SIMT_ONLINE_LABEL_MAX_PARTS);
+  SIMT_CHECK(d->mode == 0 || d->mode == 1);
+  hipLaunchKernelGGL(label_quality_kernel, dim3(1), dim3(LQ_BLOCK), 0, (hipStream_t)stream, d->conf_part, d->q, d->B, d->rows,
+                     (long)d->H * d->W, d->mode);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
 }
 
 // The thresholds' side: class_thresholds() of tools/make_pseudo_labels.py on the device, the fold into thr, and the histogram's reset.  ONE

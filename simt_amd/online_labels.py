@@ -33,6 +33,16 @@ the labels as BYTES plus the per-item class-presence words of the same pass -- a
 and those bytes straight into the student's input and `trainer.label` (int64); there is no input copy and no staging pair.  The draws are the
 loader's (`simt_amd.data.class_mix`: `generator(S, rank)`, one `draw_batch` per micro-batch).  `labelled` and `label_thresholds` stay statistics
 of the teacher's labels BEFORE the mix.
+
+Quality weights (keyword `online_labels_weighted="batch" | "item"`, flag --online-labels-weighted): the rule of DACS / DAFormer /
+MIC.  The threshold deletes no pixel: step 3 becomes `simt_online_label_w` (`_w_u8` with the mix) -- the arg-max at EVERY pixel, the counts of
+the launch it replaces (`labelled` keeps its meaning: the share of confident pixels) and the per-item numbers of confident pixels -- followed
+by `simt_label_quality` on the same stream: q[B], the share of confident pixels of the micro-batch ("batch": one scalar, the published rule)
+or of every item ("item").  The head launches become `simt_head_loss_weighted` / `simt_head_grad_weighted`: every pixel's cross-entropy
+times its item's q, still divided by the number of labelled pixels.  With `online_mix` in "item" mode the mix is `simt_class_mix_u8_items`
+and the head reads a pasted pixel's weight from its partner's entry through that map; in "batch" mode all entries are equal and there is
+no map.  `label_quality` below restates the second launch in numpy.  `losses()` gains `label_quality`, the weights of the last micro-batch.
+Rank-local, as `labelled` is.  Not with `online_labels_balanced` in this version.
 """
 import ctypes as C
 
@@ -49,6 +59,8 @@ DEFAULT_THRESHOLD = 0.968      # DACS / DAFormer
 DEFAULT_PORTION = 0.5          # BDL's label generator keeps the more confident half of every class
 DEFAULT_MOMENTUM = 0.9         # IAST's exponential average of the per-class thresholds
 MAX_BALANCED_CLASSES = 64      # CONF_MAX_C of csrc/label_sweep.hip: the confidence histogram lives in LDS
+WEIGHTED_MODES = ("batch", "item")      # online_labels_weighted; simt_label_quality_desc.mode through _lib.LABEL_QUALITY_MODES
+MAX_WEIGHTED_ITEMS = 32        # SIMT_CLASS_MIX_MAX: one LDS word per item in the label launch, a byte per pixel in the item map
 
 
 def check_threshold(tau):
@@ -132,6 +144,37 @@ def check_mix(online_mix, online_mix_seed, tau, batch_size, num_classes):
     if not 1 <= num_classes <= class_mix.MAX_CLASSES:
         raise ValueError(f"online_mix with num_classes = {num_classes}: the presence word holds 1 to {class_mix.MAX_CLASSES} classes")
     return p, int(seed)
+
+
+def check_weighted(online_labels_weighted, tau, balanced, batch_size):
+    """The keyword of the quality weights -> "batch" | "item" | None; `tau` is check_settings' first value, `balanced`
+    check_balanced's first.  ValueError that starts with the keyword."""
+    mode = online_labels_weighted
+    if mode is None:
+        return None
+    if not isinstance(mode, str) or mode not in WEIGHTED_MODES:
+        raise ValueError(f"online_labels_weighted {mode!r}: expected \"batch\" (one weight for the micro-batch, the rule of DACS) or \"item\" "
+                         "(one weight per image)")
+    if tau is None:
+        raise ValueError("online_labels_weighted needs online_labels: it weighs the teacher's labels, and this trainer has no teacher")
+    if balanced is not None:
+        raise ValueError("online_labels_weighted cannot be combined with online_labels_balanced in this version: the weight is the share of "
+                         "pixels above the ONE threshold, and the per-class thresholds have no such share yet")
+    if not 1 <= batch_size <= MAX_WEIGHTED_ITEMS:
+        raise ValueError(f"online_labels_weighted with a batch of {batch_size}: the label launch counts at most {MAX_WEIGHTED_ITEMS} items")
+    return mode
+
+
+def label_quality(n, N, mode):
+    """`simt_label_quality` in numpy -> float32 [B].  n: the number of confident pixels of every item (integers), N = H * W.  "item":
+    q[b] = float32(float64(n_b) / float64(N)); "batch": every entry float32(float64(sum n) / float64(B * N)).  Integer sums, one
+    conversion, one division, one rounding."""
+    n = [int(v) for v in np.asarray(n).reshape(-1)]
+    if mode not in WEIGHTED_MODES:
+        raise ValueError(f"label_quality mode {mode!r}: expected one of {WEIGHTED_MODES}")
+    if mode == "item":
+        return np.array([np.float32(np.float64(v) / np.float64(int(N))) for v in n], dtype=np.float32)
+    return np.full(len(n), np.float32(np.float64(sum(n)) / np.float64(len(n) * int(N))), dtype=np.float32)
 
 
 def balanced_update(thr, hist, P, T, M):
@@ -234,6 +277,52 @@ class OnlineLabelMixin(TeacherMixin):
         self.mix_desc = m
         self._mix_stage = None             # for an image the launch cannot read where it lies; allocated on first need
 
+    def _init_weighted(self, mode):
+        """mode: check_weighted's value (None: off -- no buffer, no launch).  Behind _init_online and _init_mix.  The per-item counts of
+        confident pixels, the weights, the `_w` descriptor that replaces the label launch's (the geometry of the one it replaces) and, with
+        the mix in "item" mode, the item map the mix writes and the head reads."""
+        self.online_labels_weighted = mode
+        if mode is None:
+            return
+        dev, one = self.dev, self.online_desc
+        probe = L.OnlineLabelU8Desc()
+        probe.B, probe.H, probe.W, probe.family = one.B, one.H, one.W, one.family
+        rows = L.load().simt_online_label_parts(C.byref(probe))
+        if rows < 1:
+            raise L.SimtHipError(f"simt_online_label_parts: {rows} for B = {self.B}, {self.H} x {self.W}")
+        self.conf_part = torch.zeros(self.B, rows, device=dev, dtype=torch.int32)      # every word is written by every label launch
+        self.label_q = torch.zeros(self.B, device=dev, dtype=torch.float32)
+        if self.online_mix is None:
+            d = L.OnlineLabelWDesc()
+            d.fix, d.label, d.counts, d.conf_part = one.fix, one.label, one.counts, self.conf_part.data_ptr()
+        else:
+            u = self.online_u8_desc
+            d = L.OnlineLabelWU8Desc()
+            d.fix, d.lab8, d.counts, d.part, d.conf_part = u.fix, u.lab8, u.counts, u.part, self.conf_part.data_ptr()
+        d.B, d.h, d.w, d.ld, d.H, d.W, d.C, d.family, d.threshold = one.B, one.h, one.w, one.ld, one.H, one.W, one.C, one.family, one.threshold
+        self.online_w_desc = d
+        q = L.LabelQualityDesc()
+        q.conf_part, q.q, q.B, q.rows, q.H, q.W, q.mode = self.conf_part.data_ptr(), self.label_q.data_ptr(), self.B, rows, self.H, self.W, \
+            L.LABEL_QUALITY_MODES[mode]
+        self.quality_desc = q
+        # "batch": all entries are equal, so a pasted pixel's weight is its own item's and no map is needed
+        self.w_item = torch.zeros(self.B, self.H, self.W, device=dev, dtype=torch.uint8) if (self.online_mix is not None and mode == "item") else None
+
+    def _head_loss(self, st):
+        """simt_head_loss of the micro-batch, or its weighted form (the map: the mix's item map in "item" mode, else NULL)."""
+        if getattr(self, "online_labels_weighted", None) is None:
+            L.call("simt_head_loss", C.byref(self.head_desc), st)
+        else:
+            L.call("simt_head_loss_weighted", C.byref(self.head_desc), self.label_q.data_ptr(),
+                   None if self.w_item is None else self.w_item.data_ptr(), st)
+
+    def _head_grad(self, st):
+        if getattr(self, "online_labels_weighted", None) is None:
+            L.call("simt_head_grad", C.byref(self.head_desc), st)
+        else:
+            L.call("simt_head_grad_weighted", C.byref(self.head_desc), self.label_q.data_ptr(),
+                   None if self.w_item is None else self.w_item.data_ptr(), st)
+
     def _mix_source(self, image):
         """The student's image as simt_class_mix_u8 reads it: the caller's tensor where it is a contiguous fp32 tensor of this device at a
         16-byte base (and not the plan's input itself, which the launch writes), else a copy in a staging buffer of the trainer's own."""
@@ -262,7 +351,10 @@ class OnlineLabelMixin(TeacherMixin):
         self._fix_fwd.run()
         if not self._family:
             ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
-        if self.online_labels_balanced is None:
+        if getattr(self, "online_labels_weighted", None) is not None:      # every arg-max, the counts at tau, the weights
+            L.call("simt_online_label_w_u8", C.byref(self.online_w_desc), st)
+            L.call("simt_label_quality", C.byref(self.quality_desc), st)
+        elif self.online_labels_balanced is None:
             L.call("simt_online_label_u8", C.byref(self.online_u8_desc), st)
         else:
             L.call("simt_online_label_cb_u8", C.byref(self.online_cb_u8_desc), st)
@@ -275,7 +367,10 @@ class OnlineLabelMixin(TeacherMixin):
         C.memmove(m.rank, table.ctypes.data, table.nbytes)
         for i in range(self.B):
             m.apply[i] = 1 if apply[i] else 0
-        L.call("simt_class_mix_u8", C.byref(m), st)
+        if getattr(self, "w_item", None) is not None:      # "item" weights: the head reads a pasted pixel's weight from its partner's entry
+            L.call("simt_class_mix_u8_items", C.byref(m), self.w_item.data_ptr(), st)
+        else:
+            L.call("simt_class_mix_u8", C.byref(m), st)
 
     def _views(self, label, teacher_image, n):
         """step()'s `label` / `teacher_image` as lists of n = iter_size entries; ValueError when they do not fit the trainer."""
@@ -314,7 +409,10 @@ class OnlineLabelMixin(TeacherMixin):
             self._fix_fwd.run()
             if not self._family:
                 ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
-            if self.online_labels_balanced is None:
+            if getattr(self, "online_labels_weighted", None) is not None:      # (the main stream waits for both below)
+                L.call("simt_online_label_w", C.byref(self.online_w_desc), side.cuda_stream)
+                L.call("simt_label_quality", C.byref(self.quality_desc), side.cuda_stream)
+            elif self.online_labels_balanced is None:
                 L.call("simt_online_label", C.byref(self.online_desc), side.cuda_stream)
             else:          # label with the thresholds as they stand and count; then move them and zero the histogram
                 L.call("simt_online_label_cb", C.byref(self.online_cb_desc), side.cuda_stream)
@@ -329,4 +427,6 @@ class OnlineLabelMixin(TeacherMixin):
             out["labelled"], self._counts_reported = labelled_share(self.label_counts.cpu().tolist(), self._counts_reported)
             if getattr(self, "online_labels_balanced", None) is not None:
                 out["label_thresholds"] = self.label_thr.cpu().tolist()
+            if getattr(self, "online_labels_weighted", None) is not None:      # the weights of the last micro-batch
+                out["label_quality"] = self.label_q.cpu().tolist()
         return out

@@ -27,7 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_weighted
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -494,7 +494,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None):
         """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
         online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
@@ -505,10 +505,16 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         the teacher and in front of the student's forward -- with probability P item i receives, image and label, the pixels of half of the
         classes the teacher found in item (i + 1) % B.  The draws are those of simt_amd.data.class_mix (`generator(online_mix_seed, rank)`,
         one `draw_batch` per micro-batch).  `labelled` and `label_thresholds` stay statistics of the teacher's labels BEFORE the mix, as the
-        label launch counts them.  None: the trainer it was -- no buffer, no launch, no draw."""
+        label launch counts them.  None: the trainer it was -- no buffer, no launch, no draw.
+        online_labels_weighted="batch" | "item" (needs online_labels, not with online_labels_balanced, B <= 32): the rule of DACS /
+        DAFormer / MIC -- the student trains on the teacher's arg-max at EVERY pixel and each pixel's cross-entropy is multiplied by q, the share
+        of the micro-batch's ("batch", the published rule) or of its item's ("item") pixels whose confidence is above online_labels; the
+        threshold deletes nothing.  With online_mix in "item" mode a pasted pixel carries its partner's q.  `labelled` keeps its meaning (the
+        share of confident pixels); `losses()` gains `label_quality`.  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
+        weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -554,6 +560,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         fix = (self.fixed.out["x2"], self.fixed.ldp["x2"]) if tau is not None else (None, 0)
         self._init_online(tau, every, *fix, 0, balanced)      # (family 0: the posterior is resampled align_corners=True)
         self._init_mix(mix)
+        self._init_weighted(weighted)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -588,9 +595,9 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
                 ev_in = self._teacher_input(img, teachers[mi])
                 self.plan.forward()
                 self._teacher_labels(ev_in)
-            L.call("simt_head_loss", C.byref(self.head_desc), st)
+            self._head_loss(st)          # simt_head_loss; with online_labels_weighted its weighted form (OnlineLabelMixin)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
-            L.call("simt_head_grad", C.byref(self.head_desc), st)
+            self._head_grad(st)
             if self.reducer is not None and hp.iter_size == 1:
                 self.reducer.start()
                 self.plan.backward(hook=self.reducer.ready_upto)

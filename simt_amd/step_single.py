@@ -28,7 +28,7 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_weighted
 from .step import check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
@@ -290,17 +290,19 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
         online_labels_momentum: as for step.WarmupTrainer; the
         teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample).  online_mix /
         online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
-        statistics of the teacher's labels before the mix."""
+        statistics of the teacher's labels before the mix.  online_labels_weighted: the quality weights of DACS, as for step.WarmupTrainer
+        (DESIGN 7.19)."""
         assert model in ("v3", "vgg")
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
+        weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -370,6 +372,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self._init_ema(ema_decay)
         self._init_online(tau, every, fix_out, ldf, half, balanced)      # (family 1 = the half-pixel model, DeepLabv3)
         self._init_mix(mix)
+        self._init_weighted(weighted)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -406,9 +409,9 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
                 ev_in = self._teacher_input(img, teachers[mi])
                 self._fwd.run()
                 self._teacher_labels(ev_in)
-            L.call("simt_head_loss", C.byref(self.head_desc), st)
+            self._head_loss(st)          # simt_head_loss; with online_labels_weighted its weighted form (OnlineLabelMixin)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
-            L.call("simt_head_grad", C.byref(self.head_desc), st)
+            self._head_grad(st)
             if self.reducer is not None and hp.iter_size == 1:
                 self.reducer.start()
                 self._bwd.run()

@@ -23,6 +23,11 @@ label, the pixels of half of the classes the teacher found in item i+1 (one laun
 --colour-jitter, --gaussian-blur or --mask-patches the teacher labels the weak view and the mix selects from the students' strong views: a pasted
 region carries its partner's jitter, blur and blanked patches.  ` labelled` stays the share of the teacher's labels before the mix.  --train-state
 carries the draws' generator and refuses a resume with the flag added, dropped or changed.
+--online-labels-weighted [batch|item] (needs --online-labels, --batch-size <= 32; not with --online-labels-balanced): the quality
+weights of DACS / DAFormer / MIC -- the model trains on the teacher's arg-max at EVERY pixel and each pixel's cross-entropy is multiplied by q,
+the share of pixels whose confidence is above T (T deletes nothing).  batch (no value): one q per batch, the published rule; item: one per image,
+and with --online-mix a pasted pixel carries its partner's.  ` labelled` stays the share of confident pixels; the loss line gains
+` q = <min>..<max>`.  --train-state refuses a resume with the flag added, dropped or changed.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -135,11 +140,21 @@ def thresholds_text(args, l):
     return " thr = {0:.3f}..{1:.3f}".format(min(l["label_thresholds"]), max(l["label_thresholds"]))
 
 
+def quality_text(args, l):
+    """` q = <min>..<max>` of the loss line, the lowest and the highest weight of the last micro-batch: only with --online-labels-weighted."""
+    if getattr(args, "online_labels_weighted", None) is None:
+        return ""
+    return " q = {0:.3f}..{1:.3f}".format(min(l["label_quality"]), max(l["label_quality"]))
+
+
 def balanced_kwargs(args):
-    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed) when on."""
+    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed) and
+    --online-labels-weighted when on."""
     kw = {"online_labels_balanced": args.online_labels_balanced, "online_labels_momentum": args.online_labels_momentum}
     if args.online_mix is not None:
         kw.update(online_mix=args.online_mix, online_mix_seed=args.random_seed)
+    if getattr(args, "online_labels_weighted", None) is not None:
+        kw.update(online_labels_weighted=args.online_labels_weighted)
     return kw
 
 
@@ -212,7 +227,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -301,7 +316,7 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

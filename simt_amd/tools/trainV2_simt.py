@@ -354,8 +354,8 @@ def _online_mix(text):
 
 
 def add_online_label_args(p):
-    """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17) and --online-mix (7.18)
-    of trainV1_warmup; `check_online_label_args` holds their refusals."""
+    """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17), --online-mix (7.18) and
+    --online-labels-weighted (7.19) of trainV1_warmup; `check_online_label_args` holds their refusals."""
     from simt_amd.online_labels import DEFAULT_PORTION, DEFAULT_THRESHOLD
     p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
                    help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
@@ -378,6 +378,12 @@ def add_online_label_args(p):
                         "teacher found in item i+1.  Needs --batch-size 2 ... 32 and --num-classes <= 32; the draws are seeded by --random-seed.  "
                         "With --colour-jitter, --gaussian-blur or --mask-patches the teacher labels the weak view and the mix selects from the "
                         "strong views.  Default: off")
+    p.add_argument("--online-labels-weighted", choices=["batch", "item"], nargs="?", const="batch", default=None, metavar="MODE",
+                   help="with --online-labels: the quality weights of DACS / DAFormer / MIC (simt_amd/online_labels.py; DESIGN 7.19) -- the model "
+                        "trains on the teacher's arg-max at EVERY pixel and each pixel's cross-entropy is multiplied by q, the share of pixels "
+                        "whose confidence is above T; T deletes nothing.  MODE batch (no value): one q for the batch, the published rule; item: "
+                        "one q per image (with --online-mix a pasted pixel carries its partner's).  Needs --batch-size <= 32; not with "
+                        "--online-labels-balanced.  Default: off")
 
 
 def check_online_label_args(p, args):
@@ -397,6 +403,15 @@ def check_online_label_args(p, args):
     if args.online_labels is not None and args.class_mix is not None:
         p.error("--online-labels cannot be combined with --class-mix: the mix reads the classes to paste from the partner's label, and "
                 "the teacher makes the labels behind the loader (--online-mix mixes behind the teacher)")
+    if getattr(args, "online_labels_weighted", None) is not None:
+        from simt_amd.online_labels import MAX_WEIGHTED_ITEMS
+        if args.online_labels is None:
+            p.error("--online-labels-weighted needs --online-labels: it weighs the teacher's labels")
+        if args.online_labels_balanced is not None:
+            p.error("--online-labels-weighted cannot be combined with --online-labels-balanced in this version: the weight is the share of "
+                    "pixels above the one threshold T")
+        if not 1 <= args.batch_size <= MAX_WEIGHTED_ITEMS:
+            p.error(f"--online-labels-weighted with --batch-size {args.batch_size}: the label launch counts at most {MAX_WEIGHTED_ITEMS} items")
     if getattr(args, "online_mix", None) is not None:
         from simt_amd.data.class_mix import MAX_CLASSES, MAX_ITEMS
         if args.online_labels is None:
@@ -416,7 +431,7 @@ def online_label_line(args):
     weak = online_weak_view(args)
     print(f"online labels: {who} labels every batch, kept where its confidence is > {args.online_labels}; the teacher sees "
           f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}" + balanced_clause(args) +
-          mix_clause(args, weak))
+          mix_clause(args, weak) + weighted_clause(args))
 
 
 def online_balanced(args):
@@ -445,6 +460,16 @@ def mix_clause(args, weak):
     views = (f"; the mix selects from the students' strong views: a pasted region carries its partner's {', '.join(weak)}" if weak else "")
     return (f"; online mix: with probability {p} an item receives, image and label, half of the classes the teacher found in its neighbour, "
             f"behind the teacher and in front of the student's forward" + views)
+
+
+def weighted_clause(args):
+    """What --online-labels-weighted adds to the start-up line ("" without it)."""
+    mode = getattr(args, "online_labels_weighted", None)
+    if mode is None:
+        return ""
+    whose = "the batch's" if mode == "batch" else "its image's"
+    return (f"; quality weights ({mode}): every pixel keeps the teacher's arg-max and its loss is multiplied by the share of {whose} pixels "
+            f"whose confidence is > {args.online_labels}")
 
 
 def online_weak_view(args):
@@ -614,7 +639,7 @@ class EmaSnapshots:
 
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
-                "online_labels": False, "online_labels_balanced": False, "online_mix": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -645,6 +670,8 @@ def run_identity(args, class_dist):
             ident["online_labels_balanced"] = online_balanced(args)      # [P, M]
         if getattr(args, "online_mix", None) is not None:
             ident["online_mix"] = float(args.online_mix)                 # P (the seed is random_seed)
+        if getattr(args, "online_labels_weighted", None) is not None:
+            ident["online_labels_weighted"] = str(args.online_labels_weighted)      # "batch" | "item"
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

@@ -35,6 +35,9 @@ VALUE_FIELDS = ("online_labels", "online_labels_every")
 BALANCE_FIELDS = ("online_labels_balanced", "online_labels_momentum")
 # and the mix behind that teacher (online_mix = P, online_mix_seed = S: DESIGN 7.18), compared through value_mismatches(..., fields=MIX_FIELDS)
 MIX_FIELDS = ("online_mix", "online_mix_seed")
+# and the quality weights of that teacher's labels (online_labels_weighted = "batch" | "item": DESIGN 7.19), compared through
+# value_mismatches(..., fields=WEIGHTED_FIELDS)
+WEIGHTED_FIELDS = ("online_labels_weighted",)
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -145,6 +148,8 @@ class TrainStateMixin:
             if getattr(self, "online_mix", None) is not None:
                 hy["online_mix"] = float(self.online_mix)
                 hy["online_mix_seed"] = int(self.online_mix_seed)
+            if getattr(self, "online_labels_weighted", None) is not None:
+                hy["online_labels_weighted"] = str(self.online_labels_weighted)
         return hy
 
     def _nbt_steps(self, key):
@@ -167,7 +172,8 @@ class TrainStateMixin:
         with their host twin; without the keyword the dict is what it was.  With `online_labels_balanced` `hyper` also carries P and M
         and `accumulators` the per-class thresholds (`label_thresholds`); their histogram is zero between steps and is not stored.  With
         `online_mix` `hyper` also carries P and S and the dict gains `mix_rng`, the `bit_generator.state` of the mix's generator:
-        the resumed run draws what the uninterrupted one draws.
+        the resumed run draws what the uninterrupted one draws.  With `online_labels_weighted` `hyper` also carries the mode and
+        `accumulators` the last micro-batch's weights (`label_quality`); without the keyword the dict is what it was.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -190,6 +196,8 @@ class TrainStateMixin:
                 ts["accumulators"].update(label_counts=self.label_counts.detach().cpu(), counts_reported=[int(c) for c in self._counts_reported])
                 if getattr(self, "online_labels_balanced", None) is not None:
                     ts["accumulators"]["label_thresholds"] = self.label_thr.detach().cpu()
+                if getattr(self, "online_labels_weighted", None) is not None:      # the last micro-batch's weights: `label_quality` resumes exactly
+                    ts["accumulators"]["label_quality"] = self.label_q.detach().cpu()
         if getattr(self, "online_mix", None) is not None:      # the position of the mix's own generator (numpy's plain dict of Python ints)
             ts["mix_rng"] = self._mix_rng.bit_generator.state
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
@@ -207,7 +215,8 @@ class TrainStateMixin:
         counted once).  Data parallel: every rank loads the same dict (see training_state)."""
         bad = (hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state()) +
                value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -268,6 +277,8 @@ class TrainStateMixin:
                 self._counts_reported = [int(c) for c in acc["counts_reported"]]
                 if getattr(self, "online_labels_balanced", None) is not None:
                     self.label_thr.copy_(acc["label_thresholds"])
+                if getattr(self, "online_labels_weighted", None) is not None:
+                    self.label_q.copy_(acc["label_quality"])
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "online_mix", None) is not None:
             self._mix_rng.bit_generator.state = ts["mix_rng"]
