@@ -802,6 +802,47 @@ int simt_head_loss_weighted(const simt_head_desc* d, const float* w, const uint8
 int simt_head_grad_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream);
 int simt_class_mix_u8_items(const simt_class_mix_u8_desc* d, uint8_t* item_out, simt_stream_t stream);
 
+/* ---- A labelled source batch in the same step (the warm-up trainers' online_source; csrc/class_mix.hip, csrc/head_loss.hip) --
+ * DACS: classes of a labelled SOURCE item pasted onto a TARGET item that a teacher has just labelled.  Target item i is paired with source
+ * item i.
+ *
+ * simt_source_mix -- the cross-domain selection, into the buffers the student's forward and the head launches read.  part_s: the words of
+ *   simt_label_presence(labs, B, h * w, n_classes, part_s), run before it on the same stream.  With
+ *     P_i = the classes below n_classes whose bit is set in the OR of part_s[i][0 .. SIMT_CLASS_MIX_PARTS-1],
+ *     k = (|P_i| + 1) / 2 and S_i = the k classes of P_i with the smallest rank[i] (simt_class_mix's rule),
+ *     m(p) = apply[i] and 0 <= labs[i][p] < n_classes and labs[i][p] in S_i   (a 255 or an out-of-range source label is never pasted):
+ *     x_out[i][ch][p] = m ? xs[i][ch][p] : xt[i][ch][p]   (no bit changes);   lab_out[i][p] = m ? labs[i][p] : (int64)lab8[i][p].
+ *   apply[i] == 0: x_out[i] = xt[i], lab_out[i] = lab8[i] widened; source item i (xs, labs, part_s) is not read.
+ * simt_source_mix_items -- the same, and item_out[i][p] = m ? B + i : i, [B][h][w] bytes, 4-byte aligned: the entry of a [2B] weight table
+ *   (simt_head_loss_weighted_n) that the pixel carries -- target items first, source items behind them.  x_out and lab_out are
+ *   simt_source_mix's, bit for bit.  A NULL map is refused.
+ *   Refused (SIMT_ERR_INVALID, nothing launched): a NULL pointer; xs, labs, xt, lab8, x_out or lab_out not 16-byte aligned, part_s not
+ *   4-byte aligned; B outside 1 .. SIMT_CLASS_MIX_MAX; n_classes outside 1 .. SIMT_CLASS_MIX_CLASSES; h, w <= 0 or h * w >= 2^31; a rank >=
+ *   n_classes; x_out overlapping xs or xt; lab_out overlapping labs.  Any h, w otherwise (h * w % 4 != 0 takes the scalar flavour).
+ *   NOT checked, the caller's responsibility (as for simt_class_mix_u8): lab_out must not overlap lab8, and item_out must overlap no input
+ *   and no other output.
+ *
+ * simt_head_loss_weighted_n / simt_head_grad_weighted_n -- simt_head_loss_weighted / simt_head_grad_weighted with a table of nw entries,
+ *   B <= nw <= SIMT_HEAD_WEIGHTS_MAX: pixel p of item b has weight w[b] when w_item is NULL, else w[min(w_item[p], nw - 1)].  The two
+ *   launches without _n are the nw = B case of the same kernels.  Refused: what those refuse, nw outside B .. SIMT_HEAD_WEIGHTS_MAX. */
+#define SIMT_HEAD_WEIGHTS_MAX 64
+typedef struct {
+  const float* xs;           /* [B][3][h][w] fp32: the source images */
+  const long long* labs;     /* [B][h][w] int64: the source ground truth */
+  const uint32_t* part_s;    /* [B][SIMT_CLASS_MIX_PARTS]: simt_label_presence's words for `labs` */
+  const float* xt;           /* [B][3][h][w] fp32: the target images */
+  const uint8_t* lab8;       /* [B][h][w] bytes: the teacher's labels of the target images */
+  float* x_out;              /* [B][3][h][w] fp32 */
+  long long* lab_out;        /* [B][h][w] int64 */
+  int32_t B, h, w, n_classes;
+  uint8_t apply[SIMT_CLASS_MIX_MAX];
+  uint8_t rank[SIMT_CLASS_MIX_MAX][SIMT_CLASS_MIX_CLASSES];
+} simt_source_mix_desc;
+int simt_source_mix(const simt_source_mix_desc* d, simt_stream_t stream);
+int simt_source_mix_items(const simt_source_mix_desc* d, uint8_t* item_out, simt_stream_t stream);
+int simt_head_loss_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream);
+int simt_head_grad_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream);
+
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
  * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another

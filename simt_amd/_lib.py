@@ -157,6 +157,16 @@ class ClassMixU8Desc(C.Structure):
                 ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
 
 
+HEAD_WEIGHTS_MAX = 64    # include/simt_hip.h SIMT_HEAD_WEIGHTS_MAX: the longest weight table of simt_head_*_weighted_n
+
+
+class SourceMixDesc(C.Structure):
+    """simt_source_mix_desc (include/simt_hip.h): a labelled source batch, a target batch and its teacher's byte labels -> the mixed batch."""
+    _fields_ = [("xs", c_p), ("labs", c_p), ("part_s", c_p), ("xt", c_p), ("lab8", c_p), ("x_out", c_p), ("lab_out", c_p),
+                ("B", i32), ("h", i32), ("w", i32), ("n_classes", i32),
+                ("apply", C.c_uint8 * CLASS_MIX_MAX), ("rank", (C.c_uint8 * CLASS_MIX_CLASSES) * CLASS_MIX_MAX)]
+
+
 PHOTOMETRIC_MAX = 32     # include/simt_hip.h SIMT_PHOTOMETRIC_MAX
 PHOTOMETRIC_PARTS = 64   # SIMT_PHOTOMETRIC_PARTS
 
@@ -375,6 +385,10 @@ SIGNATURES = {
     "simt_head_loss_weighted": (_I, [C.POINTER(HeadDesc), c_p, c_p, c_p]),
     "simt_head_grad_weighted": (_I, [C.POINTER(HeadDesc), c_p, c_p, c_p]),
     "simt_class_mix_u8_items": (_I, [C.POINTER(ClassMixU8Desc), c_p, c_p]),
+    "simt_source_mix": (_I, [C.POINTER(SourceMixDesc), c_p]),
+    "simt_source_mix_items": (_I, [C.POINTER(SourceMixDesc), c_p, c_p]),
+    "simt_head_loss_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
+    "simt_head_grad_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
 }
 
 _lib = None

@@ -392,3 +392,140 @@ extern "C" int simt_class_mix_u8(const simt_class_mix_u8_desc* d, simt_stream_t 
 extern "C" int simt_class_mix_u8_items(const simt_class_mix_u8_desc* d, uint8_t* item_out, simt_stream_t stream) {
   return class_mix_u8_launch(d, item_out, true, stream);
 }
+
+// ---- simt_source_mix: the cross-domain mix of DACS, behind a teacher and beside a labelled source batch.  class_mix_u8_kernel's
+// shape -- MIX8_QPT quads per lane 256 * 4 pixels apart, the paste mask once per wave, a quad whose four decisions agree reads one image --
+// with the pasted side a SOURCE item: its image xs[i], its ground truth labs[i] as int64 (what the loader hands out: there is no byte copy
+// of it) and its presence words from simt_label_presence, SIMT_CLASS_MIX_PARTS = 64 of them: one contiguous word per lane, no loop.  The
+// decision needs the quad's four source labels (32 bytes); the target's label dword is read only where a pixel is not pasted.  Byte floor per
+// pixel: 12 + 8 written, 12 + 8 read, + 1 where not pasted = 40-41; the item map adds one.  apply[i] == 0 (workgroup-uniform): mask 0 and no
+// source pointer is dereferenced.
+template <bool VEC, class... ItemOut>
+__global__ __launch_bounds__(256) void source_mix_kernel(const simt_source_mix_desc d, ItemOut... item_out) {
+  constexpr bool ITEMS = sizeof...(ItemOut) > 0;
+  const int i = blockIdx.y;
+  const int apply = d.apply[i];
+  const int C = d.n_classes;
+  const long HW = (long)d.h * d.w;
+  const long nquad = HW >> 2;
+  const uint32_t* __restrict__ xs = (const uint32_t*)d.xs + (long)i * 3 * HW;
+  const uint32_t* __restrict__ xt = (const uint32_t*)d.xt + (long)i * 3 * HW;
+  const long long* __restrict__ ls = d.labs + (long)i * HW;
+  const uint8_t* __restrict__ lt = d.lab8 + (long)i * HW;
+  uint32_t* __restrict__ xo = (uint32_t*)d.x_out + (long)i * 3 * HW;
+  long long* __restrict__ lo = d.lab_out + (long)i * HW;
+  uint8_t* __restrict__ io = ITEMS ? first_item_out(item_out...) + (long)i * HW : nullptr;
+  const uint32_t ti = (uint32_t)i, si = (uint32_t)(d.B + i);      // (ITEMS: the table entries of a target and of a pasted pixel; B + i <= 63)
+  uint32_t mask = 0u;
+  if (apply) mask = paste_mask_of(d.part_s[i * SIMT_CLASS_MIX_PARTS + (threadIdx.x & 63)], (const uint32_t*)d.rank[i], C);
+  for (int r = 0; r < MIX8_QPT; ++r) {
+    const long q = ((long)blockIdx.x * MIX8_QPT + r) * 256 + threadIdx.x;
+    if (q < nquad) {
+      const long p = q << 2;
+      long long a[4] = {0, 0, 0, 0};                     // the source's four labels, then the output's
+      bool m0 = false, m1 = false, m2 = false, m3 = false;
+      if (apply) {
+        if (VEC) {
+          const i64x2 u = *(const i64x2*)(ls + p), v = *(const i64x2*)(ls + p + 2);
+          a[0] = u.x; a[1] = u.y; a[2] = v.x; a[3] = v.y;
+        } else {
+          a[0] = ls[p]; a[1] = ls[p + 1]; a[2] = ls[p + 2]; a[3] = ls[p + 3];
+        }
+        m0 = pasted(a[0], C, mask); m1 = pasted(a[1], C, mask); m2 = pasted(a[2], C, mask); m3 = pasted(a[3], C, mask);
+      }
+      const bool all = m0 && m1 && m2 && m3, none = !(m0 || m1 || m2 || m3);
+      if (!all) {
+        const uint32_t t = load_labels4<VEC>(lt, p);
+        a[0] = m0 ? a[0] : (long long)(t & 255u); a[1] = m1 ? a[1] : (long long)((t >> 8) & 255u);
+        a[2] = m2 ? a[2] : (long long)((t >> 16) & 255u); a[3] = m3 ? a[3] : (long long)(t >> 24);
+      }
+      if (VEC) {
+        const i64x2 u = {a[0], a[1]}, v = {a[2], a[3]};
+        *(i64x2*)(lo + p) = u;
+        *(i64x2*)(lo + p + 2) = v;
+      } else {
+        lo[p] = a[0]; lo[p + 1] = a[1]; lo[p + 2] = a[2]; lo[p + 3] = a[3];
+      }
+      if (ITEMS) {
+        const uint32_t b0 = m0 ? si : ti, b1 = m1 ? si : ti, b2 = m2 ? si : ti, b3 = m3 ? si : ti;
+        if (VEC) {
+          *(uint32_t*)(io + p) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        } else {
+          io[p] = (uint8_t)b0; io[p + 1] = (uint8_t)b1; io[p + 2] = (uint8_t)b2; io[p + 3] = (uint8_t)b3;
+        }
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const long o = ch * HW + p;
+        if (VEC) {
+          uint4 v;
+          if (all) {
+            v = *(const uint4*)(xs + o);
+          } else if (none) {
+            v = *(const uint4*)(xt + o);
+          } else {
+            const uint4 s = *(const uint4*)(xs + o), t = *(const uint4*)(xt + o);
+            v = make_uint4(m0 ? s.x : t.x, m1 ? s.y : t.y, m2 ? s.z : t.z, m3 ? s.w : t.w);
+          }
+          *(uint4*)(xo + o) = v;
+        } else if (none) {                               // (also apply[i] == 0: the source is not read)
+          const uint32_t v0 = xt[o], v1 = xt[o + 1], v2 = xt[o + 2], v3 = xt[o + 3];
+          xo[o] = v0; xo[o + 1] = v1; xo[o + 2] = v2; xo[o + 3] = v3;
+        } else {
+          const uint32_t v0 = m0 ? xs[o] : xt[o], v1 = m1 ? xs[o + 1] : xt[o + 1], v2 = m2 ? xs[o + 2] : xt[o + 2],
+                         v3 = m3 ? xs[o + 3] : xt[o + 3];
+          xo[o] = v0; xo[o + 1] = v1; xo[o + 2] = v2; xo[o + 3] = v3;
+        }
+      }
+    } else if (q == nquad) {                             // scalar tail: h*w % 4 pixels
+      for (long p = nquad << 2; p < HW; ++p) {
+        const long long l = apply ? ls[p] : 255;
+        const bool m = pasted(l, C, mask);
+        lo[p] = m ? l : (long long)lt[p];
+        for (int ch = 0; ch < 3; ++ch) xo[ch * HW + p] = m ? xs[ch * HW + p] : xt[ch * HW + p];
+        if (ITEMS) io[p] = (uint8_t)(m ? si : ti);
+      }
+    }
+  }
+}
+
+static bool ranges_overlap(const void* a, const void* b, uintptr_t bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return !(a0 + bytes <= b0 || b0 + bytes <= a0);
+}
+
+static int source_mix_launch(const simt_source_mix_desc* d, uint8_t* item_out, bool items, simt_stream_t stream) {
+  SIMT_CHECK(d && d->xs && d->labs && d->part_s && d->xt && d->lab8 && d->x_out && d->lab_out);
+  SIMT_CHECK(!items || (item_out && ((uintptr_t)item_out & 3) == 0));
+  SIMT_CHECK(((uintptr_t)d->xs & 15) == 0 && ((uintptr_t)d->labs & 15) == 0 && ((uintptr_t)d->xt & 15) == 0 && ((uintptr_t)d->lab8 & 15) == 0);
+  SIMT_CHECK(((uintptr_t)d->x_out & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0 && ((uintptr_t)d->part_s & 3) == 0);
+  SIMT_CHECK(d->B >= 1 && d->B <= SIMT_CLASS_MIX_MAX && d->h > 0 && d->w > 0);
+  SIMT_CHECK(d->n_classes >= 1 && d->n_classes <= SIMT_CLASS_MIX_CLASSES);
+  const long HW = (long)d->h * d->w;
+  SIMT_CHECK(HW < (1L << 31));
+  const uintptr_t xbytes = (uintptr_t)d->B * 3 * HW * sizeof(float), lbytes = (uintptr_t)d->B * HW * sizeof(long long);
+  SIMT_CHECK(!ranges_overlap(d->x_out, d->xs, xbytes) && !ranges_overlap(d->x_out, d->xt, xbytes));      // a lane's stores may land in front of
+  SIMT_CHECK(!ranges_overlap(d->lab_out, d->labs, lbytes));                                              // another lane's loads
+  for (int b = 0; b < d->B; ++b)
+    for (int c = 0; c < d->n_classes; ++c) SIMT_CHECK(d->rank[b][c] < d->n_classes);
+  const long lanes = (HW >> 2) + ((HW & 3) ? 1 : 0);
+  const dim3 grid((unsigned)((lanes + 256 * MIX8_QPT - 1) / (256 * MIX8_QPT)), (unsigned)d->B);
+  const bool vec = (HW & 3) == 0;
+  if (vec && !items)
+    hipLaunchKernelGGL((source_mix_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else if (!items)
+    hipLaunchKernelGGL((source_mix_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else if (vec)
+    hipLaunchKernelGGL((source_mix_kernel<true, uint8_t*>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
+  else
+    hipLaunchKernelGGL((source_mix_kernel<false, uint8_t*>), grid, dim3(256), 0, (hipStream_t)stream, *d, item_out);
+  SIMT_LAUNCH_CHECK();
+  return SIMT_OK;
+}
+
+extern "C" int simt_source_mix(const simt_source_mix_desc* d, simt_stream_t stream) { return source_mix_launch(d, nullptr, false, stream); }
+
+// simt_source_mix plus the item map: a pasted pixel reads entry B + i of the head's [2B] weight table (1.0), a target pixel entry i (q).
+extern "C" int simt_source_mix_items(const simt_source_mix_desc* d, uint8_t* item_out, simt_stream_t stream) {
+  return source_mix_launch(d, item_out, true, stream);
+}

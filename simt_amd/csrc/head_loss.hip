@@ -237,6 +237,7 @@ struct HeadArgs {
   const unsigned char* fix_item;  // optional [B][H][W] (simt_head_*_views): the item of fixp a pixel reads its frozen operand from
   const float* w;                 // simt_head_*_weighted: [B] per-item weights of the warm-up cross-entropy (device memory), else NULL
   const unsigned char* w_item;    // optional [B][H][W] (simt_head_*_weighted): the item whose weight a pixel carries
+  int nw;                         // simt_head_*_weighted: the entries of w the map may name (B; simt_head_*_weighted_n: B .. SIMT_HEAD_WEIGHTS_MAX)
 };
 
 // The flavour pack of the two pass kernels: <> the SimT / DeepLab-v2 warm-up code (names as before any flavour existed), <true> ONE,
@@ -251,11 +252,12 @@ __device__ __forceinline__ const float* fixp_of_item(const HeadArgs& a, const He
   return a.fixp + (long)(fb - b) * g.h * g.w * g.ldf;
 }
 
-// WEIGHTED: pixel pix of item b carries the weight of item wb = min(w_item[pix], B - 1), or of its own item without a map --
-// fixp_of_item's lookup on the [B] table.  The map is tested at run time: the two forms are ONE kernel, so a constant map per item gives
+// WEIGHTED: pixel pix of item b carries the weight of entry wb = min(w_item[pix], nw - 1), or of its own item without a
+// map -- fixp_of_item's lookup on the [nw] table (nw = B; simt_head_*_weighted_n: up to SIMT_HEAD_WEIGHTS_MAX, the entries behind B - 1 for
+// pixels that came from outside the batch).  The map is tested at run time: the two forms are ONE kernel, so a constant map per item gives
 // what the map-less launch gives on the gathered table, bit for bit.
 __device__ __forceinline__ float weight_of_item(const HeadArgs& a, const HeadGeom& g, int b, long pix) {
-  const int wb = a.w_item ? min((int)a.w_item[pix], g.B - 1) : b;
+  const int wb = a.w_item ? min((int)a.w_item[pix], a.nw - 1) : b;
   return a.w[wb];
 }
 
@@ -1084,7 +1086,7 @@ static int fill_args(const simt_head_desc* d, const uint8_t* fix_item, HeadArgs&
   a.conf_out = d->conf_out;
   a.label_ws = d->label_ws;
   a.fix_item = fix_item;
-  a.w = nullptr; a.w_item = nullptr;
+  a.w = nullptr; a.w_item = nullptr; a.nw = 0;
   SIMT_CHECK(d->mode == 0 || d->mode == 1);
   SIMT_CHECK(!fix_item || d->mode == 0);      // the warm-up stage has no frozen operand to move
   return SIMT_OK;
@@ -1104,19 +1106,20 @@ extern "C" int simt_head_keys_count(void) { return 2 * QMAX + 2; }
 
 // losses (pass 1 + finalize).  keys must be zeroed by this call: done here with a memset node on the stream.
 // the weighted launches' side of the arguments: mode 1 only, as a map is refused for mode 1 above
-static int fill_weights(const simt_head_desc* d, const float* w, const uint8_t* w_item, HeadArgs& a) {
+static int fill_weights(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, HeadArgs& a) {
   SIMT_CHECK(w && ((uintptr_t)w & 3) == 0);
   SIMT_CHECK(d->mode == 1);
-  a.w = w; a.w_item = w_item;
+  SIMT_CHECK(nw >= d->B && nw <= SIMT_HEAD_WEIGHTS_MAX);
+  a.w = w; a.w_item = w_item; a.nw = nw;
   return SIMT_OK;
 }
 
-static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, const uint8_t* w_item,
+static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
                             simt_stream_t stream) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (weighted) { if (int rw = fill_weights(d, w, w_item, a)) return rw; }
+  if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   hipStream_t st = (hipStream_t)stream;
   const int nblk = simt_head_nblk(d->B, d->H, d->W);
   (void)hipMemsetAsync(d->keys, 0, (2 * QMAX + 2) * sizeof(unsigned long long), st);
@@ -1165,12 +1168,12 @@ static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
 }
 
 // gradients w.r.t. the low-res logits (pass 2 + y reduction); needs hout from simt_head_loss of the same inputs.
-static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, const uint8_t* w_item,
+static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
                             simt_stream_t stream) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (weighted) { if (int rw = fill_weights(d, w, w_item, a)) return rw; }
+  if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   SIMT_CHECK(d->g1 && d->QP >= d->Q);
   hipStream_t st = (hipStream_t)stream;
   size_t lds2 = pass2_lds(d->Q, d->C, d->w);
@@ -1219,18 +1222,26 @@ static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
 }
 
 extern "C" int simt_head_loss_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
-  return head_loss_launch(d, fix_item, false, nullptr, nullptr, stream);
+  return head_loss_launch(d, fix_item, false, nullptr, 0, nullptr, stream);
 }
 extern "C" int simt_head_grad_views(const simt_head_desc* d, const uint8_t* fix_item, simt_stream_t stream) {
-  return head_grad_launch(d, fix_item, false, nullptr, nullptr, stream);
+  return head_grad_launch(d, fix_item, false, nullptr, 0, nullptr, stream);
 }
 
 // the weighted warm-up cross-entropy: mode 1 with a [B] weight table in device memory and an optional item map
 extern "C" int simt_head_loss_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream) {
-  return head_loss_launch(d, nullptr, true, w, w_item, stream);
+  return d ? head_loss_launch(d, nullptr, true, w, d->B, w_item, stream) : SIMT_ERR_INVALID;
 }
 extern "C" int simt_head_grad_weighted(const simt_head_desc* d, const float* w, const uint8_t* w_item, simt_stream_t stream) {
-  return head_grad_launch(d, nullptr, true, w, w_item, stream);
+  return d ? head_grad_launch(d, nullptr, true, w, d->B, w_item, stream) : SIMT_ERR_INVALID;
+}
+
+// the same with a table longer than the batch: entries B .. nw - 1 for pixels that came from outside it (simt_source_mix_items)
+extern "C" int simt_head_loss_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream) {
+  return head_loss_launch(d, nullptr, true, w, nw, w_item, stream);
+}
+extern "C" int simt_head_grad_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream) {
+  return head_grad_launch(d, nullptr, true, w, nw, w_item, stream);
 }
 
 // the one-view forms: the NULL case of the same code

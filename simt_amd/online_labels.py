@@ -43,6 +43,15 @@ times its item's q, still divided by the number of labelled pixels.  With `onlin
 and the head reads a pasted pixel's weight from its partner's entry through that map; in "batch" mode all entries are equal and there is
 no map.  `label_quality` below restates the second launch in numpy.  `losses()` gains `label_quality`, the weights of the last micro-batch.
 Rank-local, as `labelled` is.  Not with `online_labels_balanced` in this version.
+
+A labelled source batch in the same step (keyword `online_source=True`, flag --online-source): the published DACS step.  Every
+micro-batch is TWO passes into one gradient, through the accumulation path `iter_size > 1` uses (the head's gscale stays 1 / iter_size: the
+two losses are summed).  Pass a: `source_image` / `source_label` into the plan's input and `trainer.label`, forward, the plain
+`simt_head_loss` / `simt_head_grad`, backward; two floats of `hout` are kept by a device copy (`source_seg1` / `source_seg2` of `losses()`).
+Pass b: the target micro-batch as above.  With `online_mix` the mix of pass b is the cross-domain one: `simt_label_presence` of the source
+labels and `simt_source_mix` paste half of source item i's classes -- image and GROUND TRUTH -- onto target item i; with
+`online_labels_weighted` (either mode) it is `simt_source_mix_items`, and the head launches become `simt_head_loss_weighted_n` /
+`simt_head_grad_weighted_n` over a [2B] table whose entries B .. 2B-1 are 1.0f: a pasted pixel has weight 1, a target pixel its q.
 """
 import ctypes as C
 
@@ -163,6 +172,18 @@ def check_weighted(online_labels_weighted, tau, balanced, batch_size):
     if not 1 <= batch_size <= MAX_WEIGHTED_ITEMS:
         raise ValueError(f"online_labels_weighted with a batch of {batch_size}: the label launch counts at most {MAX_WEIGHTED_ITEMS} items")
     return mode
+
+
+def check_source(online_source, tau):
+    """The keyword of the source batch -> bool; `tau` is check_settings' first value.  ValueError that starts with the keyword."""
+    if online_source is None:
+        return False
+    if not isinstance(online_source, (bool, np.bool_)):
+        raise ValueError(f"online_source {online_source!r}: expected True (a labelled source batch in every optimiser step) or False")
+    if online_source and tau is None:
+        raise ValueError("online_source needs online_labels: the source batch is trained beside a target batch that a teacher labels, and "
+                         "this trainer has no teacher")
+    return bool(online_source)
 
 
 def label_quality(n, N, mode):
@@ -308,10 +329,46 @@ class OnlineLabelMixin(TeacherMixin):
         # "batch": all entries are equal, so a pasted pixel's weight is its own item's and no map is needed
         self.w_item = torch.zeros(self.B, self.H, self.W, device=dev, dtype=torch.uint8) if (self.online_mix is not None and mode == "item") else None
 
+    def _init_source(self, on):
+        """on: check_source's value (False: off -- no buffer, no launch).  Behind _init_online, _init_mix and _init_weighted.  The two
+        kept floats of the source pass; with the mix the presence words of the source labels and the descriptor of simt_source_mix, whose
+        outputs are the mix's -- the source pair itself is read where the caller left it, or from a staging pair allocated on first need
+        (`_source_input`); with the quality weights also the [2B] table -- q in 0 .. B-1 (`label_q` becomes a
+        view of it, so simt_label_quality writes there), 1.0f behind, written once -- and the item map in either mode."""
+        self.online_source = bool(on)
+        if not on:
+            return
+        dev, B = self.dev, self.B
+        self.source_hout = torch.zeros(2, device=dev)
+        if self.online_mix is None:
+            return
+        self.src_x = self.src_lab = None      # the source pair as the mix reads it: set per micro-batch by _source_input
+        self._src_stage = [None, None]        # for a pair the launch cannot read where it lies; allocated on first need
+        self.src_part = torch.zeros(B, L.CLASS_MIX_PARTS, device=dev, dtype=torch.int32)      # every word is written by every presence launch
+        m = L.SourceMixDesc()
+        m.part_s, m.lab8 = self.src_part.data_ptr(), self.lab8.data_ptr()
+        m.x_out, m.lab_out = self.plan.x_in.data_ptr(), self.label.data_ptr()
+        m.B, m.h, m.w, m.n_classes = B, self.H, self.W, self.C
+        self.source_mix_desc = m
+        if self.online_labels_weighted is not None:
+            table = torch.ones(2 * B, device=dev, dtype=torch.float32)
+            table[:B] = self.label_q
+            self.label_w, self.label_q = table, table[:B]
+            self.quality_desc.q = self.label_q.data_ptr()
+            if self.w_item is None:        # "batch": the entries 0 .. B-1 are equal, but a pasted pixel reads entry B + i
+                self.w_item = torch.zeros(B, self.H, self.W, device=dev, dtype=torch.uint8)
+
+    def _source_table(self):
+        """True when the weighted head launches read the [2B] table through the source mix's item map."""
+        return getattr(self, "online_source", False) and self.online_mix is not None
+
     def _head_loss(self, st):
-        """simt_head_loss of the micro-batch, or its weighted form (the map: the mix's item map in "item" mode, else NULL)."""
+        """simt_head_loss of the micro-batch, or its weighted form (the map: the mix's item map in "item" mode, else NULL; with
+        online_source and the mix the [2B] table and the source mix's map)."""
         if getattr(self, "online_labels_weighted", None) is None:
             L.call("simt_head_loss", C.byref(self.head_desc), st)
+        elif self._source_table():
+            L.call("simt_head_loss_weighted_n", C.byref(self.head_desc), self.label_w.data_ptr(), 2 * self.B, self.w_item.data_ptr(), st)
         else:
             L.call("simt_head_loss_weighted", C.byref(self.head_desc), self.label_q.data_ptr(),
                    None if self.w_item is None else self.w_item.data_ptr(), st)
@@ -319,9 +376,58 @@ class OnlineLabelMixin(TeacherMixin):
     def _head_grad(self, st):
         if getattr(self, "online_labels_weighted", None) is None:
             L.call("simt_head_grad", C.byref(self.head_desc), st)
+        elif self._source_table():
+            L.call("simt_head_grad_weighted_n", C.byref(self.head_desc), self.label_w.data_ptr(), 2 * self.B, self.w_item.data_ptr(), st)
         else:
             L.call("simt_head_grad_weighted", C.byref(self.head_desc), self.label_q.data_ptr(),
                    None if self.w_item is None else self.w_item.data_ptr(), st)
+
+    def _sources(self, source_image, source_label, n):
+        """step()'s `source_image` / `source_label` as lists of n = iter_size entries; ValueError when they do not fit the trainer."""
+        if not getattr(self, "online_source", False):
+            if source_image is not None or source_label is not None:
+                raise ValueError("step(): source_image / source_label need a trainer built with online_source=True (this one has no source pass)")
+            return [None] * n, [None] * n
+        if source_image is None or source_label is None:
+            raise ValueError("step(): this trainer was built with online_source and needs source_image and source_label")
+        imgs = list(source_image) if isinstance(source_image, (list, tuple)) else [source_image]
+        labs = list(source_label) if isinstance(source_label, (list, tuple)) else [source_label]
+        if len(imgs) != n or len(labs) != n:
+            raise ValueError(f"step() needs {n} source_image(s) and source_label(s) (hp.iter_size), got {len(imgs)} and {len(labs)}")
+        for x, l in zip(imgs, labs):
+            if tuple(x.shape) != (self.B, 3, self.H, self.W):
+                raise ValueError(f"source_image of shape {tuple(x.shape)}, expected {(self.B, 3, self.H, self.W)}")
+            if tuple(l.shape) != (self.B, self.H, self.W):
+                raise ValueError(f"source_label of shape {tuple(l.shape)}, expected {(self.B, self.H, self.W)}")
+        return imgs, labs
+
+    def _readable(self, t, dtype, out):
+        """True when a launch can read the caller's tensor where it lies: contiguous, of `dtype`, on this device, at a 16-byte base, and not
+        the buffer `out` that the launch writes."""
+        return (t.device == out.device and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % 16 == 0 and t.data_ptr() != out.data_ptr())
+
+    def _source_input(self, source_image, source_label):
+        """Pass a's input, main stream: the source pair into `plan.x_in` and `self.label`.  Behind everything the previous pass enqueued on
+        the main stream (its head kernels read `label`, its stem weight gradient `plan.x_in`): the write-after-read ordering of the input
+        copy.  With the mix, pass b's simt_label_presence and simt_source_mix read the pair again (`src_x`, `src_lab`): the caller's
+        tensors themselves where they are contiguous fp32 / int64 tensors of this device at a 16-byte base (`_mix_source`'s test on the
+        target side; step() holds them until it returns), else copies in a staging pair of the trainer's own."""
+        if self.online_mix is not None:
+            pair = []
+            for k, (t, dtype, out) in enumerate(((source_image, torch.float32, self.plan.x_in), (source_label, torch.int64, self.label))):
+                if not self._readable(t, dtype, out):
+                    if self._src_stage[k] is None:
+                        self._src_stage[k] = torch.empty_like(out)
+                    self._src_stage[k].copy_(t, non_blocking=True)
+                    t = self._src_stage[k]
+                pair.append(t)
+            source_image, source_label = self.src_x, self.src_lab = pair
+        self.plan.x_in.copy_(source_image, non_blocking=True)
+        self.label.copy_(source_label, non_blocking=True)
+
+    def _source_kept(self):
+        """Behind pass a's simt_head_loss, main stream: its two losses, kept for losses() (pass b's launch overwrites `hout`)."""
+        self.source_hout.copy_(self.hout[:2], non_blocking=True)
 
     def _mix_source(self, image):
         """The student's image as simt_class_mix_u8 reads it: the caller's tensor where it is a contiguous fp32 tensor of this device at a
@@ -344,7 +450,11 @@ class OnlineLabelMixin(TeacherMixin):
           the previous micro-batch's head kernels (they read `label`), stem weight gradient (it reads `plan.x_in`; the backward joins its
           side stream before it returns) and optimiser come first -- the write-after-read ordering the input copy had;
           an EMA-teacher refresh (`_teacher_follows`, main stream, behind the update) lies behind this step's teacher forward and in front
-          of the next one, which runs on the same stream."""
+          of the next one, which runs on the same stream.
+        With online_source this is pass b and the mix is simt_label_presence(src_lab) + simt_source_mix: pass a -- its input
+        copies (a staging copy of the source pair among them, when one is needed), its forward, head kernels and backward -- lies in
+        front of all of this on the same stream, so the source pair is complete and nothing of pass a still reads `plan.x_in` or `label`
+        when the mix writes them."""
         st = ops.stream_ptr()
         x = self._mix_source(image)
         self.fixed.x_in.copy_(image if teacher_image is None else teacher_image, non_blocking=True)
@@ -360,13 +470,22 @@ class OnlineLabelMixin(TeacherMixin):
             L.call("simt_online_label_cb_u8", C.byref(self.online_cb_u8_desc), st)
             L.call("simt_class_thresholds", C.byref(self.thresholds_desc), st)
         apply, rank = class_mix.draw_batch(self._mix_rng, self.B, self.C, self.online_mix)      # one call per micro-batch, in order
-        m = self.mix_desc
-        m.x = x.data_ptr()
+        source = getattr(self, "online_source", False)
+        m = self.source_mix_desc if source else self.mix_desc
         table = np.zeros((L.CLASS_MIX_MAX, L.CLASS_MIX_CLASSES), dtype=np.uint8)
         table[:self.B, :self.C] = rank
         C.memmove(m.rank, table.ctypes.data, table.nbytes)
         for i in range(self.B):
             m.apply[i] = 1 if apply[i] else 0
+        if source:      # the pasted side is source item i (`src_x`, `src_lab`: what pass a trained on), image and ground truth
+            m.xs, m.labs, m.xt = self.src_x.data_ptr(), self.src_lab.data_ptr(), x.data_ptr()
+            L.call("simt_label_presence", self.src_lab.data_ptr(), self.B, self.H * self.W, self.C, self.src_part.data_ptr(), st)
+            if getattr(self, "online_labels_weighted", None) is not None:      # either mode: a pasted pixel reads entry B + i, 1.0f
+                L.call("simt_source_mix_items", C.byref(m), self.w_item.data_ptr(), st)
+            else:
+                L.call("simt_source_mix", C.byref(m), st)
+            return
+        m.x = x.data_ptr()
         if getattr(self, "w_item", None) is not None:      # "item" weights: the head reads a pasted pixel's weight from its partner's entry
             L.call("simt_class_mix_u8_items", C.byref(m), self.w_item.data_ptr(), st)
         else:
@@ -429,4 +548,6 @@ class OnlineLabelMixin(TeacherMixin):
                 out["label_thresholds"] = self.label_thr.cpu().tolist()
             if getattr(self, "online_labels_weighted", None) is not None:      # the weights of the last micro-batch
                 out["label_quality"] = self.label_q.cpu().tolist()
+            if getattr(self, "online_source", False):      # the source pass of the last micro-batch
+                out["source_seg1"], out["source_seg2"] = self.source_hout.cpu().tolist()
         return out

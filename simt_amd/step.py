@@ -27,7 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_weighted
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -486,6 +486,24 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         return dict(zip(keys, v))
 
 
+def accumulate_pass(tr, k, n, st):
+    """Behind the backward of pass k of n > 1 passes into one gradient of a warm-up trainer (hp.iter_size micro-batches; with online_source
+    two passes each): the first pass starts the sum in `tr._grad_acc`, the ones between add to it, the last adds the sum to its
+    own gradient, where the optimiser reads it -- and under data parallelism the one exchange starts there."""
+    flat = tr.plan.flat_grad
+    if tr._grad_acc is None:
+        tr._grad_acc = torch.zeros_like(flat)
+    if k == 0:
+        tr._grad_acc.copy_(flat)
+    elif k < n - 1:
+        L.call("simt_vec_acc", tr._grad_acc.data_ptr(), flat.data_ptr(), flat.numel(), 1, st)
+    else:
+        L.call("simt_vec_acc", flat.data_ptr(), tr._grad_acc.data_ptr(), flat.numel(), 1, st)
+        if tr.reducer is not None:
+            tr.reducer.start()
+            tr.reducer.finish()
+
+
 class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
@@ -494,7 +512,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0, online_labels_weighted=None):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None):
         """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
         online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
@@ -510,11 +528,16 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         DAFormer / MIC -- the student trains on the teacher's arg-max at EVERY pixel and each pixel's cross-entropy is multiplied by q, the share
         of the micro-batch's ("batch", the published rule) or of its item's ("item") pixels whose confidence is above online_labels; the
         threshold deletes nothing.  With online_mix in "item" mode a pasted pixel carries its partner's q.  `labelled` keeps its meaning (the
-        share of confident pixels); `losses()` gains `label_quality`.  None: the trainer it was."""
+        share of confident pixels); `losses()` gains `label_quality`.  None: the trainer it was.
+        online_source=True (needs online_labels): the published DACS step -- every micro-batch is two passes into one gradient,
+        supervised cross-entropy on a labelled source pair (`step(source_image=, source_label=)`), then the target pass above; with
+        online_mix the mix pastes half of SOURCE item i's classes, image and ground truth, onto target item i (simt_source_mix), and with
+        online_labels_weighted a pasted pixel has weight 1.  `losses()` gains `source_seg1` / `source_seg2`.  None / False: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
+        source = check_source(online_source, tau)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -561,6 +584,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self._init_online(tau, every, *fix, 0, balanced)      # (family 0: the posterior is resampled align_corners=True)
         self._init_mix(mix)
         self._init_weighted(weighted)
+        self._init_source(source)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -569,20 +593,34 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self.reducer = BucketReducer(self.plan.flat_grad, buckets, group=self.pg, extra=[self.bad_labels])
         self._grad_acc = None
 
-    def step(self, image, label=None, it=None, teacher_image=None):
+    def step(self, image, label=None, it=None, teacher_image=None, source_image=None, source_label=None):
         """One micro-batch, or sequences of hp.iter_size micro-batches (trainV1_warmup.py:212-231: loss / iter_size,
         gradients accumulated, one optimiser step).  Built with online_labels: `label` must be None (the labels come from the teacher),
-        teacher_image is the teacher's view (None: it sees `image`); sequences like image when hp.iter_size > 1."""
+        teacher_image is the teacher's view (None: it sees `image`); sequences like image when hp.iter_size > 1.  Built with online_source:
+        source_image [B,3,H,W] / source_label [B,H,W] int64 are the labelled source pair of every micro-batch (sequences likewise); refused
+        without the keyword."""
         hp = self.hp
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
+        src_images, src_labels = self._sources(source_image, source_label, hp.iter_size)
         if len(images) != hp.iter_size or len(labels) != hp.iter_size:
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
-        flat = self.plan.flat_grad
+        # passes into the one gradient: a micro-batch is one, with online_source two (DESIGN 7.20: the source pass, then the target pass)
+        per = 2 if self.online_source else 1
+        n_pass = hp.iter_size * per
         for mi, (img, lab) in enumerate(zip(images, labels)):
+            if self.online_source:      # pass a: supervised cross-entropy on the source pair, the plain head launches, into the same gradient
+                self._source_input(src_images[mi], src_labels[mi])
+                self.plan.forward()
+                L.call("simt_head_loss", C.byref(self.head_desc), st)
+                L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # the source labels count too
+                self._source_kept()
+                L.call("simt_head_grad", C.byref(self.head_desc), st)
+                self.plan.backward()
+                accumulate_pass(self, mi * per, n_pass, st)
             if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
                 self._mixed_batch(img, teachers[mi])
                 self.plan.forward()
@@ -598,24 +636,14 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self._head_loss(st)          # simt_head_loss; with online_labels_weighted its weighted form (OnlineLabelMixin)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
             self._head_grad(st)
-            if self.reducer is not None and hp.iter_size == 1:
+            if self.reducer is not None and n_pass == 1:
                 self.reducer.start()
                 self.plan.backward(hook=self.reducer.ready_upto)
                 self.reducer.finish()
                 continue
             self.plan.backward()
-            if hp.iter_size > 1:
-                if self._grad_acc is None:
-                    self._grad_acc = torch.zeros_like(flat)
-                if mi == 0:
-                    self._grad_acc.copy_(flat)
-                elif mi < hp.iter_size - 1:
-                    L.call("simt_vec_acc", self._grad_acc.data_ptr(), flat.data_ptr(), flat.numel(), 1, st)
-                else:
-                    L.call("simt_vec_acc", flat.data_ptr(), self._grad_acc.data_ptr(), flat.numel(), 1, st)
-                    if self.reducer is not None:
-                        self.reducer.start()
-                        self.reducer.finish()
+            if n_pass > 1:      # the accumulation of hp.iter_size > 1, over passes (accumulate_pass); the exchange behind the last
+                accumulate_pass(self, mi * per + per - 1, n_pass, st)
         d = self.sgd_desc
         d.lr[0], d.lr[1] = lr, lr * 10.0
         d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay

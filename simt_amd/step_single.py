@@ -28,8 +28,8 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_weighted
-from .step import check_views, lr_poly
+from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
+from .step import accumulate_pass, check_views, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -290,19 +290,20 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0, online_labels_weighted=None):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
         online_labels_momentum: as for step.WarmupTrainer; the
         teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample).  online_mix /
         online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
         statistics of the teacher's labels before the mix.  online_labels_weighted: the quality weights of DACS, as for step.WarmupTrainer
-        (DESIGN 7.19)."""
+        (DESIGN 7.19).  online_source: a labelled source pair in every micro-batch, as for step.WarmupTrainer."""
         assert model in ("v3", "vgg")
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
+        source = check_source(online_source, tau)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -373,6 +374,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self._init_online(tau, every, fix_out, ldf, half, balanced)      # (family 1 = the half-pixel model, DeepLabv3)
         self._init_mix(mix)
         self._init_weighted(weighted)
+        self._init_source(source)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -383,20 +385,33 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     optim_groups = SimTSingleTrainer.optim_groups
 
-    def step(self, image, label=None, it=None, teacher_image=None):
+    def step(self, image, label=None, it=None, teacher_image=None, source_image=None, source_label=None):
         """One micro-batch, or sequences of hp.iter_size micro-batches (trainV1_warmup.py:212-231: loss / iter_size, gradients accumulated,
         one optimiser step; under data parallelism one exchange of the accumulated gradient).  Built with online_labels: `label` must be
-        None, teacher_image is the teacher's view (None: it sees `image`), as for step.WarmupTrainer."""
+        None, teacher_image is the teacher's view (None: it sees `image`), as for step.WarmupTrainer.  Built with online_source:
+        source_image / source_label are the labelled source pair of every micro-batch, as for step.WarmupTrainer."""
         hp = self.hp
         it = self.it_done if it is None else it
         lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
+        src_images, src_labels = self._sources(source_image, source_label, hp.iter_size)
         if len(images) != hp.iter_size or len(labels) != hp.iter_size:
             raise ValueError(f"step() needs {hp.iter_size} micro-batch(es) (hp.iter_size), got {len(images)}")
-        flat = self.plan.flat_grad
+        # passes into the one gradient: a micro-batch is one, with online_source two (DESIGN 7.20: the source pass, then the target pass)
+        per = 2 if self.online_source else 1
+        n_pass = hp.iter_size * per
         for mi, (img, lab) in enumerate(zip(images, labels)):
+            if self.online_source:      # pass a: supervised cross-entropy on the source pair, the plain head launches, into the same gradient
+                self._source_input(src_images[mi], src_labels[mi])
+                self._fwd.run()
+                L.call("simt_head_loss", C.byref(self.head_desc), st)
+                L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # the source labels count too
+                self._source_kept()
+                L.call("simt_head_grad", C.byref(self.head_desc), st)
+                self._bwd.run()
+                accumulate_pass(self, mi * per, n_pass, st)
             if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
                 self._mixed_batch(img, teachers[mi])
                 self._fwd.run()
@@ -412,24 +427,14 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self._head_loss(st)          # simt_head_loss; with online_labels_weighted its weighted form (OnlineLabelMixin)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
             self._head_grad(st)
-            if self.reducer is not None and hp.iter_size == 1:
+            if self.reducer is not None and n_pass == 1:
                 self.reducer.start()
                 self._bwd.run()
                 self.reducer.finish()
                 continue
             self._bwd.run()
-            if hp.iter_size > 1:
-                if self._grad_acc is None:
-                    self._grad_acc = torch.zeros_like(flat)
-                if mi == 0:
-                    self._grad_acc.copy_(flat)
-                elif mi < hp.iter_size - 1:
-                    L.call("simt_vec_acc", self._grad_acc.data_ptr(), flat.data_ptr(), flat.numel(), 1, st)
-                else:
-                    L.call("simt_vec_acc", flat.data_ptr(), self._grad_acc.data_ptr(), flat.numel(), 1, st)
-                    if self.reducer is not None:
-                        self.reducer.start()
-                        self.reducer.finish()
+            if n_pass > 1:      # the accumulation of hp.iter_size > 1, over passes (step.accumulate_pass); the exchange behind the last
+                accumulate_pass(self, mi * per + per - 1, n_pass, st)
         d = self.sgd_desc
         d.lr[0], d.lr[1] = lr, lr * 10.0
         d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay

@@ -28,6 +28,12 @@ weights of DACS / DAFormer / MIC -- the model trains on the teacher's arg-max at
 the share of pixels whose confidence is above T (T deletes nothing).  batch (no value): one q per batch, the published rule; item: one per image,
 and with --online-mix a pasted pixel carries its partner's.  ` labelled` stays the share of confident pixels; the loss line gains
 ` q = <min>..<max>`.  --train-state refuses a resume with the flag added, dropped or changed.
+--online-source (needs --online-labels): the published DACS step -- every optimiser step also trains, by the plain cross-entropy, on
+a labelled SOURCE batch: --data-dir / --data-list (GTA5: `images/<name>`, `labels/<name>`, ids mapped to train ids; simt_amd/dataset/gta5_dataset.py)
+through a second loader at --input-size-target with a seed of its own derived from --random-seed; it honours --random-mirror and --scale-crop, none of
+the target-side augmentations, and is not cached.  With --online-mix the mix is the cross-domain one: half of the classes of source image i are
+pasted, image and ground truth, onto target image i (simt_source_mix); with --online-labels-weighted a pasted pixel has weight 1.  The loss line
+gains ` src = <loss_seg2 of the source pass>`; --train-state resumes both loaders at the same batch and refuses the flag added or dropped.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -49,12 +55,12 @@ from simt_amd.step import Hyper, WarmupTrainer, lr_poly
 from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
                                           add_ema_args, add_online_label_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args,
                                           add_train_state_args, add_v3_layers, batches, check_online_label_args, check_patch_mask_args,
-                                          online_label_line, patch_mask_line, restore, save_atomic, shutdown)
+                                          online_label_line, patch_mask_line, restore, save_atomic, shutdown, source_batches)
 
 
 def get_arguments(argv=None):
     """Every flag of the reference (trainV1_warmup.py:60-150), same names / types / defaults; the ones the reference parses and never
-    reads (--target, --data-dir, --data-list, --ignore-label, --input-size, --is-training, --learning-rate-T, --not-restore-last,
+    reads (--target, --data-dir and --data-list without --online-source, --ignore-label, --input-size, --is-training, --learning-rate-T, --not-restore-last,
     --open-classes, --random-scale, --set, --log-dir) are parsed and ignored here too.  --model picks the network (check_model)."""
     p = argparse.ArgumentParser(description="DeepLab-ResNet warm-up on MI355X")
     p.add_argument("--model", type=str, default="DeepLab")
@@ -116,16 +122,21 @@ def get_arguments(argv=None):
     return args
 
 
-def step_args(args, mb):
+def step_args(args, mb, sb=None):
     """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
-    (image, None) and the keyword teacher_image where the loader made a weak view."""
+    (image, None) and the keyword teacher_image where the loader made a weak view; sb: the micro-batches of `source_batches`
+    (--online-source) -> the keywords source_image / source_label."""
     one = args.iter_size == 1
     img = mb[0][0] if one else [m[0] for m in mb]
     if args.online_labels is None:
         return (img, mb[0][1] if one else [m[1] for m in mb]), {}
+    kw = {}
+    if sb is not None:
+        kw.update(source_image=sb[0][0] if one else [m[0] for m in sb], source_label=sb[0][1] if one else [m[1] for m in sb])
     if mb[0][2] is None:
-        return (img, None), {}
-    return (img, None), {"teacher_image": mb[0][2] if one else [m[2] for m in mb]}
+        return (img, None), kw
+    kw["teacher_image"] = mb[0][2] if one else [m[2] for m in mb]
+    return (img, None), kw
 
 
 def labelled_text(args, l):
@@ -147,14 +158,21 @@ def quality_text(args, l):
     return " q = {0:.3f}..{1:.3f}".format(min(l["label_quality"]), max(l["label_quality"]))
 
 
+def source_text(args, l):
+    """` src = <loss_seg2 of the source pass>` of the loss line: only with --online-source."""
+    return " src = {0:.3f}".format(l["source_seg2"]) if getattr(args, "online_source", False) else ""
+
+
 def balanced_kwargs(args):
-    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed) and
-    --online-labels-weighted when on."""
+    """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed),
+    --online-labels-weighted and --online-source when on."""
     kw = {"online_labels_balanced": args.online_labels_balanced, "online_labels_momentum": args.online_labels_momentum}
     if args.online_mix is not None:
         kw.update(online_mix=args.online_mix, online_mix_seed=args.random_seed)
     if getattr(args, "online_labels_weighted", None) is not None:
         kw.update(online_labels_weighted=args.online_labels_weighted)
+    if getattr(args, "online_source", False):
+        kw.update(online_source=True)
     return kw
 
 
@@ -217,17 +235,19 @@ def main(argv=None):
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
     data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
+    source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        a, kw = step_args(args, mb)
+        sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
+        a, kw = step_args(args, mb, sb)
         tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:              # :231-234 (every 100 iterations there)
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -306,17 +326,19 @@ def main_single(args):
     if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
         return shutdown(world)
     data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
+    source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        a, kw = step_args(args, mb)
+        sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
+        a, kw = step_args(args, mb, sb)
         tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

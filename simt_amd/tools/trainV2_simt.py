@@ -354,8 +354,8 @@ def _online_mix(text):
 
 
 def add_online_label_args(p):
-    """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17), --online-mix (7.18) and
-    --online-labels-weighted (7.19) of trainV1_warmup; `check_online_label_args` holds their refusals."""
+    """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17), --online-mix (7.18),
+    --online-labels-weighted (7.19) and --online-source (7.20) of trainV1_warmup; `check_online_label_args` holds their refusals."""
     from simt_amd.online_labels import DEFAULT_PORTION, DEFAULT_THRESHOLD
     p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
                    help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
@@ -384,6 +384,12 @@ def add_online_label_args(p):
                         "whose confidence is above T; T deletes nothing.  MODE batch (no value): one q for the batch, the published rule; item: "
                         "one q per image (with --online-mix a pasted pixel carries its partner's).  Needs --batch-size <= 32; not with "
                         "--online-labels-balanced.  Default: off")
+    p.add_argument("--online-source", action="store_true",
+                   help="with --online-labels: the published DACS step (simt_amd/online_labels.py; DESIGN 7.20) -- every batch is trained beside a "
+                        "labelled source batch of --data-dir / --data-list (GTA5: images/<name>, labels/<name>) at --input-size-target, in the same "
+                        "optimiser step; with --online-mix half of a source image's classes are pasted, image and ground truth, onto the target "
+                        "image, and with --online-labels-weighted a pasted pixel has weight 1.  The source loader honours --random-mirror and "
+                        "--scale-crop only.  Default: off")
 
 
 def check_online_label_args(p, args):
@@ -412,6 +418,8 @@ def check_online_label_args(p, args):
                     "pixels above the one threshold T")
         if not 1 <= args.batch_size <= MAX_WEIGHTED_ITEMS:
             p.error(f"--online-labels-weighted with --batch-size {args.batch_size}: the label launch counts at most {MAX_WEIGHTED_ITEMS} items")
+    if getattr(args, "online_source", False) and args.online_labels is None:
+        p.error("--online-source needs --online-labels: the source batch is trained beside a target batch that a teacher labels")
     if getattr(args, "online_mix", None) is not None:
         from simt_amd.data.class_mix import MAX_CLASSES, MAX_ITEMS
         if args.online_labels is None:
@@ -432,6 +440,7 @@ def online_label_line(args):
     print(f"online labels: {who} labels every batch, kept where its confidence is > {args.online_labels}; the teacher sees "
           f"{'the batch before ' + ', '.join(weak) + ' (the weak view)' if weak else 'the same batch as the student'}" + balanced_clause(args) +
           mix_clause(args, weak) + weighted_clause(args))
+    source_line(args)
 
 
 def online_balanced(args):
@@ -457,9 +466,26 @@ def mix_clause(args, weak):
     p = getattr(args, "online_mix", None)
     if p is None:
         return ""
+    if getattr(args, "online_source", False):      # the pasted side is the labelled source batch
+        return (f"; online mix: with probability {p} a target item receives, image and ground truth, half of the classes of its source item, "
+                f"behind the teacher and in front of the student's forward")
     views = (f"; the mix selects from the students' strong views: a pasted region carries its partner's {', '.join(weak)}" if weak else "")
     return (f"; online mix: with probability {p} an item receives, image and label, half of the classes the teacher found in its neighbour, "
             f"behind the teacher and in front of the student's forward" + views)
+
+
+def source_line(args):
+    """--online-source: one start-up line that says what an optimiser step consists of."""
+    if not getattr(args, "online_source", False):
+        return
+    parts = ["supervised cross-entropy on a labelled source batch" + (" (synthetic)" if args.synthetic else f" of {args.data_list}"),
+             "the teacher's labels on the target batch" +
+             (" weighted by q" if getattr(args, "online_labels_weighted", None) is not None else "")]
+    if getattr(args, "online_mix", None) is not None:
+        parts[1] += (f", onto which half of the source image's classes are pasted with probability {args.online_mix}: ground truth" +
+                     (" and weight 1" if getattr(args, "online_labels_weighted", None) is not None else "") + " where pasted")
+    print("online source: one optimiser step = (1) " + parts[0] + " + (2) " + parts[1] +
+          "; both passes into one gradient, the losses summed; the source loader honours --random-mirror and --scale-crop only")
 
 
 def weighted_clause(args):
@@ -639,7 +665,8 @@ class EmaSnapshots:
 
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
-                "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
+                "online_source": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -672,6 +699,10 @@ def run_identity(args, class_dist):
             ident["online_mix"] = float(args.online_mix)                 # P (the seed is random_seed)
         if getattr(args, "online_labels_weighted", None) is not None:
             ident["online_labels_weighted"] = str(args.online_labels_weighted)      # "batch" | "item"
+        if getattr(args, "online_source", False):
+            ident["online_source"] = True
+            if not args.synthetic and osp.isfile(args.data_list):
+                ident["source_list_sha256"] = hashlib.sha256(open(args.data_list, "rb").read()).hexdigest()
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -834,6 +865,36 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
         return ((img, None, None) for (img, _lab, _sizes, _names) in loader)
     if ds.teacher_view:
         return ((img, lab, weak, item) for (img, lab, _sizes, _names, weak, item) in loader)
+    return ((img, lab) for (img, lab, _sizes, _names) in loader)
+
+
+SOURCE_SEED_OFFSET = 0x5372      # "Sr": the source loader's seed is --random-seed + this (order, mirror and scale-crop draws of its own)
+
+
+def source_batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
+    """--online-source: -> iterator of (source image f32 [B,3,H,W], source label i64 [B,H,W]) resident on the device, from this rank's
+    batch number `start_batch` on -- the position of `batches`, so a resumed run continues both loaders together.  A second GpuLoader over
+    GTA5DataSet(--data-dir, --data-list) at the target's size (the plan has one geometry), seeded by --random-seed + SOURCE_SEED_OFFSET; it
+    honours --random-mirror and --scale-crop and none of the target-side augmentations, and is not cached.  --synthetic: labelled
+    synthetic batches from the same seed."""
+    seed = args.random_seed + SOURCE_SEED_OFFSET
+    if args.synthetic:
+        def synth():
+            it = start_batch
+            while True:
+                yield ms.synthetic_batch(B, H, W, cd, seed=seed + it * world + rank, device=dev)
+                it += 1
+        return synth()
+    if not args.data_dir or not osp.isdir(args.data_dir):
+        raise SystemExit(f"--online-source: --data-dir {args.data_dir!r} is not a directory; pass --synthetic for synthetic batches")
+    if not osp.isfile(args.data_list):
+        raise SystemExit(f"--online-source: --data-list {args.data_list!r} is not a file")
+    from simt_amd.data.pipeline import IMG_MEAN, GpuLoader
+    from simt_amd.dataset.gta5_dataset import GTA5DataSet
+    ds = GTA5DataSet(args.data_dir, args.data_list, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
+                     scale_crop=scale_crop_choices(args))
+    loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=seed, rank=rank, world=world,
+                       hold=max(1, getattr(args, "iter_size", 1)), start_batch=start_batch)
     return ((img, lab) for (img, lab, _sizes, _names) in loader)
 
 

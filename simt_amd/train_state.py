@@ -38,6 +38,9 @@ MIX_FIELDS = ("online_mix", "online_mix_seed")
 # and the quality weights of that teacher's labels (online_labels_weighted = "batch" | "item": DESIGN 7.19), compared through
 # value_mismatches(..., fields=WEIGHTED_FIELDS)
 WEIGHTED_FIELDS = ("online_labels_weighted",)
+# and the labelled source batch trained beside that teacher's labels (online_source = True: DESIGN 7.20), compared through
+# value_mismatches(..., fields=SOURCE_FIELDS)
+SOURCE_FIELDS = ("online_source",)
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -150,14 +153,17 @@ class TrainStateMixin:
                 hy["online_mix_seed"] = int(self.online_mix_seed)
             if getattr(self, "online_labels_weighted", None) is not None:
                 hy["online_labels_weighted"] = str(self.online_labels_weighted)
+            if getattr(self, "online_source", False):
+                hy["online_source"] = True
         return hy
 
     def _nbt_steps(self, key):
         """What state_dict() adds to the `num_batches_tracked` the trainer was given: the train-mode forwards of that BatchNorm so far.  Every
-        BatchNorm of DeepLab-v2 runs; of DeepLabv3 those of the plan (not layer4's: DeepLabv3._dead_bns); DeepLab-VGG16 has none."""
+        BatchNorm of DeepLab-v2 runs; of DeepLabv3 those of the plan (not layer4's: DeepLabv3._dead_bns); DeepLab-VGG16 has none.  With
+        `online_source` a micro-batch is two train-mode forwards, the source pass and the target pass."""
         model = getattr(self, "model", "v2")
         live = model == "v2" or (model == "v3" and key[:-len(".num_batches_tracked")] in self.plan.bn)
-        return self.it_done * self.hp.iter_size if live else 0
+        return self.it_done * self.hp.iter_size * (2 if getattr(self, "online_source", False) else 1) if live else 0
 
     def training_state(self):
         """Everything the next `step()` depends on, as a plain dict of host tensors and Python scalars: `model` (= state_dict()),
@@ -173,7 +179,8 @@ class TrainStateMixin:
         and `accumulators` the per-class thresholds (`label_thresholds`); their histogram is zero between steps and is not stored.  With
         `online_mix` `hyper` also carries P and S and the dict gains `mix_rng`, the `bit_generator.state` of the mix's generator:
         the resumed run draws what the uninterrupted one draws.  With `online_labels_weighted` `hyper` also carries the mode and
-        `accumulators` the last micro-batch's weights (`label_quality`); without the keyword the dict is what it was.
+        `accumulators` the last micro-batch's weights (`label_quality`); without the keyword the dict is what it was.  With `online_source`
+         `hyper` also carries `online_source: True` and `accumulators` the two kept losses of the last source pass (`source_hout`).
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -198,6 +205,8 @@ class TrainStateMixin:
                     ts["accumulators"]["label_thresholds"] = self.label_thr.detach().cpu()
                 if getattr(self, "online_labels_weighted", None) is not None:      # the last micro-batch's weights: `label_quality` resumes exactly
                     ts["accumulators"]["label_quality"] = self.label_q.detach().cpu()
+                if getattr(self, "online_source", False):      # the last source pass's losses: `source_seg1` / `source_seg2` resume exactly
+                    ts["accumulators"]["source_hout"] = self.source_hout.detach().cpu()
         if getattr(self, "online_mix", None) is not None:      # the position of the mix's own generator (numpy's plain dict of Python ints)
             ts["mix_rng"] = self._mix_rng.bit_generator.state
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
@@ -216,7 +225,8 @@ class TrainStateMixin:
         bad = (hyper_mismatches(ts["hyper"], self._hyper_state()) + switch_mismatches(ts["hyper"], self._hyper_state()) +
                value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -279,6 +289,8 @@ class TrainStateMixin:
                     self.label_thr.copy_(acc["label_thresholds"])
                 if getattr(self, "online_labels_weighted", None) is not None:
                     self.label_q.copy_(acc["label_quality"])
+                if getattr(self, "online_source", False):
+                    self.source_hout.copy_(acc["source_hout"])
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "online_mix", None) is not None:
             self._mix_rng.bit_generator.state = ts["mix_rng"]
