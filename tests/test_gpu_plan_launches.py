@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 import _launch_oracle as lo
-from _plan_replay import Run, _env, _k, _neg, _perturb, _two_ulps, match_layers, replay
+from _plan_layers import v3_layers, vgg_layers
+from _plan_replay import Run, _env, _perturb, _two_ulps, match_layers, replay
 from oracle import simt_oracle as so
 from simt_amd import _lib as L
 from simt_amd import model_spec as ms
@@ -34,55 +35,6 @@ CD = so.load_class_dist()
 # tag -> the test that holds launches of that tag instead.  Empty: with SIMT_BN_GRID=0 the plans carry no fused-BatchNorm launch (the only
 # form this oracle refuses), and every other entry point has a handler.
 NOT_HERE = {}
-
-
-def v3_layers(B, H, W, layers, Q, width=64, ac=256):
-    """{parameter prefix: {"fwd": geometry, "bwd": geometry or None}} of DeepLabv3, restated from the layer specs (model/deeplabv3.py via
-    engine_v3's tables): the conv launch whose weight operand was packed from that parameter must have exactly this geometry."""
-    from simt_amd.engine_v3 import ASSP_BRANCHES, R50, v3_block_specs, v3_geometry
-    (H0, W0), (Hp, Wp) = v3_geometry(H, W)
-    one = [(0, 0)]
-    out = {R50 + "conv1": {"fwd": _k(1, 1, B * H0 * W0, 192, 1, B * H0 * W0, width, 1, one), "bwd": None}}
-    Hc, Wc = Hp, Wp
-    t3 = ops.conv_taps(3, 3, 1, 1)
-    for (n, inpl, p, s, down) in v3_block_specs(layers, width):
-        Ho, Wo, c4 = (Hc - 1) // s + 1, (Wc - 1) // s + 1, 4 * p
-        out[n + ".conv1"] = {"fwd": _k(B, Hc, Wc, inpl, Hc, Wc, p, 1, one), "bwd": _k(B, Hc, Wc, p, Hc, Wc, inpl, 1, one)}
-        out[n + ".conv2"] = {"fwd": _k(B, Hc, Wc, p, Ho, Wo, p, s, t3), "bwd": _k(B, Hc, Wc, p, Hc, Wc, p, 1, _neg(t3))}
-        out[n + ".conv3"] = {"fwd": _k(B, Ho, Wo, p, Ho, Wo, c4, 1, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, p, 1, one)}
-        if down:
-            out[n + ".downsample.0"] = {"fwd": _k(B, Hc, Wc, inpl, Ho, Wo, c4, s, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, inpl, 1, one)}
-        Hc, Wc, cin = Ho, Wo, c4
-    h, w = Hc, Wc
-    for (i, k, dil) in ASSP_BRANCHES:
-        taps = ops.conv_taps(3, 3, dil, dil) if k == 3 else one
-        out[f"assp.conv{i}"] = {"fwd": _k(B, h, w, cin, h, w, ac, 1, taps), "bwd": _k(B, h, w, ac, h, w, cin, 1, _neg(taps))}
-    # convf: 5 taps stepping one plane over the virtual concat; its dgrad plane by plane
-    out["assp.convf"] = {"fwd": _k(1, 5 * B * h, w, ac, B * h, w, ac, 1, [(t * B * h, 0) for t in range(5)]), "bwd": _k(B, h, w, ac, h, w, ac, 1, one)}
-    for pre in (("conv", "conv_1") if Q > 19 else ("conv",)):                    # classifier(s): fp32 logits, K-padded dgrad
-        out[pre] = {"fwd": _k(B, h, w, ac, h, w, Q, 1, one), "bwd": _k(B, h, w, ops.round_up(Q, 64), h, w, ac, 1, one)}
-    return out
-
-
-def vgg_layers(B, H, W, Q, kq=64):
-    from simt_amd.engine_vgg import VGG_LAYERS
-    one = [(0, 0)]
-    out = {}
-    Hc, Wc = H, W
-    for li, (idx, cin, cout, dil, pool) in enumerate(VGG_LAYERS):
-        M = B * Hc * Wc
-        if li == 0:                                                              # im2col matrix, K = 27 padded to 64
-            out[f"features.{idx}"] = {"fwd": _k(1, 1, M, kq, 1, M, cout, 1, one), "bwd": None}
-        else:
-            t3 = ops.conv_taps(3, 3, dil, dil)
-            out[f"features.{idx}"] = {"fwd": _k(B, Hc, Wc, cin, Hc, Wc, cout, 1, t3), "bwd": _k(B, Hc, Wc, cout, Hc, Wc, cin, 1, _neg(t3))}
-        if pool:
-            Hc, Wc = Hc // 2, Wc // 2
-    nt, QP, c = 18, ops.round_up(Q, 8), VGG_LAYERS[-1][2]
-    for i in range(2):                                                           # the two live branches, one tap-expanded GEMM
-        out[f"classifier.conv2d_list.{i}"] = {"fwd": _k(B, Hc, Wc, c, Hc, Wc, nt * QP, 1, one),
-                                              "bwd": _k(B, Hc, Wc, ops.round_up(nt * QP, kq), Hc, Wc, c, 1, one)}
-    return out
 
 
 def _seed_and_backward(plan, lists_bwd, run, red, B, Q, dev, v3):

@@ -27,11 +27,11 @@ import pytest
 import torch
 
 import _launch_oracle as lo
-from _plan_replay import STEM_TAPS, Run, _env, _k, _neg, _perturb, _two_ulps, match_layers, replay
+from _plan_layers import v2_layers
+from _plan_replay import Run, _env, _perturb, _two_ulps, match_layers, replay
 from _plan_trace import Tracer, check_rules
 from oracle import simt_oracle as so
 from simt_amd import model_spec as ms
-from simt_amd import ops
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -41,42 +41,6 @@ Q = 19 + K
 
 # tag -> the test that holds launches of that tag instead.  Empty: every entry point of the two plans has a handler.
 NOT_HERE = {}
-
-
-def v2_layers(B, H, W, K):
-    """{parameter prefix: {"fwd": geometry, "bwd": geometry or None}} of DeepLab-v2 (ResNet-101, layers (3, 4, 23, 3)) restated from
-    engine.block_specs / trunk_geometry / multi_heads: layer2 strides 2 in its first conv1 and downsample, layer3 / layer4 keep the stride-8
-    map with dilation 2 / 4; the ASPP heads (dilations 6, 12) in the tap-expanded form the bf16 plans launch (K = Cin, N = 18 taps x QP)."""
-    from simt_amd.engine import LAYERS, block_specs, multi_heads, trunk_geometry
-    (H0, W0), (Hp, Wp), _ = trunk_geometry(H, W)
-    assert (H0, W0) == ((H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1) and LAYERS == (3, 4, 23, 3)
-    one = [(0, 0)]
-    out = {"conv1": {"fwd": _k(B, H, W, 3, H0, W0, 64, 2, STEM_TAPS), "bwd": None}}
-    Hc, Wc = Hp, Wp
-    feat = {}
-    specs = block_specs(LAYERS)
-    assert len(specs) == 33
-    for (n, inpl, p, s, dil, down) in specs:
-        li, bi = int(n[5]), int(n.split(".")[1])
-        assert (p, dil) == ((64, 128, 256, 512)[li - 1], (1, 1, 2, 4)[li - 1]) and s == (2 if (li == 2 and bi == 0) else 1) and down == (bi == 0)
-        Ho, Wo, c4 = (Hc - 1) // s + 1, (Wc - 1) // s + 1, 4 * p
-        t3 = ops.conv_taps(3, 3, dil, dil)
-        out[n + ".conv1"] = {"fwd": _k(B, Hc, Wc, inpl, Ho, Wo, p, s, one), "bwd": _k(B, Ho, Wo, p, Ho, Wo, inpl, 1, one)}
-        out[n + ".conv2"] = {"fwd": _k(B, Ho, Wo, p, Ho, Wo, p, 1, t3), "bwd": _k(B, Ho, Wo, p, Ho, Wo, p, 1, _neg(t3))}
-        out[n + ".conv3"] = {"fwd": _k(B, Ho, Wo, p, Ho, Wo, c4, 1, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, p, 1, one)}
-        if down:
-            out[n + ".downsample.0"] = {"fwd": _k(B, Hc, Wc, inpl, Ho, Wo, c4, s, one), "bwd": _k(B, Ho, Wo, c4, Ho, Wo, inpl, 1, one)}
-        Hc, Wc = Ho, Wo
-        feat[li] = (Hc, Wc, c4)
-    for hd in multi_heads(19, K, K > 0):
-        h, w, cin = feat[hd.feat_layer]
-        assert hd.dilations == (6, 12) and cin == hd.cin
-        nexp = 9 * len(hd.dilations) * ops.round_up(hd.Q, 8)
-        for prefix, _c in hd.groups:
-            for i in range(len(hd.dilations)):
-                out[f"{prefix}.conv2d_list.{i}"] = {"fwd": _k(B, h, w, cin, h, w, nexp, 1, one),
-                                                    "bwd": _k(B, h, w, ops.round_up(nexp, 64), h, w, cin, 1, one)}
-    return out
 
 
 def _params(st, dev):
