@@ -647,6 +647,50 @@ typedef struct {
 long simt_scale_crop_lds_bytes(const simt_scale_crop_desc* d);   /* < 0: the descriptor is invalid */
 int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stream);
 
+/* ---- rare-class crops: the window is picked on the device (simt_amd/data/rare_class.py; csrc/rare_crop.hip) ------------
+ * DAFormer's rare-class sampling re-draws the crop until it holds enough pixels of the sampled class.  Here the host draws K candidate
+ * windows (choice, ox, oy) per item, and three launches on one stream count, pick and crop -- the pick reaches the crop through `win`
+ * in device memory, nothing is read back.
+ *
+ * simt_rare_crop_counts: for item b < B, candidate k < K and c = cls[b] < 255, with ws, hs, xtab, ytab those of choice
+ *   ci = cand_choice[b][k] and (ox, oy) = (cand_ox[b][k], cand_oy[b][k]):
+ *     count[b][k] = #{ (y, x) in h x w : 0 <= y + oy < hs, 0 <= x + ox < ws, lab[b][ytab[y + oy]][xtab[x + ox]] == c }
+ *   -- (lab_out[b] == c).sum() of simt_scale_crop at that window (the mirror does not change it).  It leaves as
+ *   parts[b][k][0 .. SIMT_RARE_CROP_PARTS-1], whose sum is the count; EVERY word is written by a plain store on every call (no atomics,
+ *   nothing to zero).  cls[b] == 255: nothing is counted for b, its words are 0.
+ * simt_rare_crop_pick: win[b] = (choice, ox, oy, count) of candidate k*, the smallest k with count[b][k] > min_count, or K - 1 when no
+ *   candidate passes (DAFormer keeps the last crop tried); cls[b] == 255: k* = 0.  Reads `parts`, so it runs behind the counts.
+ * simt_scale_crop_win: simt_scale_crop whose per-item (choice, ox, oy) are win[b][0..2], read on the device; x, lab_out, mirror, tables
+ *   and LDS as there, bit for bit the launch of simt_scale_crop at those windows.  A choice >= n_choices is clamped to n_choices - 1 and
+ *   an origin to its choice's range [min(0, ws - w), max(0, ws - w)] (hs, h likewise): whatever `win` holds, no table is read out of range.
+ * All three refuse (SIMT_ERR_INVALID, nothing launched or written) what simt_scale_crop refuses and: K outside 1 .. SIMT_RARE_CROP_CANDS,
+ * a candidate choice >= n_choices, a candidate origin outside its choice's range, min_count < 0, parts NULL or not 4-byte aligned, win
+ * NULL or not 16-byte aligned, a NULL label pointer.  B <= SIMT_RARE_CROP_MAX: with K candidates per item the descriptor of 64 items
+ * would not fit the kernel-argument segment.  The descriptor travels as kernel arguments, like simt_scale_crop_desc. */
+#define SIMT_RARE_CROP_MAX 16
+#define SIMT_RARE_CROP_CANDS 16
+#define SIMT_RARE_CROP_PARTS 16
+typedef struct {
+  const unsigned char* img[SIMT_RARE_CROP_MAX];    /* [Hs][Ws][3] u8 RGB */
+  const unsigned char* lab[SIMT_RARE_CROP_MAX];    /* [Hs][Ws] u8 */
+  int32_t cand_ox[SIMT_RARE_CROP_MAX][SIMT_RARE_CROP_CANDS], cand_oy[SIMT_RARE_CROP_MAX][SIMT_RARE_CROP_CANDS];
+  unsigned char cand_choice[SIMT_RARE_CROP_MAX][SIMT_RARE_CROP_CANDS];
+  unsigned char mirror[SIMT_RARE_CROP_MAX];
+  unsigned char cls[SIMT_RARE_CROP_MAX];           /* the class counted for item b; 255: none, candidate 0 is taken */
+  simt_scale_crop_choice c[SIMT_SCALE_CROP_CHOICES];
+  const int32_t* tables;
+  float* x;              /* [B][3][h][w] fp32 */
+  long long* lab_out;    /* [B][h][w] int64, or NULL */
+  int32_t* parts;        /* [B][K][SIMT_RARE_CROP_PARTS] */
+  int32_t* win;          /* [B][4]: choice, ox, oy, count */
+  int32_t B, Hs, Ws, h, w, n_choices, max_rows, n_tables;
+  int32_t K, min_count;
+  float mean[3];
+} simt_rare_crop_desc;
+int simt_rare_crop_counts(const simt_rare_crop_desc* d, simt_stream_t stream);
+int simt_rare_crop_pick(const simt_rare_crop_desc* d, simt_stream_t stream);
+int simt_scale_crop_win(const simt_rare_crop_desc* d, simt_stream_t stream);
+
 /* ---- ClassMix: class-mask mixing of batch items on the device (simt_amd/data/class_mix.py; csrc/class_mix.hip) ---------------
  * x [B][3][h][w] fp32 and lab [B][h][w] int64 are a finished batch; a label outside [0, n_classes) is "ignore".  Item i's partner is
  * j = partner[i].  P_j = the classes c < n_classes that occur in lab[j], n = |P_j|, k = (n + 1) / 2, S_j = the k classes of P_j with the

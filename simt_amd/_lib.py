@@ -133,6 +133,22 @@ class ScaleCropDesc(C.Structure):
                 ("mean", f32 * 3)]
 
 
+RARE_CROP_MAX = 16       # include/simt_hip.h SIMT_RARE_CROP_MAX
+RARE_CROP_CANDS = 16     # SIMT_RARE_CROP_CANDS
+RARE_CROP_PARTS = 16     # SIMT_RARE_CROP_PARTS
+
+
+class RareCropDesc(C.Structure):
+    """simt_rare_crop_desc (include/simt_hip.h): one batch of source frames and K candidate windows per item -> counts, pick, crop."""
+    _fields_ = [("img", c_p * RARE_CROP_MAX), ("lab", c_p * RARE_CROP_MAX),
+                ("cand_ox", (i32 * RARE_CROP_CANDS) * RARE_CROP_MAX), ("cand_oy", (i32 * RARE_CROP_CANDS) * RARE_CROP_MAX),
+                ("cand_choice", (C.c_uint8 * RARE_CROP_CANDS) * RARE_CROP_MAX), ("mirror", C.c_uint8 * RARE_CROP_MAX),
+                ("cls", C.c_uint8 * RARE_CROP_MAX), ("c", ScaleCropChoice * SCALE_CROP_CHOICES),
+                ("tables", c_p), ("x", c_p), ("lab_out", c_p), ("parts", c_p), ("win", c_p),
+                ("B", i32), ("Hs", i32), ("Ws", i32), ("h", i32), ("w", i32), ("n_choices", i32), ("max_rows", i32), ("n_tables", i32),
+                ("K", i32), ("min_count", i32), ("mean", f32 * 3)]
+
+
 CLASS_MIX_MAX = 32       # include/simt_hip.h SIMT_CLASS_MIX_MAX
 CLASS_MIX_CLASSES = 32   # SIMT_CLASS_MIX_CLASSES
 CLASS_MIX_PARTS = 64     # SIMT_CLASS_MIX_PARTS
@@ -389,6 +405,9 @@ SIGNATURES = {
     "simt_source_mix_items": (_I, [C.POINTER(SourceMixDesc), c_p, c_p]),
     "simt_head_loss_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
     "simt_head_grad_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
+    "simt_rare_crop_counts": (_I, [C.POINTER(RareCropDesc), c_p]),
+    "simt_rare_crop_pick": (_I, [C.POINTER(RareCropDesc), c_p]),
+    "simt_scale_crop_win": (_I, [C.POINTER(RareCropDesc), c_p]),
 }
 
 _lib = None

@@ -29,11 +29,16 @@ __device__ __forceinline__ int sc_clip8(int acc) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void scale_crop_kernel(const simt_scale_crop_desc d, int ksx_max) {
+// WIN_: empty for simt_scale_crop (name and code as before the flavour existed); {true} for simt_scale_crop_win (csrc/rare_crop.hip), whose
+// block-uniform choice and origin are three words of device memory, win[b][0..2], clamped so that whatever they hold no table is read out
+// of range: the choice to n_choices - 1, the origin to its choice's origin range (the range max_rows was computed over).
+template <bool VEC, bool... WIN_>
+__global__ __launch_bounds__(256) void scale_crop_kernel(const simt_scale_crop_desc d, int ksx_max, const int32_t* __restrict__ win) {
+  constexpr bool WIN = (false || ... || WIN_);
   extern __shared__ __attribute__((aligned(16))) unsigned char sc_smem[];
   const int b = blockIdx.z, tid = threadIdx.x;
-  const int ci = d.choice[b];
+  int ci = d.choice[b];
+  if (WIN) ci = (int)min((unsigned)__builtin_amdgcn_readfirstlane(win[4 * b]), (unsigned)(d.n_choices - 1));
   const int ws = d.c[ci].ws, hs = d.c[ci].hs, ksx = d.c[ci].ksx, ksy = d.c[ci].ksy;
   const int32_t* __restrict__ T = d.tables;
   const int32_t* __restrict__ bx = T + d.c[ci].bounds_x;
@@ -41,8 +46,13 @@ __global__ __launch_bounds__(256) void scale_crop_kernel(const simt_scale_crop_d
   const int32_t* __restrict__ by = T + d.c[ci].bounds_y;
   const int32_t* __restrict__ ky = T + d.c[ci].coef_y;
   const unsigned char* __restrict__ img = d.img[b];
-  const int ox = d.ox[b], oy = d.oy[b], mirror = d.mirror[b];
   const int w = d.w, h = d.h, Ws = d.Ws, max_rows = d.max_rows;
+  int ox = d.ox[b], oy = d.oy[b];
+  if (WIN) {
+    ox = min(max(__builtin_amdgcn_readfirstlane(win[4 * b + 1]), min(0, ws - w)), max(0, ws - w));
+    oy = min(max(__builtin_amdgcn_readfirstlane(win[4 * b + 2]), min(0, hs - h)), max(0, hs - h));
+  }
+  const int mirror = d.mirror[b];
   const int x0 = blockIdx.x * SC_TW, y0 = blockIdx.y * SC_TH;
   // the rows [sy_lo, sy_hi) and columns [sx_lo, sx_hi) of S this tile shows
   const int sy_lo = max(0, y0 + oy), sy_hi = min(hs, min(y0 + SC_TH, h) + oy);
@@ -195,7 +205,8 @@ extern "C" long simt_scale_crop_lds_bytes(const simt_scale_crop_desc* d) {
   return (long)d->max_rows * 3 * SC_TW + ((long)SC_TW * ksx + (long)SC_TH * ksy) * 4;
 }
 
-extern "C" int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stream) {
+// The launch of both flavours: win NULL is simt_scale_crop, else simt_scale_crop_win (csrc/rare_crop.hip builds `d` from its descriptor).
+int simt_scale_crop_launch(const simt_scale_crop_desc* d, const int32_t* win, simt_stream_t stream) {
   SIMT_CHECK(sc_valid(d));
   const bool vec = (d->w & 3) == 0;
   SIMT_CHECK(!vec || (((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->lab_out & 15) == 0));
@@ -211,10 +222,17 @@ extern "C" int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stre
   }
   const dim3 grid((unsigned)((d->w + SC_TW - 1) / SC_TW), (unsigned)((d->h + SC_TH - 1) / SC_TH), (unsigned)d->B);
   SIMT_CHECK(grid.y <= 65535);
-  if (vec)
-    hipLaunchKernelGGL((scale_crop_kernel<true>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx);
+  const int32_t* none = nullptr;
+  if (win && vec)
+    hipLaunchKernelGGL((scale_crop_kernel<true, true>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx, win);
+  else if (win)
+    hipLaunchKernelGGL((scale_crop_kernel<false, true>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx, win);
+  else if (vec)
+    hipLaunchKernelGGL((scale_crop_kernel<true>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx, none);
   else
-    hipLaunchKernelGGL((scale_crop_kernel<false>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx);
+    hipLaunchKernelGGL((scale_crop_kernel<false>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, *d, ksx, none);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }
+
+extern "C" int simt_scale_crop(const simt_scale_crop_desc* d, simt_stream_t stream) { return simt_scale_crop_launch(d, nullptr, stream); }

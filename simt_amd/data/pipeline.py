@@ -20,6 +20,7 @@ from . import resample as rs
 from . import class_mix as cm
 from . import patch_mask as pm
 from . import photometric as ph
+from . import rare_class as rc
 from . import scale_crop as sc
 
 IMG_MEAN = (104.00698793, 116.66876762, 122.67891434)      # tools/trainV2_simt.py:34 (BGR)
@@ -189,6 +190,50 @@ class InputPrep:
             d.mean[0], d.mean[1], d.mean[2] = self.mean
             L.call("simt_scale_crop", C.byref(d), stream)
 
+    def rare_crop_batch(self, img_ptrs, lab_ptrs, draws, cls, min_count, x_out, lab_out, parts, win, stream):
+        """scale_crop_batch whose window is picked on the device (rare-class crops, csrc/rare_crop.hip): draws = (mirror flags [B],
+        choice indices [B][K], ox [B][K], oy [B][K]) (scale_crop.draw_batch_candidates), cls [B] the class counted per item (255: none).
+        Three launches on `stream` per SIMT_RARE_CROP_MAX items: simt_rare_crop_counts -> parts (int32 [B, K, SIMT_RARE_CROP_PARTS]),
+        simt_rare_crop_pick -> win (int32 [B, 4]: choice, ox, oy, count of the first candidate with count > min_count, else the last),
+        simt_scale_crop_win -> x_out, lab_out at that window.  Nothing is read back."""
+        for d in self.rare_crop_descs(img_ptrs, lab_ptrs, draws, cls, min_count, x_out, lab_out, parts, win):
+            L.call("simt_rare_crop_counts", C.byref(d), stream)
+            L.call("simt_rare_crop_pick", C.byref(d), stream)
+            L.call("simt_scale_crop_win", C.byref(d), stream)
+
+    def rare_crop_descs(self, img_ptrs, lab_ptrs, draws, cls, min_count, x_out, lab_out, parts, win):
+        """The simt_rare_crop_desc of every SIMT_RARE_CROP_MAX items of the batch (arguments: rare_crop_batch's)."""
+        assert self.sc is not None, "built without scale_crop choices"
+        assert x_out.dtype == torch.float32 and tuple(x_out.shape) == (self.B, 3, self.h, self.w) and x_out.is_contiguous()
+        assert lab_out is None or (lab_out.dtype == torch.int64 and tuple(lab_out.shape) == (self.B, self.h, self.w) and lab_out.is_contiguous())
+        mirror, pick, ox, oy = draws
+        K = len(pick[0])
+        assert len(img_ptrs) == len(lab_ptrs) == len(mirror) == len(pick) == len(ox) == len(oy) == len(cls) == self.B
+        assert all(len(r) == K for rows in (pick, ox, oy) for r in rows) and 1 <= K <= L.RARE_CROP_CANDS
+        assert parts.dtype == torch.int32 and tuple(parts.shape) == (self.B, K, L.RARE_CROP_PARTS) and parts.is_contiguous()
+        assert win.dtype == torch.int32 and tuple(win.shape) == (self.B, 4) and win.is_contiguous()
+        out = []
+        for b0 in range(0, self.B, L.RARE_CROP_MAX):
+            n = min(L.RARE_CROP_MAX, self.B - b0)
+            d = L.RareCropDesc()
+            for k in range(n):
+                d.img[k], d.lab[k] = img_ptrs[b0 + k], lab_ptrs[b0 + k]
+                d.mirror[k], d.cls[k] = 1 if mirror[b0 + k] else 0, cls[b0 + k]
+                for j in range(K):
+                    d.cand_choice[k][j], d.cand_ox[k][j], d.cand_oy[k][j] = pick[b0 + k][j], ox[b0 + k][j], oy[b0 + k][j]
+            for c, e in enumerate(self.sc.entries):
+                for name, v in e.items():
+                    setattr(d.c[c], name, v)
+            d.tables, d.n_tables = self.sc_tables.data_ptr(), self.sc_tables.numel()
+            d.x, d.lab_out = x_out[b0].data_ptr(), (lab_out[b0].data_ptr() if lab_out is not None else None)
+            d.parts, d.win = parts[b0].data_ptr(), win[b0].data_ptr()
+            d.B, d.Hs, d.Ws, d.h, d.w = n, self.Hs, self.Ws, self.h, self.w
+            d.n_choices, d.max_rows = len(self.sc.entries), self.sc.max_rows
+            d.K, d.min_count = K, int(min_count)
+            d.mean[0], d.mean[1], d.mean[2] = self.mean
+            out.append(d)
+        return out
+
     def class_mix_batch(self, x, lab, draws, x_out, lab_out, stream, item_out=None):
         """ClassMix of a finished batch: x [B,3,h,w] f32 / lab [B,h,w] i64 -> x_out / lab_out (other buffers: item i reads item
         (i + 1) % B while another workgroup writes it).  draws = (apply [B] bool, rank [B, n_classes] permutations)
@@ -281,10 +326,15 @@ class DevicePrefetcher:
     it.  2*hold slots, so the next group of `hold` batches is uploaded while the current one is being consumed."""
 
     def __init__(self, source, prep, mirror_fn=None, hold=1, depth=None, cache=None, draw_fn=None, mix_fn=None, photo_fn=None,
-                 teacher_view=False, mask_fn=None):
+                 teacher_view=False, mask_fn=None, rare=None):
         self.src, self.prep, self.mirror_fn, self.cache = iter(source), prep, mirror_fn, cache
         self.draw_fn = draw_fn          # scale-crop mode (prep.sc): B -> (mirror flags, choice indices, ox, oy); replaces mirror_fn
         assert (draw_fn is not None) == (prep.sc is not None)
+        # rare-class crops: (K, min_count); draw_fn then yields K candidates per item (scale_crop.draw_batch_candidates), the source's meta
+        # carries the items' classes as its third entry, and the window is picked on the copy stream (prep.rare_crop_batch) into s["win"]
+        self.rare = rare
+        assert rare is None or draw_fn is not None, "rare-class crops pick among scale-crop windows"
+        self.last_win = None            # the `win` words of the batch handed out last
         self.mix_fn = mix_fn            # class-mix mode (prep.cm): B -> (apply, rank); the slot's finished batch is mixed into xm / labm
         assert (mix_fn is not None) == (prep.cm is not None)
         self.photo_fn = photo_fn        # photometric mode (prep.ph): B -> draws; the finished (mixed) batch is jittered and blurred into xp
@@ -311,6 +361,9 @@ class DevicePrefetcher:
                 s["lab_h"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8).pin_memory()
                 s["lab_d"] = torch.empty(B, prep.Hs, prep.Ws, dtype=torch.uint8, device=dev)
                 s["lab"] = torch.empty(B, prep.h, prep.w, dtype=torch.int64, device=dev)
+            if rare is not None:
+                s["parts"] = torch.empty(B, rare[0], L.RARE_CROP_PARTS, dtype=torch.int32, device=dev)
+                s["win"] = torch.empty(B, 4, dtype=torch.int32, device=dev)
             if mix_fn is not None:                     # what __next__ hands out in class-mix mode: same life time as x / lab
                 s["xm"], s["labm"] = torch.empty_like(s["x"]), torch.empty_like(s["lab"])
                 if self.teacher_view:
@@ -364,9 +417,8 @@ class DevicePrefetcher:
             if lab is not None:
                 s["lab_d"].copy_(lab, non_blocking=True)
             if self.draw_fn is not None:           # one launch replaces the resample, image_to_input and label_nearest launches
-                self.prep.scale_crop_batch([s["rgb_d"][b].data_ptr() for b in range(self.prep.B)],
-                                           [s["lab_d"][b].data_ptr() if lab is not None else None for b in range(self.prep.B)],
-                                           self.draw_fn(self.prep.B), s["x"], s["lab"] if lab is not None else None, cs.cuda_stream)
+                self._crop(s, [s["rgb_d"][b].data_ptr() for b in range(self.prep.B)],
+                           [s["lab_d"][b].data_ptr() if lab is not None else None for b in range(self.prep.B)], lab is not None, meta, cs)
             else:
                 mirror = self.mirror_fn(self.prep.B) if self.mirror_fn is not None else False
                 self.prep.run(s["rgb_d"], s["x"], s["lab_d"] if lab is not None else None, s["lab"] if lab is not None else None,
@@ -377,6 +429,16 @@ class DevicePrefetcher:
             s["ready"].record(cs)
         s["meta"], s["has_lab"], s["used"] = meta, lab is not None, True
         self.filled += 1
+
+    def _crop(self, s, img_ptrs, lab_ptrs, has_lab, meta, cs):
+        """Scale-crop mode: the batch out of B source frames on the device, on the copy stream -- one simt_scale_crop at the window drawn,
+        or, with rare-class crops, counts, pick and simt_scale_crop_win over the K windows drawn."""
+        if self.rare is None:
+            return self.prep.scale_crop_batch(img_ptrs, lab_ptrs, self.draw_fn(self.prep.B), s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+        if not has_lab:
+            raise ValueError("rare-class crops: a batch without labels has no class to count")
+        self.prep.rare_crop_batch(img_ptrs, lab_ptrs, self.draw_fn(self.prep.B), meta[2], self.rare[1], s["x"], s["lab"], s["parts"], s["win"],
+                                  cs.cuda_stream)
 
     def _mix(self, s, has_lab, cs):
         """Class-mix mode: the slot's finished batch x / lab -> xm / labm, on the copy stream, behind the launches that made it."""
@@ -443,7 +505,7 @@ class DevicePrefetcher:
                 else:
                     prep.resize_into(s["rgb_d"][:M], s["lab_d"][:M] if has_lab else None, dests, cs.cuda_stream)
             if self.draw_fn is not None:
-                prep.scale_crop_batch(img_ptrs, lab_ptrs, self.draw_fn(prep.B), s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
+                self._crop(s, img_ptrs, lab_ptrs, has_lab, meta, cs)
             else:
                 mirror = self.mirror_fn(prep.B) if self.mirror_fn is not None else False
                 prep.gather(img_ptrs, lab_ptrs, mirror, s["x"], s["lab"] if has_lab else None, cs.cuda_stream)
@@ -474,6 +536,7 @@ class DevicePrefetcher:
             out = (s["xk"], out[1], out[2])
         if self.teacher_view:              # the weak view: what this slot would have handed out without the mix, the photometric step and the mask
             out = out + (s["x"], s.get("item"))
+        self.last_win = s.get("win")
         self.filled -= 1
         self.calls += 1
         self.head = (i + 1) % len(self.slots)
@@ -556,7 +619,16 @@ class GpuLoader:
 
     dataset.teacher_view = True (--weak-teacher) needs one of the three above and hands out both views: (strong image, labels, sizes,
     names, weak image, item map | None) -- the weak image is the batch of the loader without class-mix, photometric and patch mask, bit for
-    bit, the item map ([B,h,w] u8, None without class-mix) names the item each pixel of the strong view was taken from.  Not one draw changes."""
+    bit, the item map ([B,h,w] u8, None without class-mix) names the item each pixel of the strong view was taken from.  Not one draw changes.
+
+    dataset.rare_class = a rare_class.RareClass (GTA5DataSet(rare_class=...), --rare-class-sampling) turns on DAFormer's rare-class
+    sampling (simt_amd/data/rare_class.py).  `_order` is not used: batch n's items are the n-th rare_class.draw_batch of
+    rare_class.generator(seed, rank) -- a class by softmax((1 - f) / T), then a frame that holds it -- so every rank draws its own batches
+    and there is no shard; an "epoch" keeps its length (loader_position) for start_batch, on_epoch and epochs=, the decode look-ahead and
+    the cache work unchanged (a repeated item is a hit).  With dataset.scale_crop the loader's generator draws K candidate windows per item
+    (scale_crop.draw_batch_candidates) and the copy stream counts the item's class in each, picks the first that holds more than
+    min_count pixels (else the last) and crops there (InputPrep.rare_crop_batch): nothing is read back; last_windows() names the slot's
+    `win` words for logging.  Without scale_crop the sampler is all there is.  start_batch skips both generators' draws."""
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, device="cuda:0", seed=1234, rank=0, world=1, epochs=None,
                  hold=1, cache=None, on_epoch=None, start_batch=0):
@@ -589,6 +661,12 @@ class GpuLoader:
         if self.teacher_view and self.class_mix is None and self.photometric is None and self.patch_mask is None:
             raise ValueError("dataset.teacher_view needs dataset.class_mix, dataset.photometric or dataset.patch_mask (--weak-teacher needs "
                              "--class-mix, --colour-jitter or --gaussian-blur, or --mask-patches): without them the two views are the same batch")
+        self.rare_class = getattr(dataset, "rare_class", None)
+        self._rcs_rng, self._pf = None, None
+        if self.rare_class is not None:
+            if self.rare_class.counts.shape[0] != len(dataset):
+                raise ValueError(f"rare-class statistics of {self.rare_class.counts.shape[0]} items for a dataset of {len(dataset)}")
+            self._rcs_rng = rc.skip_draws(rc.generator(seed, rank), batch_size, int(start_batch))
         self._src_hw = None         # the geometry of the first frame decoded: every other one must have it
         if cache is not None and self.scale_crop is None:
             assert (cache.w, cache.h) == tuple(dataset.crop_size), "the cache holds frames of ONE crop"
@@ -597,7 +675,8 @@ class GpuLoader:
         self.start_batch = int(start_batch)
         self._epoch0, self._batch0, _ = loader_position(len(dataset), batch_size, rank, world, self.start_batch)
         if self.start_batch and self.scale_crop is not None:
-            sc.skip_scale_crop_draws(self._rng, batch_size, self.start_batch, len(self.scale_crop), bool(getattr(dataset, "is_mirror", False)))
+            sc.skip_scale_crop_draws(self._rng, batch_size, self.start_batch, len(self.scale_crop), bool(getattr(dataset, "is_mirror", False)),
+                                     candidates=None if self.rare_class is None else self.rare_class.K)
         elif self.start_batch and getattr(dataset, "is_mirror", False):
             skip_mirror_draws(self._rng, batch_size, self.start_batch)
 
@@ -620,11 +699,27 @@ class GpuLoader:
             idx = list(range(n))
         return idx[self.rank::self.world]               # data parallel: disjoint strided shards of one global order
 
+    def _epoch_items(self, epoch, b0):
+        """-> (item indices, classes | None) of epoch `epoch`, batch b at [b * B, (b + 1) * B); the batches before b0 are never read.
+        With rare-class sampling the epoch's batches from b0 on are the sampler's next draws (None stands for the skipped ones)."""
+        if self.rare_class is None:
+            return self._order(epoch), None
+        nb = loader_position(len(self.ds), self.B, self.rank, self.world, 0)[2]
+        idx, cls = [None] * (b0 * self.B), [None] * (b0 * self.B)
+        for _ in range(b0, nb):
+            c, i = rc.draw_batch(self._rcs_rng, self.B, self.rare_class.cdf, self.rare_class.lists)
+            idx += i
+            cls += c
+        return idx, cls
+
+    def _meta(self, sizes, names, cls, b):
+        return (sizes, names) if cls is None else (sizes, names, cls[b * self.B:(b + 1) * self.B])
+
     def _host_batches(self):
         epoch, b0 = self._epoch0, self._batch0         # (start_batch: the first epoch begins at its batch b0)
         with ThreadPoolExecutor(self.workers) as pool:
             while self.epochs is None or epoch < self.epochs:
-                idx = self._order(epoch)
+                idx, cls = self._epoch_items(epoch, b0)
                 nb = len(idx) // self.B
                 pending = [pool.map(self.ds.decode, idx[b * self.B:(b + 1) * self.B]) for b in range(b0, min(b0 + 2, nb))]
                 for b in range(b0, nb):
@@ -635,7 +730,7 @@ class GpuLoader:
                     rgb = np.stack([it[0] for it in items])
                     lab = np.stack([it[1] for it in items]) if items[0][1] is not None else None
                     sizes = np.stack([np.array([self.ds.crop_size[1], self.ds.crop_size[0], 3]) for _ in items])
-                    yield rgb, lab, (sizes, [it[2] for it in items])
+                    yield rgb, lab, self._meta(sizes, [it[2] for it in items], cls, b)
                 epoch, b0 = epoch + 1, 0
 
     def _host_batches_cached(self):
@@ -661,7 +756,7 @@ class GpuLoader:
 
         with ThreadPoolExecutor(self.workers) as pool:
             while self.epochs is None or epoch < self.epochs:
-                idx = self._order(epoch)
+                idx, cls = self._epoch_items(epoch, b0)
                 nb = len(idx) // self.B
                 h0, m0 = cache.hits, cache.misses
                 pending = [plan(pool, idx[b * self.B:(b + 1) * self.B]) for b in range(b0, min(b0 + 2, nb))]
@@ -678,7 +773,7 @@ class GpuLoader:
                     for slot, fut, _i in entries:
                         where.append((slot, m if fut is not None else None))
                         m += fut is not None
-                    yield rgb, lab, ((sizes, [ds.files[i]["name"] for (_s, _f, i) in entries]), where)
+                    yield rgb, lab, (self._meta(sizes, [ds.files[i]["name"] for (_s, _f, i) in entries], cls, b), where)
                 if self.on_epoch is not None:
                     self.on_epoch(epoch, cache.hits - h0, cache.misses - m0, cache.bytes)
                 epoch, b0 = epoch + 1, 0
@@ -709,6 +804,8 @@ class GpuLoader:
         if self.scale_crop is not None:
             mirror_on = bool(getattr(self.ds, "is_mirror", False))
             draw_fn = lambda n: sc.draw_batch(self._rng, n, self.scale_crop, tuple(self.ds.crop_size), mirror_on)
+            if self.rare_class is not None:
+                draw_fn = lambda n: sc.draw_batch_candidates(self._rng, n, self.rare_class.K, self.scale_crop, tuple(self.ds.crop_size), mirror_on)
         mix_fn = None
         if self.class_mix is not None:
             mix_fn = lambda n: cm.draw_batch(self._mix_rng, n, *self.class_mix)
@@ -719,7 +816,14 @@ class GpuLoader:
         if self.patch_mask is not None:
             mask_fn = lambda n: pm.draw_batch(self._mask_rng, n, self.patch_mask[2], self.patch_mask[3], self.patch_mask[1])
         pf = DevicePrefetcher(chain(), self._prep, mirror_fn=mirror_fn, hold=self.hold, cache=self.cache, draw_fn=draw_fn, mix_fn=mix_fn,
-                              photo_fn=photo_fn, teacher_view=self.teacher_view, mask_fn=mask_fn)
+                              photo_fn=photo_fn, teacher_view=self.teacher_view, mask_fn=mask_fn,
+                              rare=None if self.rare_class is None or draw_fn is None else (self.rare_class.K, self.rare_class.min_count))
+        self._pf = pf
         if self.teacher_view:
             return ((x, lab, meta[0], meta[1], xw, item) for (x, lab, meta, xw, item) in pf)
         return ((x, lab, meta[0], meta[1]) for (x, lab, meta) in pf)
+
+    def last_windows(self):
+        """Rare-class crops: the `win` words (int32 [B, 4] on the device: choice, ox, oy, count) of the batch handed out last, valid as long
+        as that batch; None without them.  For logging: reading it synchronises, so read it where the consumer synchronises anyway."""
+        return None if self._pf is None else self._pf.last_win

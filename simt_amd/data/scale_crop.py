@@ -8,7 +8,8 @@ smaller one (0.0 = the mean / label 255 around it).  The choices are DECIMAL TEX
 
 Draws come from the loader's generator, per batch, in a fixed order and number (so a resumed loader can skip them without knowing them):
 the mirror draw as ever (`integers(0, 2, B)`, only when mirroring is on), then `integers(0, n_choices, B)`, `random(B)` for x, `random(B)`
-for y.
+for y.  With rare-class crops (simt_amd/data/rare_class.py) the last three have shape (B, K): K candidate windows per item, one of which
+the device picks.
 """
 import math
 from fractions import Fraction
@@ -66,15 +67,29 @@ def draw_batch(rng, batch_size, choices, crop_wh, mirror):
     return flags, pick, ox, oy
 
 
-def skip_scale_crop_draws(rng, batch_size, n_batches, n_choices, mirror):
+def draw_batch_candidates(rng, batch_size, n_cand, choices, crop_wh, mirror):
+    """One batch's draws with K = n_cand candidate windows per item (rare-class crops, simt_amd/data/rare_class.py) -> (mirror flags [B],
+    choice index [B][K], ox [B][K], oy [B][K]) as lists: the mirror draw as ever, then `integers(0, n_choices, (B, K))`, `random((B, K))`
+    for x, `random((B, K))` for y."""
+    flags = (rng.integers(0, 2, batch_size) == 0).tolist() if mirror else [False] * batch_size
+    pick = rng.integers(0, len(choices), (batch_size, n_cand)).tolist()
+    ux, uy = rng.random((batch_size, n_cand)), rng.random((batch_size, n_cand))
+    w, h = crop_wh
+    ox = [[origin(float(ux[b, k]), *origin_range(scaled_size(w, choices[pick[b][k]]), w)) for k in range(n_cand)] for b in range(batch_size)]
+    oy = [[origin(float(uy[b, k]), *origin_range(scaled_size(h, choices[pick[b][k]]), h)) for k in range(n_cand)] for b in range(batch_size)]
+    return flags, pick, ox, oy
+
+
+def skip_scale_crop_draws(rng, batch_size, n_batches, n_choices, mirror, candidates=None):
     """Advance the loader's generator by the draws `n_batches` batches make with scale-crop on (skip_mirror_draws' sibling): the
-    number of draws does not depend on their values."""
+    number of draws does not depend on their values.  candidates = K: the draws of draw_batch_candidates."""
+    shape = batch_size if candidates is None else (batch_size, int(candidates))
     for _ in range(n_batches):
         if mirror:
             rng.integers(0, 2, batch_size)
-        rng.integers(0, n_choices, batch_size)
-        rng.random(batch_size)
-        rng.random(batch_size)
+        rng.integers(0, n_choices, shape)
+        rng.random(shape)
+        rng.random(shape)
     return rng
 
 

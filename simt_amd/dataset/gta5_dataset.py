@@ -30,10 +30,12 @@ class GTA5DataSet(_Base):
     """Image + ground-truth label of the GTA5 set, labels as train ids."""
 
     def __init__(self, root, list_path, max_iters=None, crop_size=(321, 321), mean=(128, 128, 128), scale=True, mirror=True, ignore_label=255,
-                 scale_crop=None):
+                 scale_crop=None, rare_class=None):
         super().__init__(root, list_path, max_iters, crop_size, mean, scale, mirror, ignore_label)
         # decimal scale choices or None: GpuLoader's random scale + crop (simt_amd/data/scale_crop.py); `scale` is stored and never read
         self.scale_crop = None if scale_crop is None else tuple(str(c) for c in scale_crop)
+        # a simt_amd.data.rare_class.RareClass or None: GpuLoader's rare-class sampling (which frame; with scale_crop, which window)
+        self.rare_class = rare_class
         self.id_to_trainid = dict(ID_TO_TRAINID)
         self._table = trainid_table(ignore_label)
         self.img_ids = self._repeat([i_id.strip() for i_id in open(list_path) if i_id.strip()], max_iters)

@@ -34,6 +34,12 @@ through a second loader at --input-size-target with a seed of its own derived fr
 the target-side augmentations, and is not cached.  With --online-mix the mix is the cross-domain one: half of the classes of source image i are
 pasted, image and ground truth, onto target image i (simt_source_mix); with --online-labels-weighted a pasted pixel has weight 1.  The loss line
 gains ` src = <loss_seg2 of the source pass>`; --train-state resumes both loaders at the same batch and refuses the flag added or dropped.
+--rare-class-sampling [T] (needs --online-source and --rcs-stats FILE): DAFormer's sampler for the source batch -- a class is drawn
+with probability softmax((1 - f) / T) of the class frequencies (no value: T = 0.01), then a frame with at least --rcs-min-pixels N (3000) pixels of
+it; FILE comes from `python -m simt_amd.tools.compute_class_stats`.  With --scale-crop --rcs-crops K (10) candidate windows are drawn per item and
+the first that shows more than floor(N * --rcs-min-crop-ratio R (0.5)) pixels of the class is taken, the last when none does: counted, picked and
+cropped on the copy stream, nothing read back; the loss line gains ` rcs = <share of the source items whose window met the bar>`.  One start-up
+line gives the class probabilities and the frames per class.  --train-state refuses the flag added, dropped or changed.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -163,6 +169,13 @@ def source_text(args, l):
     return " src = {0:.3f}".format(l["source_seg2"]) if getattr(args, "online_source", False) else ""
 
 
+def rcs_text(source):
+    """` rcs = <share>` of the loss line, the share of the source items since the last line whose chosen window met the bar: only with
+    --rare-class-sampling and --scale-crop (read behind tr.losses(), which has synchronised)."""
+    share = source.rcs_share() if hasattr(source, "rcs_share") else None
+    return "" if share is None else " rcs = {0:.3f}".format(share)
+
+
 def balanced_kwargs(args):
     """The trainers' keywords of --online-labels-balanced / --online-labels-momentum, and of --online-mix (seeded by --random-seed),
     --online-labels-weighted and --online-source when on."""
@@ -247,7 +260,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -338,7 +351,7 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

@@ -355,7 +355,8 @@ def _online_mix(text):
 
 def add_online_label_args(p):
     """--online-labels / --online-labels-every, --online-labels-balanced / --online-labels-momentum (7.17), --online-mix (7.18),
-    --online-labels-weighted (7.19) and --online-source (7.20) of trainV1_warmup; `check_online_label_args` holds their refusals."""
+    --online-labels-weighted (7.19), --online-source (7.20) and --rare-class-sampling / --rcs-* (7.21) of trainV1_warmup;
+    `check_online_label_args` holds their refusals."""
     from simt_amd.online_labels import DEFAULT_PORTION, DEFAULT_THRESHOLD
     p.add_argument("--online-labels", type=_online_threshold, nargs="?", const=DEFAULT_THRESHOLD, default=None, metavar="T",
                    help="train on a teacher's labels instead of label files (simt_amd/online_labels.py): a frozen copy of the start model "
@@ -390,6 +391,29 @@ def add_online_label_args(p):
                         "optimiser step; with --online-mix half of a source image's classes are pasted, image and ground truth, onto the target "
                         "image, and with --online-labels-weighted a pasted pixel has weight 1.  The source loader honours --random-mirror and "
                         "--scale-crop only.  Default: off")
+    p.add_argument("--rare-class-sampling", nargs="?", const="0.01", default=None, metavar="T",
+                   help="with --online-source: DAFormer's rare-class sampling of the source batch (simt_amd/data/rare_class.py; DESIGN 7.21) -- "
+                        "a class is drawn with probability softmax((1 - f) / T) of the class frequencies f (no value: T = 0.01), then a frame "
+                        "that holds it; with --scale-crop K candidate windows are drawn per item and the first that shows enough of the class "
+                        "is taken, counted and picked on the device.  Needs --rcs-stats (simt_amd.tools.compute_class_stats).  Default: off")
+    p.add_argument("--rcs-stats", type=str, default=None, metavar="FILE", help="the per-frame class statistics of --data-list")
+    p.add_argument("--rcs-min-pixels", default=None, metavar="N",
+                   help="a frame holds a class when it has at least N pixels of it, at full size.  Default: 3000")
+    p.add_argument("--rcs-min-crop-ratio", default=None, metavar="R",
+                   help="a window is taken when it shows more than floor(N * R) pixels of the class (0 <= R <= 1).  Default: 0.5")
+    p.add_argument("--rcs-crops", default=None, metavar="K", help="candidate windows per item, 1 to 16.  Default: 10")
+
+
+RCS_DEFAULTS = {"rcs_min_pixels": "3000", "rcs_min_crop_ratio": "0.5", "rcs_crops": "10"}
+
+
+def rare_class_setting(args):
+    """-> (T, min_pixels, ratio text, K, min_count) of --rare-class-sampling and the --rcs-* flags (rare_class.parse), or None when off."""
+    if getattr(args, "rare_class_sampling", None) is None:
+        return None
+    from simt_amd.data.rare_class import parse
+    v = {k: (d if getattr(args, k, None) is None else getattr(args, k)) for k, d in RCS_DEFAULTS.items()}
+    return parse(args.rare_class_sampling, v["rcs_min_pixels"], v["rcs_min_crop_ratio"], v["rcs_crops"])
 
 
 def check_online_label_args(p, args):
@@ -420,6 +444,19 @@ def check_online_label_args(p, args):
             p.error(f"--online-labels-weighted with --batch-size {args.batch_size}: the label launch counts at most {MAX_WEIGHTED_ITEMS} items")
     if getattr(args, "online_source", False) and args.online_labels is None:
         p.error("--online-source needs --online-labels: the source batch is trained beside a target batch that a teacher labels")
+    if getattr(args, "rare_class_sampling", None) is None:
+        for flag in ("rcs_stats",) + tuple(RCS_DEFAULTS):
+            if getattr(args, flag, None) is not None:
+                p.error(f"--{flag.replace('_', '-')} needs --rare-class-sampling: it sets the sampler")
+    else:
+        if not getattr(args, "online_source", False):
+            p.error("--rare-class-sampling needs --online-source: it samples the labelled source batch")
+        try:
+            rare_class_setting(args)
+        except ValueError as e:
+            p.error(str(e))
+        if not args.synthetic and not args.rcs_stats:
+            p.error("--rare-class-sampling needs --rcs-stats FILE (python -m simt_amd.tools.compute_class_stats), or --synthetic")
     if getattr(args, "online_mix", None) is not None:
         from simt_amd.data.class_mix import MAX_CLASSES, MAX_ITEMS
         if args.online_labels is None:
@@ -666,7 +703,7 @@ class EmaSnapshots:
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
                 "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
-                "online_source": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_source": False, "rare_class_sampling": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -703,6 +740,11 @@ def run_identity(args, class_dist):
             ident["online_source"] = True
             if not args.synthetic and osp.isfile(args.data_list):
                 ident["source_list_sha256"] = hashlib.sha256(open(args.data_list, "rb").read()).hexdigest()
+            rcs = rare_class_setting(args)
+            if rcs is not None:                                          # [T, min-pixels, ratio, K, the statistics file's SHA-256 | None]
+                stats = getattr(args, "rcs_stats", None)
+                sha = hashlib.sha256(open(stats, "rb").read()).hexdigest() if not args.synthetic and stats and osp.isfile(stats) else None
+                ident["rare_class_sampling"] = [rcs[0], rcs[1], rcs[2], rcs[3], sha]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
@@ -871,12 +913,52 @@ def batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
 SOURCE_SEED_OFFSET = 0x5372      # "Sr": the source loader's seed is --random-seed + this (order, mirror and scale-crop draws of its own)
 
 
+class SourceStream:
+    """The source loader's batches as (image, label) pairs, and, with rare-class crops, the share of items whose chosen window met the bar:
+    every batch adds its count to a device word on the consumer's stream (no synchronisation); `rcs_share()` reads and clears it -- call it
+    where the loop has synchronised anyway (behind tr.losses())."""
+
+    def __init__(self, loader, min_count=None):
+        self.loader, self.it, self.min_count = loader, iter(loader), min_count
+        self.acc, self.n = None, 0
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        img, lab = next(self.it)[:2]
+        win = self.loader.last_windows() if self.min_count is not None else None
+        if win is not None:
+            if self.acc is None:
+                self.acc = torch.zeros((), dtype=torch.int64, device=win.device)
+            self.acc += (win[:, 3] > self.min_count).sum()
+            self.n += win.shape[0]
+        return img, lab
+
+    def rcs_share(self):
+        """-> the share since the last call, or None (no rare-class crops, or no batch since)."""
+        if self.acc is None or self.n == 0:
+            return None
+        v = int(self.acc.item()) / self.n
+        self.acc.zero_()
+        self.n = 0
+        return v
+
+
+def rare_class_line(rc):
+    """One start-up line: the class probabilities and the number of frames per class."""
+    print(f"rare-class sampling: T = {rc.T}, a frame holds a class with >= {rc.min_pixels} pixels; P(class) = "
+          f"[{', '.join(f'{p:.4f}' for p in rc.probs)}]; frames per class = [{', '.join(str(len(l)) for l in rc.lists)}]; "
+          f"with --scale-crop the first of {rc.K} windows with more than {rc.min_count} pixels of the class is taken")
+
+
 def source_batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     """--online-source: -> iterator of (source image f32 [B,3,H,W], source label i64 [B,H,W]) resident on the device, from this rank's
     batch number `start_batch` on -- the position of `batches`, so a resumed run continues both loaders together.  A second GpuLoader over
     GTA5DataSet(--data-dir, --data-list) at the target's size (the plan has one geometry), seeded by --random-seed + SOURCE_SEED_OFFSET; it
     honours --random-mirror and --scale-crop and none of the target-side augmentations, and is not cached.  --synthetic: labelled
-    synthetic batches from the same seed."""
+    synthetic batches from the same seed.  --rare-class-sampling: the loader samples by simt_amd/data/rare_class.py (one start-up line says
+    how); the result is a SourceStream, whose rcs_share() feeds the loss line."""
     seed = args.random_seed + SOURCE_SEED_OFFSET
     if args.synthetic:
         def synth():
@@ -893,9 +975,18 @@ def source_batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     from simt_amd.dataset.gta5_dataset import GTA5DataSet
     ds = GTA5DataSet(args.data_dir, args.data_list, crop_size=(W, H), scale=False, mirror=args.random_mirror, mean=IMG_MEAN,
                      scale_crop=scale_crop_choices(args))
+    rcs = rare_class_setting(args)
+    if rcs is not None:
+        from simt_amd.data import rare_class
+        try:
+            ds.rare_class = rare_class.RareClass(rare_class.load_stats(args.rcs_stats, ds), rcs[0], rcs[1], rcs[2], rcs[3])
+        except (OSError, ValueError, KeyError) as e:
+            raise SystemExit(f"--rcs-stats: {e}")
+        if rank == 0:
+            rare_class_line(ds.rare_class)
     loader = GpuLoader(ds, B, shuffle=True, num_workers=args.num_workers, device=dev, seed=seed, rank=rank, world=world,
                        hold=max(1, getattr(args, "iter_size", 1)), start_batch=start_batch)
-    return ((img, lab) for (img, lab, _sizes, _names) in loader)
+    return SourceStream(loader, ds.rare_class.min_count if rcs is not None and ds.scale_crop is not None else None)
 
 
 def shutdown(world):
