@@ -1,5 +1,5 @@
 // MIC patch masking (Hoyer et al., CVPR'23) of a finished batch (simt_amd/data/patch_mask.py): the square patches the row words name become
-// +0.0f -- the mean colour of a batch that holds colour - mean -- in all three planes.  Pure selection, like class_mix_kernel: a kept value
+// +0.0f -- the mean colour of a batch that holds colour - mean -- in all three planes.  Pure selection, like mix_sweep_kernel: a kept value
 // travels as an integer word.  One streaming kernel, descriptor by value in the kernel-argument segment:
 //   patch_mask_kernel<VEC, INPLACE>   grid (ceil(h / 4), B), 256 lanes: wave v of workgroup (g, i) owns pixel row y = 4 g + v of item i in all
 //                                     three planes.  Its patch row y / patch is wave-uniform, so the mask word rows[i][y / patch] is ONE scalar

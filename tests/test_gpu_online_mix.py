@@ -287,7 +287,8 @@ def _existing_mix(x, lab64, apply, rank, Cn, dev):
 MIX_CASES = [(2, 8, 12, 19, 1, "all"), (2, 8, 12, 19, 3, "none"), (3, 8, 12, 19, 70, "mixed"),          # h * w % 4 == 0: the 16-byte flavour
              (2, 7, 9, 19, 5, "all"), (3, 7, 9, 19, 64, "mixed"), (2, 7, 9, 1, 2, "all"),                # h * w % 4 == 3: the scalar flavour and its tail
              (32, 6, 10, 32, 1024, "mixed"), (32, 5, 5, 32, 65, "mixed"),                                # B = 32, C = 32, the most rows
-             (2, 72, 64, 19, 512, "all"), (4, 67, 65, 7, 9, "mixed")]                                    # more than one workgroup per item
+             (2, 72, 64, 19, 512, "all"), (4, 67, 65, 7, 9, "mixed"),                                    # more than one workgroup per item
+             (3, 33, 37, 19, 7, "mixed")]                                                                # 305 quads + 1 pixel: the tail lane in a lane's SECOND quad round
 
 
 @pytest.mark.parametrize("case", MIX_CASES, ids=lambda c: "B{}-{}x{}-C{}-rows{}-{}".format(*c))
