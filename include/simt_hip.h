@@ -1023,6 +1023,60 @@ typedef struct {
 } simt_patch_mask_desc;
 int simt_patch_mask(const simt_patch_mask_desc* d, simt_stream_t stream);
 
+/* ---- DAFormer's thing-class ImageNet feature distance (simt_amd/feat_dist.py; csrc/feat_dist.hip) ---------------------------------
+ * The pass that trains on ground-truth labels adds  lambda * mean over kept cells m of || fs[m, :] - fi[m, :] ||_2 : fs [M][C] is the student's
+ * layer-4 output (train-mode forward), fi [M][C] that of a frozen eval-mode trunk with ImageNet weights, M = B * h * w.  Three launches; the
+ * gradient with respect to fs (`seed`) enters the backward as the `res` of the layer-4 head's input-gradient launch.
+ * CONTRACT (tests/_feat_dist_ref.py is its numpy / float64 restatement).
+ *   CELLS.  Cell (i, j) of item b, 0 <= i < h, 0 <= j < w, owns the label pixels of rows [(i*H)/h, ((i+1)*H)/h) and columns
+ *     [(j*W)/w, ((j+1)*W)/w) (integer division); h <= H and w <= W, so no window is empty and the windows partition the label.  n = the pixels
+ *     of the window.  Where H = s*h and W = s*w these are the s x s blocks of DAFormer's downscale_label_ratio.
+ *   KEPT.  mask[cell] = 1 iff some class c with bit c of `classes` set has  (float)count_c >= min_ratio * (float)n  in binary32 with ONE
+ *     multiply, count_c = the window pixels whose int64 label == c; else 0.  A label that is 255, negative or >= 64 matches no class and counts
+ *     against the ratio.  0.5 < min_ratio <= 1: at most one class qualifies.  part[g] = the kept cells of workgroup g (plain store; the buffer
+ *     holds simt_feat_dist_mask_parts(B, h, w) words); N = their sum.
+ *   DISTANCE of a kept row:  diff_c = (float)fs[c] - (float)fi[c];  s = sum_c diff_c * diff_c in binary32 in a FIXED order (lane-local in
+ *     element order, then the wave's xor butterfly);  d = sqrtf(s).  No atomics: a launch repeats bit for bit.
+ *   SEED, in the features' dtype:  a kept row with d > 0:  seed[m][c] = round(((lam_g / (float)N) / d) * diff_c);  any other row (not kept, or
+ *     d == 0, or d NaN): +0 in every column.  Rows that are not kept are never read from fs or fi.  EVERY row of seed is written by every
+ *     launch: no memset is ever needed.  d[m] = the distance of a kept row, 0 elsewhere.  lam_g = (float)(lambda * gscale), gscale as in
+ *     simt_head_desc.
+ *   SCALARS (simt_feat_dist_finalize):  S = the sum over workgroups, in double and in index order, of the launch's per-workgroup binary32
+ *     sums of d (simt_feat_dist_parts(M) of them);  out[0] = lambda * S / N, out[1] = S / N, out[2] = (float)N.  N == 0: all three are 0 and
+ *     the seed is all +0 (torch's mean over an empty selection is NaN: a departure).
+ * Refused with SIMT_ERR_INVALID, no launch and nothing written: a NULL descriptor or pointer; B, H, W, h or w < 1; h > H or w > W;
+ * min_ratio outside (0.5, 1] or NaN; H * W or B * h * w >= 2^31; a label base that is not 8-byte aligned; (main pass, finalize) M < 1,
+ * C < 8 or C % 8 != 0, ld != C, a dtype code other than SIMT_F32 / SIMT_BF16, n_kept_part < 1, fs / fi / seed not 16-byte aligned, a NaN
+ * lam_g or lambda.  No LDS beyond 4 words per workgroup, no scratch, no atomics. */
+typedef struct {
+  const int64_t* label;    /* [B][H][W] */
+  uint8_t* mask;           /* out [B*h*w] */
+  int32_t* part;           /* out [simt_feat_dist_mask_parts(B, h, w)]: kept cells per workgroup */
+  uint64_t classes;        /* bit c: class c is a thing class */
+  int32_t B, H, W, h, w;
+  float min_ratio;
+} simt_feat_dist_mask_desc;
+typedef struct {
+  const void* fs;          /* [M][C] student features, dtype */
+  const void* fi;          /* [M][C] ImageNet features, dtype */
+  const uint8_t* mask;     /* [M] of simt_feat_dist_mask */
+  const int32_t* kept_part;/* [n_kept_part] of simt_feat_dist_mask */
+  void* seed;              /* out [M][C], dtype */
+  float* d;                /* out [M] */
+  float* part;             /* out [simt_feat_dist_parts(M)]: sum of d per workgroup */
+  float* out;              /* out [3], written by simt_feat_dist_finalize */
+  double lambda;
+  int64_t M;
+  int32_t C, ld, dtype, n_kept_part;
+  float lam_g;             /* (float)(lambda * gscale) */
+  int32_t reserved_;
+} simt_feat_dist_desc;
+int simt_feat_dist_mask_parts(int B, int h, int w);       /* 0: a geometry the launch refuses */
+int simt_feat_dist_parts(long M);
+int simt_feat_dist_mask(const simt_feat_dist_mask_desc* d, simt_stream_t stream);
+int simt_feat_dist(const simt_feat_dist_desc* d, simt_stream_t stream);
+int simt_feat_dist_finalize(const simt_feat_dist_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

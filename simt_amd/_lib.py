@@ -288,6 +288,19 @@ class TtaDesc(C.Structure):
                 ("thr", c_p), ("pred", c_p), ("out", c_p), ("counts", c_p), ("hist", c_p)]
 
 
+class FeatDistMaskDesc(C.Structure):
+    """simt_feat_dist_mask_desc (include/simt_hip.h): int64 labels -> the byte map of the kept feature cells and their count per workgroup."""
+    _fields_ = [("label", c_p), ("mask", c_p), ("part", c_p), ("classes", C.c_uint64), ("B", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32),
+                ("min_ratio", f32)]
+
+
+class FeatDistDesc(C.Structure):
+    """simt_feat_dist_desc (include/simt_hip.h): two layer-4 maps and the mask -> distances, their gradient (the seed) and three scalars."""
+    _fields_ = [("fs", c_p), ("fi", c_p), ("mask", c_p), ("kept_part", c_p), ("seed", c_p), ("d", c_p), ("part", c_p), ("out", c_p),
+                ("lam", C.c_double), ("M", C.c_int64), ("C", i32), ("ld", i32), ("dtype", i32), ("n_kept_part", i32), ("lam_g", f32),
+                ("reserved_", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -408,6 +421,11 @@ SIGNATURES = {
     "simt_rare_crop_counts": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_rare_crop_pick": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_scale_crop_win": (_I, [C.POINTER(RareCropDesc), c_p]),
+    "simt_feat_dist_mask_parts": (_I, [_I, _I, _I]),
+    "simt_feat_dist_parts": (_I, [_L]),
+    "simt_feat_dist_mask": (_I, [C.POINTER(FeatDistMaskDesc), c_p]),
+    "simt_feat_dist": (_I, [C.POINTER(FeatDistDesc), c_p]),
+    "simt_feat_dist_finalize": (_I, [C.POINTER(FeatDistDesc), c_p]),
 }
 
 _lib = None

@@ -303,8 +303,15 @@ class TrunkPlan:
     """
 
     def __init__(self, params, B, H, W, heads, *, dtype=torch.bfloat16, train=True, layers=LAYERS, device=None,
-                 need_input_grads=True, grad_names=None, grads_from_layer=0, stem_from=None, data_parallel=False):
+                 need_input_grads=True, grad_names=None, grads_from_layer=0, stem_from=None, data_parallel=False, feat_grad_seed=False):
         self.p = params
+        # feat_grad_seed (train plans): a gradient with respect to the LAST layer's output that comes from outside the heads (the
+        # feature distance).  `feat_seed` [Mo, c4] is the `res` of the input-gradient launch of that layer's first head -- the launch that starts
+        # the chain of dz, whose `res` is NULL without the keyword; use_feat_seed() switches it between passes.  Off: the plan it was.
+        if feat_grad_seed and not train:
+            raise ValueError("feat_grad_seed needs a train plan: an eval plan has no backward to seed")
+        self.feat_grad_seed = bool(feat_grad_seed)
+        self.feat_seed = self.feat_seed_desc = None
         self.B, self.H, self.W = B, H, W
         self.heads = heads
         self.dtype = dtype
@@ -1066,7 +1073,12 @@ class TrunkPlan:
                 for hi, hd in enumerate(hds):
                     # the LAST head GEMM of this layer produces the block's final dz: reduce for its bn3 backward there
                     bnr = self._bnr(f"{name}.bn3", rec["y3"], 3, bits=rec["zbits"]) if (hi == len(hds) - 1 and not down) else None
+                    seeded = self.feat_grad_seed and dz is None and bi == n_blocks - 1
+                    if seeded:      # (zeroed: a backward before the first feature-distance launch adds nothing)
+                        dz = self.feat_seed = self.new(Mo, c4, zero=True)
                     dz = self._build_head_bwd(hd, dz, Mo, c4, bi, bnr=bnr)
+                    if seeded:
+                        self.feat_seed_desc = self._head_dgrad_desc
                     pending_bn3 = self._head_bnr_nblk
             assert dz is not None, "no gradient reaches the last block (a head must sit on the last layer)"
             blk_start = len(b)
@@ -1263,6 +1275,7 @@ class TrunkPlan:
                              taps=[(-a, -c) for (a, c) in hd.taps], res=dz_prev, alg_k=len(hd.taps) * hd.Q,
                              mask=getattr(hd, "mask", None), bnr=bnr)
             self._head_bnr_nblk = self._fused_nblk(dsc, bnr)
+            self._head_dgrad_desc = dsc
             return dfeat
         # ---- tap-expanded backward: G[m'][t*QP+n] = dlogits[m' - d_t][n]; dW = G^T x feat; dfeat = G x Wt (+ dz_prev)
         nt, QP, nexp = len(hd.taps), hd.QP, hd.nexp
@@ -1307,7 +1320,16 @@ class TrunkPlan:
                          taps=[(0, 0)], res=dz_prev, alg_k=nt * hd.Q, mask=getattr(hd, "mask", None), bnr=bnr,
                          note=" (tap-expanded head)")
         self._head_bnr_nblk = self._fused_nblk(dsc, bnr)
+        self._head_dgrad_desc = dsc
         return dfeat
+
+    def use_feat_seed(self, on):
+        """feat_grad_seed plans: the next backward adds `feat_seed` to the gradient of the last layer's output (on), or is the backward of a
+        plan without the keyword (off: `res` NULL, the buffer is not read).  A host write into the launch's descriptor, which is read at every
+        launch: call it between passes, in front of backward()."""
+        if self.feat_seed_desc is None:
+            raise ValueError("use_feat_seed needs a plan built with feat_grad_seed=True")
+        self.feat_seed_desc.res = self.feat_seed.data_ptr() if on else None
 
     # ------------------------------------------------------------------ run
     def forward(self, x_nchw=None):

@@ -32,6 +32,32 @@ def vgg16_to_deeplab_vgg(sd):
     return out
 
 
+DEEPLAB_HEADS = ("layer5", "layer6", "layer5_1", "layer6_1")      # DeeplabMulti's classifier modules
+
+
+def imagenet_trunk(sd, shapes):
+    """The frozen ImageNet trunk of the feature distance (--feat-dist-from) -> (layout name, {trunk key: tensor}).
+
+    sd: a torchvision `resnet101` state dict -- the trunk keys are DeeplabMulti's own (conv1, bn1, layer1..layer4), its `fc.*` keys are
+    dropped -- or any file in DeeplabMulti's keys, whose head keys (layer5*, layer6*) are dropped.  shapes: {key: shape} of the trainer's
+    model (model_spec.state_shapes); every trunk key of it must be in `sd` with that shape: ValueError naming the first missing or mis-shaped
+    key otherwise.  `num_batches_tracked` is taken when present and is not required (files written before PyTorch 0.4.1 have none)."""
+    heads = tuple(h + "." for h in DEEPLAB_HEADS)
+    layout = "torchvision ResNet" if any(k.startswith("fc.") for k in sd) else "DeeplabMulti"
+    out = {}
+    for k, shp in shapes.items():
+        if k.startswith(heads):
+            continue
+        if k not in sd:
+            if k.endswith("num_batches_tracked"):
+                continue
+            raise ValueError(f"feat-dist-from: trunk key {k!r} is missing from the file ({layout} layout, {len(sd)} keys)")
+        if tuple(sd[k].shape) != tuple(shp):
+            raise ValueError(f"feat-dist-from: trunk key {k!r} has shape {tuple(sd[k].shape)}, the model needs {tuple(shp)}")
+        out[k] = sd[k]
+    return layout, out
+
+
 def checkpoint_layout(sd, model):
     """-> (layout name, state dict in the module's keys) of a checkpoint for model "v3" (DeepLabv3) or "vgg" (DeeplabVGG): the module's
     own keys (a warm-up or SimT checkpoint) are taken as they are, a torchvision ImageNet file is mapped; anything else comes back

@@ -27,6 +27,7 @@ from . import trace
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
+from .feat_dist import FeatDistMixin, check_feat_dist
 from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
 from .train_state import TrainStateMixin, state_sha256
 
@@ -504,7 +505,7 @@ def accumulate_pass(tr, k, n, st):
             tr.reducer.finish()
 
 
-class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
+class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
@@ -512,7 +513,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
+                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None):
         """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
         online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
@@ -532,12 +534,18 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         online_source=True (needs online_labels): the published DACS step -- every micro-batch is two passes into one gradient,
         supervised cross-entropy on a labelled source pair (`step(source_image=, source_label=)`), then the target pass above; with
         online_mix the mix pastes half of SOURCE item i's classes, image and ground truth, onto target item i (simt_source_mix), and with
-        online_labels_weighted a pasted pixel has weight 1.  `losses()` gains `source_seg1` / `source_seg2`.  None / False: the trainer it was."""
+        online_labels_weighted a pasted pixel has weight 1.  `losses()` gains `source_seg1` / `source_seg2`.  None / False: the trainer it was.
+        feat_dist=lambda >= 0 (simt_amd/feat_dist.py; needs feat_dist_state, and with online_labels also online_source): DAFormer's
+        thing-class ImageNet feature distance -- the pass with ground-truth labels (the source pass; without online_labels the only pass) adds
+        lambda * the mean L2 distance between the student's layer-4 output and that of a frozen eval-mode trunk over `feat_dist_state`, over the
+        cells one class of `feat_dist_classes` (default: DAFormer's ten thing classes of the 19) fills to `feat_dist_min_ratio` (default 0.75);
+        its gradient enters the backward at layer 4's output.  `losses()` gains `feat_dist` / `feat_dist_cells`.  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         source = check_source(online_source, tau)
+        fd = check_feat_dist(feat_dist, feat_dist_state, feat_dist_classes, feat_dist_min_ratio, tau, source, hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -545,8 +553,11 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         f32 = torch.float32
         self.params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
         kw = {"layers": layers} if layers is not None else {}
+        if fd[0] is not None:      # (only then: without the keyword the plan is built by the call it always was)
+            kw["feat_grad_seed"] = True
         self.plan = TrunkPlan(self.params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=True,
                               data_parallel=process_group is not None, **kw)
+        kw.pop("feat_grad_seed", None)
         h, w = self.h, self.w = self.plan.heads[1].h, self.plan.heads[1].w
         if tau is not None:      # the teacher: the frozen plan of SimTTrainer(teacher_view=True) -- stem_from=None: its own x_in and stem launch
             self.fixed_params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
@@ -585,6 +596,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         self._init_mix(mix)
         self._init_weighted(weighted)
         self._init_source(source)
+        self._init_feat_dist(*fd, feat_dist_state, dict(kw, data_parallel=process_group is not None))
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -614,11 +626,18 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         for mi, (img, lab) in enumerate(zip(images, labels)):
             if self.online_source:      # pass a: supervised cross-entropy on the source pair, the plain head launches, into the same gradient
                 self._source_input(src_images[mi], src_labels[mi])
+                if self.feat_dist is not None:      # the ImageNet forward beside the student's, the term's gradient into this backward
+                    ev_fd = self._fd_input()
                 self.plan.forward()
+                if self.feat_dist is not None:
+                    self._fd_forward(ev_fd)
                 L.call("simt_head_loss", C.byref(self.head_desc), st)
                 L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # the source labels count too
                 self._source_kept()
                 L.call("simt_head_grad", C.byref(self.head_desc), st)
+                if self.feat_dist is not None:
+                    self._fd_launches(st)
+                    self.plan.use_feat_seed(True)
                 self.plan.backward()
                 accumulate_pass(self, mi * per, n_pass, st)
             if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
@@ -627,7 +646,11 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             elif self.online_labels is None:
                 self.plan.x_in.copy_(img, non_blocking=True)
                 self.label.copy_(lab, non_blocking=True)
+                if self.feat_dist is not None:      # the only pass has the ground truth
+                    ev_fd = self._fd_input()
                 self.plan.forward()
+                if self.feat_dist is not None:
+                    self._fd_forward(ev_fd)
             else:          # the teacher writes self.label on the side stream, beside the student's forward; the main stream waits for it here
                 self.plan.x_in.copy_(img, non_blocking=True)
                 ev_in = self._teacher_input(img, teachers[mi])
@@ -636,6 +659,11 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self._head_loss(st)          # simt_head_loss; with online_labels_weighted its weighted form (OnlineLabelMixin)
             L.call("simt_vec_acc", self.bad_labels.data_ptr(), self.hout.data_ptr() + 4 * 15, 1, 1, st)      # every micro-batch counts
             self._head_grad(st)
+            if self.feat_dist is not None:
+                if self.online_labels is None:
+                    self._fd_launches(st)
+                else:      # the target pass under online_source: the seed-less launch, the parent's (the descriptor is read at every launch)
+                    self.plan.use_feat_seed(False)
             if self.reducer is not None and n_pass == 1:
                 self.reducer.start()
                 self.plan.backward(hook=self.reducer.ready_upto)
@@ -681,4 +709,4 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like SimTTrainer's
-        return self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]})
+        return self._fd_losses(self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]}))

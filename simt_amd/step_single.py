@@ -290,15 +290,22 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
-                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None):
+                 online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
+                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
         online_labels_momentum: as for step.WarmupTrainer; the
         teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample).  online_mix /
         online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
         statistics of the teacher's labels before the mix.  online_labels_weighted: the quality weights of DACS, as for step.WarmupTrainer
-        (DESIGN 7.19).  online_source: a labelled source pair in every micro-batch, as for step.WarmupTrainer."""
+        (DESIGN 7.19).  online_source: a labelled source pair in every micro-batch, as for step.WarmupTrainer.
+        feat_dist*: refused -- the ImageNet feature distance is built for DeepLab-v2 (step.WarmupTrainer) only."""
         assert model in ("v3", "vgg")
+        for name, v in (("feat_dist", feat_dist), ("feat_dist_state", feat_dist_state), ("feat_dist_classes", feat_dist_classes),
+                        ("feat_dist_min_ratio", feat_dist_min_ratio)):
+            if v is not None:
+                raise ValueError(f"{name}: the ImageNet feature distance is built for DeepLab-v2 (WarmupTrainer) only; DeepLabv3 and DeepLab-VGG16 "
+                                 "(WarmupSingleTrainer) have no seeded backward and no head-less eval plan yet (DESIGN 7.22, not built)")
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)

@@ -40,6 +40,12 @@ it; FILE comes from `python -m simt_amd.tools.compute_class_stats`.  With --scal
 the first that shows more than floor(N * --rcs-min-crop-ratio R (0.5)) pixels of the class is taken, the last when none does: counted, picked and
 cropped on the copy stream, nothing read back; the loss line gains ` rcs = <share of the source items whose window met the bar>`.  One start-up
 line gives the class probabilities and the frames per class.  --train-state refuses the flag added, dropped or changed.
+--feat-dist [LAMBDA] --feat-dist-from FILE [--feat-dist-classes C ...] [--feat-dist-min-ratio R] (--model DeepLab; with --online-labels it needs
+--online-source): DAFormer's thing-class ImageNet feature distance -- the pass with ground-truth labels adds LAMBDA (no value: 0.005)
+times the mean L2 distance between the model's layer-4 features and those of a frozen ImageNet trunk (FILE: a torchvision resnet101 state dict or a
+file in DeeplabMulti's keys) over the feature cells a thing class fills to R (0.75) of their label window; mask, distance and gradient are three
+launches on the device, the ImageNet forward runs beside the model's.  The loss line gains ` fd = <feat_dist> (<cells>)`; one start-up line names the
+file, the classes and the memory of the second trunk.  --train-state refuses the flag added, dropped or changed, or another FILE.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -122,10 +128,105 @@ def get_arguments(argv=None):
     add_train_state_args(p)
     add_ema_args(p)
     add_online_label_args(p)
+    add_feat_dist_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
+    check_feat_dist_args(p, args)
     return args
+
+
+def _feat_dist_lambda(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < float("inf"):             # (a NaN fails both comparisons)
+        raise argparse.ArgumentTypeError(f"{text!r}: expected the weight of the feature distance, a finite LAMBDA >= 0")
+    return v
+
+
+def _feat_dist_ratio(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.5 < v <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected the share of a cell's label window one thing class must fill, 0.5 < R <= 1")
+    return v
+
+
+def add_feat_dist_args(p):
+    """--feat-dist / --feat-dist-from / --feat-dist-classes / --feat-dist-min-ratio; `check_feat_dist_args` holds their refusals."""
+    from simt_amd.feat_dist import DEFAULT_CLASSES, DEFAULT_LAMBDA, DEFAULT_MIN_RATIO
+    p.add_argument("--feat-dist", type=_feat_dist_lambda, nargs="?", const=DEFAULT_LAMBDA, default=None, metavar="LAMBDA",
+                   help="DAFormer's thing-class ImageNet feature distance (simt_amd/feat_dist.py; DESIGN 7.22): the pass with ground-truth labels "
+                        "(the source pass of --online-source; without --online-labels the only pass) adds LAMBDA * the mean L2 distance between "
+                        "the model's layer-4 features and those of a frozen ImageNet trunk (--feat-dist-from), over the feature cells a thing "
+                        f"class fills (no value: LAMBDA = {DEFAULT_LAMBDA}).  --model DeepLab only; with --online-labels it needs --online-source.  "
+                        "Default: off")
+    p.add_argument("--feat-dist-from", type=str, default=None, metavar="FILE",
+                   help="with --feat-dist (required): the ImageNet weights of the frozen trunk -- a torchvision resnet101 state dict (fc.* dropped) "
+                        "or any file in DeeplabMulti's keys (head keys dropped); simt_amd/pretrained.py")
+    p.add_argument("--feat-dist-classes", type=int, nargs="+", default=None, metavar="C",
+                   help=f"with --feat-dist: the thing classes.  Default with 19 classes: {' '.join(map(str, DEFAULT_CLASSES))}")
+    p.add_argument("--feat-dist-min-ratio", type=_feat_dist_ratio, default=None, metavar="R",
+                   help=f"with --feat-dist: a cell is kept when one thing class fills at least R of its label window (0.5 < R <= 1).  Default: {DEFAULT_MIN_RATIO}")
+
+
+def check_feat_dist_args(p, args):
+    """argparse's error (exit status 2) naming the flag: a --feat-dist-* flag without --feat-dist, --feat-dist without --feat-dist-from, with
+    --online-labels but without --online-source (no ground truth for the mask), or with a one-output model."""
+    if args.feat_dist is None:
+        for flag in ("feat_dist_from", "feat_dist_classes", "feat_dist_min_ratio"):
+            if getattr(args, flag) is not None:
+                p.error(f"--{flag.replace('_', '-')} needs --feat-dist: it sets the feature distance")
+        return
+    if args.model != "DeepLab":
+        p.error(f"--feat-dist with --model {args.model}: the feature distance is built for --model DeepLab only (DESIGN 7.22, not built: "
+                "DeepLabv3 and DeepLabVGG)")
+    if not args.feat_dist_from:
+        p.error("--feat-dist needs --feat-dist-from FILE: the ImageNet weights of the frozen trunk")
+    if args.online_labels is not None and not args.online_source:
+        p.error("--feat-dist with --online-labels needs --online-source: the mask is made of ground-truth labels, and a run that trains on a "
+                "teacher's labels alone has none")
+    from simt_amd.feat_dist import check_feat_dist
+    try:
+        check_feat_dist(args.feat_dist, {"file": args.feat_dist_from}, args.feat_dist_classes, args.feat_dist_min_ratio, args.online_labels,
+                        args.online_source, args.num_classes)
+    except ValueError as e:
+        p.error(str(e))
+
+
+def feat_dist_kwargs(args, shapes, rank=0):
+    """The trainer's keywords of --feat-dist (none without it): the file is read, mapped and checked (simt_amd.pretrained.imagenet_trunk);
+    rank 0 prints the start-up line."""
+    if getattr(args, "feat_dist", None) is None:
+        return {}
+    from simt_amd.feat_dist import DEFAULT_CLASSES, DEFAULT_MIN_RATIO
+    from simt_amd.pretrained import imagenet_trunk
+    if not osp.exists(args.feat_dist_from):
+        raise SystemExit(f"--feat-dist-from {args.feat_dist_from!r}: no such file")
+    saved = torch.load(args.feat_dist_from, map_location="cpu")
+    try:
+        layout, trunk = imagenet_trunk(saved, shapes)
+    except ValueError as e:
+        raise SystemExit(f"--feat-dist-from {args.feat_dist_from!r}: {e}")
+    classes = list(DEFAULT_CLASSES) if args.feat_dist_classes is None else sorted(args.feat_dist_classes)
+    ratio = DEFAULT_MIN_RATIO if args.feat_dist_min_ratio is None else args.feat_dist_min_ratio
+    if rank == 0:
+        mb = sum(v.numel() * 4 for v in trunk.values() if v.dtype != torch.long) / 2 ** 20
+        print(f"feature distance: lambda {args.feat_dist} over the layer-4 cells one of the classes {' '.join(map(str, classes))} fills to {ratio}; "
+              f"the frozen trunk is {args.feat_dist_from} ({layout} layout, {len(trunk)} tensors), {mb:.0f} MB of fp32 masters beside the model's "
+              "(plus its packed operands and eval-mode activations)")
+    return dict(feat_dist=args.feat_dist, feat_dist_state=trunk, feat_dist_classes=args.feat_dist_classes, feat_dist_min_ratio=args.feat_dist_min_ratio)
+
+
+def feat_dist_text(args, l):
+    """` fd = <feat_dist> (<cells>)` of the loss line: only with --feat-dist."""
+    if getattr(args, "feat_dist", None) is None:
+        return ""
+    return " fd = {0:.4f} ({1:d})".format(l["feat_dist"], l["feat_dist_cells"])
 
 
 def step_args(args, mb, sb=None):
@@ -225,7 +326,8 @@ def main(argv=None):
         print("Start: " + time.asctime(time.localtime(time.time())))                       # :158
     w, h = map(int, args.input_size_target.split(","))
     C = args.num_classes
-    state = ms.reference_init(ms.state_shapes(C, 0, False), seed=args.random_seed)
+    shapes = ms.state_shapes(C, 0, False)
+    state = ms.reference_init(shapes, seed=args.random_seed)
     # trainV1_warmup.py:177: keys of the pretrained checkpoint carry a 6-character prefix (`k[6:]`); shapes are filtered
     n = restore(state, args.restore_from, strip_prefix=6, required=not (args.synthetic or args.from_scratch))
     hp = Hyper(num_classes=C, open_classes=0, lambda_seg=args.lambda_seg, lr=args.learning_rate, iter_size=args.iter_size,
@@ -234,7 +336,7 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
                        online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                       **balanced_kwargs(args))
+                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         online_label_line(args)
@@ -260,7 +362,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")

@@ -41,6 +41,9 @@ WEIGHTED_FIELDS = ("online_labels_weighted",)
 # and the labelled source batch trained beside that teacher's labels (online_source = True: DESIGN 7.20), compared through
 # value_mismatches(..., fields=SOURCE_FIELDS)
 SOURCE_FIELDS = ("online_source",)
+# and the ImageNet feature distance (feat_dist = lambda with its classes, ratio and the SHA-256 of the frozen ImageNet trunk: DESIGN 7.22),
+# compared through value_mismatches(..., fields=FEAT_DIST_FIELDS)
+FEAT_DIST_FIELDS = ("feat_dist", "feat_dist_classes", "feat_dist_min_ratio", "feat_dist_sha256")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -155,6 +158,9 @@ class TrainStateMixin:
                 hy["online_labels_weighted"] = str(self.online_labels_weighted)
             if getattr(self, "online_source", False):
                 hy["online_source"] = True
+        if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
+            hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
+                      feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
         return hy
 
     def _nbt_steps(self, key):
@@ -181,6 +187,8 @@ class TrainStateMixin:
         the resumed run draws what the uninterrupted one draws.  With `online_labels_weighted` `hyper` also carries the mode and
         `accumulators` the last micro-batch's weights (`label_quality`); without the keyword the dict is what it was.  With `online_source`
          `hyper` also carries `online_source: True` and `accumulators` the two kept losses of the last source pass (`source_hout`).
+        With `feat_dist` `hyper` also carries lambda, the classes, the ratio and `feat_dist_sha256` -- the hash of the frozen
+        ImageNet trunk, which is not stored -- and `accumulators` the three scalars of the last labelled pass (`feat_dist_out`).
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -207,6 +215,8 @@ class TrainStateMixin:
                     ts["accumulators"]["label_quality"] = self.label_q.detach().cpu()
                 if getattr(self, "online_source", False):      # the last source pass's losses: `source_seg1` / `source_seg2` resume exactly
                     ts["accumulators"]["source_hout"] = self.source_hout.detach().cpu()
+        if getattr(self, "feat_dist", None) is not None:      # the last labelled pass's three scalars: `feat_dist` / `feat_dist_cells` resume exactly
+            ts["accumulators"]["feat_dist_out"] = self.fd_out.detach().cpu()
         if getattr(self, "online_mix", None) is not None:      # the position of the mix's own generator (numpy's plain dict of Python ints)
             ts["mix_rng"] = self._mix_rng.bit_generator.state
         if getattr(self, "ema", None) is not None:      # the weight EMA (simt_amd/ema.py): decay, update count, shadow; absent without one
@@ -226,7 +236,8 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state()) + value_mismatches(ts["hyper"], self._hyper_state(), fields=BALANCE_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -291,6 +302,8 @@ class TrainStateMixin:
                     self.label_q.copy_(acc["label_quality"])
                 if getattr(self, "online_source", False):
                     self.source_hout.copy_(acc["source_hout"])
+        if getattr(self, "feat_dist", None) is not None:
+            self.fd_out.copy_(acc["feat_dist_out"])
         self._bad_reported = int(ts["bad_reported"])
         if getattr(self, "online_mix", None) is not None:
             self._mix_rng.bit_generator.state = ts["mix_rng"]
