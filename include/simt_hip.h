@@ -411,6 +411,26 @@ typedef struct {
   const uint64_t* skip_if;   /* optional device word (simt_fbn_desc.err): the launch changes nothing while it is non-zero; NULL: always update */
 } simt_sgd_desc;
 int simt_sgd_multi(const simt_sgd_desc* d, simt_stream_t stream);
+
+/* ---- multi-tensor AdamW (decoupled weight decay; torch.optim.AdamW's single-tensor order), every tensor listed once: DESIGN 7.23 ----
+ * One launch per optimiser step in the launch shape of simt_sgd_multi: one 256-lane workgroup per (segment, chunk) entry, 16-byte loads and
+ * stores where p, g, m and v are all 16-byte aligned at the chunk's start, dwords otherwise and for the tail (the same bits either way).
+ * Per element, with g the gradient and `grp` the segment's group:
+ *   p = p * decay[grp];  m = m + (g - m) * omb1;  v = v * beta2 + omb2 * g * g;  p = p - step_size[grp] * (m / (sqrtf(v) / bc2s + eps))
+ * The caller forms the per-step constants in double and rounds each once to fp32, as simt_adam_step_guarded does for its own:
+ *   step_size[grp] = lr / (1 - beta1^t),  decay[grp] = 1 - lr * wd,  bc2s = sqrt(1 - beta2^t),  omb = 1 - beta   (t = 1 on the first step).
+ * SIMT_ERR_INVALID and no launch: NULL tables, nchunks <= 0, chunk <= 0, a beta outside [0, 1), eps <= 0, bc2s <= 0, a non-finite constant. */
+typedef struct {
+  const void* segs;    /* device array of {float* p; const float* g; float* m; float* v; int64 n; int32 group; int32 pad} */
+  const void* chunks;  /* device int32 [nchunks][2]: (segment index, chunk index inside the segment), as simt_sgd_desc */
+  int32_t nchunks, chunk;
+  float step_size[4], decay[4];  /* per param group */
+  float beta1, beta2, omb1, omb2;
+  float bc2s, eps;
+  int32_t first_step;  /* 1: the moments are created (m = g * omb1, v = omb2 * g * g); m and v are not read */
+  const uint64_t* skip_if;   /* optional device word (simt_fbn_desc.err): the launch changes nothing while it is non-zero; NULL: always update */
+} simt_adamw_desc;
+int simt_adamw_multi(const simt_adamw_desc* d, simt_stream_t stream);
 /* dst[i] (+)= src[i], fp32: bias of the fused 2-branch ASPP GEMM = sum of the branch biases (deeplab_multi.py:115-119) */
 int simt_vec_acc(float* dst, const float* src, int n, int accumulate, simt_stream_t stream);
 

@@ -104,6 +104,13 @@ class SgdDesc(C.Structure):
                 ("momentum", f32), ("dampening", f32), ("first_step", i32), ("skip_if", c_p)]
 
 
+class AdamwDesc(C.Structure):
+    """simt_adamw_desc (include/simt_hip.h): the multi-tensor AdamW launch."""
+    _fields_ = [("segs", c_p), ("chunks", c_p), ("nchunks", i32), ("chunk", i32), ("step_size", f32 * 4), ("decay", f32 * 4),
+                ("beta1", f32), ("beta2", f32), ("omb1", f32), ("omb2", f32), ("bc2s", f32), ("eps", f32), ("first_step", i32),
+                ("skip_if", c_p)]
+
+
 GATHER_MAX = 64          # include/simt_hip.h SIMT_GATHER_MAX
 
 
@@ -363,6 +370,7 @@ SIGNATURES = {
     "simt_adam_step": (_I, [c_p, c_p, c_p, c_p, _L, f32, f32, f32, f32, _I, c_p]),
     "simt_adam_step_guarded": (_I, [c_p, c_p, c_p, c_p, _L, f32, f32, f32, f32, _I, c_p, c_p]),
     "simt_sgd_multi": (_I, [C.POINTER(SgdDesc), c_p]),
+    "simt_adamw_multi": (_I, [C.POINTER(AdamwDesc), c_p]),
     "simt_event_create": (_I, [C.POINTER(c_p), _I]),
     "simt_event_destroy": (_I, [c_p]),
     "simt_event_record": (_I, [c_p, c_p]),

@@ -11,6 +11,7 @@ host sync:
   5. the trunk backward (dgrad + wgrad + BN backward)                         (:428)                   TrunkPlan.backward
   6. [DP] RCCL all-reduce (mean) of the flat gradient buffer and of dNTM      (new capability)
   7. SGD with duplicate-listing semantics + Adam on NTM1/NTM2                 (:434-436)               simt_sgd_multi / simt_adam_step
+     (optimizer="adamw": simt_adamw_multi in the place of simt_sgd_multi, every tensor once -- simt_amd/optimizer.py)
 
 All state lives on the device; scalars are read back only when the caller asks (`losses()`).
 """
@@ -28,6 +29,7 @@ from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
 from .feat_dist import FeatDistMixin, check_feat_dist
+from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
 from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
 from .train_state import TrainStateMixin, state_sha256
 
@@ -48,6 +50,16 @@ class Hyper:
 
 def lr_poly(base_lr, it, max_iter, power):
     return base_lr * ((1 - float(it) / max_iter) ** power)            # trainV2_simt.py:174-175
+
+
+def lr_at(base, it, max_iter, power, warmup=0, warmup_ratio=1e-6):
+    """The model's learning rate at iteration `it`: `lr_poly`, and over the first `warmup` iterations its "linear" warm-up (DAFormer's
+    schedule) -- the poly value times a factor that rises from `warmup_ratio` at it = 0 to 1 at it = warmup.  warmup = 0 returns
+    lr_poly's float itself.  lr_T (NTM Adam, the inner W loop) is not warmed up: it stays lr_poly."""
+    lr = lr_poly(base, it, max_iter, power)
+    if warmup and it < warmup:
+        lr = lr * (1 - (1 - float(it) / warmup) * (1 - warmup_ratio))
+    return lr
 
 
 def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer5", "layer6", "layer5_1", "layer6_1")):
@@ -90,10 +102,14 @@ def check_views(tr, teacher_image, fix_item, n):
     return teachers, maps
 
 
-class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
+class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin):
     def __init__(self, state, fixed_state, ntm1, ntm2, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None, ema_teacher_every=None, teacher_view=False):
-        """teacher_view=True (the weak-view teacher): the frozen model reads an image of its own -- `step(..., teacher_image=...)`,
+                 openset=True, process_group=None, w_init=None, layers=None, ema_decay=None, ema_teacher_every=None, teacher_view=False,
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
+        """optimizer="adamw" (simt_amd/optimizer.py): simt_adamw_multi in the place of simt_sgd_multi, every applied tensor listed
+        once, with adam_betas and adam_eps; lr_warmup=N: the model's learning rate rises linearly over the first N iterations (`lr_at`), lr_T
+        does not.  The defaults are the trainer it was.
+        teacher_view=True (the weak-view teacher): the frozen model reads an image of its own -- `step(..., teacher_image=...)`,
         the weak view -- through its own one-set stem launch, and the head reads each pixel's frozen operand from the item `fix_item` names
         (simt_head_loss_views / simt_head_grad_views).  False: one image for both networks, as the reference feeds them."""
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
@@ -199,6 +215,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         self.post_desc = npd
         # ---- SGD segments (duplicate listings replayed in registers)
         self._build_sgd()
+        self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
         self._init_teacher(ema_teacher_every)      # None: the frozen model never moves (simt_amd/ema_teacher.py)
@@ -259,6 +276,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                 self.mom[n] = buf
                 recs.append((p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), mult, group))
         self.sgd_names = list(g0) + list(g1)
+        self.sgd_groups = {**{n: 0 for n in g0}, **{n: 1 for n in g1}}
         seg_dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("mult", "<i4"), ("group", "<i4")])
         segs = np.array(recs, dtype=seg_dt)
         chunk = 65536
@@ -335,8 +353,8 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         hp = self.hp
         teachers, maps = check_views(self, teacher_image, fix_item, hp.iter_size)
         it = self.it_done if it is None else it
-        lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
-        lr_T = lr_poly(hp.lr_T, it, hp.num_steps, hp.power)
+        lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
+        lr_T = lr_poly(hp.lr_T, it, hp.num_steps, hp.power)      # (not warmed up: DESIGN 7.23)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels = list(label) if isinstance(label, (list, tuple)) else [label]
@@ -407,11 +425,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         return self.lout
 
     def _sgd(self, lr, st):
-        d = self.sgd_desc
-        d.lr[0], d.lr[1] = lr, lr * 10.0
-        d.wd[0], d.wd[1] = self.hp.weight_decay, self.hp.weight_decay
-        d.first_step = 1 if self.it_done == 0 else 0
-        L.call("simt_sgd_multi", C.byref(d), st)
+        self._optim_step(lr, st)      # simt_sgd_multi, or simt_adamw_multi in its place (simt_amd/optimizer.py)
 
     def _backward_early_sgd(self, lr, st):
         """Backward with the SGD step and the re-pack of the updated layers enqueued on the side stream once the block that produced
@@ -505,7 +519,7 @@ def accumulate_pass(tr, k, n, st):
             tr.reducer.finish()
 
 
-class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
+class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, OptimizerMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
@@ -514,8 +528,10 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
     def __init__(self, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, layers=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
-                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None):
-        """online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
+                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
+        """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTTrainer; the defaults are the trainer it was.
+        online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
         online_labels_every=N (needs ema_decay): that teacher follows the weight EMA behind every N-th update.  None: the trainer it was.
         online_labels_balanced=P in (0, 1] (needs online_labels): one threshold per class, kept on the device -- it starts at tau and
@@ -589,6 +605,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
         hd.mode = 1
         self.head_desc = hd
         SimTTrainer._build_sgd(self, roots=("conv1", "layer1", "layer2", "layer3", "layer4"))
+        self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)
         fix = (self.fixed.out["x2"], self.fixed.ldp["x2"]) if tau is not None else (None, 0)
@@ -613,7 +630,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
         without the keyword."""
         hp = self.hp
         it = self.it_done if it is None else it
-        lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
+        lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
@@ -672,11 +689,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin):
             self.plan.backward()
             if n_pass > 1:      # the accumulation of hp.iter_size > 1, over passes (accumulate_pass); the exchange behind the last
                 accumulate_pass(self, mi * per + per - 1, n_pass, st)
-        d = self.sgd_desc
-        d.lr[0], d.lr[1] = lr, lr * 10.0
-        d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay
-        d.first_step = 1 if self.it_done == 0 else 0
-        L.call("simt_sgd_multi", C.byref(d), st)
+        self._optim_step(lr, st)      # simt_sgd_multi, or simt_adamw_multi in its place (simt_amd/optimizer.py)
         self.plan.repack()
         if self.ema is not None:
             self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward

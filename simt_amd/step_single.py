@@ -29,14 +29,18 @@ from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
 from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
-from .step import accumulate_pass, check_views, lr_poly
+from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
+from .step import accumulate_pass, check_views, lr_at, lr_poly
 from .train_state import TrainStateMixin, state_sha256
 
 
-class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
+class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin):
     def __init__(self, model, state, fixed_state, ntm, hp, class_dist, B, H, W, *, dtype=torch.bfloat16, device="cuda:0",
-                 process_group=None, arch=None, ema_decay=None, ema_teacher_every=None, teacher_view=False):
-        """model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
+                 process_group=None, arch=None, ema_decay=None, ema_teacher_every=None, teacher_view=False,
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
+        """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for step.SimTTrainer; the BatchNorm gamma and beta
+        this trainer trains go without weight decay under "adamw".  The defaults are the trainer it was.
+        model: "v3" | "vgg".  state: the trainable model's state_dict tensors (DeepLabv3(nc, openc, openset=True) /
         DeeplabVGG(nc + openc)); fixed_state: the frozen model's (nc outputs).  arch: plan keyword arguments (reduced depths / widths
         for tests): v3 -> layers, width, assp_ch; vgg -> vgg_layers.  teacher_view: as for SimTTrainer (the frozen plan has an input of its
         own here already: the weak view is copied into it instead of the trainable plan's image)."""
@@ -135,6 +139,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         npd.lambda_anchor, npd.gscale, npd.single = hp.lambda_anchor, 1.0 / hp.iter_size, 1
         self.post_desc = npd
         self._build_sgd()
+        self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
         # None: the frozen model never moves (simt_amd/ema_teacher.py).  DeeplabVGG has ONE classifier of Cn + K rows: the frozen model's Cn rows
@@ -167,6 +172,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                 self.mom[n] = buf
                 recs.append((p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), 1, group))
         self.sgd_names = g0 + g1
+        self.sgd_groups = {**{n: 0 for n in g0}, **{n: 1 for n in g1}}
         seg_dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("mult", "<i4"), ("group", "<i4")])
         chunk, chunks = 65536, []
         for si, r in enumerate(recs):
@@ -186,7 +192,8 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
         assert hp.iter_size == 1, "gradient accumulation is implemented for the DeepLab-v2 trainer only"
         (teacher_image,), (fix_item,) = check_views(self, teacher_image, fix_item, 1)
         it = self.it_done if it is None else it
-        lr, lr_T = lr_poly(hp.lr, it, hp.num_steps, hp.power), lr_poly(hp.lr_T, it, hp.num_steps, hp.power)
+        lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
+        lr_T = lr_poly(hp.lr_T, it, hp.num_steps, hp.power)      # (not warmed up: DESIGN 7.23)
         st = ops.stream_ptr()
         main, side = torch.cuda.current_stream(), side_stream(self.dev)
         ev0 = torch.cuda.Event()
@@ -234,11 +241,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
             self.reducer.finish()
         else:
             self._bwd.run()
-        d = self.sgd_desc
-        d.lr[0], d.lr[1] = lr, lr * 10.0
-        d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay
-        d.first_step = 1 if self.it_done == 0 else 0
-        L.call("simt_sgd_multi", C.byref(d), st)
+        self._optim_step(lr, st)      # simt_sgd_multi, or simt_adamw_multi in its place (simt_amd/optimizer.py)
         main.wait_event(ev_post)
         ops.adam_step(self.ntm, self.ntm_grad, self.ntm_m, self.ntm_v, lr=lr_T, step=self.it_done + 1, skip_if=self._skip_word)
         self.plan.repack()
@@ -280,7 +283,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin):
                 "vol_ok": v[9]}
 
 
-class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
+class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, OptimizerMixin):
     """The warm-up stage (tools/trainV1_warmup.py:156-256) over a ONE-OUTPUT model: DeepLabv3(nc) or DeeplabVGG(nc), trained by cross-entropy
     on the pseudo labels, loss = CE(interp_target(model(x)), label) with ignore_index 255 (:212-231 without the auxiliary head; for
     DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
@@ -291,9 +294,11 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
-                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None):
+                 feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
-        keyword arguments, as for SimTSingleTrainer.  online_labels / online_labels_every / online_labels_balanced /
+        keyword arguments, as for SimTSingleTrainer.  optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTSingleTrainer
+        (DESIGN 7.23).  online_labels / online_labels_every / online_labels_balanced /
         online_labels_momentum: as for step.WarmupTrainer; the
         teacher is the frozen plan of SimTSingleTrainer (DeepLabv3: without its last launch, the in-model upsample).  online_mix /
         online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
@@ -376,6 +381,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 1, 1, half, 0
         self.head_desc = hd
         SimTSingleTrainer._build_sgd(self)
+        self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)
         self._init_online(tau, every, fix_out, ldf, half, balanced)      # (family 1 = the half-pixel model, DeepLabv3)
@@ -399,7 +405,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
         source_image / source_label are the labelled source pair of every micro-batch, as for step.WarmupTrainer."""
         hp = self.hp
         it = self.it_done if it is None else it
-        lr = lr_poly(hp.lr, it, hp.num_steps, hp.power)
+        lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
         st = ops.stream_ptr()
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
@@ -442,11 +448,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin):
             self._bwd.run()
             if n_pass > 1:      # the accumulation of hp.iter_size > 1, over passes (step.accumulate_pass); the exchange behind the last
                 accumulate_pass(self, mi * per + per - 1, n_pass, st)
-        d = self.sgd_desc
-        d.lr[0], d.lr[1] = lr, lr * 10.0
-        d.wd[0], d.wd[1] = hp.weight_decay, hp.weight_decay
-        d.first_step = 1 if self.it_done == 0 else 0
-        L.call("simt_sgd_multi", C.byref(d), st)
+        self._optim_step(lr, st)      # simt_sgd_multi, or simt_adamw_multi in its place (simt_amd/optimizer.py)
         self.plan.repack()
         if self.ema is not None:
             self.ema.update(st)          # main stream, behind SGD and the re-pack, in front of the next step's forward

@@ -63,11 +63,12 @@ import time
 import torch
 
 from simt_amd import model_spec as ms
-from simt_amd.step import Hyper, WarmupTrainer, lr_poly
+from simt_amd.step import Hyper, WarmupTrainer
 from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
-                                          add_ema_args, add_online_label_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args,
+                                          add_ema_args, add_online_label_args, add_optimizer_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args,
                                           add_train_state_args, add_v3_layers, batches, check_online_label_args, check_patch_mask_args,
-                                          online_label_line, patch_mask_line, restore, save_atomic, shutdown, source_batches)
+                                          model_lr, online_label_line, optimizer_kwargs, optimizer_line, patch_mask_line, restore, save_atomic,
+                                          shutdown, source_batches)
 
 
 def get_arguments(argv=None):
@@ -129,10 +130,12 @@ def get_arguments(argv=None):
     add_ema_args(p)
     add_online_label_args(p)
     add_feat_dist_args(p)
+    add_optimizer_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
     check_feat_dist_args(p, args)
+    optimizer_kwargs(p, args)
     return args
 
 
@@ -336,9 +339,10 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
                        online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank))
+                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        optimizer_line(args)
         online_label_line(args)
         patch_mask_line(args, frozen=False)
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
@@ -361,7 +365,7 @@ def main(argv=None):
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
-                    i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                    i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], model_lr(args, i_iter),
                     args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
@@ -426,9 +430,10 @@ def main_single(args):
     eval_layers = layers if model == "v3" else None
     tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
                              ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                             **balanced_kwargs(args))
+                             **balanced_kwargs(args), **args.optimizer_kwargs)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
+        optimizer_line(args)
         online_label_line(args)
         patch_mask_line(args, frozen=False)
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
@@ -452,7 +457,7 @@ def main_single(args):
             l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
-                    i_iter, args.num_steps, l["loss_seg"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                    i_iter, args.num_steps, l["loss_seg"], model_lr(args, i_iter),
                     args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:

@@ -67,7 +67,7 @@ import numpy as np
 import torch
 
 from simt_amd import model_spec as ms
-from simt_amd.step import Hyper, SimTTrainer, lr_poly
+from simt_amd.step import Hyper, SimTTrainer, lr_at
 from simt_amd.train_state import save_atomic      # (its home; the tools and their users keep importing it from here)
 
 
@@ -134,11 +134,13 @@ def get_arguments(argv=None):
     add_train_state_args(p)
     add_ema_args(p)
     add_ema_teacher_args(p)
+    add_optimizer_args(p)
     p.add_argument("--weak-teacher", action="store_true",
                    help="the frozen model sees the batch before --class-mix / --colour-jitter / --gaussian-blur / --mask-patches (needs one of "
                         "them) and its predictions are mixed with the pixels' mask; the student trains on the augmented batch.  Default: off")
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
+    optimizer_kwargs(p, args)
     if args.ema_teacher is not None and args.ema is None:
         p.error("--ema-teacher needs --ema: the frozen model follows the weight EMA")
     if args.weak_teacher and (args.synthetic or (args.class_mix is None and args.colour_jitter is None and args.gaussian_blur is None
@@ -287,6 +289,50 @@ def add_ema_args(p):
                         "min(D, 1 - 1 / (t + 1)) at update t (no value: D = 0.999; 0 <= D < 1).  The trained model is unchanged; the averaged one is "
                         "evaluated beside it (`EMA mIoU`), kept by a rotation of its own (`..._ema_iter...`) and written at the stop as "
                         "GTA5_<stop>_ema.pth.  Default: off")
+
+
+def add_optimizer_args(p):
+    """--optimizer / --adam-betas / --adam-eps / --lr-warmup / --lr-warmup-ratio: both tools, all three models."""
+    from simt_amd.optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OPTIMIZERS
+    p.add_argument("--optimizer", choices=OPTIMIZERS, default="sgd",
+                   help="sgd: the reference's optimiser with its duplicate listings.  adamw: torch.optim.AdamW's update in one launch "
+                        "(simt_amd/optimizer.py), every tensor listed once, heads at 10x, no weight decay on trained BatchNorm parameters.  "
+                        "--learning-rate, --weight-decay and --power keep the reference's defaults: DAFormer trains AdamW with "
+                        "--learning-rate 6e-5 --weight-decay 0.01 --power 1.0 --lr-warmup.  Default: sgd")
+    p.add_argument("--adam-betas", type=float, nargs=2, default=list(DEFAULT_BETAS), metavar=("B1", "B2"),
+                   help=f"with --optimizer adamw: the betas, each in [0, 1).  Default: {DEFAULT_BETAS[0]} {DEFAULT_BETAS[1]}")
+    p.add_argument("--adam-eps", type=float, default=DEFAULT_EPS, metavar="E", help=f"with --optimizer adamw: eps > 0.  Default: {DEFAULT_EPS}")
+    p.add_argument("--lr-warmup", type=int, nargs="?", const=1500, default=0, metavar="N",
+                   help="linear warm-up of the model's learning rate over the first N iterations (simt_amd.step.lr_at; no value: N = 1500, "
+                        "DAFormer's): the poly value times a factor rising from --lr-warmup-ratio to 1.  --learning-rate-T is not warmed up.  "
+                        "Default: 0 (off)")
+    p.add_argument("--lr-warmup-ratio", type=float, default=DEFAULT_WARMUP_RATIO, metavar="R",
+                   help=f"with --lr-warmup: the factor at iteration 0, in [0, 1].  Default: {DEFAULT_WARMUP_RATIO}")
+
+
+def optimizer_kwargs(p, args):
+    """The trainers' optimiser keywords from the flags; argparse's error naming the flag that does not fit."""
+    from simt_amd.optimizer import check_optimizer
+    try:
+        check_optimizer(args.optimizer, args.adam_betas, args.adam_eps, args.lr_warmup, args.lr_warmup_ratio)
+    except ValueError as e:
+        p.error(f"optimiser flags: {e}")
+    args.optimizer_kwargs = dict(optimizer=args.optimizer, adam_betas=tuple(args.adam_betas), adam_eps=args.adam_eps, lr_warmup=args.lr_warmup,
+                                 lr_warmup_ratio=args.lr_warmup_ratio)
+
+
+def optimizer_line(args):
+    """Said once at start-up, and only when the optimiser or the schedule is not the reference's."""
+    if args.optimizer != "sgd":
+        print(f"optimiser: {args.optimizer}, betas {args.adam_betas[0]} {args.adam_betas[1]}, eps {args.adam_eps}; every tensor listed once, heads "
+              f"at 10x lr, weight decay {args.weight_decay} (none on trained BatchNorm parameters)")
+    if args.lr_warmup:
+        print(f"learning-rate warm-up: linear over the first {args.lr_warmup} iterations from {args.lr_warmup_ratio} x the poly value")
+
+
+def model_lr(args, i_iter):
+    """The learning rate the trainer gives the model at iteration i_iter, for the loss line: lr_poly itself without --lr-warmup."""
+    return lr_at(args.learning_rate, i_iter, args.num_steps, args.power, args.lr_warmup, args.lr_warmup_ratio)
 
 
 def _teacher_every(text):
@@ -1032,8 +1078,9 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
                      args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
-                     ema_teacher_every=args.ema_teacher, teacher_view=args.weak_teacher)
+                     ema_teacher_every=args.ema_teacher, teacher_view=args.weak_teacher, **args.optimizer_kwargs)
     if rank == 0:
+        optimizer_line(args)
         teacher_line(args)
         weak_teacher_line(args)
         patch_mask_line(args)
@@ -1062,7 +1109,7 @@ def main(argv=None):
                 print("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
                       "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
                           i_iter, args.num_steps, l["loss_p1"] + l["loss_p2"], l["loss_y1"] + l["loss_y2"], l["convex"], l["volume"],
-                          l["anchor"], l["place"], lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                          l["anchor"], l["place"], model_lr(args, i_iter),
                           args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))               # :438-441 (p1+p2, y1+y2)
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
@@ -1133,8 +1180,9 @@ def main_single(args):
     eval_layers = layers if model == "v3" else None
     tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
                            device=dev, process_group=pg, arch=arch, ema_decay=args.ema, ema_teacher_every=args.ema_teacher,
-                           teacher_view=args.weak_teacher)
+                           teacher_view=args.weak_teacher, **args.optimizer_kwargs)
     if rank == 0:
+        optimizer_line(args)
         teacher_line(args)
         weak_teacher_line(args)
         patch_mask_line(args)
@@ -1162,7 +1210,7 @@ def main_single(args):
                 print("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
                       "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
                           i_iter, args.num_steps, l["loss_p"], l["loss_y"], l["convex"], l["volume"], l["anchor"], l["place"],
-                          lr_poly(args.learning_rate, i_iter, args.num_steps, args.power),
+                          model_lr(args, i_iter),
                           args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:

@@ -44,6 +44,9 @@ SOURCE_FIELDS = ("online_source",)
 # and the ImageNet feature distance (feat_dist = lambda with its classes, ratio and the SHA-256 of the frozen ImageNet trunk: DESIGN 7.22),
 # compared through value_mismatches(..., fields=FEAT_DIST_FIELDS)
 FEAT_DIST_FIELDS = ("feat_dist", "feat_dist_classes", "feat_dist_min_ratio", "feat_dist_sha256")
+# and the optimiser and the learning-rate warm-up: optimizer / adam_betas / adam_eps are written only under "adamw", lr_warmup /
+# lr_warmup_ratio only with a warm-up > 0; compared through value_mismatches(..., fields=OPTIMIZER_FIELDS)
+OPTIMIZER_FIELDS = ("optimizer", "adam_betas", "adam_eps", "lr_warmup", "lr_warmup_ratio")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -84,6 +87,17 @@ def switch_mismatches(saved, current, fields=SWITCH_FIELDS):
 def value_mismatches(saved, current, fields=VALUE_FIELDS):
     """Names of the valued keywords (absent = off) in which two `hyper` dicts differ: added, dropped, or another value."""
     return [f for f in fields if _norm(saved.get(f)) != _norm(current.get(f))]
+
+
+def optimizer_hyper(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio):
+    """The `hyper` entries of the optimiser keywords, valued fields with absent = off: the optimiser's name, betas and eps only
+    under "adamw", the warm-up's length and ratio only when it is > 0 -- nothing at the defaults, so such a dict stays what it was."""
+    hy = {}
+    if optimizer == "adamw":
+        hy.update(optimizer="adamw", adam_betas=[float(b) for b in adam_betas], adam_eps=float(adam_eps))
+    if lr_warmup:
+        hy.update(lr_warmup=int(lr_warmup), lr_warmup_ratio=float(lr_warmup_ratio))
+    return hy
 
 
 def save_atomic(obj, path):
@@ -161,6 +175,8 @@ class TrainStateMixin:
         if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
             hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
                       feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
+        hy.update(optimizer_hyper(getattr(self, "optimizer", "sgd"), getattr(self, "adam_betas", None), getattr(self, "adam_eps", None),
+                                  getattr(self, "lr_warmup", 0), getattr(self, "lr_warmup_ratio", None)))
         return hy
 
     def _nbt_steps(self, key):
@@ -187,6 +203,8 @@ class TrainStateMixin:
         the resumed run draws what the uninterrupted one draws.  With `online_labels_weighted` `hyper` also carries the mode and
         `accumulators` the last micro-batch's weights (`label_quality`); without the keyword the dict is what it was.  With `online_source`
          `hyper` also carries `online_source: True` and `accumulators` the two kept losses of the last source pass (`source_hout`).
+        With `optimizer="adamw"` the dict gains `momentum2` (Adam's second moment; `momentum` is its first) and `hyper` the
+        optimiser's name, betas and eps; with `lr_warmup` > 0 `hyper` carries it and its ratio.  Without the keywords the dict is what it was.
         With `feat_dist` `hyper` also carries lambda, the classes, the ratio and `feat_dist_sha256` -- the hash of the frozen
         ImageNet trunk, which is not stored -- and `accumulators` the three scalars of the last labelled pass (`feat_dist_out`).
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
@@ -198,6 +216,8 @@ class TrainStateMixin:
         self.plan.raise_on_fbn_error()
         ts = {"model": self.state_dict(), "momentum": {n: t.detach().cpu() for n, t in self.mom.items()}, "it_done": int(self.it_done),
               "bad_reported": int(self._bad_reported), "hyper": self._hyper_state()}
+        if getattr(self, "optimizer", "sgd") == "adamw":      # Adam's second moment (its first is `momentum`); absent under SGD
+            ts["momentum2"] = {n: t.detach().cpu() for n, t in self.mom2.items()}
         for f in NTM_FIELDS:
             if hasattr(self, f):
                 ts[f] = _host(getattr(self, f))
@@ -237,7 +257,8 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state(), fields=MIX_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -256,7 +277,8 @@ class TrainStateMixin:
         if why:
             raise ValueError(why)
         problems = []
-        for what, theirs, mine in (("momentum", ts["momentum"], self.mom), ("model", ts["model"], self.params)):
+        moments2 = [("momentum2", ts.get("momentum2", {}), self.mom2)] if getattr(self, "optimizer", "sgd") == "adamw" else []
+        for what, theirs, mine in [("momentum", ts["momentum"], self.mom), ("model", ts["model"], self.params)] + moments2:
             for n in mine:
                 if n not in theirs:
                     problems.append(f"{what} {n}: missing")
@@ -282,6 +304,9 @@ class TrainStateMixin:
                 p.copy_(ts["model"][k])
         for n, buf in self.mom.items():
             buf.copy_(ts["momentum"][n])
+        if moments2:
+            for n, buf in self.mom2.items():
+                buf.copy_(ts["momentum2"][n])
         for f in NTM_FIELDS:
             if hasattr(self, f):
                 mine, theirs = getattr(self, f), ts[f]
