@@ -6,6 +6,8 @@ Build it with `python -c "import __graft_entry__ as g; g.build()"` or `simt_amd/
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SIMT_LIB_PATH") or os.path.join(_HERE, "libsimt_hip.so")      # SIMT_LIB_PATH: A/B a scratch build (measurements only)
 
@@ -222,6 +224,14 @@ class BnFoldSeg(C.Structure):
     """simt_bn_fold_seg (include/simt_hip.h): one BatchNorm of a simt_bn_fold_multi launch."""
     _fields_ = [("gamma", c_p), ("beta", c_p), ("running_mean", c_p), ("running_var", c_p), ("scale", c_p), ("shift", c_p),
                 ("C", i32), ("reserved_", i32)]
+
+
+# the `segs` records of SgdDesc, AdamwDesc, EmaDesc and BnFoldDesc for simt_amd/multi_tensor.py, which builds the tables (csrc asserts the sizes)
+SGD_SEG = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("mult", "<i4"), ("group", "<i4")])
+ADAMW_SEG = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("group", "<i4"), ("pad", "<i4")])
+EMA_SEG = np.dtype([("w", "<u8"), ("e", "<u8"), ("n", "<i8")])
+BN_FOLD_SEG = np.dtype(BnFoldSeg)
+assert (SGD_SEG.itemsize, ADAMW_SEG.itemsize, EMA_SEG.itemsize, BN_FOLD_SEG.itemsize) == (40, 48, 24, 56)
 
 
 class BnFoldDesc(C.Structure):

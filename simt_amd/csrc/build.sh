@@ -15,7 +15,12 @@ for f in "${SRCS[@]}"; do
   b=$(basename "$f")
   o=$BUILD/${b%.hip}.o
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ conv2_common.h -nt "$o" ] || [ conv2_epilogue.h -nt "$o" ] || [ bilinear_taps.h -nt "$o" ] || [ ../../include/simt_hip.h -nt "$o" ]; then
+  stale=0
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ]; then stale=1; fi
+  for h in *.h ../../include/simt_hip.h; do      # any header here, or the C ABI, newer than the object
+    if [ "$h" -nt "$o" ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     $HIPCC $FLAGS -c "$f" -o "$o" &
     pids+=($!)
   fi

@@ -5,38 +5,38 @@
 // the optimiser it ran (single-tensor loop, foreach=False) applies the update once PER LISTING, sequentially, sharing one
 // momentum buffer.  Here the `mult` listings of an element are replayed in registers, so the whole 43 M-parameter
 // update is ONE launch instead of ~3000.
-#include "common.h"
+#include "multi_sweep.h"
 
-struct SgdSeg {
-  float* p;
-  const float* g;
-  float* buf;
-  long long n;
-  int mult;
-  int group;
-};
+// One 256-lane workgroup per (segment, chunk) entry: the sweep of multi_sweep.h, 16-byte loads and stores where p, g and buf are all aligned
+// at the chunk's start.  16 bytes per element (3 loads, 2 stores; the first step does not load buf, a launch without momentum never stores it).
+struct SgdSeg { float* p; const float* g; float* buf; long long n; int mult, group; };
+static_assert(sizeof(SgdSeg) == 40, "simt_sgd_desc.segs");
 
 struct SgdArgs {
-  const SgdSeg* segs;
-  const int* chunks;  // [nchunks][2] = (segment, first element / chunk)
-  int nchunks, chunk;
+  MultiTable<SgdSeg> t;
   float lr[4], wd[4];
   float momentum, dampening;
   int first_step;
-  const unsigned long long* skip_if;   // simt_sgd_desc.skip_if: the launch changes nothing while this device word is non-zero
 };
 
-__global__ __launch_bounds__(256) void sgd_multi_kernel(SgdArgs a) {
-  const int ch = blockIdx.x;
-  // a fused-BatchNorm launch of this step bailed out (its polling timed out: conv2_epilogue.h): its gradients are not to be applied
-  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) return;
-  const SgdSeg s = a.segs[a.chunks[2 * ch]];
-  const long long start = (long long)a.chunks[2 * ch + 1] * a.chunk;
-  long long end = start + a.chunk;
-  if (end > s.n) end = s.n;
-  const float lr = a.lr[s.group], wd = a.wd[s.group];
-  auto upd = [&](float& p, float g, float& buf) {
-    for (int r = 0; r < s.mult; ++r) {
+struct SgdOp {
+  typedef SgdSeg Seg;
+  static constexpr bool VECTOR = true;
+  template <class T> struct Vals { T p, g, buf; };
+  const SgdArgs& a;
+  float* p; const float* g; float* buf; float lr, wd; int mult;      // of the chunk: set by bind()
+  __device__ __forceinline__ long long count(const Seg& s) const { return s.n; }
+  __device__ __forceinline__ void bind(const Seg& s, long long start) {
+    p = s.p + start; g = s.g + start; buf = s.buf + start;
+    lr = a.lr[s.group]; wd = a.wd[s.group]; mult = s.mult;
+  }
+  __device__ __forceinline__ bool aligned() const { return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0; }
+  template <class T> __device__ __forceinline__ Vals<T> load(int i) const {
+    return {*(const T*)(p + i), *(const T*)(g + i), a.first_step ? multi_zero<T>() : *(const T*)(buf + i)};
+  }
+  // ONE update for both widths: the aligned and the unaligned run store the same bits
+  __device__ __forceinline__ void upd(float& p, float g, float& buf) const {
+    for (int r = 0; r < mult; ++r) {
       float d = wd != 0.f ? g + wd * p : g;
       if (a.momentum != 0.f) {
         buf = a.first_step ? d : a.momentum * buf + (1.f - a.dampening) * d;
@@ -44,116 +44,91 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(SgdArgs a) {
       }
       p = p - lr * d;
     }
-  };
-  long long i0 = start;
-  // 16-byte path (the flat gradient buffer packs tensors back to back, so a segment's gradient may start unaligned)
-  if ((((uintptr_t)(s.p + start) | (uintptr_t)(s.g + start) | (uintptr_t)(s.buf + start)) & 15) == 0) {
-    const long long n4 = (end - start) >> 2;
-    for (long long q = threadIdx.x; q < n4; q += 256) {
-      const long long i = start + (q << 2);
-      float4 p = *(const float4*)(s.p + i);
-      const float4 g = *(const float4*)(s.g + i);
-      float4 b = a.first_step ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(s.buf + i);
-      upd(p.x, g.x, b.x); upd(p.y, g.y, b.y); upd(p.z, g.z, b.z); upd(p.w, g.w, b.w);
-      *(float4*)(s.p + i) = p;
-      if (a.momentum != 0.f) *(float4*)(s.buf + i) = b;
-    }
-    i0 = start + (n4 << 2);
   }
-  for (long long i = i0 + threadIdx.x; i < end; i += 256) {
-    float p = s.p[i], g = s.g[i];
-    float buf = a.first_step ? 0.f : s.buf[i];
-    upd(p, g, buf);
-    s.p[i] = p;
-    if (a.momentum != 0.f) s.buf[i] = buf;
+  __device__ __forceinline__ void update(Vals<float>& v) const { upd(v.p, v.g, v.buf); }
+  __device__ __forceinline__ void update(Vals<float4>& v) const {
+    upd(v.p.x, v.g.x, v.buf.x); upd(v.p.y, v.g.y, v.buf.y); upd(v.p.z, v.g.z, v.buf.z); upd(v.p.w, v.g.w, v.buf.w);
   }
-}
+  template <class T> __device__ __forceinline__ void store(int i, const Vals<T>& v) const {
+    *(T*)(p + i) = v.p;
+    if (a.momentum != 0.f) *(T*)(buf + i) = v.buf;
+  }
+};
+
+__global__ __launch_bounds__(256) void sgd_multi_kernel(SgdArgs a) { multi_sweep<1>(a.t, SgdOp{a}); }
 
 extern "C" int simt_sgd_multi(const simt_sgd_desc* d, simt_stream_t stream) {
   SIMT_CHECK(d && d->segs && d->chunks && d->nchunks > 0 && d->chunk > 0);
   SgdArgs a;
-  a.segs = (const SgdSeg*)d->segs; a.chunks = (const int*)d->chunks; a.nchunks = d->nchunks; a.chunk = d->chunk;
+  a.t = {(const SgdSeg*)d->segs, (const int*)d->chunks, d->nchunks, d->chunk, (const unsigned long long*)d->skip_if};
   for (int i = 0; i < 4; ++i) { a.lr[i] = d->lr[i]; a.wd[i] = d->wd[i]; }
   a.momentum = d->momentum; a.dampening = d->dampening; a.first_step = d->first_step;
-  a.skip_if = (const unsigned long long*)d->skip_if;
   hipLaunchKernelGGL(sgd_multi_kernel, dim3(d->nchunks), dim3(256), 0, (hipStream_t)stream, a);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;
 }
 
 // Multi-tensor AdamW (decoupled weight decay), torch.optim.AdamW's single-tensor order, every tensor listed ONCE.
-// Same launch shape as sgd_multi_kernel: one 256-lane workgroup per (segment, chunk) entry, 28 bytes per element (4 loads, 3 stores; the
-// first step loads neither moment), no LDS, no atomics.  step_size = lr / (1 - beta1^t), decay = 1 - lr * wd and bc2s = sqrt(1 - beta2^t) are
-// formed by the caller in double and rounded once, as simt_adam_step_guarded does (ntm.hip).
-struct AdamwSeg {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  long long n;
-  int group;
-  int pad;
-};
+// The same sweep: 28 bytes per element (4 loads, 3 stores; the first step loads neither moment), no LDS, no atomics.
+// step_size = lr / (1 - beta1^t), decay = 1 - lr * wd and bc2s = sqrt(1 - beta2^t) are formed by the caller in double and rounded once, as
+// simt_adam_step_guarded does (ntm.hip).
+struct AdamwSeg { float* p; const float* g; float* m; float* v; long long n; int group, pad; };
+static_assert(sizeof(AdamwSeg) == 48, "simt_adamw_desc.segs");
 
 struct AdamwArgs {
-  const AdamwSeg* segs;
-  const int* chunks;  // [nchunks][2] = (segment, first element / chunk)
-  int nchunks, chunk;
+  MultiTable<AdamwSeg> t;
   float step_size[4], decay[4];
   float beta2, omb1, omb2, bc2s, eps;
   int first_step;
-  const unsigned long long* skip_if;   // simt_adamw_desc.skip_if: the launch changes nothing while this device word is non-zero
 };
 
-__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamwArgs a) {
-  const int ch = blockIdx.x;
-  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) return;
-  const AdamwSeg s = a.segs[a.chunks[2 * ch]];
-  const long long start = (long long)a.chunks[2 * ch + 1] * a.chunk;
-  long long end = start + a.chunk;
-  if (end > s.n) end = s.n;
-  const float step_size = a.step_size[s.group], decay = a.decay[s.group];
-  // ONE update for both paths: the aligned and the unaligned run store the same bits
-  auto upd = [&](float& p, float g, float& m, float& v) {
+struct AdamwOp {
+  typedef AdamwSeg Seg;
+  static constexpr bool VECTOR = true;
+  template <class T> struct Vals { T p, g, m, v; };
+  const AdamwArgs& a;
+  float* p; const float* g; float* m; float* v; float step_size, decay;      // of the chunk: set by bind()
+  __device__ __forceinline__ long long count(const Seg& s) const { return s.n; }
+  __device__ __forceinline__ void bind(const Seg& s, long long start) {
+    p = s.p + start; g = s.g + start; m = s.m + start; v = s.v + start;
+    step_size = a.step_size[s.group]; decay = a.decay[s.group];
+  }
+  __device__ __forceinline__ bool aligned() const { return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0; }
+  template <class T> __device__ __forceinline__ Vals<T> load(int i) const {
+    Vals<T> r = {*(const T*)(p + i), *(const T*)(g + i), multi_zero<T>(), multi_zero<T>()};
+    if (!a.first_step) {      // the first step creates the moments: whatever the buffers hold is not read
+      r.m = *(const T*)(m + i);
+      r.v = *(const T*)(v + i);
+    }
+    return r;
+  }
+  // ONE update for both widths: the aligned and the unaligned run store the same bits
+  __device__ __forceinline__ void upd(float& p, float g, float& m, float& v) const {
     p = p * decay;
+    // omb2 * g * g is formed in front of the branch: contraction is on in this file, and with both products inside `else` the compiler
+    // may fuse either one into the sum -- it then chose differently per float4 lane.  From here only v * beta2 can fuse, the form the
+    // kernel has always stored: fma(v, beta2, round(omb2 * g * g))  (tests/test_gpu_multi_chunk.py holds the two widths to one another)
+    const float gg = a.omb2 * g * g;
     if (a.first_step) {
       m = g * a.omb1;
-      v = a.omb2 * g * g;
+      v = gg;
     } else {
       m = m + (g - m) * a.omb1;
-      v = v * a.beta2 + a.omb2 * g * g;
+      v = v * a.beta2 + gg;
     }
     const float den = sqrtf(v) / a.bc2s + a.eps;
     p = p - step_size * (m / den);
-  };
-  long long i0 = start;
-  if ((((uintptr_t)(s.p + start) | (uintptr_t)(s.g + start) | (uintptr_t)(s.m + start) | (uintptr_t)(s.v + start)) & 15) == 0) {
-    const long long n4 = (end - start) >> 2;
-    for (long long q = threadIdx.x; q < n4; q += 256) {
-      const long long i = start + (q << 2);
-      float4 p = *(const float4*)(s.p + i);
-      const float4 g = *(const float4*)(s.g + i);
-      float4 m = make_float4(0.f, 0.f, 0.f, 0.f), v = m;
-      if (!a.first_step) {      // the first step creates the moments: whatever the buffers hold is not read
-        m = *(const float4*)(s.m + i);
-        v = *(const float4*)(s.v + i);
-      }
-      upd(p.x, g.x, m.x, v.x); upd(p.y, g.y, m.y, v.y); upd(p.z, g.z, m.z, v.z); upd(p.w, g.w, m.w, v.w);
-      *(float4*)(s.p + i) = p;
-      *(float4*)(s.m + i) = m;
-      *(float4*)(s.v + i) = v;
-    }
-    i0 = start + (n4 << 2);
   }
-  for (long long i = i0 + threadIdx.x; i < end; i += 256) {
-    float p = s.p[i], g = s.g[i], m = 0.f, v = 0.f;
-    if (!a.first_step) { m = s.m[i]; v = s.v[i]; }
-    upd(p, g, m, v);
-    s.p[i] = p;
-    s.m[i] = m;
-    s.v[i] = v;
+  __device__ __forceinline__ void update(Vals<float>& r) const { upd(r.p, r.g, r.m, r.v); }
+  __device__ __forceinline__ void update(Vals<float4>& r) const {
+    upd(r.p.x, r.g.x, r.m.x, r.v.x); upd(r.p.y, r.g.y, r.m.y, r.v.y); upd(r.p.z, r.g.z, r.m.z, r.v.z); upd(r.p.w, r.g.w, r.m.w, r.v.w);
   }
-}
+  template <class T> __device__ __forceinline__ void store(int i, const Vals<T>& r) const {
+    *(T*)(p + i) = r.p; *(T*)(m + i) = r.m; *(T*)(v + i) = r.v;
+  }
+};
+
+__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamwArgs a) { multi_sweep<1>(a.t, AdamwOp{a}); }
 
 extern "C" int simt_adamw_multi(const simt_adamw_desc* d, simt_stream_t stream) {
   SIMT_CHECK(d && d->segs && d->chunks && d->nchunks > 0 && d->chunk > 0);
@@ -161,11 +136,10 @@ extern "C" int simt_adamw_multi(const simt_adamw_desc* d, simt_stream_t stream) 
   SIMT_CHECK(__builtin_isfinite(d->omb1) && __builtin_isfinite(d->omb2) && __builtin_isfinite(d->bc2s) && d->bc2s > 0.f);
   for (int i = 0; i < 4; ++i) SIMT_CHECK(__builtin_isfinite(d->step_size[i]) && __builtin_isfinite(d->decay[i]));
   AdamwArgs a;
-  a.segs = (const AdamwSeg*)d->segs; a.chunks = (const int*)d->chunks; a.nchunks = d->nchunks; a.chunk = d->chunk;
+  a.t = {(const AdamwSeg*)d->segs, (const int*)d->chunks, d->nchunks, d->chunk, (const unsigned long long*)d->skip_if};
   for (int i = 0; i < 4; ++i) { a.step_size[i] = d->step_size[i]; a.decay[i] = d->decay[i]; }
   a.beta2 = d->beta2; a.omb1 = d->omb1; a.omb2 = d->omb2; a.bc2s = d->bc2s; a.eps = d->eps;
   a.first_step = d->first_step;
-  a.skip_if = (const unsigned long long*)d->skip_if;
   hipLaunchKernelGGL(adamw_multi_kernel, dim3(d->nchunks), dim3(256), 0, (hipStream_t)stream, a);
   SIMT_LAUNCH_CHECK();
   return SIMT_OK;

@@ -21,8 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-
-CHUNK = 65536            # elements per workgroup, as simt_sgd_multi's table
+from .multi_tensor import CHUNK, Table
 
 
 def check_decay(decay):
@@ -48,21 +47,10 @@ class WeightEma:
         self.shadow = {k: v.detach().clone() for k, v in params.items() if v.is_floating_point()}
         assert all(v.dtype == torch.float32 and v.is_contiguous() and params[k].is_contiguous() for k, v in self.shadow.items())
         recs = [(params[k].data_ptr(), e.data_ptr(), e.numel()) for k, e in self.shadow.items() if e.numel() > 0]
-        seg_dt = np.dtype([("w", "<u8"), ("e", "<u8"), ("n", "<i8")])
-        assert seg_dt.itemsize == 24
-        chunks = []
-        for si, r in enumerate(recs):
-            chunks += [(si, ci) for ci in range((r[2] + CHUNK - 1) // CHUNK)]
-        dev = next(iter(params.values())).device
-        self.segs = torch.from_numpy(np.array(recs, dtype=seg_dt).view(np.uint8).copy()).to(dev)
-        self.chunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        self.elements = sum(r[2] for r in recs)
+        table = Table(recs, L.EMA_SEG, "n", CHUNK, next(iter(params.values())).device)
+        self.segs, self.chunks, self.elements = table.segs, table.chunks, table.elements
         self._skip_if = skip_if
-        d = L.EmaDesc()
-        d.segs, d.chunks, d.nchunks, d.chunk = self.segs.data_ptr(), self.chunks.data_ptr(), len(chunks), CHUNK
-        if skip_if is not None:
-            d.skip_if = skip_if.data_ptr()
-        self.desc = d
+        self.desc = table.bind(L.EmaDesc(), skip_if)
 
     @property
     def params(self):

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .ema import CHUNK
+from .multi_tensor import CHUNK, Table
 
 FOLD_CHUNK = 256         # channels per workgroup of simt_bn_fold_multi: one per lane
 
@@ -113,37 +113,26 @@ class TeacherRefresh:
         self._keep = []
         # ---- 1. shadow -> fixed_params: the EMA kernel's word copy over a table of its own
         recs = [(ema.shadow[k].data_ptr(), floating[k].data_ptr(), n) for k, n in self.copied.items() if n > 0]
-        chunks = [(si, ci) for si, r in enumerate(recs) for ci in range((r[2] + CHUNK - 1) // CHUNK)]
-        segs = torch.from_numpy(np.array(recs, dtype=np.dtype([("w", "<u8"), ("e", "<u8"), ("n", "<i8")])).view(np.uint8).copy()).to(dev)
-        cht = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        self.elements = sum(r[2] for r in recs)
-        d = L.EmaDesc()
-        d.segs, d.chunks, d.nchunks, d.chunk, d.omd = segs.data_ptr(), cht.data_ptr(), len(chunks), CHUNK, 1.0
-        if ema._skip_if is not None:
-            d.skip_if = ema._skip_if.data_ptr()
+        copy = Table(recs, L.EMA_SEG, "n", CHUNK, dev)
+        self.elements = copy.elements
+        d = copy.bind(L.EmaDesc(), ema._skip_if)
+        d.omd = 1.0
         self.copy_desc = d
-        self._keep += [segs, cht]
+        self._keep.append(copy)
         self.launches.append((lib.simt_ema_multi, (C.byref(d),)))
         # ---- 2. every BatchNorm fold of the frozen plan in one launch
         raw = fixed_plan._pack_items_raw
         folds = [it for it in raw if it.fn is lib.simt_bn_fold]
         self.fold_desc = None
         if folds:
-            host = (L.BnFoldSeg * len(folds))()
-            fchunks = []
-            for si, it in enumerate(folds):
-                g, b, rm, rv, eps, sc, sh, Cn = it.args
-                assert eps == folds[0].args[4]
-                host[si].gamma, host[si].beta, host[si].running_mean, host[si].running_var = g, b, rm, rv
-                host[si].scale, host[si].shift, host[si].C = sc, sh, Cn
-                fchunks += [(si, ci) for ci in range((Cn + FOLD_CHUNK - 1) // FOLD_CHUNK)]
-            fsegs = torch.from_numpy(np.frombuffer(bytes(host), dtype=np.uint8).copy()).to(dev)
-            fcht = torch.tensor(fchunks, dtype=torch.int32).to(dev)
-            fd = L.BnFoldDesc()
-            fd.segs, fd.segs_host, fd.chunks = fsegs.data_ptr(), host, fcht.data_ptr()
-            fd.nsegs, fd.nchunks, fd.chunk, fd.eps = len(folds), len(fchunks), FOLD_CHUNK, folds[0].args[4]
+            eps = folds[0].args[4]
+            assert all(it.args[4] == eps for it in folds)
+            fold = Table([it.args[:4] + it.args[5:] for it in folds], L.BN_FOLD_SEG, "C", FOLD_CHUNK, dev)
+            host = (L.BnFoldSeg * len(folds)).from_buffer_copy(fold.host)      # the same records in host memory: what the library's refusals read
+            fd = fold.bind(L.BnFoldDesc())
+            fd.segs_host, fd.nsegs, fd.eps = host, len(folds), eps
             self.fold_desc = fd
-            self._keep += [host, fsegs, fcht]
+            self._keep += [host, fold]
             self.launches.append((lib.simt_bn_fold_multi, (C.byref(fd),)))
         # ---- 3. the rest of the pack list in its original order, packs coalesced: the plan's own coalesced list (engine.LaunchList.coalesce_packs,
         #         device tables included) without its folds.  The folds only read parameters, so running all of them first keeps every

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .multi_tensor import CHUNK, Table
 
 OPTIMIZERS = ("sgd", "adamw")
 DEFAULT_BETAS = (0.9, 0.999)
@@ -57,12 +58,10 @@ def adamw_constants(lrs, wds, betas, t):
     return step_size, decay, f32(b1), f32(b2), f32(1.0 - b1), f32(1.0 - b2), f32(math.sqrt(bc2))
 
 
-def adamw_table(recs, chunk=65536):
+def adamw_table(recs, chunk=CHUNK):
     """recs: (p, g, m, v device pointers, n, group) per tensor -> (segment bytes as a uint8 array, [(segment, chunk index)])."""
-    seg_dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("group", "<i4"), ("pad", "<i4")])
-    segs = np.array([tuple(r) + (0,) for r in recs], dtype=seg_dt)
-    chunks = [(si, ci) for si, r in enumerate(recs) for ci in range((r[4] + chunk - 1) // chunk)]
-    return segs.view(np.uint8).copy(), chunks
+    t = Table(recs, L.ADAMW_SEG, "n", chunk, "cpu")
+    return t.host, t.pairs
 
 
 def is_norm_parameter(name, params):
@@ -72,30 +71,33 @@ def is_norm_parameter(name, params):
 
 
 class OptimizerMixin:
-    """`_init_optimizer` (behind `_build_sgd`) and `_optim_step`, the one optimiser launch of SimTTrainer, WarmupTrainer, SimTSingleTrainer
-    and WarmupSingleTrainer.  The trainer provides params, plan.grads, mom, sgd_names, sgd_groups, sgd_desc, hp, it_done and dev."""
+    """`_build_sgd`, `_init_optimizer` (behind it) and `_optim_step`, the one optimiser launch of SimTTrainer, WarmupTrainer, SimTSingleTrainer
+    and WarmupSingleTrainer.  The trainer provides params, plan.grads, hp, it_done and dev."""
+
+    def _build_sgd(self, listing):
+        """listing: [(name, mult, group)] in table order -- the SGD launch replays a tensor's `mult` duplicate listings in registers."""
+        self.mom = {n: torch.zeros_like(self.params[n]) for n, _m, _g in listing}
+        self.sgd_names = [n for n, _m, _g in listing]
+        self.sgd_groups = {n: g for n, _m, g in listing}
+        table = Table([(self.params[n].data_ptr(), self.plan.grads[n].data_ptr(), self.mom[n].data_ptr(), self.params[n].numel(), mult, g)
+                       for n, mult, g in listing], L.SGD_SEG, "n", CHUNK, self.dev)
+        self.sgd_segs, self.sgd_chunks = table.segs, table.chunks
+        self.sgd_desc = table.bind(L.SgdDesc(), getattr(self.plan, "fbn_err", None))
+        self.sgd_desc.momentum, self.sgd_desc.dampening = self.hp.momentum, 0.0
 
     def _init_optimizer(self, optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio):
         self.optimizer, self.adam_betas, self.adam_eps, self.lr_warmup, self.lr_warmup_ratio = \
             check_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         if self.optimizer != "adamw":
             return
-        chunk = 65536
         self.mom2 = {n: torch.zeros_like(self.mom[n]) for n in self.sgd_names}
-        recs = []
-        for n in self.sgd_names:      # every applied tensor ONCE, whatever the SGD table's `mult` says
-            p, g = self.params[n], self.plan.grads[n]
-            group = self.sgd_groups[n] + (2 if is_norm_parameter(n, self.params) else 0)
-            recs.append((p.data_ptr(), g.data_ptr(), self.mom[n].data_ptr(), self.mom2[n].data_ptr(), p.numel(), group))
-        segs, chunks = adamw_table(recs, chunk)
-        self.adamw_segs = torch.from_numpy(segs).to(self.dev)
-        self.adamw_chunks = torch.tensor(chunks, dtype=torch.int32).to(self.dev)
-        d = L.AdamwDesc()
-        d.segs, d.chunks, d.nchunks, d.chunk = self.adamw_segs.data_ptr(), self.adamw_chunks.data_ptr(), len(chunks), chunk
-        d.eps = self.adam_eps
-        if getattr(self.plan, "fbn_err", None) is not None:      # the guard word of the SGD launch (engine.TrunkPlan.fbn_error)
-            d.skip_if = self.plan.fbn_err.data_ptr()
-        self.adamw_desc = d
+        group = lambda n: self.sgd_groups[n] + (2 if is_norm_parameter(n, self.params) else 0)
+        table = Table([(self.params[n].data_ptr(), self.plan.grads[n].data_ptr(), self.mom[n].data_ptr(), self.mom2[n].data_ptr(),
+                        self.params[n].numel(), group(n)) for n in self.sgd_names],      # every applied tensor ONCE, whatever the SGD table's `mult` says
+                      L.ADAMW_SEG, "n", CHUNK, self.dev)
+        self.adamw_segs, self.adamw_chunks = table.segs, table.chunks
+        self.adamw_desc = table.bind(L.AdamwDesc(), getattr(self.plan, "fbn_err", None))      # the guard word of the SGD launch
+        self.adamw_desc.eps = self.adam_eps
 
     def _optim_step(self, lr, st):
         """The optimiser launch of this step on stream `st`: group 0 at `lr`, group 1 at 10 x lr (AdamW: 2 and 3 likewise, without decay)."""

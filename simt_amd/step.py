@@ -80,6 +80,11 @@ def optim_listing(names, layers_root=("layer3", "layer4"), head_prefixes=("layer
     return g0, g1
 
 
+def sgd_listing(names, roots=("layer3", "layer4")):
+    """`optim_listing` as the [(name, mult, group)] of OptimizerMixin._build_sgd: group 0, then group 1."""
+    return [(n, mult, group) for group, listing in enumerate(optim_listing(names, layers_root=roots)) for n, mult in listing.items()]
+
+
 def check_views(tr, teacher_image, fix_item, n):
     """The weak-view arguments of a SimT trainer's step() as two lists of n = iter_size entries (None where absent); ValueError when they do
     not fit the trainer's `teacher_view`."""
@@ -214,7 +219,7 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin):
         npd.lambda_anchor, npd.gscale = hp.lambda_anchor, 1.0 / hp.iter_size
         self.post_desc = npd
         # ---- SGD segments (duplicate listings replayed in registers)
-        self._build_sgd()
+        self._build_sgd(sgd_listing(self.plan.grads.keys()))
         self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
@@ -263,35 +268,6 @@ class SimTTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin):
         order = [n for n in self.plan.grad_order if n in applied and self.plan.grad_ready.get(n, 0) > 0]
         assert order == self.plan.grad_order[:len(order)], "applied gradients must form a prefix of the flat buffer"
         return order, sizes, sum(sizes[n] for n in order)
-
-    # ------------------------------------------------------------------ optimiser plumbing
-    def _build_sgd(self, roots=("layer3", "layer4")):
-        g0, g1 = optim_listing(self.plan.grads.keys(), layers_root=roots)
-        recs = []
-        self.mom = {}
-        for group, listing in ((0, g0), (1, g1)):
-            for n, mult in listing.items():
-                p, g = self.params[n], self.plan.grads[n]
-                buf = torch.zeros_like(p)
-                self.mom[n] = buf
-                recs.append((p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), mult, group))
-        self.sgd_names = list(g0) + list(g1)
-        self.sgd_groups = {**{n: 0 for n in g0}, **{n: 1 for n in g1}}
-        seg_dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("mult", "<i4"), ("group", "<i4")])
-        segs = np.array(recs, dtype=seg_dt)
-        chunk = 65536
-        chunks = []
-        for si, r in enumerate(recs):
-            for ci in range((r[3] + chunk - 1) // chunk):
-                chunks.append((si, ci))
-        self.sgd_segs = torch.from_numpy(segs.view(np.uint8).copy()).to(self.dev)
-        self.sgd_chunks = torch.tensor(chunks, dtype=torch.int32).to(self.dev)
-        d = L.SgdDesc()
-        d.segs, d.chunks, d.nchunks, d.chunk = self.sgd_segs.data_ptr(), self.sgd_chunks.data_ptr(), len(chunks), chunk
-        d.momentum, d.dampening = self.hp.momentum, 0.0
-        if getattr(self.plan, "fbn_err", None) is not None:      # a fused BatchNorm launch that gave up polling: no update (engine.TrunkPlan.fbn_error)
-            d.skip_if = self.plan.fbn_err.data_ptr()
-        self.sgd_desc = d
 
     # ------------------------------------------------------------------ one iteration
     def _micro_batch(self, image, label, st, teacher_image=None, fix_item=None):
@@ -604,7 +580,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 2.0, -1.0, hp.lambda_seg, 0.0, 1.0 / hp.iter_size
         hd.mode = 1
         self.head_desc = hd
-        SimTTrainer._build_sgd(self, roots=("conv1", "layer1", "layer2", "layer3", "layer4"))
+        self._build_sgd(sgd_listing(self.plan.grads.keys(), roots=("conv1", "layer1", "layer2", "layer3", "layer4")))
         self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)

@@ -138,7 +138,7 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin)
         npd.lambda_seg, npd.lambda_convex, npd.lambda_volume = 0.0, hp.lambda_convex, hp.lambda_volume
         npd.lambda_anchor, npd.gscale, npd.single = hp.lambda_anchor, 1.0 / hp.iter_size, 1
         self.post_desc = npd
-        self._build_sgd()
+        self._build_sgd([(n, 1, group) for group, names in enumerate(self.optim_groups()) for n in names])      # every tensor listed once
         self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)          # ema_decay=None: no shadow, no launch (simt_amd/ema.py)
@@ -161,30 +161,6 @@ class SimTSingleTrainer(TrainStateMixin, EmaMixin, TeacherMixin, OptimizerMixin)
             g1 = [n for n in names if n.startswith(("assp.", "conv.", "conv_1."))]
             return g0, g1
         return names, []
-
-    def _build_sgd(self):
-        g0, g1 = self.optim_groups()
-        recs, self.mom = [], {}
-        for group, listing in ((0, g0), (1, g1)):
-            for n in listing:
-                p, g = self.params[n], self.plan.grads[n]
-                buf = torch.zeros_like(p)
-                self.mom[n] = buf
-                recs.append((p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), 1, group))
-        self.sgd_names = g0 + g1
-        self.sgd_groups = {**{n: 0 for n in g0}, **{n: 1 for n in g1}}
-        seg_dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("mult", "<i4"), ("group", "<i4")])
-        chunk, chunks = 65536, []
-        for si, r in enumerate(recs):
-            chunks += [(si, ci) for ci in range((r[3] + chunk - 1) // chunk)]
-        self.sgd_segs = torch.from_numpy(np.array(recs, dtype=seg_dt).view(np.uint8).copy()).to(self.dev)
-        self.sgd_chunks = torch.tensor(chunks, dtype=torch.int32).to(self.dev)
-        d = L.SgdDesc()
-        d.segs, d.chunks, d.nchunks, d.chunk = self.sgd_segs.data_ptr(), self.sgd_chunks.data_ptr(), len(chunks), chunk
-        d.momentum, d.dampening = self.hp.momentum, 0.0
-        if getattr(self.plan, "fbn_err", None) is not None:      # a fused BatchNorm launch that gave up polling: no update (engine.TrunkPlan.fbn_error)
-            d.skip_if = self.plan.fbn_err.data_ptr()
-        self.sgd_desc = d
 
     # ------------------------------------------------------------------ one iteration
     def step(self, image, label, it=None, teacher_image=None, fix_item=None):
@@ -289,7 +265,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
     DeepLabv3 interp_target is the identity behind the in-model upsample), / iter_size with the gradients accumulated over hp.iter_size
     micro-batches and one SGD step.  The checkpoint it writes is what the SimT stage restores (trainV2_simt --model DeepLabv3 | DeepLabVGG).
     Engine: the plans of SimTSingleTrainer, the fused head kernels in their one-head warm-up flavour (simt_head_desc single = 1, mode = 1),
-    the model's own optim_parameters through SimTSingleTrainer.optim_groups / _build_sgd, simt_sgd_multi."""
+    the model's own optim_parameters through SimTSingleTrainer.optim_groups, OptimizerMixin._build_sgd, simt_sgd_multi."""
 
     def __init__(self, model, state, hp, B, H, W, *, dtype=torch.bfloat16, device="cuda:0", process_group=None, arch=None, ema_decay=None,
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
@@ -380,7 +356,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         hd.th_high, hd.th_low, hd.lambda_seg, hd.lambda_place, hd.gscale = 2.0, -1.0, 0.0, 0.0, 1.0 / hp.iter_size
         hd.mode, hd.single, hd.up_half_pixel, hd.fix_logits = 1, 1, half, 0
         self.head_desc = hd
-        SimTSingleTrainer._build_sgd(self)
+        self._build_sgd([(n, 1, group) for group, names in enumerate(self.optim_groups()) for n in names])      # every tensor listed once
         self._init_optimizer(optimizer, adam_betas, adam_eps, lr_warmup, lr_warmup_ratio)
         self.it_done = 0
         self._init_ema(ema_decay)

@@ -28,7 +28,7 @@ from test_gpu_step_coherence import one_rank_group
 pytestmark = pytest.mark.gpu
 D = 0.9
 CHUNK = 65536
-SIZES = [1, 3, 4, 5, 255, 256, 257, 65535, 65536, 65537, 2 * 65536 + 4]
+SIZES = [1, 3, 4, 5, 255, 256, 257, 1028, 2048, 2052, 65535, 65536, 65537, 2 * 65536 + 4]          # (1028, 2052: 257 and 513 quads, the pair loop's edges)
 GUARD = 16                   # floats: 64 bytes on either side of every e
 SENTINEL = 0x5EADBEEF
 OMDS = [1.0, 0.5, 2.0 ** -10, float(np.float32(1 - 0.999))]
