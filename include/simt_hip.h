@@ -1097,6 +1097,45 @@ int simt_feat_dist_mask(const simt_feat_dist_mask_desc* d, simt_stream_t stream)
 int simt_feat_dist(const simt_feat_dist_desc* d, simt_stream_t stream);
 int simt_feat_dist_finalize(const simt_feat_dist_desc* d, simt_stream_t stream);
 
+/* ---- FDA: Fourier low-band style transfer of the source batch (simt_amd/data/fda.py; csrc/fda.hip) --------------------------------
+ * Fourier Domain Adaptation (Yang & Soatto, CVPR'20): the low-frequency AMPLITUDE of every source image's spectrum is replaced by that of a
+ * target image, the source PHASE is kept (so the source labels stay valid).  xs, xt [B][3][h][w] fp32 as the loaders hand them out (plane c holds
+ * colour - mean[c]); source item i is paired with target item i (simt_source_mix's pairing); x_out has the same shape.
+ * CONTRACT (tests/_fda_ref.py is its numpy restatement; the result is held to a tolerance, not bit for bit).  Per item and plane c:
+ *   S = xs + mean[c], T = xt + mean[c]: FDA is defined on the raw 0..255 image -- the mean only moves the DC coefficient, but DC's amplitude is
+ *     swapped, so it is added back first.
+ *   Omega = {(u, v): -b <= u, v <= b}, frequencies taken mod h and mod w.  For (u, v) in Omega, with F_S and F_T the DFT coefficients
+ *     F(u, v) = sum_x sum_y V[x][y] * e^{-2 pi i (u x / h + v y / w)}:
+ *     D(u, v) = |F_T(u, v)| * p(u, v) - F_S(u, v),   p = F_S / |F_S|, or 1 where |F_S| == 0 (numpy's angle(0) = 0).
+ *   x_out[x][y] = xs[x][y] + (1 / (h w)) * sum over Omega of Re(D(u, v) * e^{+2 pi i (u x / h + v y / w)}).
+ *     D is Hermitian, so only v = 0 .. b are held: v = 0 has weight 1, v > 0 weight 2.  The output is NOT clipped (the published code does not
+ *     clip either).  Only the (2b+1)^2 lowest frequencies change, so this IS the published fft2 / swap / ifft2 without either transform.
+ *   TWIDDLES come from two tables the host builds in float64 and rounds to fp32: tw_w[k] = (cos, sin)(2 pi k / w) for k < w, tw_h likewise for
+ *     h.  They are indexed by the INTEGER (v * y) mod w and (u * x) mod h: no device sinf / cosf ever sees an unreduced angle.
+ *   All arithmetic is fp32; the order of the sums is the implementation's.  b = floor(min(h, w) * beta) is the caller's.
+ * ONE call, four launches on `stream` (csrc/fda.hip): row pass over xs and xt, column pass + swap, column synthesis, apply.  Partial results
+ * are plain stores into `work` (simt_fda_workspace_bytes(B, h, w, b) bytes, 0 for a geometry the call refuses); every word that is read is
+ * written by the same call: no atomics, nothing to zero, no scratch.  xs and xt are never written.
+ * Refused with SIMT_ERR_INVALID, nothing launched and nothing written: a NULL descriptor or pointer; xs, xt, x_out or work not 16-byte, tw_h or
+ * tw_w not 8-byte aligned; x_out overlapping xs or xt; B outside 1 .. SIMT_FDA_MAX_ITEMS; h or w < 1; b < 0; 2b + 1 > min(h, w);
+ * b > SIMT_FDA_MAX_BAND; h * w >= 2^31; 3 * B * h >= 2^31 (the flat pixel rows index the grids).  Any other h, w (w % 4 != 0 takes the scalar
+ * flavour). */
+#define SIMT_FDA_MAX_ITEMS 32
+#define SIMT_FDA_MAX_BAND  64
+typedef struct {
+  const float* xs;     /* [B][3][h][w] fp32: the source images */
+  const float* xt;     /* [B][3][h][w] fp32: the target images */
+  float* x_out;        /* [B][3][h][w] fp32 */
+  const float* tw_h;   /* [h][2] fp32: (cos, sin)(2 pi k / h) */
+  const float* tw_w;   /* [w][2] fp32: (cos, sin)(2 pi k / w) */
+  void* work;          /* simt_fda_workspace_bytes(B, h, w, b) bytes */
+  int32_t B, h, w, b;
+  float mean[3];
+  int32_t reserved_;
+} simt_fda_desc;
+long simt_fda_workspace_bytes(int B, int h, int w, int b);
+int simt_fda_transfer(const simt_fda_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -318,6 +318,16 @@ class FeatDistDesc(C.Structure):
                 ("reserved_", i32)]
 
 
+FDA_MAX_ITEMS = 32       # include/simt_hip.h SIMT_FDA_MAX_ITEMS
+FDA_MAX_BAND = 64        # SIMT_FDA_MAX_BAND
+
+
+class FdaDesc(C.Structure):
+    """simt_fda_desc (include/simt_hip.h): a source batch and a target batch -> the source batch with the target's low-band amplitudes."""
+    _fields_ = [("xs", c_p), ("xt", c_p), ("x_out", c_p), ("tw_h", c_p), ("tw_w", c_p), ("work", c_p),
+                ("B", i32), ("h", i32), ("w", i32), ("b", i32), ("mean", f32 * 3), ("reserved_", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -444,6 +454,8 @@ SIGNATURES = {
     "simt_feat_dist_mask": (_I, [C.POINTER(FeatDistMaskDesc), c_p]),
     "simt_feat_dist": (_I, [C.POINTER(FeatDistDesc), c_p]),
     "simt_feat_dist_finalize": (_I, [C.POINTER(FeatDistDesc), c_p]),
+    "simt_fda_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "simt_fda_transfer": (_I, [C.POINTER(FdaDesc), c_p]),
 }
 
 _lib = None

@@ -386,3 +386,23 @@ def tta_label(maps, **kw):
         assert thr.dtype.name == "float32" and thr.flags["C_CONTIGUOUS"] and thr.size >= kw["Cn"], "thr: C contiguous float32 values"
     d = make_tta_desc(maps, **kw)
     L.call("simt_tta_label", C.byref(d), stream_ptr())
+
+
+# ---- FDA: Fourier low-band style transfer (simt_fda_transfer) -------------------------------------------------------------------------
+def fda_workspace_bytes(B, h, w, b):
+    """The bytes of simt_fda_transfer's workspace; 0 for a geometry the launch refuses."""
+    return int(L.load().simt_fda_workspace_bytes(B, h, w, b))
+
+
+def make_fda_desc(xs, xt, x_out, tw_h, tw_w, work, *, B, h, w, b, mean):
+    """No check is made here: simt_fda_transfer refuses."""
+    d = L.FdaDesc()
+    d.xs, d.xt, d.x_out, d.tw_h, d.tw_w, d.work = _p(xs), _p(xt), _p(x_out), _p(tw_h), _p(tw_w), _p(work)
+    d.B, d.h, d.w, d.b = B, h, w, b
+    d.mean[0], d.mean[1], d.mean[2] = (float(m) for m in mean)
+    return d
+
+
+def fda_transfer(d, stream=None):
+    """The four launches of simt_fda_transfer on `stream` (a raw handle) or the current stream."""
+    L.call("simt_fda_transfer", C.byref(d), stream_ptr() if stream is None else stream)

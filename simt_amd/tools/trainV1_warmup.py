@@ -46,6 +46,11 @@ times the mean L2 distance between the model's layer-4 features and those of a f
 file in DeeplabMulti's keys) over the feature cells a thing class fills to R (0.75) of their label window; mask, distance and gradient are three
 launches on the device, the ImageNet forward runs beside the model's.  The loss line gains ` fd = <feat_dist> (<cells>)`; one start-up line names the
 file, the classes and the memory of the second trunk.  --train-state refuses the flag added, dropped or changed, or another FILE.
+--fda [BETA] (needs --online-source, --batch-size <= 32): Fourier Domain Adaptation (Yang & Soatto, CVPR'20) of the source batch, a
+stage between the two loaders and the trainer's step -- the amplitude of the (2b+1)^2 lowest frequencies of source image i,
+b = floor(min(h, w) * BETA) (no value: BETA = 0.01; b <= 64), is replaced by that of the same step's target image i (the weak view where the loader
+hands one out), the phase and the labels stay: four launches on the device (simt_fda_transfer), no FFT, no random draw.  It applies to --synthetic
+source batches too.  One start-up line gives BETA, b and the band; --train-state refuses the flag added, dropped or changed.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -131,10 +136,12 @@ def get_arguments(argv=None):
     add_online_label_args(p)
     add_feat_dist_args(p)
     add_optimizer_args(p)
+    add_fda_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
     check_feat_dist_args(p, args)
+    check_fda_args(p, args)
     optimizer_kwargs(p, args)
     return args
 
@@ -230,6 +237,50 @@ def feat_dist_text(args, l):
     if getattr(args, "feat_dist", None) is None:
         return ""
     return " fd = {0:.4f} ({1:d})".format(l["feat_dist"], l["feat_dist_cells"])
+
+
+def add_fda_args(p):
+    """--fda; `check_fda_args` holds its refusals."""
+    from simt_amd.data.fda import DEFAULT_BETA
+    p.add_argument("--fda", nargs="?", const=DEFAULT_BETA, default=None, metavar="BETA",
+                   help="with --online-source: Fourier Domain Adaptation of the source batch on the device (simt_amd/data/fda.py; DESIGN 7.24) -- "
+                        "the amplitude of the (2b+1)^2 lowest frequencies of source image i, b = floor(min(h, w) * BETA), is replaced by that of "
+                        f"the same step's target image i, the phase and the labels are kept (no value: BETA = {DEFAULT_BETA}; BETA > 0, 2b + 1 <= min(h, w), "
+                        "b <= 64).  Needs --batch-size <= 32.  Default: off")
+
+
+def check_fda_args(p, args):
+    """argparse's error (exit status 2) naming the flag: --fda without --online-source, a BETA outside (0, 1), a band that does not fit the
+    crop or the launch, a batch the launch does not take."""
+    if args.fda is None:
+        return
+    if not getattr(args, "online_source", False):
+        p.error("--fda needs --online-source: it restyles the labelled source batch after the target batch of the same step")
+    from simt_amd.data.fda import MAX_ITEMS, parse
+    try:
+        parse(args.fda, tuple(map(int, args.input_size_target.split(","))))
+    except ValueError as e:
+        p.error(str(e))
+    if not 1 <= args.batch_size <= MAX_ITEMS:
+        p.error(f"--fda with --batch-size {args.batch_size}: one launch takes 1 to {MAX_ITEMS} items")
+
+
+def fda_transfer(args, B, h, w, dev, rank=0):
+    """--fda: -> the FdaTransfer of the loop (None without the flag); rank 0 prints the start-up line."""
+    if getattr(args, "fda", None) is None:
+        return None
+    from simt_amd.data.fda import FdaTransfer
+    fda = FdaTransfer(B, h, w, args.fda, dev, hold=max(1, args.iter_size))
+    if rank == 0:
+        print(f"FDA: beta = {fda.beta}, b = {fda.b}: the amplitudes of the {2 * fda.b + 1} x {2 * fda.b + 1} lowest frequencies of every source "
+              f"image are those of the same step's target image ({h}x{w}); the phase and the labels are the source's")
+    return fda
+
+
+def fda_source(fda, mb, sb):
+    """The source micro-batches with their images restyled after the target micro-batches beside them: the weak view where the loader hands
+    one out, else the image the student sees.  Labels are untouched."""
+    return [(fda(s[0], m[0] if m[2] is None else m[2]), s[1]) for m, s in zip(mb, sb)]
 
 
 def step_args(args, mb, sb=None):
@@ -355,10 +406,13 @@ def main(argv=None):
         return shutdown(world)
     data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
+    fda = fda_transfer(args, args.batch_size, h, w, dev, rank)
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
         sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
+        if fda is not None:
+            sb = fda_source(fda, mb, sb)
         a, kw = step_args(args, mb, sb)
         tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:              # :231-234 (every 100 iterations there)
@@ -447,10 +501,13 @@ def main_single(args):
         return shutdown(world)
     data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
     source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
+    fda = fda_transfer(args, args.batch_size, h, w, dev, rank)
     t0 = time.time()
     for i_iter in range(start, args.num_steps):
         mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
         sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
+        if fda is not None:
+            sb = fda_source(fda, mb, sb)
         a, kw = step_args(args, mb, sb)
         tr.step(*a, i_iter, **kw)
         if i_iter % args.print_every == 0:

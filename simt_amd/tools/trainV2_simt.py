@@ -749,7 +749,7 @@ class EmaSnapshots:
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
                 "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
-                "online_source": False, "rare_class_sampling": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_source": False, "rare_class_sampling": False, "fda": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -791,6 +791,8 @@ def run_identity(args, class_dist):
                 stats = getattr(args, "rcs_stats", None)
                 sha = hashlib.sha256(open(stats, "rb").read()).hexdigest() if not args.synthetic and stats and osp.isfile(stats) else None
                 ident["rare_class_sampling"] = [rcs[0], rcs[1], rcs[2], rcs[3], sha]
+            if getattr(args, "fda", None) is not None:
+                ident["fda"] = float(args.fda)                           # beta (it restyles --synthetic source batches too)
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident
