@@ -907,6 +907,33 @@ int simt_source_mix_items(const simt_source_mix_desc* d, uint8_t* item_out, simt
 int simt_head_loss_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream);
 int simt_head_grad_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream);
 
+/* ---- Robust entropy of the target pass (the warm-up trainers' entropy_min; csrc/head_loss.hip) ------------------------------
+ * simt_head_loss_entropy / simt_head_grad_entropy -- the mode-1 launches (two heads or single = 1) plus FDA's / ADVENT's label-free term on
+ *   EVERY pixel.  For head k and pixel p, with v the Q upsampled logits, lse their log-sum-exp and q = softmax(v) as the passes form them:
+ *     u_j  = lse - v_j                 (>= 0)
+ *     H    = sum_j q_j * u_j           (a sum of non-negative terms, NOT lse - sum_j q_j v_j)
+ *     e    = H / ln(Q)
+ *     t    = e * e + eps               eps = 1e-8f, fixed: t > 0 always
+ *     rho  = exp(eta * log(t))         any eta > 0; eta = 2 is FDA's Charbonnier penalty, eta = 0.5 MinEnt up to sqrt(eps) = 1e-4
+ *     ent_k = sum over ALL B * H * W pixels of rho / (B * H * W)     labelled or not, whatever their weight or item-map byte
+ *   hout[2] = ent_1, hout[3] = ent_2 (single: hout[3] only, hout[2] = 0).
+ *   hout[14] = hout[1] + lambda_seg * hout[0] + lambda_ent * (hout[3] + lambda_seg * hout[2]);  single: hout[1] + lambda_ent * hout[3].
+ *   hout[0], hout[1], hout[6], hout[15], conf_out and label_ws as the weighted / plain mode-1 launches give them: the cross-entropy still
+ *   divides by the number of labelled pixels.
+ *   Gradient, added to the cross-entropy's per-pixel row before the x-reduction, for every pixel of the image:
+ *     d ent / d v_j = ge_k * (2 * eta * e * rho / t) / ln(Q) * (-q_j * (H - u_j)),   ge_2 = gscale * lambda_ent / (B * H * W),
+ *     ge_1 = ge_2 * lambda_seg.
+ *   w == NULL: every weight is 1 (nw must be 0 and w_item NULL); else w, nw and w_item as in simt_head_*_weighted_n.
+ *   Every descriptor runs the run-time-count kernels, one image row per pass-2 block (g1 is [2][B][H][w][QP]).
+ *   Refused (SIMT_ERR_INVALID, nothing launched, nothing written): what simt_head_loss / simt_head_grad refuse; mode 0; Q < 2; e NULL;
+ *   lambda_ent or eta non-finite or <= 0; w NULL with a map or nw != 0; w misaligned; nw outside B .. SIMT_HEAD_WEIGHTS_MAX.  A zero lambda
+ *   is the caller's business: it issues the launches above. */
+typedef struct { float lambda_ent, eta; } simt_head_entropy;
+int simt_head_loss_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
+                           simt_stream_t stream);
+int simt_head_grad_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
+                           simt_stream_t stream);
+
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
  * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another

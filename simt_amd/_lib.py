@@ -185,6 +185,11 @@ class ClassMixU8Desc(C.Structure):
 HEAD_WEIGHTS_MAX = 64    # include/simt_hip.h SIMT_HEAD_WEIGHTS_MAX: the longest weight table of simt_head_*_weighted_n
 
 
+class HeadEntropy(C.Structure):
+    """simt_head_entropy (include/simt_hip.h): the weight and the exponent of the robust entropy term of simt_head_*_entropy."""
+    _fields_ = [("lambda_ent", f32), ("eta", f32)]
+
+
 class SourceMixDesc(C.Structure):
     """simt_source_mix_desc (include/simt_hip.h): a labelled source batch, a target batch and its teacher's byte labels -> the mixed batch."""
     _fields_ = [("xs", c_p), ("labs", c_p), ("part_s", c_p), ("xt", c_p), ("lab8", c_p), ("x_out", c_p), ("lab_out", c_p),
@@ -446,6 +451,8 @@ SIGNATURES = {
     "simt_source_mix_items": (_I, [C.POINTER(SourceMixDesc), c_p, c_p]),
     "simt_head_loss_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
     "simt_head_grad_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
+    "simt_head_loss_entropy": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadEntropy), c_p]),
+    "simt_head_grad_entropy": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadEntropy), c_p]),
     "simt_rare_crop_counts": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_rare_crop_pick": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_scale_crop_win": (_I, [C.POINTER(RareCropDesc), c_p]),

@@ -238,12 +238,13 @@ struct HeadArgs {
   const float* w;                 // simt_head_*_weighted: [B] per-item weights of the warm-up cross-entropy (device memory), else NULL
   const unsigned char* w_item;    // optional [B][H][W] (simt_head_*_weighted): the item whose weight a pixel carries
   int nw;                         // simt_head_*_weighted: the entries of w the map may name (B; simt_head_*_weighted_n: B .. SIMT_HEAD_WEIGHTS_MAX)
+  float lambda_ent, eta, inv_lnq; // simt_head_*_entropy: the term's weight (0: no such term), its exponent, 1 / ln(Q)
 };
 
 // The flavour pack of the two pass kernels: <> the SimT / DeepLab-v2 warm-up code (names as before any flavour existed), <true> ONE,
-// <false, true> VIEWS, <ONE, false, true> WEIGHTED.
+// <false, true> VIEWS, <ONE, false, true> WEIGHTED, <ONE, false, true, true> ENTROPY.
 template <bool... F_>
-constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false, false}; return v[i]; }
+constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false, false, false}; return v[i]; }
 
 // VIEWS: the frozen operand of pixel pix of item b comes from item fb = min(fix_item[pix], B - 1).  The taps index pixels from fixp's base
 // and differ from the pixel's own by a constant: one byte load and one pointer offset, no second make_taps.
@@ -259,6 +260,26 @@ __device__ __forceinline__ const float* fixp_of_item(const HeadArgs& a, const He
 __device__ __forceinline__ float weight_of_item(const HeadArgs& a, const HeadGeom& g, int b, long pix) {
   const int wb = a.w_item ? min((int)a.w_item[pix], a.nw - 1) : b;
   return a.w[wb];
+}
+
+// ENTROPY: the robust entropy term of one head at one pixel, from the upsampled logits v and what eval_head formed of them.
+//   u_j = lse - v_j >= 0,  H = sum_j q_j u_j  (non-negative terms: no cancellation where the softmax is one-hot),  e = H / ln Q,
+//   t = e^2 + 1e-8,  rho = t^eta = exp2(eta * log2 t)  (t >= 1e-8: one v_log_f32 and one v_exp_f32, as exp_le0).
+// cf = d rho / d H = 2 eta e rho / t / ln Q;  d H / d v_j = -q_j (H - u_j).
+struct EntTerm { float H, rho, cf; };
+template <int QM>
+__device__ __forceinline__ EntTerm entropy_term(const float* v, int Q, const HeadEval& e, float inv_lnq, float eta) {
+  const float inv = 1.0f / e.sum;
+  float H = 0.f;
+#pragma unroll
+  for (int j = 0; j < QM; ++j)
+    if (j < Q) H += (exp_le0(v[j] - e.vmax) * inv) * (e.lse - v[j]);
+  const float en = H * inv_lnq, t = en * en + 1e-8f;
+  EntTerm r;
+  r.H = H;
+  r.rho = __builtin_amdgcn_exp2f(eta * __builtin_amdgcn_logf(t));
+  r.cf = 2.f * eta * en * r.rho / t * inv_lnq;
+  return r;
 }
 
 // Full-wave sum with DPP row operations (no LDS crossbar): result valid in lane 63.
@@ -315,11 +336,16 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
 // so the SimT terms fold away and what is left is the warm-up cross-entropy of the flavour beside it with one multiplication per pixel and
 // head.  The compile-time-count builds keep the run-time mode: with the SimT terms gone the compiler fused the softmax's product into the
 // subtraction of the one-hot (a last-bit difference on ~0.05 % of the gradient's words), and w = 1 must give the unweighted launch bit for bit.
+// {ONE, false, true, true}: ENTROPY, the WEIGHTED run-time-count body plus the robust entropy of every live pixel, labelled or
+// not: its sums travel in the accumulators the SimT placeholder terms leave idle in mode 1 (acc[2], acc[3]).  The weight table is tested at
+// run time (a.w NULL: every weight 1.f), so one flavour serves the plain, the class-balanced and the weighted trainers.
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass1_kernel(HeadArgs a) {
   constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
+  constexpr bool ENTROPY = head_flavour<ONE_...>(3);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time");
   static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
+  static_assert(!ENTROPY || (WEIGHTED && QT == 0), "the entropy flavour is the weighted mode-1 body with run-time counts");
   const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C;
@@ -361,7 +387,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
     }
     Taps tp = make_taps(g, b, y, x);
     float wp = 1.f;                                    // WEIGHTED: the pixel's weight
-    if constexpr (WEIGHTED) { if (live) wp = weight_of_item(a, g, b, p); }
+    if constexpr (WEIGHTED) { if (live && (!ENTROPY || a.w)) wp = weight_of_item(a, g, b, p); }
     if constexpr (ONE) {
       // warm-up stage of a one-output model: CrossEntropyLoss(ignore_index=255) of its one head against the label (hout[1]); the
       // out-of-range count as in the other modes.  No frozen posterior, T, placeholder or anchor term.
@@ -380,6 +406,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
         if constexpr (WEIGHTED) l2 = wp * l2;
         acc[1] += l2; acc[8] += 1.f;
       }
+      if constexpr (ENTROPY) { if (live) acc[3] += entropy_term<QM>(v2, Q, e2, a.inv_lnq, a.eta).rho; }
       if (live && a.conf_out) a.conf_out[p] = lab_ok ? (unsigned char)lab : (unsigned char)255;
       if (live && a.label_ws) a.label_ws[p] = 255;
       continue;
@@ -432,6 +459,10 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
           if (j == conf) { l1 = e1.lse - v1[j]; l2 = e2.lse - v2[j]; }
         if constexpr (WEIGHTED) { l1 = wp * l1; l2 = wp * l2; }
         acc[0] += l1; acc[1] += l2; acc[8] += 1.f;
+      }
+      if constexpr (ENTROPY) {
+        acc[2] += entropy_term<QM>(v1, Q, e1, a.inv_lnq, a.eta).rho;
+        acc[3] += entropy_term<QM>(v2, Q, e2, a.inv_lnq, a.eta).rho;
       }
       if (e1.pseudo1 != 255) {
         acc[2] += e1.lse - e1.vmax;
@@ -664,6 +695,11 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(HeadArgs a, int nblk
     o[10] = k1; o[11] = k2; o[12] = u1; o[13] = u2;
     o[14] = o[1] + a.lambda_seg * o[0];      // warm-up total: loss_seg2 + lambda_seg * loss_seg1 (trainV1_warmup.py:224)
     o[15] = (float)sc[12];                   // pixels whose label is out of range (neither a class nor 255): the reference raises
+    if (a.lambda_ent > 0.f) {                // simt_head_loss_entropy: the mean over ALL pixels of rho, per head (one head: sc[2] = 0)
+      const double P = (double)g.B * (double)g.H * (double)g.W;
+      o[2] = (float)(sc[2] / P); o[3] = (float)(sc[3] / P);
+      o[14] = o[1] + a.lambda_seg * o[0] + a.lambda_ent * (o[3] + a.lambda_seg * o[2]);
+    }
   }
   // dTy: -(1/Ny) * sum_p [label=c] q_j / r
   float* dTy = o + 16 + 2 * QC + 4 * QMAX;
@@ -719,8 +755,10 @@ __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass2_kernel(HeadArgs a) {
   constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
+  constexpr bool ENTROPY = head_flavour<ONE_...>(3);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time (rows = 1)");
   static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
+  static_assert(!ENTROPY || (WEIGHTED && QT == 0), "the entropy flavour is the weighted mode-1 body with run-time counts (rows = 1)");
   const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C, QP = a.QP;
@@ -754,6 +792,8 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
   const float gk1 = gs * a.lambda_seg / Nk1, gk2 = gs / Nk2;
   const float gu1 = gk1 * a.lambda_place, gu2 = gk2 * a.lambda_place;
   const float gy1 = gs * a.lambda_seg / Ny, gy2 = gs / Ny;
+  // ENTROPY: gscale * lambda_ent / (B H W) for the main head, times lambda_seg for the auxiliary one
+  const float ge2 = ENTROPY ? gs * a.lambda_ent / ((float)g.B * (float)g.H * (float)g.W) : 0.f, ge1 = ge2 * a.lambda_seg;
   for (int rr = 0; rr < R; ++rr) {
   const int y = y0 + rr;
   for (int i = tid + (ONE ? g.w * Q : 0); i < 2 * g.w * Q; i += 256) sAcc[i] = 0.f;     // (ONE: the head-2 half only)
@@ -789,7 +829,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
       // WEIGHTED: the pixel's two gradient factors carry its weight (gscale * w_p / N; head 1 also lambda_seg), formed once per pixel
       float gw1 = gp1, gw2 = gp2;
       if constexpr (WEIGHTED) {
-        const float wp = live ? weight_of_item(a, g, b, pix) : 0.f;
+        const float wp = !live ? 0.f : (ENTROPY && !a.w) ? 1.f : weight_of_item(a, g, b, pix);
         gw1 = gp1 * wp; gw2 = gp2 * wp;
       }
       if constexpr (ONE) {
@@ -806,12 +846,18 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
           conf = (live && lab >= 0 && lab != 255 && lab < C) ? (int)lab : 255;
         }
         const float inv2 = 1.0f / e2.sum;
+        float H2 = 0.f, c2 = 0.f;             // ENTROPY: the pixel's entropy and ge2 * d rho / d H
+        if constexpr (ENTROPY) {
+          const EntTerm t2 = entropy_term<QM>(v2, Q, e2, a.inv_lnq, a.eta);
+          H2 = t2.H; c2 = ge2 * t2.cf;
+        }
 #pragma unroll
         for (int j = 0; j < QM; ++j)
           if (j < Q) {
             const float q2 = exp_le0(v2[j] - e2.vmax) * inv2;
             float G2 = 0.f;
             if (live && conf != 255) G2 += (WEIGHTED ? gw2 : gp2) * (q2 - ((j == conf) ? 1.f : 0.f));
+            if constexpr (ENTROPY) { if (live) G2 += c2 * (q2 * ((e2.lse - v2[j]) - H2)); }
             sG[(1 * 256 + tid) * GP + j] = G2;
           }
       } else {
@@ -865,12 +911,21 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
       }
       const float is1 = 1.0f / e1.sum2, is2 = 1.0f / e2.sum2;
       const float ir1 = lab_ok ? 1.0f / r1 : 0.f, ir2 = lab_ok ? 1.0f / r2 : 0.f;
+      float H1 = 0.f, H2 = 0.f, c1 = 0.f, c2 = 0.f;      // ENTROPY: the pixel's entropies and ge_k * d rho / d H
+      if constexpr (ENTROPY) {
+        const EntTerm t1 = entropy_term<QM>(v1, Q, e1, a.inv_lnq, a.eta), t2 = entropy_term<QM>(v2, Q, e2, a.inv_lnq, a.eta);
+        H1 = t1.H; c1 = ge1 * t1.cf; H2 = t2.H; c2 = ge2 * t2.cf;
+      }
 #pragma unroll
       for (int j = 0; j < QM; ++j)
         if (j < Q) {
           float q1 = exp_le0(v1[j] - e1.vmax) * inv1, q2 = exp_le0(v2[j] - e2.vmax) * inv2;
           float G1 = 0.f, G2 = 0.f;
           if (live) {
+            if constexpr (ENTROPY) {
+              G1 += c1 * (q1 * ((e1.lse - v1[j]) - H1));
+              G2 += c2 * (q2 * ((e2.lse - v2[j]) - H2));
+            }
             if (conf != 255) {
               float oh = (j == conf) ? 1.f : 0.f;
               G1 += (WEIGHTED ? gw1 : gp1) * (q1 - oh);
@@ -1087,6 +1142,7 @@ static int fill_args(const simt_head_desc* d, const uint8_t* fix_item, HeadArgs&
   a.label_ws = d->label_ws;
   a.fix_item = fix_item;
   a.w = nullptr; a.w_item = nullptr; a.nw = 0;
+  a.lambda_ent = 0.f; a.eta = 0.f; a.inv_lnq = 0.f;
   SIMT_CHECK(d->mode == 0 || d->mode == 1);
   SIMT_CHECK(!fix_item || d->mode == 0);      // the warm-up stage has no frozen operand to move
   return SIMT_OK;
@@ -1114,12 +1170,30 @@ static int fill_weights(const simt_head_desc* d, const float* w, int nw, const u
   return SIMT_OK;
 }
 
+// the entropy launches' side: mode 1 only; w NULL = every weight 1 (then no map and nw = 0), else as fill_weights.  Only the
+// run-time-count builds carry the flavour, so every descriptor -- (22, 19) and (25, 19) included -- runs one image row per pass-2 block.
+static int fill_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e, HeadArgs& a) {
+  SIMT_CHECK(d->mode == 1);
+  SIMT_CHECK(e != nullptr);
+  SIMT_CHECK(isfinite(e->lambda_ent) && e->lambda_ent > 0.f && isfinite(e->eta) && e->eta > 0.f);
+  SIMT_CHECK(d->Q >= 2);                      // (ln Q normalises the entropy)
+  if (w) {
+    if (int rw = fill_weights(d, w, nw, w_item, a)) return rw;
+  } else {
+    SIMT_CHECK(nw == 0 && w_item == nullptr);
+  }
+  a.lambda_ent = e->lambda_ent; a.eta = e->eta; a.inv_lnq = (float)(1.0 / log((double)d->Q));
+  a.rows = 1;
+  return SIMT_OK;
+}
+
 static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
-                            simt_stream_t stream) {
+                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
+  if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
+  else if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   hipStream_t st = (hipStream_t)stream;
   const int nblk = simt_head_nblk(d->B, d->H, d->W);
   (void)hipMemsetAsync(d->keys, 0, (2 * QMAX + 2) * sizeof(unsigned long long), st);
@@ -1132,11 +1206,19 @@ static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
     P1ATTR(24, 22, 19, false, true); P1ATTR(28, 25, 19, false, true); P1ATTR(24, 0, 0, false, true); P1ATTR(QMAX, 0, 0, false, true);
     P1ATTR(24, 0, 0, true, false, true); P1ATTR(QMAX, 0, 0, true, false, true); P1ATTR(24, 22, 19, false, false, true);
     P1ATTR(28, 25, 19, false, false, true); P1ATTR(24, 0, 0, false, false, true); P1ATTR(QMAX, 0, 0, false, false, true);
+    P1ATTR(24, 0, 0, true, false, true, true); P1ATTR(QMAX, 0, 0, true, false, true, true);
+    P1ATTR(24, 0, 0, false, false, true, true); P1ATTR(QMAX, 0, 0, false, false, true, true);
 #undef P1ATTR
   }
 #define P1(...) hipLaunchKernelGGL((head_pass1_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), lds1, st, a)
   const bool one = d->single && d->mode == 1;            // warm-up stage of a one-output model: one head, plain CE
-  if (weighted) {                                        // the dispatch below, flavour for flavour (no map: mode 1)
+  if (entropy) {                                         // run-time counts only
+    if (one && d->Q <= 24) P1(24, 0, 0, true, false, true, true);
+    else if (one) P1(QMAX, 0, 0, true, false, true, true);
+    else if (d->Q <= 24) P1(24, 0, 0, false, false, true, true);
+    else P1(QMAX, 0, 0, false, false, true, true);
+  }
+  else if (weighted) {                                   // the dispatch below, flavour for flavour (no map: mode 1)
     if (one && d->Q <= 24) P1(24, 0, 0, true, false, true);
     else if (one) P1(QMAX, 0, 0, true, false, true);
     else if (d->Q == 22 && d->C == 19) P1(24, 22, 19, false, false, true);
@@ -1169,11 +1251,12 @@ static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
 
 // gradients w.r.t. the low-res logits (pass 2 + y reduction); needs hout from simt_head_loss of the same inputs.
 static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
-                            simt_stream_t stream) {
+                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
+  if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
+  else if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   SIMT_CHECK(d->g1 && d->QP >= d->Q);
   hipStream_t st = (hipStream_t)stream;
   size_t lds2 = pass2_lds(d->Q, d->C, d->w);
@@ -1185,11 +1268,19 @@ static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
     P2ATTR(24, 22, 19, false, true); P2ATTR(28, 25, 19, false, true); P2ATTR(24, 0, 0, false, true); P2ATTR(QMAX, 0, 0, false, true);
     P2ATTR(24, 0, 0, true, false, true); P2ATTR(QMAX, 0, 0, true, false, true); P2ATTR(24, 22, 19, false, false, true);
     P2ATTR(28, 25, 19, false, false, true); P2ATTR(24, 0, 0, false, false, true); P2ATTR(QMAX, 0, 0, false, false, true);
+    P2ATTR(24, 0, 0, true, false, true, true); P2ATTR(QMAX, 0, 0, true, false, true, true);
+    P2ATTR(24, 0, 0, false, false, true, true); P2ATTR(QMAX, 0, 0, false, false, true, true);
 #undef P2ATTR
   }
 #define P2(...) hipLaunchKernelGGL((head_pass2_kernel<__VA_ARGS__>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
   const bool one = d->single && d->mode == 1;            // (fill_args: a.rows = 1)
-  if (weighted) {
+  if (entropy) {                                         // (fill_entropy: a.rows = 1)
+    if (one && d->Q <= 24) P2(24, 0, 0, true, false, true, true);
+    else if (one) P2(QMAX, 0, 0, true, false, true, true);
+    else if (d->Q <= 24) P2(24, 0, 0, false, false, true, true);
+    else P2(QMAX, 0, 0, false, false, true, true);
+  }
+  else if (weighted) {
     if (one && d->Q <= 24) P2(24, 0, 0, true, false, true);
     else if (one) P2(QMAX, 0, 0, true, false, true);
     else if (d->Q == 22 && d->C == 19) P2(24, 22, 19, false, false, true);
@@ -1242,6 +1333,16 @@ extern "C" int simt_head_loss_weighted_n(const simt_head_desc* d, const float* w
 }
 extern "C" int simt_head_grad_weighted_n(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, simt_stream_t stream) {
   return head_grad_launch(d, nullptr, true, w, nw, w_item, stream);
+}
+
+// the warm-up cross-entropy plus the robust entropy of every pixel: weights optional (NULL: every weight 1)
+extern "C" int simt_head_loss_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
+                                      simt_stream_t stream) {
+  return head_loss_launch(d, nullptr, w != nullptr, w, nw, w_item, stream, e, true);
+}
+extern "C" int simt_head_grad_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
+                                      simt_stream_t stream) {
+  return head_grad_launch(d, nullptr, w != nullptr, w, nw, w_item, stream, e, true);
 }
 
 // the one-view forms: the NULL case of the same code

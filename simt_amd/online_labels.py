@@ -52,6 +52,13 @@ Pass b: the target micro-batch as above.  With `online_mix` the mix of pass b is
 labels and `simt_source_mix` paste half of source item i's classes -- image and GROUND TRUTH -- onto target item i; with
 `online_labels_weighted` (either mode) it is `simt_source_mix_items`, and the head launches become `simt_head_loss_weighted_n` /
 `simt_head_grad_weighted_n` over a [2B] table whose entries B .. 2B-1 are 1.0f: a pasted pixel has weight 1, a target pixel its q.
+
+Entropy minimisation on the target pass (keywords `entropy_min=lambda` / `entropy_eta` / `entropy_after=N`, flags --entropy-min /
+--entropy-eta / --entropy-after): FDA's robust entropy term (eta = 2) or ADVENT's MinEnt (eta = 0.5) on EVERY pixel of the target pass, label or
+not, inside the fused head: from iteration N on the target pass's head launches are `simt_head_loss_entropy` / `simt_head_grad_entropy` with
+the weights the launches they replace would take -- none (NULL: the plain and the class-balanced trainers), q[B], or the [2B] table.  Before N,
+and in the source pass of `online_source` at every iteration, the launches are the ones above.  `losses()` gains `entropy1` / `entropy2`
+(`hout[2]`, `hout[3]`; the one-output models: `entropy2` only) while the term is on.  Nothing new is exchanged under data parallelism.
 """
 import ctypes as C
 
@@ -70,6 +77,8 @@ DEFAULT_MOMENTUM = 0.9         # IAST's exponential average of the per-class thr
 MAX_BALANCED_CLASSES = 64      # CONF_MAX_C of csrc/label_sweep.hip: the confidence histogram lives in LDS
 WEIGHTED_MODES = ("batch", "item")      # online_labels_weighted; simt_label_quality_desc.mode through _lib.LABEL_QUALITY_MODES
 MAX_WEIGHTED_ITEMS = 32        # SIMT_CLASS_MIX_MAX: one LDS word per item in the label launch, a byte per pixel in the item map
+DEFAULT_ENTROPY_LAMBDA = 0.005 # FDA's --entW
+DEFAULT_ENTROPY_ETA = 2.0      # FDA's --ita (Charbonnier penalty); 0.5: ADVENT's MinEnt up to sqrt(eps) = 1e-4
 
 
 def check_threshold(tau):
@@ -184,6 +193,39 @@ def check_source(online_source, tau):
         raise ValueError("online_source needs online_labels: the source batch is trained beside a target batch that a teacher labels, and "
                          "this trainer has no teacher")
     return bool(online_source)
+
+
+def check_entropy(entropy_min, entropy_eta, entropy_after, tau):
+    """The three keywords of the entropy term -> (lambda | None, eta, N); `tau` is check_settings' first value.  ValueError
+    that starts with the keyword that does not fit.  lambda None: off (eta and N must then be their defaults: they would change nothing)."""
+    eta = DEFAULT_ENTROPY_ETA if entropy_eta is None else entropy_eta
+    after = 0 if entropy_after is None else entropy_after
+    what = "expected the exponent of the penalty (e^2 + 1e-8)^eta, a finite eta > 0"
+    try:
+        e = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"entropy_eta {entropy_eta!r}: {what}") from None
+    if isinstance(eta, bool) or not (1.0e-38 <= e <= 3.0e38):          # (a NaN fails both comparisons; the launch takes a finite float32 > 0)
+        raise ValueError(f"entropy_eta {entropy_eta!r}: {what}")
+    if isinstance(after, bool) or not isinstance(after, (int, np.integer)) or after < 0:
+        raise ValueError(f"entropy_after {entropy_after!r}: expected the first iteration that carries the term, an integer >= 0")
+    if entropy_min is None:
+        if e != DEFAULT_ENTROPY_ETA:
+            raise ValueError("entropy_eta needs entropy_min: it shapes the entropy term, and this trainer has none")
+        if after != 0:
+            raise ValueError("entropy_after needs entropy_min: it switches the entropy term on, and this trainer has none")
+        return None, DEFAULT_ENTROPY_ETA, 0
+    what = "expected the weight of the entropy term, a finite lambda > 0 (None: no term)"
+    try:
+        lam = float(entropy_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"entropy_min {entropy_min!r}: {what}") from None
+    if isinstance(entropy_min, bool) or not (1.0e-38 <= lam <= 3.0e38):          # (likewise)
+        raise ValueError(f"entropy_min {entropy_min!r}: {what}")
+    if tau is None:
+        raise ValueError("entropy_min needs online_labels: the term is a loss on an UNLABELLED target pass, and without a teacher the only pass "
+                         "of this trainer has ground truth")
+    return lam, e, int(after)
 
 
 def label_quality(n, N, mode):
@@ -358,14 +400,46 @@ class OnlineLabelMixin(TeacherMixin):
             if self.w_item is None:        # "batch": the entries 0 .. B-1 are equal, but a pasted pixel reads entry B + i
                 self.w_item = torch.zeros(B, self.H, self.W, device=dev, dtype=torch.uint8)
 
+    def _init_entropy(self, entropy):
+        """entropy: check_entropy's triple (lambda None: off -- nothing kept, every launch the one it was).  Behind _init_online."""
+        self.entropy_min, self.entropy_eta, self.entropy_after = entropy
+        self._entropy_on, self._entropy_it = False, None
+        if self.entropy_min is not None:
+            self.entropy_rec = L.HeadEntropy(self.entropy_min, self.entropy_eta)
+
+    def _entropy_at(self, it):
+        """step(): whether the target pass of iteration `it` carries the term (FDA's switch2entropy); kept for the launches and losses()."""
+        self._entropy_it = int(it)
+        self._entropy_on = getattr(self, "entropy_min", None) is not None and int(it) >= self.entropy_after
+        return self._entropy_on
+
+    def _entropy_reported(self):
+        """losses(): whether the last step carried the term (a trainer resumed and not yet stepped: the step before `it_done`)."""
+        if getattr(self, "entropy_min", None) is None:
+            return False
+        it = self._entropy_it if self._entropy_it is not None else self.it_done - 1
+        return it >= self.entropy_after and self.it_done > 0
+
+    def _weight_args(self):
+        """The (w, nw, map) triple of the entropy launches: the table the weighted launches of this trainer read, or (NULL, 0, NULL)."""
+        if getattr(self, "online_labels_weighted", None) is None:
+            return None, 0, None
+        if self._source_table():
+            return self.label_w.data_ptr(), 2 * self.B, self.w_item.data_ptr()
+        return self.label_q.data_ptr(), self.B, None if self.w_item is None else self.w_item.data_ptr()
+
     def _source_table(self):
         """True when the weighted head launches read the [2B] table through the source mix's item map."""
         return getattr(self, "online_source", False) and self.online_mix is not None
 
     def _head_loss(self, st):
         """simt_head_loss of the micro-batch, or its weighted form (the map: the mix's item map in "item" mode, else NULL; with
-        online_source and the mix the [2B] table and the source mix's map)."""
-        if getattr(self, "online_labels_weighted", None) is None:
+        online_source and the mix the [2B] table and the source mix's map).  At an iteration that carries the entropy term (_entropy_at):
+        simt_head_loss_entropy with the same weights."""
+        if getattr(self, "_entropy_on", False):
+            w, nw, item = self._weight_args()
+            L.call("simt_head_loss_entropy", C.byref(self.head_desc), w, nw, item, C.byref(self.entropy_rec), st)
+        elif getattr(self, "online_labels_weighted", None) is None:
             L.call("simt_head_loss", C.byref(self.head_desc), st)
         elif self._source_table():
             L.call("simt_head_loss_weighted_n", C.byref(self.head_desc), self.label_w.data_ptr(), 2 * self.B, self.w_item.data_ptr(), st)
@@ -374,7 +448,10 @@ class OnlineLabelMixin(TeacherMixin):
                    None if self.w_item is None else self.w_item.data_ptr(), st)
 
     def _head_grad(self, st):
-        if getattr(self, "online_labels_weighted", None) is None:
+        if getattr(self, "_entropy_on", False):
+            w, nw, item = self._weight_args()
+            L.call("simt_head_grad_entropy", C.byref(self.head_desc), w, nw, item, C.byref(self.entropy_rec), st)
+        elif getattr(self, "online_labels_weighted", None) is None:
             L.call("simt_head_grad", C.byref(self.head_desc), st)
         elif self._source_table():
             L.call("simt_head_grad_weighted_n", C.byref(self.head_desc), self.label_w.data_ptr(), 2 * self.B, self.w_item.data_ptr(), st)
@@ -550,4 +627,9 @@ class OnlineLabelMixin(TeacherMixin):
                 out["label_quality"] = self.label_q.cpu().tolist()
             if getattr(self, "online_source", False):      # the source pass of the last micro-batch
                 out["source_seg1"], out["source_seg2"] = self.source_hout.cpu().tolist()
+            if self._entropy_reported():      # the target pass of the last micro-batch
+                e1, e2 = self.hout[2:4].cpu().tolist()
+                if not self.head_desc.single:
+                    out["entropy1"] = e1
+                out["entropy2"] = e2
         return out

@@ -30,7 +30,8 @@ from .ema_teacher import TeacherMixin
 from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
 from .feat_dist import FeatDistMixin, check_feat_dist
 from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
+from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
+                            check_weighted)
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -505,7 +506,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
-                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
+                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0):
         """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTTrainer; the defaults are the trainer it was.
         online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
@@ -531,12 +533,17 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         thing-class ImageNet feature distance -- the pass with ground-truth labels (the source pass; without online_labels the only pass) adds
         lambda * the mean L2 distance between the student's layer-4 output and that of a frozen eval-mode trunk over `feat_dist_state`, over the
         cells one class of `feat_dist_classes` (default: DAFormer's ten thing classes of the 19) fills to `feat_dist_min_ratio` (default 0.75);
-        its gradient enters the backward at layer 4's output.  `losses()` gains `feat_dist` / `feat_dist_cells`.  None: the trainer it was."""
+        its gradient enters the backward at layer 4's output.  `losses()` gains `feat_dist` / `feat_dist_cells`.  None: the trainer it was.
+        entropy_min=lambda > 0 (needs online_labels): FDA's robust entropy term on the target pass, inside the fused head -- every
+        pixel, labelled or not, adds lambda * (e^2 + 1e-8)^entropy_eta / (B H W) with e its softmax entropy / ln(C) (entropy_eta = 2: FDA's
+        penalty; 0.5: ADVENT's MinEnt), from iteration entropy_after on (FDA's switch2entropy); the source pass of online_source never carries
+        it.  `losses()` gains `entropy1` / `entropy2` while it is on.  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         source = check_source(online_source, tau)
+        entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
         fd = check_feat_dist(feat_dist, feat_dist_state, feat_dist_classes, feat_dist_min_ratio, tau, source, hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
@@ -589,6 +596,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         self._init_mix(mix)
         self._init_weighted(weighted)
         self._init_source(source)
+        self._init_entropy(entropy)
         self._init_feat_dist(*fd, feat_dist_state, dict(kw, data_parallel=process_group is not None))
         self.reducer = None
         if self.pg is not None:
@@ -608,6 +616,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         it = self.it_done if it is None else it
         lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
         st = ops.stream_ptr()
+        self._entropy_at(it)      # whether this iteration's target passes carry the entropy term (entropy_after)
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
         src_images, src_labels = self._sources(source_image, source_label, hp.iter_size)

@@ -28,7 +28,8 @@ from . import ops
 from .ema import EmaMixin
 from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
-from .online_labels import OnlineLabelMixin, check_balanced, check_mix, check_settings, check_source, check_weighted
+from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
+                            check_weighted)
 from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
 from .step import accumulate_pass, check_views, lr_at, lr_poly
 from .train_state import TrainStateMixin, state_sha256
@@ -271,7 +272,8 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
                  online_labels=None, online_labels_every=None, online_labels_balanced=None, online_labels_momentum=None,
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
-                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO):
+                 optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
+                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTSingleTrainer
         (DESIGN 7.23).  online_labels / online_labels_every / online_labels_balanced /
@@ -280,7 +282,9 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         online_mix_seed: ClassMix by the teacher's labels, as for step.WarmupTrainer; `labelled` and `label_thresholds` stay
         statistics of the teacher's labels before the mix.  online_labels_weighted: the quality weights of DACS, as for step.WarmupTrainer
         (DESIGN 7.19).  online_source: a labelled source pair in every micro-batch, as for step.WarmupTrainer.
-        feat_dist*: refused -- the ImageNet feature distance is built for DeepLab-v2 (step.WarmupTrainer) only."""
+        feat_dist*: refused -- the ImageNet feature distance is built for DeepLab-v2 (step.WarmupTrainer) only.
+        entropy_min / entropy_eta / entropy_after: the entropy term of the target pass, as for step.WarmupTrainer (one head:
+        `entropy2` only)."""
         assert model in ("v3", "vgg")
         for name, v in (("feat_dist", feat_dist), ("feat_dist_state", feat_dist_state), ("feat_dist_classes", feat_dist_classes),
                         ("feat_dist_min_ratio", feat_dist_min_ratio)):
@@ -292,6 +296,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         source = check_source(online_source, tau)
+        entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -364,6 +369,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         self._init_mix(mix)
         self._init_weighted(weighted)
         self._init_source(source)
+        self._init_entropy(entropy)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -383,6 +389,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         it = self.it_done if it is None else it
         lr = lr_at(hp.lr, it, hp.num_steps, hp.power, self.lr_warmup, self.lr_warmup_ratio)
         st = ops.stream_ptr()
+        self._entropy_at(it)      # whether this iteration's target passes carry the entropy term (entropy_after)
         images = list(image) if isinstance(image, (list, tuple)) else [image]
         labels, teachers = self._views(label, teacher_image, hp.iter_size)
         src_images, src_labels = self._sources(source_image, source_label, hp.iter_size)

@@ -51,6 +51,11 @@ stage between the two loaders and the trainer's step -- the amplitude of the (2b
 b = floor(min(h, w) * BETA) (no value: BETA = 0.01; b <= 64), is replaced by that of the same step's target image i (the weak view where the loader
 hands one out), the phase and the labels stay: four launches on the device (simt_fda_transfer), no FFT, no random draw.  It applies to --synthetic
 source batches too.  One start-up line gives BETA, b and the band; --train-state refuses the flag added, dropped or changed.
+--entropy-min [LAMBDA] (needs --online-labels): FDA's robust entropy term on the TARGET pass, inside the fused head -- every pixel,
+labelled or not, adds LAMBDA (no value: 0.005) * (e^2 + 1e-8)^ETA / (B H W), e its softmax entropy / ln(C); --entropy-eta ETA (2.0: FDA's
+Charbonnier penalty; 0.5: ADVENT's MinEnt) and --entropy-after N (0: FDA's switch2entropy -- the term is on from iteration N).  From iteration N on
+the loss line gains ` ent = <the main head's mean penalty>`; before it the line is the one without the flag.  One start-up line states the term
+and its departures; --train-state refuses the flags added, dropped or changed.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -137,11 +142,13 @@ def get_arguments(argv=None):
     add_feat_dist_args(p)
     add_optimizer_args(p)
     add_fda_args(p)
+    add_entropy_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
     check_feat_dist_args(p, args)
     check_fda_args(p, args)
+    check_entropy_args(p, args)
     optimizer_kwargs(p, args)
     return args
 
@@ -283,6 +290,56 @@ def fda_source(fda, mb, sb):
     return [(fda(s[0], m[0] if m[2] is None else m[2]), s[1]) for m, s in zip(mb, sb)]
 
 
+def add_entropy_args(p):
+    """--entropy-min / --entropy-eta / --entropy-after; `check_entropy_args` holds their refusals."""
+    from simt_amd.online_labels import DEFAULT_ENTROPY_ETA, DEFAULT_ENTROPY_LAMBDA
+    p.add_argument("--entropy-min", nargs="?", type=float, const=DEFAULT_ENTROPY_LAMBDA, default=None, metavar="LAMBDA",
+                   help="with --online-labels: FDA's robust entropy term on the target pass, in the fused head (simt_head_loss_entropy; DESIGN "
+                        f"7.25) -- LAMBDA * mean over ALL pixels of (e^2 + 1e-8)^ETA, e = softmax entropy / ln(C) (no value: LAMBDA = {DEFAULT_ENTROPY_LAMBDA})")
+    p.add_argument("--entropy-eta", type=float, default=DEFAULT_ENTROPY_ETA, metavar="ETA",
+                   help=f"the exponent of the penalty (default {DEFAULT_ENTROPY_ETA}: FDA's Charbonnier penalty; 0.5: ADVENT's MinEnt up to 1e-4)")
+    p.add_argument("--entropy-after", type=int, default=0, metavar="N",
+                   help="the first iteration that carries the term (FDA's switch2entropy; default 0: every iteration)")
+
+
+def check_entropy_args(p, args):
+    """argparse's error (exit status 2) naming the flag: --entropy-min without --online-labels, a LAMBDA or ETA that is not finite and > 0, a
+    negative N, --entropy-eta / --entropy-after without --entropy-min."""
+    from simt_amd.online_labels import check_entropy
+    if args.entropy_min is not None and args.online_labels is None:
+        p.error("--entropy-min needs --online-labels: the term is a loss on an unlabelled target pass, and without a teacher the only pass "
+                "has ground truth")
+    try:
+        check_entropy(args.entropy_min, args.entropy_eta, args.entropy_after, args.online_labels)
+    except ValueError as e:
+        msg = str(e)
+        for k in ("entropy_min", "entropy_eta", "entropy_after"):      # the keywords' names -> the flags'
+            msg = msg.replace(k, "--" + k.replace("_", "-"))
+        p.error(msg)
+
+
+def entropy_kwargs(args):
+    """The trainers' keywords of --entropy-min / --entropy-eta / --entropy-after: nothing without the flag."""
+    if getattr(args, "entropy_min", None) is None:
+        return {}
+    return {"entropy_min": args.entropy_min, "entropy_eta": args.entropy_eta, "entropy_after": args.entropy_after}
+
+
+def entropy_line(args):
+    """The start-up line of --entropy-min: the term and its departures from FDA's code."""
+    if getattr(args, "entropy_min", None) is None:
+        return
+    when = "every iteration" if args.entropy_after == 0 else f"iteration {args.entropy_after} on"
+    print(f"entropy term: lambda {args.entropy_min} * mean of (e^2 + 1e-8)^{args.entropy_eta} over the target pass, e = entropy / ln({args.num_classes}), "
+          f"from {when}, inside the fused head; departures: EVERY pixel counts (unlabelled and pasted source pixels included), eps = 1e-8 on the "
+          "normalised entropy, one lambda for both heads (the auxiliary head's share times --lambda-seg), no multi-band ensemble")
+
+
+def entropy_text(l):
+    """` ent = <hout[3]>` of the loss line: only at iterations that carry the term (losses() has `entropy2` exactly then)."""
+    return " ent = {0:.3f}".format(l["entropy2"]) if "entropy2" in l else ""
+
+
 def step_args(args, mb, sb=None):
     """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
     (image, None) and the keyword teacher_image where the loader made a weak view; sb: the micro-batches of `source_batches`
@@ -390,11 +447,12 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
                        online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs)
+                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs, **entropy_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         optimizer_line(args)
         online_label_line(args)
+        entropy_line(args)
         patch_mask_line(args, frozen=False)
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
@@ -420,7 +478,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l) + entropy_text(l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -484,11 +542,12 @@ def main_single(args):
     eval_layers = layers if model == "v3" else None
     tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
                              ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                             **balanced_kwargs(args), **args.optimizer_kwargs)
+                             **balanced_kwargs(args), **args.optimizer_kwargs, **entropy_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         optimizer_line(args)
         online_label_line(args)
+        entropy_line(args)
         patch_mask_line(args, frozen=False)
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}")
@@ -515,7 +574,7 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + entropy_text(l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

@@ -47,6 +47,9 @@ FEAT_DIST_FIELDS = ("feat_dist", "feat_dist_classes", "feat_dist_min_ratio", "fe
 # and the optimiser and the learning-rate warm-up: optimizer / adam_betas / adam_eps are written only under "adamw", lr_warmup /
 # lr_warmup_ratio only with a warm-up > 0; compared through value_mismatches(..., fields=OPTIMIZER_FIELDS)
 OPTIMIZER_FIELDS = ("optimizer", "adam_betas", "adam_eps", "lr_warmup", "lr_warmup_ratio")
+# and the entropy term of the target pass (entropy_min = lambda with its exponent and the iteration that switches it on: DESIGN 7.25),
+# written only when on; compared through value_mismatches(..., fields=ENTROPY_FIELDS)
+ENTROPY_FIELDS = ("entropy_min", "entropy_eta", "entropy_after")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -172,6 +175,8 @@ class TrainStateMixin:
                 hy["online_labels_weighted"] = str(self.online_labels_weighted)
             if getattr(self, "online_source", False):
                 hy["online_source"] = True
+            if getattr(self, "entropy_min", None) is not None:
+                hy.update(entropy_min=float(self.entropy_min), entropy_eta=float(self.entropy_eta), entropy_after=int(self.entropy_after))
         if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
             hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
                       feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
@@ -207,6 +212,8 @@ class TrainStateMixin:
         optimiser's name, betas and eps; with `lr_warmup` > 0 `hyper` carries it and its ratio.  Without the keywords the dict is what it was.
         With `feat_dist` `hyper` also carries lambda, the classes, the ratio and `feat_dist_sha256` -- the hash of the frozen
         ImageNet trunk, which is not stored -- and `accumulators` the three scalars of the last labelled pass (`feat_dist_out`).
+        With `entropy_min` `hyper` also carries lambda, eta and the iteration that switches the term on; nothing else is kept (the
+        term's two scalars ride in `hout`).
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -258,7 +265,8 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state(), fields=WEIGHTED_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=ENTROPY_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
