@@ -1163,6 +1163,70 @@ typedef struct {
 long simt_fda_workspace_bytes(int B, int h, int w, int b);
 int simt_fda_transfer(const simt_fda_desc* d, simt_stream_t stream);
 
+/* ---- ProDA's prototype weights on the teacher's output (simt_amd/proto.py; csrc/proto.hip) -----------------------------------------
+ * Zhang et al., CVPR'21: the teacher's posterior of a feature cell is weighed by how close the cell's feature lies to running class
+ * prototypes, before the label launch reads it.  F [M][ldF] (SIMT_F32 / SIMT_BF16, D columns used) is the input of the teacher's main
+ * classifier, M = B * h * w; P [M][ldp] fp32 its low-res output -- probabilities (family 0) or logits (family 1), the `fix` of the label
+ * launches; eta [C][D] fp32 the prototypes; n [C] int32 the updates every class has received (0: unseen).  Three launches.
+ * CONTRACT (tests/_proto_ref.py is its numpy restatement, float32 sequential and float64).
+ *   RECTIFY (simt_proto_rectify), per cell m.  For every class c with n[c] > 0:  s_c = sum_k ((float)F[m][k] - eta[c][k])^2 in binary32 in a
+ *     FIXED order (lane-local in element order, then the wave's xor butterfly);  d_c = sqrtf(s_c).  d_min = the minimum over the seen classes
+ *     (fminf: a NaN loses to a number).  A class with n[c] == 0 takes d_c = d_min: an unseen class is not penalised, and its row of eta is
+ *     never read.  z_c = -(d_c - d_min) / temp.  Family 0:  r_c = expf(z_c) * P[m][c],  out[m][c] = r_c / sum_c r_c  (the sum by the
+ *     butterfly over the lanes c < C).  Family 1:  out[m][c] = P[m][c] + z_c  -- the same weights in the logit domain: softmax(v + log w) =
+ *     w * softmax(v) / sum.  Columns C .. ldp-1 of out are copies of P's.  If NO class is seen, out[m][:] is P[m][:] word for word.
+ *     arg(v) = the first index of the maximum of v[0 .. C-1], a NaN counting as -inf.  conf = the maximum of out (family 0), or
+ *     1 / sum_c expf(out_c - max) (family 1).  lab[m] (one byte) = arg(out) if conf > thr and no out_c is a NaN, else 255; thr = -inf keeps
+ *     every such cell.  changed_part[g] = the number of workgroup g's cells with arg(out) != arg(P[m]) (plain store; the buffer holds
+ *     simt_proto_parts(M) words, every one written by every launch).  out and P are distinct buffers.
+ *   ACCUMULATE (simt_proto_accumulate).  Part p owns the cells 256 p .. min(256 p + 255, M - 1).  ws[(p * C + c) * D + k] = the sum, in cell
+ *     order and binary32, from +0, of (float)F[m][k] over the part's cells with lab[m] == c; behind the parts * C * D sums, as int32 words,
+ *     cnt[p * C + c] = the number of those cells.  parts = ceil(M / 256); the workspace holds simt_proto_ws_floats(M, C, D) =
+ *     parts * C * (D + 1) words, every one written by every launch.  A byte >= C (255 among them) belongs to no class.
+ *   UPDATE (simt_proto_update).  S_c[k] = the parts' sums added in part order from +0, cnt_c = the parts' counts.  For every class with
+ *     cnt_c > 0:  mean = S_c / (float)cnt_c;  n[c] == 0: eta[c] = mean, a word copy;  else a = fmaxf((float)(1.0 - momentum), 1.f / (float)(n[c] + 1))
+ *     and eta[c][k] = fmaf(a, mean[k] - eta[c][k], eta[c][k]);  then n[c] += 1.  A class with cnt_c == 0 keeps every word of eta[c] and n[c].
+ *   No atomics: every launch repeats bit for bit.
+ * Refused with SIMT_ERR_INVALID, nothing launched and nothing written: a NULL descriptor or pointer; M < 1 or M >= 2^31; C outside
+ * 2 .. SIMT_PROTO_MAX_CLASSES; D outside 8 .. SIMT_PROTO_MAX_DIM or D % 8 != 0; ldF < D or ldF % 8 != 0 (rows start on 16-byte boundaries); ldp < C; a
+ * dtype code other than SIMT_F32 / SIMT_BF16; a family other than 0 / 1; temp not a finite float > 0; a NaN thr; momentum outside [0, 1);
+ * F, eta or ws not 16-byte aligned; P, out, n or changed_part not 4-byte aligned.
+ * LDS: rectify 4 words; accumulate C * 256 * V floats (V = 4 / 2 / 1 for C <= 16 / 32 / 64: at most 64 KB); no scratch. */
+#define SIMT_PROTO_MAX_CLASSES 64
+#define SIMT_PROTO_MAX_DIM     4096
+typedef struct {
+  const void* F;           /* [M][ldF] teacher features, dtype */
+  const float* P;          /* [M][ldp] the teacher's output */
+  float* out;              /* out [M][ldp] the rectified map */
+  const float* eta;        /* [C][D] */
+  const int32_t* n;        /* [C] */
+  uint8_t* lab;            /* out [M] */
+  int32_t* changed_part;   /* out [simt_proto_parts(M)] */
+  int64_t M;
+  int32_t D, ldF, C, ldp, dtype, family;
+  float temp, thr;
+} simt_proto_rectify_desc;
+typedef struct {
+  const void* F;           /* [M][ldF] teacher features, dtype */
+  const uint8_t* lab;      /* [M] of simt_proto_rectify */
+  float* ws;               /* out [simt_proto_ws_floats(M, C, D)] */
+  int64_t M;
+  int32_t D, ldF, C, dtype;
+} simt_proto_acc_desc;
+typedef struct {
+  const float* ws;         /* [simt_proto_ws_floats(M, C, D)] of simt_proto_accumulate */
+  float* eta;              /* in/out [C][D] */
+  int32_t* n;              /* in/out [C] */
+  int64_t M;
+  int32_t D, C;
+  double momentum;
+} simt_proto_update_desc;
+int simt_proto_parts(long M);                             /* 0: an M the launch refuses */
+long simt_proto_ws_floats(long M, int C, int D);          /* 0: a geometry the launches refuse */
+int simt_proto_rectify(const simt_proto_rectify_desc* d, simt_stream_t stream);
+int simt_proto_accumulate(const simt_proto_acc_desc* d, simt_stream_t stream);
+int simt_proto_update(const simt_proto_update_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

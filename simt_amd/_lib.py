@@ -333,6 +333,27 @@ class FdaDesc(C.Structure):
                 ("B", i32), ("h", i32), ("w", i32), ("b", i32), ("mean", f32 * 3), ("reserved_", i32)]
 
 
+PROTO_MAX_CLASSES = 64  # include/simt_hip.h SIMT_PROTO_MAX_CLASSES
+PROTO_MAX_DIM = 4096    # SIMT_PROTO_MAX_DIM
+
+
+class ProtoRectifyDesc(C.Structure):
+    """simt_proto_rectify_desc (include/simt_hip.h): the teacher's features, its output and the prototypes -> the rectified map, byte labels
+    at feature resolution and the count of moved cells per workgroup."""
+    _fields_ = [("F", c_p), ("P", c_p), ("out", c_p), ("eta", c_p), ("n", c_p), ("lab", c_p), ("changed_part", c_p), ("M", C.c_int64),
+                ("D", i32), ("ldF", i32), ("C", i32), ("ldp", i32), ("dtype", i32), ("family", i32), ("temp", f32), ("thr", f32)]
+
+
+class ProtoAccDesc(C.Structure):
+    """simt_proto_acc_desc (include/simt_hip.h): the features and the byte labels -> per-part class sums and counts in the workspace."""
+    _fields_ = [("F", c_p), ("lab", c_p), ("ws", c_p), ("M", C.c_int64), ("D", i32), ("ldF", i32), ("C", i32), ("dtype", i32)]
+
+
+class ProtoUpdateDesc(C.Structure):
+    """simt_proto_update_desc (include/simt_hip.h): the workspace -> the prototypes' moving average and their update counts."""
+    _fields_ = [("ws", c_p), ("eta", c_p), ("n", c_p), ("M", C.c_int64), ("D", i32), ("C", i32), ("momentum", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -463,6 +484,11 @@ SIGNATURES = {
     "simt_feat_dist_finalize": (_I, [C.POINTER(FeatDistDesc), c_p]),
     "simt_fda_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "simt_fda_transfer": (_I, [C.POINTER(FdaDesc), c_p]),
+    "simt_proto_parts": (_I, [_L]),
+    "simt_proto_ws_floats": (_L, [_L, _I, _I]),
+    "simt_proto_rectify": (_I, [C.POINTER(ProtoRectifyDesc), c_p]),
+    "simt_proto_accumulate": (_I, [C.POINTER(ProtoAccDesc), c_p]),
+    "simt_proto_update": (_I, [C.POINTER(ProtoUpdateDesc), c_p]),
 }
 
 _lib = None

@@ -59,6 +59,11 @@ not, inside the fused head: from iteration N on the target pass's head launches 
 the weights the launches they replace would take -- none (NULL: the plain and the class-balanced trainers), q[B], or the [2B] table.  Before N,
 and in the source pass of `online_source` at every iteration, the launches are the ones above.  `losses()` gains `entropy1` / `entropy2`
 (`hout[2]`, `hout[3]`; the one-output models: `entropy2` only) while the term is on.  Nothing new is exchanged under data parallelism.
+
+Prototype weights in front of every label launch (keywords `proto_denoise=temp` / `proto_momentum=M`, flags --proto-denoise /
+--proto-momentum; simt_amd/proto.py): behind step 2 three launches weigh the teacher's low-res output by the distance of every cell's feature
+to running class prototypes, into a map of the same layout; the label launches of every mode above read that map instead -- their
+descriptors are re-pointed once -- and nothing else changes.  `losses()` gains `proto_seen` / `proto_changed`.
 """
 import ctypes as C
 
@@ -70,6 +75,7 @@ from . import ops
 from .data import class_mix
 from .ema_teacher import TeacherMixin, check_every
 from .engine import side_stream
+from .proto import ProtoMixin
 
 DEFAULT_THRESHOLD = 0.968      # DACS / DAFormer
 DEFAULT_PORTION = 0.5          # BDL's label generator keeps the more confident half of every class
@@ -265,7 +271,7 @@ def labelled_share(counts, reported):
     return (d_kept / d_total if d_total > 0 else 0.0), [kept, total]
 
 
-class OnlineLabelMixin(TeacherMixin):
+class OnlineLabelMixin(TeacherMixin, ProtoMixin):
     """The teacher's side of WarmupTrainer and WarmupSingleTrainer.  The trainer builds `fixed_params`, `fixed` (the eval-mode plan), `_fix_fwd`
     (its forward launches) and names the teacher's low-res output; this class owns the per-step launches, the counts and the read-out."""
 
@@ -538,6 +544,7 @@ class OnlineLabelMixin(TeacherMixin):
         self._fix_fwd.run()
         if not self._family:
             ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
+        self._proto_launches(st)      # with proto_denoise the label launches below read the rectified map
         if getattr(self, "online_labels_weighted", None) is not None:      # every arg-max, the counts at tau, the weights
             L.call("simt_online_label_w_u8", C.byref(self.online_w_desc), st)
             L.call("simt_label_quality", C.byref(self.quality_desc), st)
@@ -605,6 +612,7 @@ class OnlineLabelMixin(TeacherMixin):
             self._fix_fwd.run()
             if not self._family:
                 ops.softmax_rows(self._fix_out, self.ldf, self.fixp, self.ldf, self.B * self.h * self.w, self.C)
+            self._proto_launches(side.cuda_stream)      # with proto_denoise the label launches below read the rectified map
             if getattr(self, "online_labels_weighted", None) is not None:      # (the main stream waits for both below)
                 L.call("simt_online_label_w", C.byref(self.online_w_desc), side.cuda_stream)
                 L.call("simt_label_quality", C.byref(self.quality_desc), side.cuda_stream)
@@ -632,4 +640,5 @@ class OnlineLabelMixin(TeacherMixin):
                 if not self.head_desc.single:
                     out["entropy1"] = e1
                 out["entropy2"] = e2
+            self._proto_losses(out)      # proto_seen / proto_changed of the last micro-batch
         return out

@@ -32,6 +32,7 @@ from .feat_dist import FeatDistMixin, check_feat_dist
 from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
 from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
                             check_weighted)
+from .proto import DEFAULT_MOMENTUM as DEFAULT_PROTO_MOMENTUM, check_proto
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -507,7 +508,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
                  optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
-                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0):
+                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM):
         """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTTrainer; the defaults are the trainer it was.
         online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
@@ -537,7 +538,11 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         entropy_min=lambda > 0 (needs online_labels): FDA's robust entropy term on the target pass, inside the fused head -- every
         pixel, labelled or not, adds lambda * (e^2 + 1e-8)^entropy_eta / (B H W) with e its softmax entropy / ln(C) (entropy_eta = 2: FDA's
         penalty; 0.5: ADVENT's MinEnt), from iteration entropy_after on (FDA's switch2entropy); the source pass of online_source never carries
-        it.  `losses()` gains `entropy1` / `entropy2` while it is on.  None: the trainer it was."""
+        it.  `losses()` gains `entropy1` / `entropy2` while it is on.  None: the trainer it was.
+        proto_denoise=temp > 0 (simt_amd/proto.py; needs online_labels): ProDA's prototype weights -- the teacher's low-res posterior
+        is weighed by softmax(-(d - d_min) / temp), d the distance of the cell's layer-4 feature to running class prototypes (momentum
+        proto_momentum, default 0.9999), in front of the label launch of every mode; a batch is labelled with the prototypes of the batches
+        before it.  `losses()` gains `proto_seen` / `proto_changed`.  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
@@ -545,6 +550,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         source = check_source(online_source, tau)
         entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
         fd = check_feat_dist(feat_dist, feat_dist_state, feat_dist_classes, feat_dist_min_ratio, tau, source, hp.num_classes)
+        proto = check_proto(proto_denoise, proto_momentum, tau, hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -597,6 +603,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         self._init_weighted(weighted)
         self._init_source(source)
         self._init_entropy(entropy)
+        # the input of the teacher's layer-4 classifier -- the last block's output, which no later launch of the eval plan overwrites
+        self._init_proto(proto, next(hd for hd in self.fixed.heads if hd.name == "x2").feat if proto[0] is not None else None)
         self._init_feat_dist(*fd, feat_dist_state, dict(kw, data_parallel=process_group is not None))
         self.reducer = None
         if self.pg is not None:

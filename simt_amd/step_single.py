@@ -30,6 +30,7 @@ from .ema_teacher import TeacherMixin
 from .engine import LaunchList, side_stream
 from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
                             check_weighted)
+from .proto import DEFAULT_MOMENTUM as DEFAULT_PROTO_MOMENTUM, check_proto
 from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
 from .step import accumulate_pass, check_views, lr_at, lr_poly
 from .train_state import TrainStateMixin, state_sha256
@@ -273,7 +274,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
                  optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
-                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0):
+                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTSingleTrainer
         (DESIGN 7.23).  online_labels / online_labels_every / online_labels_balanced /
@@ -284,7 +285,8 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         (DESIGN 7.19).  online_source: a labelled source pair in every micro-batch, as for step.WarmupTrainer.
         feat_dist*: refused -- the ImageNet feature distance is built for DeepLab-v2 (step.WarmupTrainer) only.
         entropy_min / entropy_eta / entropy_after: the entropy term of the target pass, as for step.WarmupTrainer (one head:
-        `entropy2` only)."""
+        `entropy2` only).  proto_denoise / proto_momentum: ProDA's prototype weights in front of the label launch, as for step.WarmupTrainer
+        (DESIGN 7.26); the features are the trunk output the ASSP reads (DeepLabv3) or fc7's output (DeepLab-VGG16)."""
         assert model in ("v3", "vgg")
         for name, v in (("feat_dist", feat_dist), ("feat_dist_state", feat_dist_state), ("feat_dist_classes", feat_dist_classes),
                         ("feat_dist_min_ratio", feat_dist_min_ratio)):
@@ -297,6 +299,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         source = check_source(online_source, tau)
         entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
+        proto = check_proto(proto_denoise, proto_momentum, tau, hp.num_classes)
         self.model, self.hp, self.B, self.H, self.W, self.dtype = model, hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -370,6 +373,8 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         self._init_weighted(weighted)
         self._init_source(source)
         self._init_entropy(entropy)
+        # the input of the teacher's main classifier; neither eval plan recycles it (every activation is a buffer of its own)
+        self._init_proto(proto, None if proto[0] is None else self.fixed.feat if model == "v3" else self.fixed.heads[0].feat)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets

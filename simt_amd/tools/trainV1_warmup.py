@@ -56,6 +56,11 @@ labelled or not, adds LAMBDA (no value: 0.005) * (e^2 + 1e-8)^ETA / (B H W), e i
 Charbonnier penalty; 0.5: ADVENT's MinEnt) and --entropy-after N (0: FDA's switch2entropy -- the term is on from iteration N).  From iteration N on
 the loss line gains ` ent = <the main head's mean penalty>`; before it the line is the one without the flag.  One start-up line states the term
 and its departures; --train-state refuses the flags added, dropped or changed.
+--proto-denoise [TEMP] (needs --online-labels): ProDA's prototype weights -- in front of the label launch of every mode the teacher's
+low-res posterior is weighed by softmax(-(d - d_min) / TEMP) (no value: 1.0), d the distance of the cell's feature (the input of the teacher's
+main classifier) to running class prototypes kept on the device, momentum --proto-momentum M (0.9999).  A batch is labelled with the
+prototypes of the batches before it; the first one with the teacher's output as it is.  The loss line gains ` proto = <seen>/<C> moved <share>`.
+One start-up line states the rule and its departures; --train-state refuses the flags added, dropped or changed.  All three models.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -143,12 +148,14 @@ def get_arguments(argv=None):
     add_optimizer_args(p)
     add_fda_args(p)
     add_entropy_args(p)
+    add_proto_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
     check_feat_dist_args(p, args)
     check_fda_args(p, args)
     check_entropy_args(p, args)
+    check_proto_args(p, args)
     optimizer_kwargs(p, args)
     return args
 
@@ -340,6 +347,55 @@ def entropy_text(l):
     return " ent = {0:.3f}".format(l["entropy2"]) if "entropy2" in l else ""
 
 
+def add_proto_args(p):
+    """--proto-denoise / --proto-momentum; `check_proto_args` holds their refusals."""
+    from simt_amd.proto import DEFAULT_MOMENTUM, DEFAULT_TEMP
+    p.add_argument("--proto-denoise", nargs="?", type=float, const=DEFAULT_TEMP, default=None, metavar="TEMP",
+                   help="with --online-labels: ProDA's prototype weights on the teacher's posterior, in front of the label launch (simt_proto_rectify / "
+                        f"_accumulate / _update; DESIGN 7.26) -- softmax(-(d - d_min) / TEMP) over the distances to running class prototypes (no value: TEMP = {DEFAULT_TEMP})")
+    p.add_argument("--proto-momentum", type=float, default=None, metavar="M",
+                   help=f"the prototypes' momentum, 0 <= M < 1 (default {DEFAULT_MOMENTUM}: ProDA's)")
+
+
+def check_proto_args(p, args):
+    """argparse's error (exit status 2) naming the flag: --proto-denoise without --online-labels, a TEMP that is not finite and > 0, an M outside
+    [0, 1), --proto-momentum without --proto-denoise."""
+    from simt_amd.proto import check_proto
+    if args.proto_denoise is not None and args.online_labels is None:
+        p.error("--proto-denoise needs --online-labels: it weighs the teacher's posterior, and without the flag there is no teacher")
+    try:
+        check_proto(args.proto_denoise, args.proto_momentum, args.online_labels, args.num_classes)
+    except ValueError as e:
+        msg = str(e)
+        for k in ("proto_denoise", "proto_momentum"):      # the keywords' names -> the flags'
+            msg = msg.replace(k, "--" + k.replace("_", "-"))
+        p.error(msg)
+
+
+def proto_kwargs(args):
+    """The trainers' keywords of --proto-denoise / --proto-momentum: nothing without the flag."""
+    if getattr(args, "proto_denoise", None) is None:
+        return {}
+    from simt_amd.proto import DEFAULT_MOMENTUM
+    return {"proto_denoise": args.proto_denoise, "proto_momentum": DEFAULT_MOMENTUM if args.proto_momentum is None else args.proto_momentum}
+
+
+def proto_line(args):
+    """The start-up line of --proto-denoise: the rule and its departures from ProDA's code."""
+    if getattr(args, "proto_denoise", None) is None:
+        return
+    kw = proto_kwargs(args)
+    print(f"prototype weights: the teacher's posterior times softmax(-(d - d_min) / {kw['proto_denoise']}), d = the distance of the classifier-input "
+          f"feature to {args.num_classes} running class prototypes (momentum {kw['proto_momentum']}), then the label rule at --online-labels; "
+          "departures: the prototypes start from the first labelled batch (no dataset pass), the features are the classifier's input (no 256-d "
+          "bottleneck), no symmetric cross-entropy, no source features, prototypes per rank")
+
+
+def proto_text(args, l):
+    """` proto = <seen>/<C> moved <share>` of the loss line: only with --proto-denoise (losses() has `proto_seen` exactly then)."""
+    return " proto = {0}/{1} moved {2:.4f}".format(l["proto_seen"], args.num_classes, l["proto_changed"]) if "proto_seen" in l else ""
+
+
 def step_args(args, mb, sb=None):
     """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
     (image, None) and the keyword teacher_image where the loader made a weak view; sb: the micro-batches of `source_batches`
@@ -447,12 +503,13 @@ def main(argv=None):
     eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
     tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
                        online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs, **entropy_kwargs(args))
+                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs, **entropy_kwargs(args), **proto_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         optimizer_line(args)
         online_label_line(args)
         entropy_line(args)
+        proto_line(args)
         patch_mask_line(args, frozen=False)
         print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
@@ -478,7 +535,7 @@ def main(argv=None):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l) + entropy_text(l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:                         # :236-239
             if rank == 0:
                 print("save model ...")
@@ -542,12 +599,13 @@ def main_single(args):
     eval_layers = layers if model == "v3" else None
     tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
                              ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                             **balanced_kwargs(args), **args.optimizer_kwargs, **entropy_kwargs(args))
+                             **balanced_kwargs(args), **args.optimizer_kwargs, **entropy_kwargs(args), **proto_kwargs(args))
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         optimizer_line(args)
         online_label_line(args)
         entropy_line(args)
+        proto_line(args)
         patch_mask_line(args, frozen=False)
         print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
               f"{h}x{w}, {args.compute_dtype}")
@@ -574,7 +632,7 @@ def main_single(args):
             if rank == 0:
                 print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
                     i_iter, args.num_steps, l["loss_seg"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + entropy_text(l)))
+                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + entropy_text(l) + proto_text(args, l)))
         if i_iter >= args.num_steps_stop - 1:
             if rank == 0:
                 print("save model ...")

@@ -749,7 +749,7 @@ class EmaSnapshots:
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
                 "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
-                "online_source": False, "rare_class_sampling": False, "fda": False, "entropy_min": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_source": False, "rare_class_sampling": False, "fda": False, "entropy_min": False, "proto_denoise": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -795,6 +795,9 @@ def run_identity(args, class_dist):
                 ident["fda"] = float(args.fda)                           # beta (it restyles --synthetic source batches too)
         if getattr(args, "entropy_min", None) is not None:               # [lambda, eta, N] (trainV1_warmup --entropy-min)
             ident["entropy_min"] = [float(args.entropy_min), float(args.entropy_eta), int(args.entropy_after)]
+        if getattr(args, "proto_denoise", None) is not None:             # [temp, M] (trainV1_warmup --proto-denoise)
+            from simt_amd.proto import DEFAULT_MOMENTUM
+            ident["proto_denoise"] = [float(args.proto_denoise), float(DEFAULT_MOMENTUM if args.proto_momentum is None else args.proto_momentum)]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

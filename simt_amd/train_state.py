@@ -50,6 +50,9 @@ OPTIMIZER_FIELDS = ("optimizer", "adam_betas", "adam_eps", "lr_warmup", "lr_warm
 # and the entropy term of the target pass (entropy_min = lambda with its exponent and the iteration that switches it on: DESIGN 7.25),
 # written only when on; compared through value_mismatches(..., fields=ENTROPY_FIELDS)
 ENTROPY_FIELDS = ("entropy_min", "entropy_eta", "entropy_after")
+# and the prototype weights on the teacher's labels (proto_denoise = temp, proto_momentum = M: DESIGN 7.26), written only when on; compared
+# through value_mismatches(..., fields=PROTO_FIELDS)
+PROTO_FIELDS = ("proto_denoise", "proto_momentum")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -177,6 +180,8 @@ class TrainStateMixin:
                 hy["online_source"] = True
             if getattr(self, "entropy_min", None) is not None:
                 hy.update(entropy_min=float(self.entropy_min), entropy_eta=float(self.entropy_eta), entropy_after=int(self.entropy_after))
+            if getattr(self, "proto_denoise", None) is not None:
+                hy.update(proto_denoise=float(self.proto_denoise), proto_momentum=float(self.proto_momentum))
         if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
             hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
                       feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
@@ -214,6 +219,8 @@ class TrainStateMixin:
         ImageNet trunk, which is not stored -- and `accumulators` the three scalars of the last labelled pass (`feat_dist_out`).
         With `entropy_min` `hyper` also carries lambda, eta and the iteration that switches the term on; nothing else is kept (the
         term's two scalars ride in `hout`).
+        With `proto_denoise` `hyper` also carries temp and M and `accumulators` the prototypes, their update counts and the
+        moved-cell counts of the last micro-batch (`proto_eta`, `proto_n`, `proto_changed_part`); without the keyword the dict is what it was.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
         stored.  The one other device word `losses()` reads, the plan's sticky fused-BatchNorm error word, is not carried but CHECKED: while
         it is set the optimiser launches skip their updates yet `it_done` goes on counting, so what the trainer holds is no state of the
@@ -242,6 +249,9 @@ class TrainStateMixin:
                     ts["accumulators"]["label_quality"] = self.label_q.detach().cpu()
                 if getattr(self, "online_source", False):      # the last source pass's losses: `source_seg1` / `source_seg2` resume exactly
                     ts["accumulators"]["source_hout"] = self.source_hout.detach().cpu()
+                if getattr(self, "proto_denoise", None) is not None:      # the prototypes: the next micro-batch is labelled with them
+                    ts["accumulators"].update(proto_eta=self.proto_eta.detach().cpu(), proto_n=self.proto_n.detach().cpu(),
+                                              proto_changed_part=self.proto_changed_part.detach().cpu())
         if getattr(self, "feat_dist", None) is not None:      # the last labelled pass's three scalars: `feat_dist` / `feat_dist_cells` resume exactly
             ts["accumulators"]["feat_dist_out"] = self.fd_out.detach().cpu()
         if getattr(self, "online_mix", None) is not None:      # the position of the mix's own generator (numpy's plain dict of Python ints)
@@ -266,7 +276,8 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state(), fields=SOURCE_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=ENTROPY_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=ENTROPY_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
@@ -335,6 +346,10 @@ class TrainStateMixin:
                     self.label_q.copy_(acc["label_quality"])
                 if getattr(self, "online_source", False):
                     self.source_hout.copy_(acc["source_hout"])
+                if getattr(self, "proto_denoise", None) is not None:
+                    self.proto_eta.copy_(acc["proto_eta"])
+                    self.proto_n.copy_(acc["proto_n"])
+                    self.proto_changed_part.copy_(acc["proto_changed_part"])
         if getattr(self, "feat_dist", None) is not None:
             self.fd_out.copy_(acc["feat_dist_out"])
         self._bad_reported = int(ts["bad_reported"])
