@@ -5,7 +5,9 @@ driven by `WarmupTrainer` (simt_amd/step.py).  EVERY flag of the reference (trai
 --synthetic, Cityscapes-shaped synthetic batches.  --restore-from must exist and match (the reference's `k[6:]` prefix strip of :177
 is honoured) unless --from-scratch is given.
 --cache-dataset device [--cache-gb G], --scale-crop [S ...], --class-mix [P], --colour-jitter [S], --gaussian-blur [P] and
---mask-patches [R] [--mask-patch-size P] as in trainV2_simt (both tools share its `batches`).
+--mask-patches [R] [--mask-patch-size P] as in trainV2_simt: the flags they share, `batches` and the snapshot and train-state keepers live there,
+the device set-up and the outer loop of both tools in simt_amd/tools/train_loop.py; `main` below builds the trainer of --model
+(`build_trainer`) and hands the loop its step arguments (`step_args`), its loss line (`loss_tail`) and its evaluation.
 --train-state FILE [--train-state-every N] as in trainV2_simt: resume from FILE if it exists, keep it current (simt_amd/train_state.py).
 --ema [D] as in trainV2_simt: a weight EMA beside the trained model (simt_amd/ema.py), evaluated beside it, kept as
 GTA5_BAPA_warmup_ema_iter<i>_mIoU<m>.pth and written at the stop as GTA5_<stop>_ema.pth.
@@ -79,11 +81,12 @@ import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, WarmupTrainer
-from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, EmaSnapshots, SnapshotKeeper, TrainStateFile, add_cache_args, add_class_mix_args,
+from simt_amd.tools.train_loop import scorer, setup_devices, train
+from simt_amd.tools.trainV2_simt import (ENGINE_MODEL, MODELS, add_cache_args, add_class_mix_args,
                                           add_ema_args, add_online_label_args, add_optimizer_args, add_patch_mask_args, add_photometric_args, add_scale_crop_args,
                                           add_train_state_args, add_v3_layers, batches, check_online_label_args, check_patch_mask_args,
                                           model_lr, online_label_line, optimizer_kwargs, optimizer_line, patch_mask_line, restore, save_atomic,
-                                          shutdown, source_batches)
+                                          single_model_state, source_batches)      # (save_atomic: for those who import it from here)
 
 
 def get_arguments(argv=None):
@@ -463,108 +466,6 @@ def check_model(args):
         raise SystemExit(f"--model {args.model!r}: expected one of {', '.join(MODELS)}")
 
 
-def setup_devices(args):
-    """-> (rank, world, device, process group or None): this rank's GPU and, under torchrun (WORLD_SIZE > 1), the RCCL group."""
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if not torch.cuda.is_available():
-        raise SystemExit("trainV1_warmup needs a GPU: no CPU fallback")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    pg = None
-    if world > 1:
-        import torch.distributed as dist
-        from simt_amd.engine import reserve_streams
-        reserve_streams(dev)                                    # the plan's streams take their hardware queues before RCCL makes its own
-        os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")      # the conv tile lists leave 20 CUs to the collective's kernels (engine.TrunkPlan.cu_budget)
-        dist.init_process_group("nccl", device_id=dev)
-        pg = dist.group.WORLD
-    return rank, world, dev, pg
-
-
-def main(argv=None):
-    args = get_arguments(argv)
-    check_model(args)
-    if args.model != "DeepLab":
-        return main_single(args)
-    rank, world, dev, pg = setup_devices(args)
-    if rank == 0:
-        print("Start: " + time.asctime(time.localtime(time.time())))                       # :158
-    w, h = map(int, args.input_size_target.split(","))
-    C = args.num_classes
-    shapes = ms.state_shapes(C, 0, False)
-    state = ms.reference_init(shapes, seed=args.random_seed)
-    # trainV1_warmup.py:177: keys of the pretrained checkpoint carry a 6-character prefix (`k[6:]`); shapes are filtered
-    n = restore(state, args.restore_from, strip_prefix=6, required=not (args.synthetic or args.from_scratch))
-    hp = Hyper(num_classes=C, open_classes=0, lambda_seg=args.lambda_seg, lr=args.learning_rate, iter_size=args.iter_size,
-               momentum=args.momentum, weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
-    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
-    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    tr = WarmupTrainer(state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
-                       online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                       **balanced_kwargs(args), **feat_dist_kwargs(args, shapes, rank), **args.optimizer_kwargs, **entropy_kwargs(args), **proto_kwargs(args))
-    cd = ms.load_class_dist("bapa")
-    if rank == 0:
-        optimizer_line(args)
-        online_label_line(args)
-        entropy_line(args)
-        proto_line(args)
-        patch_mask_line(args, frozen=False)
-        print(f"restored {n} tensors; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
-        os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
-    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
-    resume = TrainStateFile(args, rank, world, cd)
-    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
-    start = resume.resume(tr, keeper)
-    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
-        return shutdown(world)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
-    source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
-    fda = fda_transfer(args, args.batch_size, h, w, dev, rank)
-    t0 = time.time()
-    for i_iter in range(start, args.num_steps):
-        mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
-        if fda is not None:
-            sb = fda_source(fda, mb, sb)
-        a, kw = step_args(args, mb, sb)
-        tr.step(*a, i_iter, **kw)
-        if i_iter % args.print_every == 0:              # :231-234 (every 100 iterations there)
-            l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
-            if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg1 = {2:.3f} loss_seg2 = {3:.3f}{6}  lr = {4:.2e}  ({5:.1f} img/s)".format(
-                    i_iter, args.num_steps, l["loss_seg1"], l["loss_seg2"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l)))
-        if i_iter >= args.num_steps_stop - 1:                         # :236-239
-            if rank == 0:
-                print("save model ...")
-                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
-            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
-            resume.write(tr, keeper)
-            break
-        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
-            # :241-256: evaluate_warmup on the validation set, keep only the best-mIoU snapshot `GTA5_BAPA_warmup_iter<i>_mIoU<m>.pth`
-            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_warmup
-            if evaluator is None:
-                evaluator = Evaluator(tr.params, num_classes=C, open_classes=0, dtype=eval_dtype, device=dev)
-            if rank == 0:
-                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            score = lambda params: evaluate_warmup(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                                   device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world, process_group=pg)
-            mIoU = score(tr.params)
-            if rank == 0:
-                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
-                keeper.best(tr.state_dict(), i_iter, mIoU)
-            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
-        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
-            # no validation set given (the reference hard-codes one, evaluate_cityscapes.py:26-28): a rolling periodic snapshot instead
-            keeper.rolling(tr.state_dict(), i_iter)
-            ema_snap.rolling(i_iter)
-        resume.after_iteration(i_iter, tr, keeper)
-    shutdown(world)
-
-
 def restore_single(state, path, model, required):
     """--restore-from of the one-output warm-up: a checkpoint in the module's keys, or a torchvision ImageNet file mapped onto them
     (simt_amd.pretrained.checkpoint_layout); then the key / shape filter of trainV2_simt.restore.  -> (tensors loaded, layout name)."""
@@ -579,27 +480,46 @@ def restore_single(state, path, model, required):
     return n, (seen[0] if seen else "no file")
 
 
-def main_single(args):
-    """--model DeepLabv3 | DeepLabVGG: the same outer loop as main() over WarmupSingleTrainer."""
+def build_trainer(args, h, w, rank, dev, pg):
+    """What --model decides: the state and its restore, the trainer (WarmupTrainer | WarmupSingleTrainer, the flags' keywords composed once for
+    both), the head of the start-up `restored` line, the model's own part of the loss line (a format of losses()) and the Evaluator's
+    model= / layers=.  -> (trainer, restored text, loss format, evaluator keywords)."""
+    C, required = args.num_classes, not (args.synthetic or args.from_scratch)
+    hyper = dict(num_classes=C, open_classes=0, lr=args.learning_rate, iter_size=args.iter_size, momentum=args.momentum,
+                 weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
+    kw = dict(dtype=torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32, device=dev, process_group=pg, ema_decay=args.ema,
+              online_labels=args.online_labels, online_labels_every=args.online_labels_every,
+              **balanced_kwargs(args), **args.optimizer_kwargs, **entropy_kwargs(args), **proto_kwargs(args))
+    if args.model == "DeepLab":
+        shapes = ms.state_shapes(C, 0, False)
+        state = ms.reference_init(shapes, seed=args.random_seed)
+        # trainV1_warmup.py:177: keys of the pretrained checkpoint carry a 6-character prefix (`k[6:]`); shapes are filtered
+        n = restore(state, args.restore_from, strip_prefix=6, required=required)
+        tr = WarmupTrainer(state, Hyper(lambda_seg=args.lambda_seg, **hyper), args.batch_size, h, w, **kw, **feat_dist_kwargs(args, shapes, rank))
+        return tr, f"restored {n} tensors", "loss_seg1 = {loss_seg1:.3f} loss_seg2 = {loss_seg2:.3f}", {}
     from simt_amd.step_single import WarmupSingleTrainer
-    from simt_amd.tools.trainV2_simt import single_model_state
-    rank, world, dev, pg = setup_devices(args)
-    if rank == 0:
-        print("Start: " + time.asctime(time.localtime(time.time())))
-    w, h = map(int, args.input_size_target.split(","))
-    C = args.num_classes
     model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
     state = single_model_state(args.model, C, layers, seed=args.random_seed)
-    n, layout = restore_single(state, args.restore_from, model, required=not (args.synthetic or args.from_scratch))
-    hp = Hyper(num_classes=C, open_classes=0, lr=args.learning_rate, iter_size=args.iter_size, momentum=args.momentum,
-               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
-    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
-    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    arch = {"layers": layers} if model == "v3" else None
-    eval_layers = layers if model == "v3" else None
-    tr = WarmupSingleTrainer(model, state, hp, args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, arch=arch,
-                             ema_decay=args.ema, online_labels=args.online_labels, online_labels_every=args.online_labels_every,
-                             **balanced_kwargs(args), **args.optimizer_kwargs, **entropy_kwargs(args), **proto_kwargs(args))
+    n, layout = restore_single(state, args.restore_from, model, required=required)
+    tr = WarmupSingleTrainer(model, state, Hyper(**hyper), args.batch_size, h, w, arch={"layers": layers} if model == "v3" else None, **kw)
+    return (tr, f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}", "loss_seg = {loss_seg:.3f}",
+            dict(model=model, layers=layers if model == "v3" else None))
+
+
+def loss_tail(args, l, source):
+    """What the flags add to the loss line behind the model's own losses, in this order; each term is "" without its flag."""
+    return (labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) +
+            feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l))
+
+
+def main(argv=None):
+    args = get_arguments(argv)
+    check_model(args)
+    rank, world, dev, pg = setup_devices(args, "trainV1_warmup needs a GPU: no CPU fallback")
+    if rank == 0:
+        print("Start: " + time.asctime(time.localtime(time.time())))                       # :158
+    w, h = map(int, args.input_size_target.split(","))
+    tr, restored, losses, eval_kw = build_trainer(args, h, w, rank, dev, pg)
     cd = ms.load_class_dist("bapa")
     if rank == 0:
         optimizer_line(args)
@@ -607,58 +527,28 @@ def main_single(args):
         entropy_line(args)
         proto_line(args)
         patch_mask_line(args, frozen=False)
-        print(f"{args.model}: restored {n} tensors ({layout} layout) from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
-              f"{h}x{w}, {args.compute_dtype}")
-        os.makedirs(args.snapshot_dir, exist_ok=True)
-    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_BAPA_warmup_iter")
-    resume = TrainStateFile(args, rank, world, cd)
-    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
-    start = resume.resume(tr, keeper)
-    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
-        return shutdown(world)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
-    source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size) if args.online_source else None
-    fda = fda_transfer(args, args.batch_size, h, w, dev, rank)
-    t0 = time.time()
-    for i_iter in range(start, args.num_steps):
-        mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
-        sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
-        if fda is not None:
-            sb = fda_source(fda, mb, sb)
-        a, kw = step_args(args, mb, sb)
-        tr.step(*a, i_iter, **kw)
-        if i_iter % args.print_every == 0:
-            l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
-            if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg = {2:.3f}{5}  lr = {3:.2e}  ({4:.1f} img/s)".format(
-                    i_iter, args.num_steps, l["loss_seg"], model_lr(args, i_iter),
-                    args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9), labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) + entropy_text(l) + proto_text(args, l)))
-        if i_iter >= args.num_steps_stop - 1:
-            if rank == 0:
-                print("save model ...")
-                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
-            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
-            resume.write(tr, keeper)
-            break
-        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
-            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
-            if evaluator is None:
-                evaluator = Evaluator(tr.params, num_classes=C, open_classes=0, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
-            if rank == 0:
-                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                                 open_classes=0, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
-                                                 process_group=pg, model=model, layers=eval_layers)
-            mIoU = score(tr.params)
-            if rank == 0:
-                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
-                keeper.best(tr.state_dict(), i_iter, mIoU)
-            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
-        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
-            keeper.rolling(tr.state_dict(), i_iter)
-            ema_snap.rolling(i_iter)
-        resume.after_iteration(i_iter, tr, keeper)
-    shutdown(world)
+        print(f"{restored}; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
+        os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186
+    source = None
+
+    def open_data(start_batch):
+        nonlocal source
+        data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start_batch)
+        source = source_batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start_batch) if args.online_source else None
+        fda = fda_transfer(args, args.batch_size, h, w, dev, rank)
+
+        def next_step():
+            mb = [next(data) for _ in range(args.iter_size)]             # gradient accumulation: iter_size micro-batches per step
+            sb = [next(source) for _ in range(args.iter_size)] if source is not None else None      # --online-source: a source pair beside each
+            if fda is not None:
+                sb = fda_source(fda, mb, sb)
+            return step_args(args, mb, sb)      # (this module's, looked up at every step)
+        return next_step
+
+    def loss_line(i_iter, l, rate):
+        return "iter = {0:8d}/{1:8d}, {2}{3}  lr = {4:.2e}  ({5:.1f} img/s)".format(
+            i_iter, args.num_steps, losses.format(**l), loss_tail(args, l, source), model_lr(args, i_iter), rate)
+    train(args, tr, "GTA5_BAPA_warmup_iter", cd, rank, world, open_data, loss_line, scorer(args, tr, 0, dev, rank, world, pg, **eval_kw))
 
 
 if __name__ == "__main__":

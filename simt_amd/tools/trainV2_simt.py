@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """SimT training stage on MI355X: the reference's tools/trainV2_simt.py with the same command-line flags
 (tools/trainV2_simt.py:72-157) driving `SimTTrainer` (simt_amd/step.py) -- the whole iteration body of the reference
-(:308-436) runs as HIP kernels; this script is only the outer loop: flags, checkpoint restore by key filter (:248-255),
-data, LR schedule, printing every 100 iterations (:438-441), snapshots (:447-450).
+(:308-436) runs as HIP kernels; this script is what surrounds it: flags, checkpoint restore by key filter (:248-255), data, the loss line
+of every 100 iterations (:438-441), the snapshot and train-state keepers.  The loop itself (step, print, snapshots :447-450, evaluation
+:452-464) and the device set-up are simt_amd/tools/train_loop.py's, shared with trainV1_warmup and the same for all three --model values:
+`main` builds the trainer of --model (`build_trainer`) and hands the loop its step arguments (`step_args`), loss line and evaluation.
 
     python -m simt_amd.tools.trainV2_simt --open-classes 15 --learning-rate 6e-4 --learning-rate-T 6e-3 ...
     torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 8 -m simt_amd.tools.trainV2_simt ...   (data parallel)
@@ -61,13 +63,13 @@ simt_amd.model).  --iter-size > 1 is implemented for DeepLab only.
 import argparse
 import os
 import os.path as osp
-import time
 
 import numpy as np
 import torch
 
 from simt_amd import model_spec as ms
 from simt_amd.step import Hyper, SimTTrainer, lr_at
+from simt_amd.tools.train_loop import scorer, setup_devices, train
 from simt_amd.train_state import save_atomic      # (its home; the tools and their users keep importing it from here)
 
 
@@ -1042,209 +1044,72 @@ def source_batches(args, B, H, W, cd, rank, world, dev, start_batch=0):
     return SourceStream(loader, ds.rare_class.min_count if rcs is not None and ds.scale_crop is not None else None)
 
 
-def shutdown(world):
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+def step_args(args, mb):
+    """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label) and, with --weak-teacher, the keywords
+    teacher_image / fix_item; the bare tensors with --iter-size 1, lists of iter_size otherwise."""
+    def col(j):
+        return mb[0][j] if args.iter_size == 1 else [m[j] for m in mb]
+    return (col(0), col(1)), ({"teacher_image": col(2), "fix_item": col(3)} if args.weak_teacher else {})
+
+
+def build_trainer(args, cd, h, w, dev, pg):
+    """What --model decides: the two states and their restore, the trainer (SimTTrainer | SimTSingleTrainer), the head of the start-up
+    `restored` line, the two segmentation losses of the loss line and the Evaluator's model= / layers=.
+    -> (trainer, restored text, losses() -> (loss_seg_p, loss_seg_y), evaluator keywords)."""
+    C, K, required = args.num_classes, args.open_classes, not (args.synthetic or args.from_scratch)
+    hp = Hyper(num_classes=C, open_classes=K, th_high=args.Threshold_high, th_low=args.Threshold_low,
+               lambda_seg=args.lambda_seg, lambda_place=args.lambda_Place, lambda_convex=args.lambda_Convex,
+               lambda_volume=args.lambda_Volume, lambda_anchor=args.lambda_Anchor, iter_size=args.iter_size,
+               lr=args.learning_rate, lr_T=args.learning_rate_T, momentum=args.momentum,
+               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
+    kw = dict(dtype=torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32, device=dev, process_group=pg, ema_decay=args.ema,
+              ema_teacher_every=args.ema_teacher, teacher_view=args.weak_teacher, **args.optimizer_kwargs)
+    if args.model == "DeepLab":
+        state = ms.reference_init(ms.state_shapes(C, K, True), seed=args.random_seed)
+        fixed = ms.reference_init(ms.state_shapes(C, 0, False), seed=args.random_seed)
+        n1 = restore(state, args.restore_from, args.not_restore_last, required=required)
+        n2 = restore(fixed, args.restore_from, required=required)
+        tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
+                         args.batch_size, h, w, **kw)
+        return tr, f"restored {n1}/{n2} tensors", lambda l: (l["loss_p1"] + l["loss_p2"], l["loss_y1"] + l["loss_y2"]), {}   # :438-441 (p1+p2, y1+y2)
+    from simt_amd.step_single import SimTSingleTrainer
+    model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
+    state, fixed = single_model_states(args.model, C, K, layers, seed=args.random_seed)
+    n1 = restore(state, args.restore_from, args.not_restore_last, required=required, last=RESTORE_LAST[args.model])
+    n2 = restore(fixed, args.restore_from, required=required)
+    tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w,
+                           arch={"layers": layers} if model == "v3" else None, **kw)
+    return (tr, f"{args.model}: restored {n1}/{n2} tensors", lambda l: (l["loss_p"], l["loss_y"]),
+            dict(model=model, layers=layers if model == "v3" else None))
 
 
 def main(argv=None):
     args = get_arguments(argv)
     check_model_args(args)
-    if args.model != "DeepLab":
-        return main_single(args)
     class_dist = load_class_dist_arg(args.class_dist, args.num_classes) if args.class_dist else None
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if not torch.cuda.is_available():
-        raise SystemExit("trainV2_simt needs a GPU: the SimT hot path has no CPU fallback")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    pg = None
-    if world > 1:
-        import torch.distributed as dist
-        from simt_amd.engine import reserve_streams
-        reserve_streams(dev)                                    # the plan's streams take their hardware queues before RCCL makes its own
-        os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")      # the conv tile lists leave 20 CUs to the collective's kernels (engine.TrunkPlan.cu_budget)
-        dist.init_process_group("nccl", device_id=dev)
-        pg = dist.group.WORLD
+    rank, world, dev, pg = setup_devices(args, "trainV2_simt needs a GPU: the SimT hot path has no CPU fallback")
     w, h = map(int, args.input_size_target.split(","))
-    C, K = args.num_classes, args.open_classes
-    state = ms.reference_init(ms.state_shapes(C, K, True), seed=args.random_seed)
-    fixed = ms.reference_init(ms.state_shapes(C, 0, False), seed=args.random_seed)
-    n1 = restore(state, args.restore_from, args.not_restore_last, required=not (args.synthetic or args.from_scratch))
-    n2 = restore(fixed, args.restore_from, required=not (args.synthetic or args.from_scratch))
     cd = class_dist if class_dist is not None else ms.load_class_dist("bapa")
-    hp = Hyper(num_classes=C, open_classes=K, th_high=args.Threshold_high, th_low=args.Threshold_low,
-               lambda_seg=args.lambda_seg, lambda_place=args.lambda_Place, lambda_convex=args.lambda_Convex,
-               lambda_volume=args.lambda_Volume, lambda_anchor=args.lambda_Anchor, iter_size=args.iter_size,
-               lr=args.learning_rate, lr_T=args.learning_rate_T, momentum=args.momentum,
-               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
-    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
-    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    tr = SimTTrainer(state, fixed, ms.ntm_init(C, K, args.random_seed + 1), ms.ntm_init(C, K, args.random_seed + 2), hp, cd,
-                     args.batch_size, h, w, dtype=dtype, device=dev, process_group=pg, ema_decay=args.ema,
-                     ema_teacher_every=args.ema_teacher, teacher_view=args.weak_teacher, **args.optimizer_kwargs)
+    tr, restored, seg_losses, eval_kw = build_trainer(args, cd, h, w, dev, pg)
     if rank == 0:
         optimizer_line(args)
         teacher_line(args)
         weak_teacher_line(args)
         patch_mask_line(args)
-        print(f"restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
-              f"{h}x{w}, {args.compute_dtype}, K={K}")
+        print(f"{restored} from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
+              f"{h}x{w}, {args.compute_dtype}, K={args.open_classes}")
         os.makedirs(args.snapshot_dir, exist_ok=True)
-    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
-    resume = TrainStateFile(args, rank, world, cd)
-    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
-    start = resume.resume(tr, keeper)
-    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
-        return shutdown(world)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
-    t0 = time.time()
-    for i_iter in range(start, args.num_steps):
-        mb = [next(data) for _ in range(args.iter_size)]           # gradient accumulation: iter_size micro-batches per step
-        img, lab = ([m[0] for m in mb], [m[1] for m in mb]) if args.iter_size > 1 else mb[0][:2]
-        if args.weak_teacher:
-            weak, item = ([m[2] for m in mb], [m[3] for m in mb]) if args.iter_size > 1 else mb[0][2:]
-            tr.step(img, lab, i_iter, teacher_image=weak, fix_item=item)
-        else:
-            tr.step(img, lab, i_iter)
-        if i_iter % args.print_every == 0:
-            l = tr.losses()                        # every rank (DP: a bad-label error is raised on all of them together)
-            if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
-                      "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
-                          i_iter, args.num_steps, l["loss_p1"] + l["loss_p2"], l["loss_y1"] + l["loss_y2"], l["convex"], l["volume"],
-                          l["anchor"], l["place"], model_lr(args, i_iter),
-                          args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))               # :438-441 (p1+p2, y1+y2)
-        if i_iter >= args.num_steps_stop - 1:
-            if rank == 0:
-                print("save model ...")
-                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))   # :447-450
-            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
-            resume.write(tr, keeper)
-            break
-        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
-            # :452-464: evaluate, keep only the best-mIoU snapshot
-            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
-            if evaluator is None:
-                evaluator = Evaluator(tr.params, num_classes=C, open_classes=K, dtype=eval_dtype, device=dev)
-            if rank == 0:
-                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
-                                                 process_group=pg)
-            mIoU = score(tr.params)
-            if rank == 0:
-                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
-                keeper.best(tr.state_dict(), i_iter, mIoU)
-            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
-        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
-            # no validation set given (the reference hard-codes one, :452-464): without an evaluation there is no best-mIoU snapshot,
-            # so keep a rolling periodic one -- a crash must not lose the run
-            keeper.rolling(tr.state_dict(), i_iter)
-            ema_snap.rolling(i_iter)
-        resume.after_iteration(i_iter, tr, keeper)
-    shutdown(world)
 
+    def open_data(start_batch):
+        data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start_batch)
+        # gradient accumulation: iter_size micro-batches per step (check_model_args: 1 for the one-output models)
+        return lambda: step_args(args, [next(data) for _ in range(args.iter_size)])
 
-def main_single(args):
-    """--model DeepLabv3 | DeepLabVGG: the same outer loop as main() over SimTSingleTrainer."""
-    from simt_amd.step_single import SimTSingleTrainer
-    class_dist = load_class_dist_arg(args.class_dist, args.num_classes) if args.class_dist else None
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if not torch.cuda.is_available():
-        raise SystemExit("trainV2_simt needs a GPU: the SimT hot path has no CPU fallback")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    pg = None
-    if world > 1:
-        import torch.distributed as dist
-        from simt_amd.engine import reserve_streams
-        reserve_streams(dev)
-        os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")
-        dist.init_process_group("nccl", device_id=dev)
-        pg = dist.group.WORLD
-    w, h = map(int, args.input_size_target.split(","))
-    C, K = args.num_classes, args.open_classes
-    model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
-    state, fixed = single_model_states(args.model, C, K, layers, seed=args.random_seed)
-    required = not (args.synthetic or args.from_scratch)
-    n1 = restore(state, args.restore_from, args.not_restore_last, required=required, last=RESTORE_LAST[args.model])
-    n2 = restore(fixed, args.restore_from, required=required)
-    cd = class_dist if class_dist is not None else ms.load_class_dist("bapa")
-    hp = Hyper(num_classes=C, open_classes=K, th_high=args.Threshold_high, th_low=args.Threshold_low,
-               lambda_seg=args.lambda_seg, lambda_place=args.lambda_Place, lambda_convex=args.lambda_Convex,
-               lambda_volume=args.lambda_Volume, lambda_anchor=args.lambda_Anchor, iter_size=args.iter_size,
-               lr=args.learning_rate, lr_T=args.learning_rate_T, momentum=args.momentum,
-               weight_decay=args.weight_decay, power=args.power, num_steps=args.num_steps)
-    dtype = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
-    eval_dtype = torch.bfloat16 if args.eval_dtype == "bf16" else torch.float32
-    arch = {"layers": layers} if model == "v3" else None
-    eval_layers = layers if model == "v3" else None
-    tr = SimTSingleTrainer(model, state, fixed, ms.ntm_init(C, K, args.random_seed + 1), hp, cd, args.batch_size, h, w, dtype=dtype,
-                           device=dev, process_group=pg, arch=arch, ema_decay=args.ema, ema_teacher_every=args.ema_teacher,
-                           teacher_view=args.weak_teacher, **args.optimizer_kwargs)
-    if rank == 0:
-        optimizer_line(args)
-        teacher_line(args)
-        weak_teacher_line(args)
-        patch_mask_line(args)
-        print(f"{args.model}: restored {n1}/{n2} tensors from {args.restore_from}; {world} GPU(s), batch {args.batch_size}/GPU, "
-              f"{h}x{w}, {args.compute_dtype}, K={K}")
-        os.makedirs(args.snapshot_dir, exist_ok=True)
-    evaluator, keeper = None, SnapshotKeeper(args.snapshot_dir, "GTA5_iter")
-    resume = TrainStateFile(args, rank, world, cd)
-    ema_snap = EmaSnapshots(tr, keeper, resume, rank)
-    start = resume.resume(tr, keeper)
-    if resume.complete(start, args.num_steps_stop, tr, args.snapshot_dir):
-        return shutdown(world)
-    data = batches(args, args.batch_size, h, w, cd, rank, world, dev, start_batch=start * args.iter_size)
-    t0 = time.time()
-    for i_iter in range(start, args.num_steps):
-        if args.weak_teacher:
-            img, lab, weak, item = next(data)
-            tr.step(img, lab, i_iter, teacher_image=weak, fix_item=item)
-        else:
-            img, lab = next(data)
-            tr.step(img, lab, i_iter)
-        if i_iter % args.print_every == 0:
-            l = tr.losses()
-            if rank == 0:
-                print("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
-                      "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
-                          i_iter, args.num_steps, l["loss_p"], l["loss_y"], l["convex"], l["volume"], l["anchor"], l["place"],
-                          model_lr(args, i_iter),
-                          args.batch_size * world * (i_iter + 1 - start) / max(time.time() - t0, 1e-9)))
-        if i_iter >= args.num_steps_stop - 1:
-            if rank == 0:
-                print("save model ...")
-                save_atomic(tr.state_dict(), osp.join(args.snapshot_dir, "GTA5_" + str(args.num_steps_stop) + ".pth"))
-            ema_snap.final(args.snapshot_dir, args.num_steps_stop)
-            resume.write(tr, keeper)
-            break
-        if i_iter % args.save_pred_every == 0 and i_iter != 0 and args.data_dir_val:
-            from simt_amd.tools.evaluate_cityscapes import Evaluator, evaluate_simt
-            if evaluator is None:
-                evaluator = Evaluator(tr.params, num_classes=C, open_classes=K, dtype=eval_dtype, device=dev, model=model, layers=eval_layers)
-            if rank == 0:
-                print(time.strftime("%Y-%m-%d %H:%M:%S"), "  Begin evaluation on iter {0:8d}/{1:8d}  ".format(i_iter, args.num_steps))
-            score = lambda params: evaluate_simt(params, args.data_dir_val, args.data_list_val, args.gt_dir_val, args.devkit_dir, num_classes=C,
-                                                 open_classes=K, device=dev, dtype=eval_dtype, evaluator=evaluator, rank=rank, world=world,
-                                                 process_group=pg)
-            mIoU = score(tr.params)
-            if rank == 0:
-                print("Finish Evaluation: " + time.asctime(time.localtime(time.time())))
-                keeper.best(tr.state_dict(), i_iter, mIoU)
-            ema_snap.evaluated(score, i_iter)          # --ema: the averaged model through the same Evaluator, a rotation of its own
-        elif i_iter % args.save_pred_every == 0 and i_iter != 0 and rank == 0:
-            keeper.rolling(tr.state_dict(), i_iter)
-            ema_snap.rolling(i_iter)
-        resume.after_iteration(i_iter, tr, keeper)
-    shutdown(world)
+    def loss_line(i_iter, l, rate):
+        return ("iter = {0:8d}/{1:8d}, loss_seg_p = {2:.3f} loss_seg_y = {3:.3f} Convex = {4:.3f} Volume = {5:.3f} "
+                "Anchor = {6:.3f} Place_loss = {7:.3f}  lr = {8:.2e}  ({9:.1f} img/s)".format(
+                    i_iter, args.num_steps, *seg_losses(l), l["convex"], l["volume"], l["anchor"], l["place"], model_lr(args, i_iter), rate))
+    train(args, tr, "GTA5_iter", cd, rank, world, open_data, loss_line, scorer(args, tr, args.open_classes, dev, rank, world, pg, **eval_kw))
 
 
 if __name__ == "__main__":
