@@ -1227,6 +1227,80 @@ int simt_proto_rectify(const simt_proto_rectify_desc* d, simt_stream_t stream);
 int simt_proto_accumulate(const simt_proto_acc_desc* d, simt_stream_t stream);
 int simt_proto_update(const simt_proto_update_desc* d, simt_stream_t stream);
 
+/* ---- Prototype contrastive loss on the student's layer-4 features (simt_amd/proto_contrast.py; csrc/proto_contrast.hip) -------------
+ * SePiCo (Xie et al., TPAMI'23) / the second half of ProDA: every pass of a micro-batch adds
+ *     lambda * (1 / N) * sum over valid cells m of  -log softmax_seen( cos(f_m, eta_c) / T )[y_m]
+ * fs [M][D] (SIMT_F32 / SIMT_BF16) is the student's layer-4 output, M = B * h * w; eta [C][D] fp32 and n [C] int32 are the prototypes of 7.26 as
+ * they stand when the launch runs; y_m the cell's label.  Four launches; the gradient with respect to fs (`seed`) enters the backward as the `res`
+ * of the layer-4 head's input-gradient launch, as in 7.22.
+ * CONTRACT (tests/_proto_contrast_ref.py is its numpy restatement, float32 sequential and float64).
+ *   CELL LABELS (simt_cell_labels).  The windows are exactly the CELLS rule of 7.22.  lab[cell] = c if class c < C has
+ *     (float)count_c >= min_ratio * (float)n  in binary32 with ONE multiply, count_c = the window pixels whose int64 label == c; else 255.
+ *     0.5 < min_ratio <= 1: at most one class qualifies (were two to pass in binary32, the lower id wins).  A label that is 255, negative or >= C
+ *     matches no class and counts against the ratio.  C <= 64.  part[g] = the number of workgroup g's cells whose class has n[c] > 0 (plain
+ *     store; the buffer holds simt_cell_labels_parts(B, h, w) words, every one written by every launch); a NULL n counts every labelled cell.
+ *     With `classes` a set of class ids, (lab[cell] < C and lab[cell] in classes) == simt_feat_dist_mask's mask[cell].
+ *   PREP (simt_proto_contrast_prep).  ne_c = sqrtf(sum_k eta[c][k]^2) in binary32 in a FIXED order (lane-local in element order, then the wave's
+ *     xor butterfly).  Class c is SEEN iff n[c] > 0 and ne_c is a finite float > 0 (a seen prototype with ne_c == 0 is treated as unseen).
+ *     phat[c][k] = eta[c][k] / ne_c for a seen class, +0 for every other row up to Cpad = 32 (C <= 32) or 64; phat holds
+ *     simt_proto_contrast_phat_floats(C, D) = Cpad * D words, every one written by every launch.  hdr[0], hdr[1] = the low and high words of the
+ *     seen set, hdr[3] = the number of seen classes; FEWER THAN TWO seen classes: the set is stored as 0.  A cell is VALID iff lab[m] < C and
+ *     its class is in the stored set; hdr[2] = N = the number of valid cells.  Rows of eta of classes with n[c] <= 0 are never read.
+ *   CONTRAST (simt_proto_contrast), per valid cell m.  nf = sqrtf(sum_k f[k]^2), f = (float)fs[m][:], in binary32 in a FIXED order.
+ *     cos_c = (f . phat_c) / nf  (a k-ordered binary32 fmaf chain: mfma_f32_32x32x2f32);  s_c = cos_c / T  for seen c -- the restatement's
+ *     (f . eta_c) / (nf * ne_c) / T up to two roundings.  lse = max + logf(sum expf(s_c - max)) over the seen classes, q_c = expf(s_c - lse),
+ *     loss_m = lse - s_y.  With a_c = q_c - [c == y], k = lam_g / (float)N:
+ *         seed[m][:] = round_dtype( (k / (T * nf)) * ( sum_c a_c * phat_c  -  ((sum_c a_c * cos_c) / nf) * f ) )
+ *     the exact gradient of lam_g * loss_m / N with respect to f_m.  A row that is not valid: +0 in every column, and the row is never read from
+ *     fs.  A valid row whose nf is 0 or not finite: loss 0, a +0 row, and it still counts in N (a stated departure, the analogue of 7.22's d == 0
+ *     rule).  EVERY row of seed is written by every launch: no memset is ever needed.  d[m] = loss_m of a valid row, 0 elsewhere.  part[g] = the
+ *     binary32 sum of workgroup g's losses, tile by tile (a tile: 32 consecutive cells, summed by the xor butterfly), by a plain store; the
+ *     buffer holds simt_proto_contrast_parts(M) words.  N == 0 (no valid cell, or fewer than two seen classes): every output is +0 / 0.
+ *     lam_g = (float)(lambda * gscale), as in simt_feat_dist_desc.
+ *   SCALARS (simt_proto_contrast_finalize):  S = the sum of part[] in double and in index order;  out[0] = lambda * S / N, out[1] = S / N,
+ *     out[2] = (float)N.  N == 0: all three are 0.
+ *   No atomics: every launch repeats bit for bit.
+ * Refused with SIMT_ERR_INVALID, nothing launched and nothing written: a NULL descriptor or pointer (simt_cell_labels: n may be NULL); B, H, W, h
+ * or w < 1; h > H or w > W; min_ratio outside (0.5, 1] or NaN; H * W or B * h * w >= 2^31; a label base that is not 8-byte aligned; M < 1 or
+ * M >= 2^31; C outside 2 .. SIMT_PROTO_MAX_CLASSES; D outside 8 .. SIMT_PROTO_MAX_DIM or D % 8 != 0; a dtype code other than SIMT_F32 / SIMT_BF16;
+ * temp not a finite float > 0; a NaN lam_g or lambda; fs, seed, eta or phat not 16-byte aligned; n, hdr, d, part or out not 4-byte aligned.
+ * Rows are dense: the leading dimension of fs, seed, eta and phat is D.
+ * LDS: cell labels 4 words, prep 83 words, contrast and finalize none; no scratch. */
+typedef struct {
+  const int64_t* label;    /* [B][H][W] */
+  uint8_t* lab;            /* out [B*h*w] */
+  int32_t* part;           /* out [simt_cell_labels_parts(B, h, w)]: cells of a seen class per workgroup */
+  const int32_t* n;        /* [C] of 7.26, or NULL: every class counts as seen */
+  int32_t B, H, W, h, w, C;
+  float min_ratio;
+  int32_t reserved_;
+} simt_cell_labels_desc;
+typedef struct {
+  const void* fs;          /* [M][D] student features, dtype */
+  const uint8_t* lab;      /* [M] of simt_cell_labels */
+  const float* eta;        /* [C][D] */
+  const int32_t* n;        /* [C] */
+  float* phat;             /* [simt_proto_contrast_phat_floats(C, D)]: out of prep, in of the main launch */
+  uint32_t* hdr;           /* [4]: out of prep, in of the main launch and finalize */
+  void* seed;              /* out [M][D], dtype */
+  float* d;                /* out [M] */
+  float* part;             /* out [simt_proto_contrast_parts(M)]: sum of the losses per workgroup */
+  float* out;              /* out [3], written by simt_proto_contrast_finalize */
+  double lambda;
+  int64_t M;
+  int32_t D, C, dtype;
+  float temp;              /* T */
+  float lam_g;             /* (float)(lambda * gscale) */
+  int32_t reserved_;
+} simt_proto_contrast_desc;
+int simt_cell_labels_parts(int B, int h, int w);          /* 0: a geometry the launch refuses */
+int simt_proto_contrast_parts(long M);                    /* 0: an M the launches refuse */
+long simt_proto_contrast_phat_floats(int C, int D);       /* 0: a geometry the launches refuse */
+int simt_cell_labels(const simt_cell_labels_desc* d, simt_stream_t stream);
+int simt_proto_contrast_prep(const simt_proto_contrast_desc* d, simt_stream_t stream);
+int simt_proto_contrast(const simt_proto_contrast_desc* d, simt_stream_t stream);
+int simt_proto_contrast_finalize(const simt_proto_contrast_desc* d, simt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -354,6 +354,20 @@ class ProtoUpdateDesc(C.Structure):
     _fields_ = [("ws", c_p), ("eta", c_p), ("n", c_p), ("M", C.c_int64), ("D", i32), ("C", i32), ("momentum", C.c_double)]
 
 
+class CellLabelsDesc(C.Structure):
+    """simt_cell_labels_desc (include/simt_hip.h): int64 labels -> one byte label per feature cell and the count of seen-class cells per workgroup."""
+    _fields_ = [("label", c_p), ("lab", c_p), ("part", c_p), ("n", c_p), ("B", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("C", i32),
+                ("min_ratio", f32), ("reserved_", i32)]
+
+
+class ProtoContrastDesc(C.Structure):
+    """simt_proto_contrast_desc (include/simt_hip.h): the student's layer-4 map, the cell labels and the prototypes -> the losses, their gradient
+    (the seed) and three scalars."""
+    _fields_ = [("fs", c_p), ("lab", c_p), ("eta", c_p), ("n", c_p), ("phat", c_p), ("hdr", c_p), ("seed", c_p), ("d", c_p), ("part", c_p),
+                ("out", c_p), ("lam", C.c_double), ("M", C.c_int64), ("D", i32), ("C", i32), ("dtype", i32), ("temp", f32), ("lam_g", f32),
+                ("reserved_", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/simt_hip.h declares
 _L = C.c_long
 _I = C.c_int
@@ -489,6 +503,13 @@ SIGNATURES = {
     "simt_proto_rectify": (_I, [C.POINTER(ProtoRectifyDesc), c_p]),
     "simt_proto_accumulate": (_I, [C.POINTER(ProtoAccDesc), c_p]),
     "simt_proto_update": (_I, [C.POINTER(ProtoUpdateDesc), c_p]),
+    "simt_cell_labels_parts": (_I, [_I, _I, _I]),
+    "simt_proto_contrast_parts": (_I, [_L]),
+    "simt_proto_contrast_phat_floats": (_L, [_I, _I]),
+    "simt_cell_labels": (_I, [C.POINTER(CellLabelsDesc), c_p]),
+    "simt_proto_contrast_prep": (_I, [C.POINTER(ProtoContrastDesc), c_p]),
+    "simt_proto_contrast": (_I, [C.POINTER(ProtoContrastDesc), c_p]),
+    "simt_proto_contrast_finalize": (_I, [C.POINTER(ProtoContrastDesc), c_p]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@ from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, Optimiz
 from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
                             check_weighted)
 from .proto import DEFAULT_MOMENTUM as DEFAULT_PROTO_MOMENTUM, check_proto
+from .proto_contrast import ProtoContrastMixin, check_proto_contrast
 from .train_state import TrainStateMixin, state_sha256
 
 
@@ -497,7 +498,7 @@ def accumulate_pass(tr, k, n, st):
             tr.reducer.finish()
 
 
-class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, OptimizerMixin):
+class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, ProtoContrastMixin, OptimizerMixin):
     """The warm-up stage of the reference (tools/trainV1_warmup.py:156-256) on gfx950: DeeplabMulti(num_classes) without
     open-set heads, loss = CE(up(pred2), label) + lambda_seg * CE(up(pred1), label) with ignore_index 255 (:217-224), SGD over
     conv1 ... layer4 with the duplicate listings of `optim_parameters(args, warmup=True)` + heads at 10x lr (:192-193).
@@ -508,7 +509,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                  online_mix=None, online_mix_seed=0, online_labels_weighted=None, online_source=None,
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
                  optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
-                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM):
+                 entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM,
+                 proto_contrast=None, proto_contrast_temp=None, proto_contrast_min_ratio=None):
         """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTTrainer; the defaults are the trainer it was.
         online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
@@ -542,7 +544,13 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         proto_denoise=temp > 0 (simt_amd/proto.py; needs online_labels): ProDA's prototype weights -- the teacher's low-res posterior
         is weighed by softmax(-(d - d_min) / temp), d the distance of the cell's layer-4 feature to running class prototypes (momentum
         proto_momentum, default 0.9999), in front of the label launch of every mode; a batch is labelled with the prototypes of the batches
-        before it.  `losses()` gains `proto_seen` / `proto_changed`.  None: the trainer it was."""
+        before it.  `losses()` gains `proto_seen` / `proto_changed`.  None: the trainer it was.
+        proto_contrast=lambda >= 0 (simt_amd/proto_contrast.py; needs proto_denoise, refused with feat_dist): the prototype contrastive
+        term of SePiCo / ProDA -- every pass adds lambda * the mean over the valid layer-4 cells of -log softmax_seen(cos(f, eta_c) / T)[y], f the
+        STUDENT's layer-4 output, eta the prototypes of proto_denoise, y the class that fills the cell's window of the pass's labels to
+        proto_contrast_min_ratio (default 0.75), T = proto_contrast_temp (default 0.1); its gradient enters the backward at layer 4's output.
+        proto_denoise=1e30 leaves the labels all but untouched for a user who wants the contrast alone.  `losses()` gains `proto_contrast` /
+        `proto_contrast_cells` (and `source_proto_contrast` with online_source).  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
@@ -551,6 +559,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
         fd = check_feat_dist(feat_dist, feat_dist_state, feat_dist_classes, feat_dist_min_ratio, tau, source, hp.num_classes)
         proto = check_proto(proto_denoise, proto_momentum, tau, hp.num_classes)
+        pc = check_proto_contrast(proto_contrast, proto_contrast_temp, proto_contrast_min_ratio, proto[0], fd[0], hp.num_classes)
         self.hp, self.B, self.H, self.W, self.dtype = hp, B, H, W, dtype
         dev = self.dev = torch.device(device)
         self.pg = process_group
@@ -558,7 +567,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         f32 = torch.float32
         self.params = {k: v.detach().to(dev, f32 if v.dtype != torch.long else torch.long).clone() for k, v in state.items()}
         kw = {"layers": layers} if layers is not None else {}
-        if fd[0] is not None:      # (only then: without the keyword the plan is built by the call it always was)
+        if fd[0] is not None or pc[0] is not None:      # (only then: without the keyword the plan is built by the call it always was)
             kw["feat_grad_seed"] = True
         self.plan = TrunkPlan(self.params, B, H, W, multi_heads(Cn, 0, False), dtype=dtype, train=True,
                               data_parallel=process_group is not None, **kw)
@@ -606,6 +615,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         # the input of the teacher's layer-4 classifier -- the last block's output, which no later launch of the eval plan overwrites
         self._init_proto(proto, next(hd for hd in self.fixed.heads if hd.name == "x2").feat if proto[0] is not None else None)
         self._init_feat_dist(*fd, feat_dist_state, dict(kw, data_parallel=process_group is not None))
+        self._init_proto_contrast(*pc)
         self.reducer = None
         if self.pg is not None:
             from .dp import BucketReducer, make_buckets
@@ -648,6 +658,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                 if self.feat_dist is not None:
                     self._fd_launches(st)
                     self.plan.use_feat_seed(True)
+                if self.proto_contrast is not None:      # the source pass's term, on the prototypes before this micro-batch's update
+                    self._pc_launches(st, source=True)
                 self.plan.backward()
                 accumulate_pass(self, mi * per, n_pass, st)
             if self.online_mix is not None:      # the mix writes plan.x_in and self.label itself, behind the teacher (main stream): no input copy
@@ -674,6 +686,8 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                     self._fd_launches(st)
                 else:      # the target pass under online_source: the seed-less launch, the parent's (the descriptor is read at every launch)
                     self.plan.use_feat_seed(False)
+            if self.proto_contrast is not None:      # `self.label` is final (teacher labels, the mix), the teacher's event is waited for
+                self._pc_launches(st)
             if self.reducer is not None and n_pass == 1:
                 self.reducer.start()
                 self.plan.backward(hook=self.reducer.ready_upto)
@@ -715,4 +729,4 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like SimTTrainer's
-        return self._fd_losses(self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]}))
+        return self._pc_losses(self._fd_losses(self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]})))

@@ -63,6 +63,11 @@ low-res posterior is weighed by softmax(-(d - d_min) / TEMP) (no value: 1.0), d 
 main classifier) to running class prototypes kept on the device, momentum --proto-momentum M (0.9999).  A batch is labelled with the
 prototypes of the batches before it; the first one with the teacher's output as it is.  The loss line gains ` proto = <seen>/<C> moved <share>`.
 One start-up line states the rule and its departures; --train-state refuses the flags added, dropped or changed.  All three models.
+--proto-contrast [LAMBDA] (needs --proto-denoise, not with --feat-dist, --model DeepLab only): the prototype contrastive term of
+SePiCo / ProDA -- every pass adds LAMBDA (no value: 0.1) * the mean over the valid layer-4 cells of -log softmax_seen(cos(f, prototype_c) / T)[y], f
+the STUDENT's layer-4 feature, the prototypes --proto-denoise's, y the class that fills --proto-contrast-min-ratio R (0.75) of the cell's window of
+the pass's labels, T = --proto-contrast-temp (0.1); its gradient enters the backward at layer 4's output.  The loss line gains
+` pc = <value> (<cells>)`.  --proto-denoise 1e30 leaves the labels all but untouched for a run that wants the contrast alone.
 
 --model: DeepLab (the reference's DeeplabMulti, `WarmupTrainer`), DeepLabv3 (model/deeplabv3.py, trunk depth --v3-layers) or DeepLabVGG
 (model/deeplab_vgg.py); the last two run `WarmupSingleTrainer` (simt_amd/step_single.py), the same loss on the model's one output, and
@@ -152,6 +157,7 @@ def get_arguments(argv=None):
     add_fda_args(p)
     add_entropy_args(p)
     add_proto_args(p)
+    add_proto_contrast_args(p)
     args = p.parse_args(argv)
     check_patch_mask_args(p, args)
     check_online_label_args(p, args)
@@ -159,6 +165,7 @@ def get_arguments(argv=None):
     check_fda_args(p, args)
     check_entropy_args(p, args)
     check_proto_args(p, args)
+    check_proto_contrast_args(p, args)
     optimizer_kwargs(p, args)
     return args
 
@@ -399,6 +406,66 @@ def proto_text(args, l):
     return " proto = {0}/{1} moved {2:.4f}".format(l["proto_seen"], args.num_classes, l["proto_changed"]) if "proto_seen" in l else ""
 
 
+def add_proto_contrast_args(p):
+    """--proto-contrast / --proto-contrast-temp / --proto-contrast-min-ratio; `check_proto_contrast_args` holds their refusals."""
+    from simt_amd.proto_contrast import DEFAULT_LAMBDA, DEFAULT_MIN_RATIO, DEFAULT_TEMP
+    p.add_argument("--proto-contrast", nargs="?", type=float, const=DEFAULT_LAMBDA, default=None, metavar="LAMBDA",
+                   help="with --proto-denoise: the prototype contrastive term of SePiCo / ProDA on the student's layer-4 features (simt_cell_labels / "
+                        "simt_proto_contrast_prep / simt_proto_contrast / _finalize; DESIGN 7.27) -- every pass adds LAMBDA * the mean over the valid cells "
+                        f"of -log softmax_seen(cos(f, prototype_c) / T)[y] (no value: LAMBDA = {DEFAULT_LAMBDA}); --model DeepLab only")
+    p.add_argument("--proto-contrast-temp", type=float, default=None, metavar="T",
+                   help=f"the temperature of the cosine logits, a finite T > 0 (default {DEFAULT_TEMP})")
+    p.add_argument("--proto-contrast-min-ratio", type=float, default=None, metavar="R",
+                   help=f"a cell takes the class that fills at least R of its label window, 0.5 < R <= 1 (default {DEFAULT_MIN_RATIO})")
+
+
+def check_proto_contrast_args(p, args):
+    """argparse's error (exit status 2) naming the flag: a --proto-contrast-* flag without --proto-contrast, --proto-contrast without
+    --proto-denoise, beside --feat-dist, with a one-output model, or with a value its keyword refuses."""
+    from simt_amd.proto_contrast import check_proto_contrast
+    if args.proto_contrast is not None and args.model != "DeepLab":
+        p.error(f"--proto-contrast with --model {args.model}: the term seeds the backward at layer 4's output, which is built for --model DeepLab "
+                "only (DESIGN 7.27, not built: DeepLabv3 and DeepLabVGG)")
+    if args.proto_contrast is not None and args.proto_denoise is None:
+        p.error("--proto-contrast needs --proto-denoise: the prototypes are --proto-denoise's (--proto-denoise 1e30 leaves the labels all but untouched)")
+    try:
+        check_proto_contrast(args.proto_contrast, args.proto_contrast_temp, args.proto_contrast_min_ratio, args.proto_denoise, args.feat_dist,
+                             args.num_classes)
+    except ValueError as e:
+        msg = str(e)
+        for k in ("proto_contrast_min_ratio", "proto_contrast_temp", "proto_contrast", "proto_denoise", "feat_dist"):      # the keywords' names -> the flags'
+            msg = msg.replace(k, "--" + k.replace("_", "-"))          # (longest names first: a replaced name no longer has an underscore)
+        p.error(msg)
+
+
+def proto_contrast_kwargs(args):
+    """The trainer's keywords of --proto-contrast and its two flags: nothing without the flag."""
+    if getattr(args, "proto_contrast", None) is None:
+        return {}
+    from simt_amd.proto_contrast import DEFAULT_MIN_RATIO, DEFAULT_TEMP
+    return {"proto_contrast": args.proto_contrast,
+            "proto_contrast_temp": DEFAULT_TEMP if args.proto_contrast_temp is None else args.proto_contrast_temp,
+            "proto_contrast_min_ratio": DEFAULT_MIN_RATIO if args.proto_contrast_min_ratio is None else args.proto_contrast_min_ratio}
+
+
+def proto_contrast_line(args):
+    """The start-up line of --proto-contrast: the term and its departures from the published methods."""
+    if getattr(args, "proto_contrast", None) is None:
+        return
+    kw = proto_contrast_kwargs(args)
+    print(f"prototype contrast: every pass adds {kw['proto_contrast']} * the mean over the valid layer-4 cells of -log softmax_seen(cos(f, prototype_c) / "
+          f"{kw['proto_contrast_temp']})[y], y the class that fills {kw['proto_contrast_min_ratio']} of the cell's label window; departures: cosine "
+          "logits, prototypes from the teacher's features of thresholded cells, no distribution (variance) term, lambda and T are conventional "
+          "InfoNCE values and not checked against SePiCo's published configuration")
+
+
+def proto_contrast_text(args, l):
+    """` pc = <proto_contrast> (<cells>)` of the loss line: only with --proto-contrast."""
+    if getattr(args, "proto_contrast", None) is None:
+        return ""
+    return " pc = {0:.4f} ({1:d})".format(l["proto_contrast"], l["proto_contrast_cells"])
+
+
 def step_args(args, mb, sb=None):
     """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
     (image, None) and the keyword teacher_image where the loader made a weak view; sb: the micro-batches of `source_batches`
@@ -495,7 +562,8 @@ def build_trainer(args, h, w, rank, dev, pg):
         state = ms.reference_init(shapes, seed=args.random_seed)
         # trainV1_warmup.py:177: keys of the pretrained checkpoint carry a 6-character prefix (`k[6:]`); shapes are filtered
         n = restore(state, args.restore_from, strip_prefix=6, required=required)
-        tr = WarmupTrainer(state, Hyper(lambda_seg=args.lambda_seg, **hyper), args.batch_size, h, w, **kw, **feat_dist_kwargs(args, shapes, rank))
+        tr = WarmupTrainer(state, Hyper(lambda_seg=args.lambda_seg, **hyper), args.batch_size, h, w, **kw, **feat_dist_kwargs(args, shapes, rank),
+                           **proto_contrast_kwargs(args))
         return tr, f"restored {n} tensors", "loss_seg1 = {loss_seg1:.3f} loss_seg2 = {loss_seg2:.3f}", {}
     from simt_amd.step_single import WarmupSingleTrainer
     model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
@@ -509,7 +577,7 @@ def build_trainer(args, h, w, rank, dev, pg):
 def loss_tail(args, l, source):
     """What the flags add to the loss line behind the model's own losses, in this order; each term is "" without its flag."""
     return (labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) +
-            feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l))
+            feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l) + proto_contrast_text(args, l))
 
 
 def main(argv=None):
@@ -526,6 +594,7 @@ def main(argv=None):
         online_label_line(args)
         entropy_line(args)
         proto_line(args)
+        proto_contrast_line(args)
         patch_mask_line(args, frozen=False)
         print(f"{restored}; {world} GPU(s), batch {args.batch_size}/GPU, {h}x{w}, {args.compute_dtype}")
         os.makedirs(args.snapshot_dir, exist_ok=True)                                       # :185-186

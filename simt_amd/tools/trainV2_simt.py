@@ -751,7 +751,8 @@ class EmaSnapshots:
 
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
                 "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
-                "online_source": False, "rare_class_sampling": False, "fda": False, "entropy_min": False, "proto_denoise": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "online_source": False, "rare_class_sampling": False, "fda": False, "entropy_min": False, "proto_denoise": False,
+                "proto_contrast": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -800,6 +801,10 @@ def run_identity(args, class_dist):
         if getattr(args, "proto_denoise", None) is not None:             # [temp, M] (trainV1_warmup --proto-denoise)
             from simt_amd.proto import DEFAULT_MOMENTUM
             ident["proto_denoise"] = [float(args.proto_denoise), float(DEFAULT_MOMENTUM if args.proto_momentum is None else args.proto_momentum)]
+        if getattr(args, "proto_contrast", None) is not None:            # [lambda, T, R] (trainV1_warmup --proto-contrast)
+            from simt_amd.proto_contrast import DEFAULT_MIN_RATIO, DEFAULT_TEMP
+            ident["proto_contrast"] = [float(args.proto_contrast), float(DEFAULT_TEMP if args.proto_contrast_temp is None else args.proto_contrast_temp),
+                                       float(DEFAULT_MIN_RATIO if args.proto_contrast_min_ratio is None else args.proto_contrast_min_ratio)]
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

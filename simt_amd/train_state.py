@@ -53,6 +53,9 @@ ENTROPY_FIELDS = ("entropy_min", "entropy_eta", "entropy_after")
 # and the prototype weights on the teacher's labels (proto_denoise = temp, proto_momentum = M: DESIGN 7.26), written only when on; compared
 # through value_mismatches(..., fields=PROTO_FIELDS)
 PROTO_FIELDS = ("proto_denoise", "proto_momentum")
+# and the prototype contrastive term on the student's layer-4 features (proto_contrast = lambda with its temperature and ratio: DESIGN 7.27),
+# written only when on; compared through value_mismatches(..., fields=PROTO_CONTRAST_FIELDS).  No accumulator: the term keeps no state of its own.
+PROTO_CONTRAST_FIELDS = ("proto_contrast", "proto_contrast_temp", "proto_contrast_min_ratio")
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -182,6 +185,9 @@ class TrainStateMixin:
                 hy.update(entropy_min=float(self.entropy_min), entropy_eta=float(self.entropy_eta), entropy_after=int(self.entropy_after))
             if getattr(self, "proto_denoise", None) is not None:
                 hy.update(proto_denoise=float(self.proto_denoise), proto_momentum=float(self.proto_momentum))
+            if getattr(self, "proto_contrast", None) is not None:
+                hy.update(proto_contrast=float(self.proto_contrast), proto_contrast_temp=float(self.proto_contrast_temp),
+                          proto_contrast_min_ratio=float(self.proto_contrast_min_ratio))
         if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
             hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
                       feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
@@ -277,7 +283,8 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=ENTROPY_FIELDS) +
-               value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_FIELDS))
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_CONTRAST_FIELDS))
         if bad:
             mine = self._hyper_state()
             raise ValueError("the train state was written by a different run: " +
