@@ -934,6 +934,37 @@ int simt_head_loss_entropy(const simt_head_desc* d, const float* w, int nw, cons
 int simt_head_grad_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
                            simt_stream_t stream);
 
+/* ---- Uncertainty-rectified pseudo-label loss (WarmupTrainer's uncertainty_rectify; csrc/head_loss.hip) ---------------------
+ * simt_head_loss_uncertain / simt_head_grad_uncertain -- the two-head mode-1 launches with Zheng & Yang's rectification (IJCV 2021): the KL
+ *   divergence between the two heads' predictions is a pixel's label uncertainty; its cross-entropy is multiplied by exp(-KL) and the KL is
+ *   added as a regulariser.  Per pixel p of the B * H * W upsampled pixels, head k in {1 (aux, pred1), 2 (main, pred2)}, o the other head,
+ *   v the Q upsampled logits, lse their log-sum-exp and q = softmax(v) as the passes form them, u_j = lse - v_j >= 0:
+ *     D_k   = KL(q_o || q_k) = sum_j q_o,j * (u_k,j - u_o,j)            (summed in that form; not clamped)
+ *     R_k   = [ sum over labelled p of w_p * exp(-D_k) * u_k,label ] / N   N = labelled pixels (hout[6]); w_p as simt_head_*_weighted_n
+ *                                                                          (w == NULL: 1)
+ *     K_k   = sum over ALL p of D_k / (B * H * W)
+ *     total = R_2 + lambda_kl * K_2 + lambda_seg * (R_1 + lambda_kl * K_1)
+ *   The gradient flows through BOTH arguments of the KL; nothing is detached.  With a_k = w_p * exp(-D_k) / N (0 where unlabelled),
+ *   c_k = lambda_kl / (B * H * W) - a_k * u_k,label, L_2 = 1 and L_1 = lambda_seg, the gradient row of head k, added per pixel before the
+ *   x-reduction, is
+ *     G_k,j = gscale * { L_k * [ a_k * (q_k,j - onehot_j) + c_k * (q_k,j - q_o,j) ] + L_o * c_o * q_k,j * ((u_o,j - u_k,j) - D_o) }
+ *   lambda_kl enters every word through one product (gscale * lambda_kl / (B * H * W)): at w = 0 doubling it doubles every word exactly.
+ *   hout[0], hout[1] = R_1, R_2;  hout[2], hout[3] = K_1, K_2;  hout[4], hout[5] = the mean over labelled pixels of exp(-D_k), the average
+ *   rectification weight;  hout[14] = total;  hout[6], hout[15], conf_out, label_ws and every other scalar as the weighted / plain mode-1
+ *   launches give them.
+ *   w == NULL: every weight is 1 (nw must be 0 and w_item NULL); else w, nw and w_item as in simt_head_*_weighted_n.
+ *   Every descriptor runs the run-time-count kernels, one image row per pass-2 block (g1 is [2][B][H][w][QP]).
+ *   Departures from the published method: the cross-entropy keeps this project's division by N (the paper takes both means over all pixels);
+ *   one lambda_seg serves both of a head's terms; there are no class weights.
+ *   Refused (SIMT_ERR_INVALID, nothing launched, nothing written): what simt_head_loss / simt_head_grad refuse; mode 0; single = 1; pred1
+ *   NULL; u NULL; lambda_kl non-finite or < 0 (0 is allowed: the rectified cross-entropy alone); w NULL with a map or nw != 0; w misaligned;
+ *   nw outside B .. SIMT_HEAD_WEIGHTS_MAX. */
+typedef struct { float lambda_kl; } simt_head_uncertainty;
+int simt_head_loss_uncertain(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_uncertainty* u,
+                             simt_stream_t stream);
+int simt_head_grad_uncertain(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_uncertainty* u,
+                             simt_stream_t stream);
+
 /* ---- Photometric augmentation: colour jitter, then Gaussian blur, on a finished batch (simt_amd/data/photometric.py;
  * csrc/photometric.hip) -----------------------------------------------------------------------------------------------------------
  * Input is a finished batch x [B][3][h][w] fp32 as every loader path produces it: plane p holds colour - mean[p].  Output goes to another

@@ -190,6 +190,11 @@ class HeadEntropy(C.Structure):
     _fields_ = [("lambda_ent", f32), ("eta", f32)]
 
 
+class HeadUncertainty(C.Structure):
+    """simt_head_uncertainty (include/simt_hip.h): the weight of the two KL regularisers of simt_head_*_uncertain."""
+    _fields_ = [("lambda_kl", f32)]
+
+
 class SourceMixDesc(C.Structure):
     """simt_source_mix_desc (include/simt_hip.h): a labelled source batch, a target batch and its teacher's byte labels -> the mixed batch."""
     _fields_ = [("xs", c_p), ("labs", c_p), ("part_s", c_p), ("xt", c_p), ("lab8", c_p), ("x_out", c_p), ("lab_out", c_p),
@@ -488,6 +493,8 @@ SIGNATURES = {
     "simt_head_grad_weighted_n": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, c_p]),
     "simt_head_loss_entropy": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadEntropy), c_p]),
     "simt_head_grad_entropy": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadEntropy), c_p]),
+    "simt_head_loss_uncertain": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadUncertainty), c_p]),
+    "simt_head_grad_uncertain": (_I, [C.POINTER(HeadDesc), c_p, C.c_int, c_p, C.POINTER(HeadUncertainty), c_p]),
     "simt_rare_crop_counts": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_rare_crop_pick": (_I, [C.POINTER(RareCropDesc), c_p]),
     "simt_scale_crop_win": (_I, [C.POINTER(RareCropDesc), c_p]),

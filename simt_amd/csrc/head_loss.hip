@@ -239,12 +239,14 @@ struct HeadArgs {
   const unsigned char* w_item;    // optional [B][H][W] (simt_head_*_weighted): the item whose weight a pixel carries
   int nw;                         // simt_head_*_weighted: the entries of w the map may name (B; simt_head_*_weighted_n: B .. SIMT_HEAD_WEIGHTS_MAX)
   float lambda_ent, eta, inv_lnq; // simt_head_*_entropy: the term's weight (0: no such term), its exponent, 1 / ln(Q)
+  float lambda_kl;                // simt_head_*_uncertain: the weight of the two KL regularisers (0 is allowed)
+  int uncertain;                  // 1: a simt_head_*_uncertain launch (the finalize writes its hout layout), else 0
 };
 
 // The flavour pack of the two pass kernels: <> the SimT / DeepLab-v2 warm-up code (names as before any flavour existed), <true> ONE,
-// <false, true> VIEWS, <ONE, false, true> WEIGHTED, <ONE, false, true, true> ENTROPY.
+// <false, true> VIEWS, <ONE, false, true> WEIGHTED, <ONE, false, true, true> ENTROPY, <false, false, true, false, true> UNCERTAIN.
 template <bool... F_>
-constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false, false, false}; return v[i]; }
+constexpr bool head_flavour(int i) { const bool v[] = {F_..., false, false, false, false, false}; return v[i]; }
 
 // VIEWS: the frozen operand of pixel pix of item b comes from item fb = min(fix_item[pix], B - 1).  The taps index pixels from fixp's base
 // and differ from the pixel's own by a constant: one byte load and one pointer offset, no second make_taps.
@@ -279,6 +281,25 @@ __device__ __forceinline__ EntTerm entropy_term(const float* v, int Q, const Hea
   r.H = H;
   r.rho = __builtin_amdgcn_exp2f(eta * __builtin_amdgcn_logf(t));
   r.cf = 2.f * eta * en * r.rho / t * inv_lnq;
+  return r;
+}
+
+// UNCERTAIN: the two KL divergences between the heads' softmaxes at one pixel, from the upsampled logits and what eval_head
+// formed of them.  u_k,j = lse_k - v_k,j;  D_1 = KL(q_2 || q_1) = sum_j q_2,j (u_1,j - u_2,j),  D_2 = KL(q_1 || q_2) = sum_j q_1,j (u_2,j -
+// u_1,j): summed in that form and not clamped (equal logits give u_1,j - u_2,j = 0 and both sums 0 exactly).
+struct KlPair { float D1, D2; };
+template <int QM>
+__device__ __forceinline__ KlPair kl_pair(const float* v1, const float* v2, int Q, const HeadEval& e1, const HeadEval& e2) {
+  const float inv1 = 1.0f / e1.sum, inv2 = 1.0f / e2.sum;
+  KlPair r;
+  r.D1 = 0.f; r.D2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < QM; ++j)
+    if (j < Q) {
+      const float du = (e1.lse - v1[j]) - (e2.lse - v2[j]);
+      r.D1 += (exp_le0(v2[j] - e2.vmax) * inv2) * du;
+      r.D2 -= (exp_le0(v1[j] - e1.vmax) * inv1) * du;
+    }
   return r;
 }
 
@@ -339,13 +360,18 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
 // {ONE, false, true, true}: ENTROPY, the WEIGHTED run-time-count body plus the robust entropy of every live pixel, labelled or
 // not: its sums travel in the accumulators the SimT placeholder terms leave idle in mode 1 (acc[2], acc[3]).  The weight table is tested at
 // run time (a.w NULL: every weight 1.f), so one flavour serves the plain, the class-balanced and the weighted trainers.
+// {false, false, true, false, true}: UNCERTAIN, the WEIGHTED run-time-count body of two heads with every cross-entropy term
+// multiplied by exp(-D_k), D_k the KL divergence from the other head (kl_pair), and the D_k of every live pixel summed as a regulariser: the
+// sums travel in acc[2..5], idle in mode 1.  The weight table is tested at run time as in ENTROPY.
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass1_kernel(HeadArgs a) {
   constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
-  constexpr bool ENTROPY = head_flavour<ONE_...>(3);
+  constexpr bool ENTROPY = head_flavour<ONE_...>(3), UNCERTAIN = head_flavour<ONE_...>(4);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time");
   static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
   static_assert(!ENTROPY || (WEIGHTED && QT == 0), "the entropy flavour is the weighted mode-1 body with run-time counts");
+  static_assert(!UNCERTAIN || (WEIGHTED && QT == 0 && !ENTROPY), "the uncertainty flavour is the weighted mode-1 body with run-time counts");
+  static_assert(!(UNCERTAIN && ONE), "the uncertainty flavour couples two heads");
   const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C;
@@ -387,7 +413,7 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
     }
     Taps tp = make_taps(g, b, y, x);
     float wp = 1.f;                                    // WEIGHTED: the pixel's weight
-    if constexpr (WEIGHTED) { if (live && (!ENTROPY || a.w)) wp = weight_of_item(a, g, b, p); }
+    if constexpr (WEIGHTED) { if (live && (!(ENTROPY || UNCERTAIN) || a.w)) wp = weight_of_item(a, g, b, p); }
     if constexpr (ONE) {
       // warm-up stage of a one-output model: CrossEntropyLoss(ignore_index=255) of its one head against the label (hout[1]); the
       // out-of-range count as in the other modes.  No frozen posterior, T, placeholder or anchor term.
@@ -452,12 +478,20 @@ __global__ __launch_bounds__(256, (QM <= 24 ? SIMT_HEAD_P1_WAVES : head_flavour<
     if (live) {
       if (a.conf_out) a.conf_out[p] = (unsigned char)conf;
       if (a.label_ws) a.label_ws[p] = lab_ok ? (unsigned char)labi : (unsigned char)255;
+      float rw1 = 1.f, rw2 = 1.f;                      // UNCERTAIN: the rectification weights exp(-D_k)
+      if constexpr (UNCERTAIN) {
+        const KlPair kl = kl_pair<QM>(v1, v2, Q, e1, e2);
+        rw1 = expf(-kl.D1); rw2 = expf(-kl.D2);
+        acc[2] += kl.D1; acc[3] += kl.D2;
+        if (conf != 255) { acc[4] += rw1; acc[5] += rw2; }
+      }
       if (conf != 255) {
         float l1 = 0.f, l2 = 0.f;
 #pragma unroll
         for (int j = 0; j < QM; ++j)
           if (j == conf) { l1 = e1.lse - v1[j]; l2 = e2.lse - v2[j]; }
         if constexpr (WEIGHTED) { l1 = wp * l1; l2 = wp * l2; }
+        if constexpr (UNCERTAIN) { l1 = rw1 * l1; l2 = rw2 * l2; }
         acc[0] += l1; acc[1] += l2; acc[8] += 1.f;
       }
       if constexpr (ENTROPY) {
@@ -700,6 +734,13 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(HeadArgs a, int nblk
       o[2] = (float)(sc[2] / P); o[3] = (float)(sc[3] / P);
       o[14] = o[1] + a.lambda_seg * o[0] + a.lambda_ent * (o[3] + a.lambda_seg * o[2]);
     }
+    if (a.uncertain) {                       // simt_head_loss_uncertain: o[0], o[1] are R_1, R_2 already (sums of w exp(-D) u / N)
+      const double P = (double)g.B * (double)g.H * (double)g.W;
+      o[2] = (float)(sc[2] / P); o[3] = (float)(sc[3] / P);            // K_k: the mean over ALL pixels of D_k
+      o[4] = (float)(sc[4] / Np); o[5] = (float)(sc[5] / Np);          // the mean over labelled pixels of exp(-D_k)
+      o[10] = o[11] = o[12] = o[13] = (float)(0.0 / Nk1);              // (what mode 1 writes: no placeholder pixel, 0 / 0)
+      o[14] = o[1] + a.lambda_kl * o[3] + a.lambda_seg * (o[0] + a.lambda_kl * o[2]);
+    }
   }
   // dTy: -(1/Ny) * sum_p [label=c] q_j / r
   float* dTy = o + 16 + 2 * QC + 4 * QMAX;
@@ -755,10 +796,12 @@ __device__ __forceinline__ float run_sum(const float* G, int GP, const float* sL
 template <int QM, int QT, int CT, bool... ONE_>
 __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2)) void head_pass2_kernel(HeadArgs a) {
   constexpr bool ONE = head_flavour<ONE_...>(0), VIEWS = head_flavour<ONE_...>(1), WEIGHTED = head_flavour<ONE_...>(2);
-  constexpr bool ENTROPY = head_flavour<ONE_...>(3);
+  constexpr bool ENTROPY = head_flavour<ONE_...>(3), UNCERTAIN = head_flavour<ONE_...>(4);
   static_assert(!ONE || QT == 0, "the one-head warm-up flavour takes its channel counts at run time (rows = 1)");
   static_assert(!(WEIGHTED && VIEWS), "the warm-up stage has no frozen operand to move");
   static_assert(!ENTROPY || (WEIGHTED && QT == 0), "the entropy flavour is the weighted mode-1 body with run-time counts (rows = 1)");
+  static_assert(!UNCERTAIN || (WEIGHTED && QT == 0 && !ENTROPY), "the uncertainty flavour is the weighted mode-1 body with run-time counts (rows = 1)");
+  static_assert(!(UNCERTAIN && ONE), "the uncertainty flavour couples two heads");
   const int mode = (WEIGHTED && QT == 0) ? 1 : a.mode;      // (compile-time counts: the body of the flavour beside it, see above)
   const HeadGeom g = a.g;
   const int Q = QT ? QT : g.Q, C = CT ? CT : g.C, QC = Q * C, QP = a.QP;
@@ -794,6 +837,8 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
   const float gy1 = gs * a.lambda_seg / Ny, gy2 = gs / Ny;
   // ENTROPY: gscale * lambda_ent / (B H W) for the main head, times lambda_seg for the auxiliary one
   const float ge2 = ENTROPY ? gs * a.lambda_ent / ((float)g.B * (float)g.H * (float)g.W) : 0.f, ge1 = ge2 * a.lambda_seg;
+  // UNCERTAIN: gscale * lambda_kl / (B H W) for the main head's KL, times lambda_seg for the auxiliary one: lambda_kl's one product
+  const float gd2 = UNCERTAIN ? gs * a.lambda_kl / ((float)g.B * (float)g.H * (float)g.W) : 0.f, gd1 = gd2 * a.lambda_seg;
   for (int rr = 0; rr < R; ++rr) {
   const int y = y0 + rr;
   for (int i = tid + (ONE ? g.w * Q : 0); i < 2 * g.w * Q; i += 256) sAcc[i] = 0.f;     // (ONE: the head-2 half only)
@@ -829,7 +874,7 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
       // WEIGHTED: the pixel's two gradient factors carry its weight (gscale * w_p / N; head 1 also lambda_seg), formed once per pixel
       float gw1 = gp1, gw2 = gp2;
       if constexpr (WEIGHTED) {
-        const float wp = !live ? 0.f : (ENTROPY && !a.w) ? 1.f : weight_of_item(a, g, b, pix);
+        const float wp = !live ? 0.f : ((ENTROPY || UNCERTAIN) && !a.w) ? 1.f : weight_of_item(a, g, b, pix);
         gw1 = gp1 * wp; gw2 = gp2 * wp;
       }
       if constexpr (ONE) {
@@ -916,6 +961,19 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
         const EntTerm t1 = entropy_term<QM>(v1, Q, e1, a.inv_lnq, a.eta), t2 = entropy_term<QM>(v2, Q, e2, a.inv_lnq, a.eta);
         H1 = t1.H; c1 = ge1 * t1.cf; H2 = t2.H; c2 = ge2 * t2.cf;
       }
+      // UNCERTAIN: D_k, and per head Lambda_k gscale c_k = gd_k - (the pixel's cross-entropy factor, now carrying exp(-D_k)) * u_k,label
+      float D1 = 0.f, D2 = 0.f, ck1 = 0.f, ck2 = 0.f;
+      if constexpr (UNCERTAIN) {
+        const KlPair kl = kl_pair<QM>(v1, v2, Q, e1, e2);
+        D1 = kl.D1; D2 = kl.D2;
+        float ul1 = 0.f, ul2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < QM; ++j)
+          if (j == conf) { ul1 = e1.lse - v1[j]; ul2 = e2.lse - v2[j]; }
+        if (conf != 255) { gw1 = gw1 * expf(-D1); gw2 = gw2 * expf(-D2); }
+        else { gw1 = 0.f; gw2 = 0.f; }
+        ck1 = gd1 - gw1 * ul1; ck2 = gd2 - gw2 * ul2;
+      }
 #pragma unroll
       for (int j = 0; j < QM; ++j)
         if (j < Q) {
@@ -925,6 +983,11 @@ __global__ __launch_bounds__(256, (QM > 24 && head_flavour<ONE_...>(1) ? 1 : 2))
             if constexpr (ENTROPY) {
               G1 += c1 * (q1 * ((e1.lse - v1[j]) - H1));
               G2 += c2 * (q2 * ((e2.lse - v2[j]) - H2));
+            }
+            if constexpr (UNCERTAIN) {         // c_k (q_k - q_o) of the head's own D_k, c_o q_k ((u_o - u_k) - D_o) of the other head's
+              const float du = (e1.lse - v1[j]) - (e2.lse - v2[j]);
+              G1 += ck1 * (q1 - q2) + ck2 * (q1 * ((0.f - du) - D2));
+              G2 += ck2 * (q2 - q1) + ck1 * (q2 * (du - D1));
             }
             if (conf != 255) {
               float oh = (j == conf) ? 1.f : 0.f;
@@ -1143,6 +1206,7 @@ static int fill_args(const simt_head_desc* d, const uint8_t* fix_item, HeadArgs&
   a.fix_item = fix_item;
   a.w = nullptr; a.w_item = nullptr; a.nw = 0;
   a.lambda_ent = 0.f; a.eta = 0.f; a.inv_lnq = 0.f;
+  a.lambda_kl = 0.f; a.uncertain = 0;
   SIMT_CHECK(d->mode == 0 || d->mode == 1);
   SIMT_CHECK(!fix_item || d->mode == 0);      // the warm-up stage has no frozen operand to move
   return SIMT_OK;
@@ -1187,12 +1251,31 @@ static int fill_entropy(const simt_head_desc* d, const float* w, int nw, const u
   return SIMT_OK;
 }
 
+// the uncertainty launches' side: mode 1 and two heads only; the weight table as in fill_entropy; run-time-count builds only,
+// so one image row per pass-2 block
+static int fill_uncertain(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_uncertainty* u, HeadArgs& a) {
+  SIMT_CHECK(d->mode == 1);
+  SIMT_CHECK(!d->single && d->pred1 != nullptr);
+  SIMT_CHECK(u != nullptr);
+  SIMT_CHECK(isfinite(u->lambda_kl) && u->lambda_kl >= 0.f);
+  if (w) {
+    if (int rw = fill_weights(d, w, nw, w_item, a)) return rw;
+  } else {
+    SIMT_CHECK(nw == 0 && w_item == nullptr);
+  }
+  a.lambda_kl = u->lambda_kl; a.uncertain = 1;
+  a.rows = 1;
+  return SIMT_OK;
+}
+
 static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
-                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false) {
+                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false,
+                            const simt_head_uncertainty* unc = nullptr, bool uncertain = false) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
+  if (uncertain) { if (int ru = fill_uncertain(d, w, nw, w_item, unc, a)) return ru; }
+  else if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
   else if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   hipStream_t st = (hipStream_t)stream;
   const int nblk = simt_head_nblk(d->B, d->H, d->W);
@@ -1208,11 +1291,16 @@ static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
     P1ATTR(28, 25, 19, false, false, true); P1ATTR(24, 0, 0, false, false, true); P1ATTR(QMAX, 0, 0, false, false, true);
     P1ATTR(24, 0, 0, true, false, true, true); P1ATTR(QMAX, 0, 0, true, false, true, true);
     P1ATTR(24, 0, 0, false, false, true, true); P1ATTR(QMAX, 0, 0, false, false, true, true);
+    P1ATTR(24, 0, 0, false, false, true, false, true); P1ATTR(QMAX, 0, 0, false, false, true, false, true);
 #undef P1ATTR
   }
 #define P1(...) hipLaunchKernelGGL((head_pass1_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), lds1, st, a)
   const bool one = d->single && d->mode == 1;            // warm-up stage of a one-output model: one head, plain CE
-  if (entropy) {                                         // run-time counts only
+  if (uncertain) {                                       // run-time counts, two heads only
+    if (d->Q <= 24) P1(24, 0, 0, false, false, true, false, true);
+    else P1(QMAX, 0, 0, false, false, true, false, true);
+  }
+  else if (entropy) {                                    // run-time counts only
     if (one && d->Q <= 24) P1(24, 0, 0, true, false, true, true);
     else if (one) P1(QMAX, 0, 0, true, false, true, true);
     else if (d->Q <= 24) P1(24, 0, 0, false, false, true, true);
@@ -1251,11 +1339,13 @@ static int head_loss_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
 
 // gradients w.r.t. the low-res logits (pass 2 + y reduction); needs hout from simt_head_loss of the same inputs.
 static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bool weighted, const float* w, int nw, const uint8_t* w_item,
-                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false) {
+                            simt_stream_t stream, const simt_head_entropy* ent = nullptr, bool entropy = false,
+                            const simt_head_uncertainty* unc = nullptr, bool uncertain = false) {
   HeadArgs a;
   int rc = fill_args(d, fix_item, a);
   if (rc) return rc;
-  if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
+  if (uncertain) { if (int ru = fill_uncertain(d, w, nw, w_item, unc, a)) return ru; }
+  else if (entropy) { if (int re = fill_entropy(d, w, nw, w_item, ent, a)) return re; }
   else if (weighted) { if (int rw = fill_weights(d, w, nw, w_item, a)) return rw; }
   SIMT_CHECK(d->g1 && d->QP >= d->Q);
   hipStream_t st = (hipStream_t)stream;
@@ -1270,11 +1360,16 @@ static int head_grad_launch(const simt_head_desc* d, const uint8_t* fix_item, bo
     P2ATTR(28, 25, 19, false, false, true); P2ATTR(24, 0, 0, false, false, true); P2ATTR(QMAX, 0, 0, false, false, true);
     P2ATTR(24, 0, 0, true, false, true, true); P2ATTR(QMAX, 0, 0, true, false, true, true);
     P2ATTR(24, 0, 0, false, false, true, true); P2ATTR(QMAX, 0, 0, false, false, true, true);
+    P2ATTR(24, 0, 0, false, false, true, false, true); P2ATTR(QMAX, 0, 0, false, false, true, false, true);
 #undef P2ATTR
   }
 #define P2(...) hipLaunchKernelGGL((head_pass2_kernel<__VA_ARGS__>), dim3(d->B * d->H / a.rows), dim3(256), lds2, st, a)
   const bool one = d->single && d->mode == 1;            // (fill_args: a.rows = 1)
-  if (entropy) {                                         // (fill_entropy: a.rows = 1)
+  if (uncertain) {                                       // (fill_uncertain: a.rows = 1)
+    if (d->Q <= 24) P2(24, 0, 0, false, false, true, false, true);
+    else P2(QMAX, 0, 0, false, false, true, false, true);
+  }
+  else if (entropy) {                                    // (fill_entropy: a.rows = 1)
     if (one && d->Q <= 24) P2(24, 0, 0, true, false, true, true);
     else if (one) P2(QMAX, 0, 0, true, false, true, true);
     else if (d->Q <= 24) P2(24, 0, 0, false, false, true, true);
@@ -1343,6 +1438,16 @@ extern "C" int simt_head_loss_entropy(const simt_head_desc* d, const float* w, i
 extern "C" int simt_head_grad_entropy(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item, const simt_head_entropy* e,
                                       simt_stream_t stream) {
   return head_grad_launch(d, nullptr, w != nullptr, w, nw, w_item, stream, e, true);
+}
+
+// the rectified cross-entropy and the two-head KL regulariser: weights optional (NULL: every weight 1)
+extern "C" int simt_head_loss_uncertain(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item,
+                                        const simt_head_uncertainty* u, simt_stream_t stream) {
+  return head_loss_launch(d, nullptr, w != nullptr, w, nw, w_item, stream, nullptr, false, u, true);
+}
+extern "C" int simt_head_grad_uncertain(const simt_head_desc* d, const float* w, int nw, const uint8_t* w_item,
+                                        const simt_head_uncertainty* u, simt_stream_t stream) {
+  return head_grad_launch(d, nullptr, w != nullptr, w, nw, w_item, stream, nullptr, false, u, true);
 }
 
 // the one-view forms: the NULL case of the same code

@@ -60,6 +60,13 @@ the weights the launches they replace would take -- none (NULL: the plain and th
 and in the source pass of `online_source` at every iteration, the launches are the ones above.  `losses()` gains `entropy1` / `entropy2`
 (`hout[2]`, `hout[3]`; the one-output models: `entropy2` only) while the term is on.  Nothing new is exchanged under data parallelism.
 
+Uncertainty rectification (keyword `uncertainty_rectify=lambda_kl`, flag --uncertainty-rectify; DeepLab-v2's two heads only): Zheng &
+Yang's rule for noisy pseudo labels -- the per-pixel KL divergence between the two heads' predictions is the label's uncertainty, a pixel's
+cross-entropy is multiplied by exp(-KL) and lambda_kl * the mean KL is added.  Every pass whose labels are not ground truth (the only pass
+without `online_source`, with or without `online_labels`; the target pass with it) launches `simt_head_loss_uncertain` /
+`simt_head_grad_uncertain` with the weights and the map of the launches they replace; the source pass keeps the plain launches.  `losses()`
+gains `uncertainty1/2` (`hout[2]`, `hout[3]`) and `rectify1/2` (`hout[4]`, `hout[5]`).  Refused beside `entropy_min`.  Nothing new is exchanged.
+
 Prototype weights in front of every label launch (keywords `proto_denoise=temp` / `proto_momentum=M`, flags --proto-denoise /
 --proto-momentum; simt_amd/proto.py): behind step 2 three launches weigh the teacher's low-res output by the distance of every cell's feature
 to running class prototypes, into a map of the same layout; the label launches of every mode above read that map instead -- their
@@ -199,6 +206,23 @@ def check_source(online_source, tau):
         raise ValueError("online_source needs online_labels: the source batch is trained beside a target batch that a teacher labels, and "
                          "this trainer has no teacher")
     return bool(online_source)
+
+
+def check_uncertainty(uncertainty_rectify, entropy):
+    """The keyword of the uncertainty rectification -> lambda_kl | None (off); `entropy` is check_entropy's lambda (None: off).
+    ValueError that starts with the keyword.  0 is allowed: the rectified cross-entropy without the KL regulariser."""
+    if uncertainty_rectify is None:
+        return None
+    what = "expected the weight of the two-head KL regulariser, a finite lambda_kl >= 0 (None: no rectification)"
+    try:
+        lam = float(uncertainty_rectify)
+    except (TypeError, ValueError):
+        raise ValueError(f"uncertainty_rectify {uncertainty_rectify!r}: {what}") from None
+    if isinstance(uncertainty_rectify, bool) or not (0.0 <= lam <= 3.0e38):          # (a NaN fails both comparisons; the launch takes a float32)
+        raise ValueError(f"uncertainty_rectify {uncertainty_rectify!r}: {what}")
+    if entropy is not None:
+        raise ValueError("uncertainty_rectify beside entropy_min is not built: one flavour of the fused head would have to carry both terms")
+    return lam
 
 
 def check_entropy(entropy_min, entropy_eta, entropy_after, tau):
@@ -426,8 +450,23 @@ class OnlineLabelMixin(TeacherMixin, ProtoMixin):
         it = self._entropy_it if self._entropy_it is not None else self.it_done - 1
         return it >= self.entropy_after and self.it_done > 0
 
+    def _init_uncertainty(self, lambda_kl):
+        """lambda_kl: check_uncertainty's value (None: off -- nothing kept, every launch the one it was).  Behind _init_entropy."""
+        self.uncertainty_rectify = lambda_kl
+        if lambda_kl is not None:
+            if self.head_desc.single:
+                raise ValueError("uncertainty_rectify needs two heads: the uncertainty is the KL divergence between them")
+            self.uncertainty_rec = L.HeadUncertainty(lambda_kl)
+
+    def _uncertainty_losses(self, out):
+        """losses(): with uncertainty_rectify adds K_k (`uncertainty1/2`) and the mean rectification weight (`rectify1/2`) of the last micro-batch's
+        pass on labels that are not ground truth; `loss_seg1/2` are then the rectified cross-entropies R_k."""
+        if getattr(self, "uncertainty_rectify", None) is not None and self.it_done > 0:
+            out["uncertainty1"], out["uncertainty2"], out["rectify1"], out["rectify2"] = self.hout[2:6].cpu().tolist()
+        return out
+
     def _weight_args(self):
-        """The (w, nw, map) triple of the entropy launches: the table the weighted launches of this trainer read, or (NULL, 0, NULL)."""
+        """The (w, nw, map) triple of the entropy and the uncertainty launches: the table the weighted launches of this trainer read, or (NULL, 0, NULL)."""
         if getattr(self, "online_labels_weighted", None) is None:
             return None, 0, None
         if self._source_table():
@@ -442,7 +481,10 @@ class OnlineLabelMixin(TeacherMixin, ProtoMixin):
         """simt_head_loss of the micro-batch, or its weighted form (the map: the mix's item map in "item" mode, else NULL; with
         online_source and the mix the [2B] table and the source mix's map).  At an iteration that carries the entropy term (_entropy_at):
         simt_head_loss_entropy with the same weights."""
-        if getattr(self, "_entropy_on", False):
+        if getattr(self, "uncertainty_rectify", None) is not None:      # DESIGN 7.28 (refused beside entropy_min)
+            w, nw, item = self._weight_args()
+            L.call("simt_head_loss_uncertain", C.byref(self.head_desc), w, nw, item, C.byref(self.uncertainty_rec), st)
+        elif getattr(self, "_entropy_on", False):
             w, nw, item = self._weight_args()
             L.call("simt_head_loss_entropy", C.byref(self.head_desc), w, nw, item, C.byref(self.entropy_rec), st)
         elif getattr(self, "online_labels_weighted", None) is None:
@@ -454,7 +496,10 @@ class OnlineLabelMixin(TeacherMixin, ProtoMixin):
                    None if self.w_item is None else self.w_item.data_ptr(), st)
 
     def _head_grad(self, st):
-        if getattr(self, "_entropy_on", False):
+        if getattr(self, "uncertainty_rectify", None) is not None:
+            w, nw, item = self._weight_args()
+            L.call("simt_head_grad_uncertain", C.byref(self.head_desc), w, nw, item, C.byref(self.uncertainty_rec), st)
+        elif getattr(self, "_entropy_on", False):
             w, nw, item = self._weight_args()
             L.call("simt_head_grad_entropy", C.byref(self.head_desc), w, nw, item, C.byref(self.entropy_rec), st)
         elif getattr(self, "online_labels_weighted", None) is None:

@@ -31,7 +31,7 @@ from .engine import LaunchList, TrunkPlan, multi_heads, side_stream
 from .feat_dist import FeatDistMixin, check_feat_dist
 from .optimizer import DEFAULT_BETAS, DEFAULT_EPS, DEFAULT_WARMUP_RATIO, OptimizerMixin
 from .online_labels import (DEFAULT_ENTROPY_ETA, OnlineLabelMixin, check_balanced, check_entropy, check_mix, check_settings, check_source,
-                            check_weighted)
+                            check_uncertainty, check_weighted)
 from .proto import DEFAULT_MOMENTUM as DEFAULT_PROTO_MOMENTUM, check_proto
 from .proto_contrast import ProtoContrastMixin, check_proto_contrast
 from .train_state import TrainStateMixin, state_sha256
@@ -510,7 +510,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
                  optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
                  entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM,
-                 proto_contrast=None, proto_contrast_temp=None, proto_contrast_min_ratio=None):
+                 proto_contrast=None, proto_contrast_temp=None, proto_contrast_min_ratio=None, uncertainty_rectify=None):
         """optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTTrainer; the defaults are the trainer it was.
         online_labels=tau in [0, 1) (simt_amd/online_labels.py): the labels of every micro-batch come from a teacher -- a
         closed-set eval-mode plan over a copy of `state`, with an input and a stem launch of its own -- kept where its confidence is > tau;
@@ -550,13 +550,20 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         STUDENT's layer-4 output, eta the prototypes of proto_denoise, y the class that fills the cell's window of the pass's labels to
         proto_contrast_min_ratio (default 0.75), T = proto_contrast_temp (default 0.1); its gradient enters the backward at layer 4's output.
         proto_denoise=1e30 leaves the labels all but untouched for a user who wants the contrast alone.  `losses()` gains `proto_contrast` /
-        `proto_contrast_cells` (and `source_proto_contrast` with online_source).  None: the trainer it was."""
+        `proto_contrast_cells` (and `source_proto_contrast` with online_source).  None: the trainer it was.
+        uncertainty_rectify=lambda_kl >= 0 (with or without online_labels, refused beside entropy_min): Zheng & Yang's rectification
+        of noisy pseudo labels, inside the fused head -- D_k, the KL divergence of head k from the other head at a pixel, is the label's
+        uncertainty: the pixel's cross-entropy is multiplied by exp(-D_k) and lambda_kl * mean(D_k) is added, for both heads, the gradient flowing
+        through both arguments.  It applies to every pass whose labels are not ground truth (the only pass without online_source, the target pass
+        with it), with the weights and the map of the launches it replaces.  `losses()` gains `uncertainty1/2` and `rectify1/2`, and
+        `loss_seg1/2` are the rectified cross-entropies.  None: the trainer it was."""
         tau, every = check_settings(online_labels, online_labels_every, ema_decay)
         balanced = check_balanced(online_labels_balanced, online_labels_momentum, tau, hp.num_classes)
         mix = check_mix(online_mix, online_mix_seed, tau, B, hp.num_classes)
         weighted = check_weighted(online_labels_weighted, tau, balanced[0], B)
         source = check_source(online_source, tau)
         entropy = check_entropy(entropy_min, entropy_eta, entropy_after, tau)
+        uncertain = check_uncertainty(uncertainty_rectify, entropy[0])
         fd = check_feat_dist(feat_dist, feat_dist_state, feat_dist_classes, feat_dist_min_ratio, tau, source, hp.num_classes)
         proto = check_proto(proto_denoise, proto_momentum, tau, hp.num_classes)
         pc = check_proto_contrast(proto_contrast, proto_contrast_temp, proto_contrast_min_ratio, proto[0], fd[0], hp.num_classes)
@@ -612,6 +619,7 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         self._init_weighted(weighted)
         self._init_source(source)
         self._init_entropy(entropy)
+        self._init_uncertainty(uncertain)
         # the input of the teacher's layer-4 classifier -- the last block's output, which no later launch of the eval plan overwrites
         self._init_proto(proto, next(hd for hd in self.fixed.heads if hd.name == "x2").feat if proto[0] is not None else None)
         self._init_feat_dist(*fd, feat_dist_state, dict(kw, data_parallel=process_group is not None))
@@ -729,4 +737,5 @@ class WarmupTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, FeatDistMixin, 
         if bad > 0:      # nn.CrossEntropyLoss(ignore_index=255) raises on such a target (trainV1_warmup.py:217-224)
             raise ValueError(f"{bad} label value(s) outside [0, {self.hp.num_classes}) that are not the ignore value 255")
         # `loss = loss / args.iter_size` (trainV1_warmup.py:227): the reported total is the scaled one, like SimTTrainer's
-        return self._pc_losses(self._fd_losses(self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]})))
+        return self._pc_losses(self._fd_losses(self._uncertainty_losses(
+            self._labelled({"total": v[14] / self.hp.iter_size, "loss_seg1": v[0], "loss_seg2": v[1]}))))

@@ -275,7 +275,7 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
                  feat_dist=None, feat_dist_state=None, feat_dist_classes=None, feat_dist_min_ratio=None,
                  optimizer="sgd", adam_betas=DEFAULT_BETAS, adam_eps=DEFAULT_EPS, lr_warmup=0, lr_warmup_ratio=DEFAULT_WARMUP_RATIO,
                  entropy_min=None, entropy_eta=DEFAULT_ENTROPY_ETA, entropy_after=0, proto_denoise=None, proto_momentum=DEFAULT_PROTO_MOMENTUM,
-                 proto_contrast=None, proto_contrast_temp=None, proto_contrast_min_ratio=None):
+                 proto_contrast=None, proto_contrast_temp=None, proto_contrast_min_ratio=None, uncertainty_rectify=None):
         """model: "v3" | "vgg".  state: the model's state_dict tensors (DeepLabv3(nc) / DeeplabVGG(nc), nc = hp.num_classes).  arch: plan
         keyword arguments, as for SimTSingleTrainer.  optimizer / adam_betas / adam_eps / lr_warmup / lr_warmup_ratio: as for SimTSingleTrainer
         (DESIGN 7.23).  online_labels / online_labels_every / online_labels_balanced /
@@ -288,8 +288,12 @@ class WarmupSingleTrainer(TrainStateMixin, EmaMixin, OnlineLabelMixin, Optimizer
         entropy_min / entropy_eta / entropy_after: the entropy term of the target pass, as for step.WarmupTrainer (one head:
         `entropy2` only).  proto_denoise / proto_momentum: ProDA's prototype weights in front of the label launch, as for step.WarmupTrainer
         (DESIGN 7.26); the features are the trunk output the ASSP reads (DeepLabv3) or fc7's output (DeepLab-VGG16).
-        proto_contrast*: refused -- the prototype contrastive term needs the seeded backward of DeepLab-v2 (step.WarmupTrainer)."""
+        proto_contrast*: refused -- the prototype contrastive term needs the seeded backward of DeepLab-v2 (step.WarmupTrainer).
+        uncertainty_rectify: refused -- the uncertainty is the KL divergence between DeepLab-v2's two heads, and this model has one."""
         assert model in ("v3", "vgg")
+        if uncertainty_rectify is not None:
+            raise ValueError("uncertainty_rectify: the label uncertainty is the KL divergence between the two classifier heads of DeepLab-v2 "
+                             "(WarmupTrainer); DeepLabv3 and DeepLab-VGG16 (WarmupSingleTrainer) have one head (DESIGN 7.28)")
         for name, v in (("proto_contrast", proto_contrast), ("proto_contrast_temp", proto_contrast_temp), ("proto_contrast_min_ratio", proto_contrast_min_ratio)):
             if v is not None:
                 raise ValueError(f"{name}: the prototype contrastive term is built for DeepLab-v2 (WarmupTrainer) only; DeepLabv3 and DeepLab-VGG16 "

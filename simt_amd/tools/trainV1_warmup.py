@@ -58,6 +58,12 @@ labelled or not, adds LAMBDA (no value: 0.005) * (e^2 + 1e-8)^ETA / (B H W), e i
 Charbonnier penalty; 0.5: ADVENT's MinEnt) and --entropy-after N (0: FDA's switch2entropy -- the term is on from iteration N).  From iteration N on
 the loss line gains ` ent = <the main head's mean penalty>`; before it the line is the one without the flag.  One start-up line states the term
 and its departures; --train-state refuses the flags added, dropped or changed.
+--uncertainty-rectify [LAMBDA_KL] (--model DeepLab only): Zheng & Yang's rectification of noisy pseudo labels, inside the fused head --
+at every pixel D_k, the KL divergence of head k from the other head, is the label's uncertainty: the cross-entropy is multiplied by exp(-D_k) and
+LAMBDA_KL (no value: 1.0; 0 is allowed) * the mean D_k is added, for both heads.  It applies to every pass whose labels are not ground truth: the
+list's pseudo labels, the teacher's labels of --online-labels, and with --online-source the target pass only.  The loss line gains
+` unc = <the main head's mean KL> x<its mean weight exp(-D)>`; one start-up line states the rule and its departures; not beside --entropy-min;
+--train-state refuses the flag added, dropped or changed.
 --proto-denoise [TEMP] (needs --online-labels): ProDA's prototype weights -- in front of the label launch of every mode the teacher's
 low-res posterior is weighed by softmax(-(d - d_min) / TEMP) (no value: 1.0), d the distance of the cell's feature (the input of the teacher's
 main classifier) to running class prototypes kept on the device, momentum --proto-momentum M (0.9999).  A batch is labelled with the
@@ -156,6 +162,7 @@ def get_arguments(argv=None):
     add_optimizer_args(p)
     add_fda_args(p)
     add_entropy_args(p)
+    add_uncertainty_args(p)
     add_proto_args(p)
     add_proto_contrast_args(p)
     args = p.parse_args(argv)
@@ -164,6 +171,7 @@ def get_arguments(argv=None):
     check_feat_dist_args(p, args)
     check_fda_args(p, args)
     check_entropy_args(p, args)
+    check_uncertainty_args(p, args)
     check_proto_args(p, args)
     check_proto_contrast_args(p, args)
     optimizer_kwargs(p, args)
@@ -466,6 +474,50 @@ def proto_contrast_text(args, l):
     return " pc = {0:.4f} ({1:d})".format(l["proto_contrast"], l["proto_contrast_cells"])
 
 
+def add_uncertainty_args(p):
+    """--uncertainty-rectify; `check_uncertainty_args` holds its refusals."""
+    p.add_argument("--uncertainty-rectify", nargs="?", type=float, const=1.0, default=None, metavar="LAMBDA_KL",
+                   help="--model DeepLab only: Zheng & Yang's rectification of noisy pseudo labels, in the fused head (simt_head_loss_uncertain; "
+                        "DESIGN 7.28) -- a pixel's cross-entropy times exp(-KL between the two heads), plus LAMBDA_KL * the mean KL (no value: 1.0; "
+                        "0: the rectified cross-entropy alone)")
+
+
+def check_uncertainty_args(p, args):
+    """argparse's error (exit status 2) naming the flag: a model with one head, a LAMBDA_KL that is not finite and >= 0, --entropy-min beside it."""
+    from simt_amd.online_labels import check_uncertainty
+    if args.uncertainty_rectify is None:
+        return
+    if args.model != "DeepLab":
+        p.error(f"--uncertainty-rectify needs --model DeepLab: the uncertainty is the KL divergence between its two classifier heads, and "
+                f"{args.model} has one")
+    try:
+        check_uncertainty(args.uncertainty_rectify, args.entropy_min)
+    except ValueError as e:
+        p.error(str(e).replace("uncertainty_rectify", "--uncertainty-rectify").replace("entropy_min", "--entropy-min"))
+
+
+def uncertainty_kwargs(args):
+    """The trainer's keyword of --uncertainty-rectify: nothing without the flag."""
+    if getattr(args, "uncertainty_rectify", None) is None:
+        return {}
+    return {"uncertainty_rectify": args.uncertainty_rectify}
+
+
+def uncertainty_line(args):
+    """The start-up line of --uncertainty-rectify: the rule and its departures from the published method."""
+    if getattr(args, "uncertainty_rectify", None) is None:
+        return
+    where = "the target pass" if getattr(args, "online_source", False) else "every pass"
+    print(f"uncertainty rectification: cross-entropy * exp(-KL between the two heads) + {args.uncertainty_rectify} * mean KL on {where}, both heads, "
+          "the gradient through both arguments, inside the fused head; departures: the cross-entropy keeps its division by the labelled pixels "
+          "(the paper: both means over all pixels), one --lambda-seg for both of the auxiliary head's terms, no class weights")
+
+
+def uncertainty_text(l):
+    """` unc = <K_2> x<rectify2>` of the loss line (losses() has `uncertainty2` exactly with the flag)."""
+    return " unc = {0:.3f} x{1:.3f}".format(l["uncertainty2"], l["rectify2"]) if "uncertainty2" in l else ""
+
+
 def step_args(args, mb, sb=None):
     """The micro-batches `batches` handed out -> the arguments of the trainer's step(): (image, label), with --online-labels
     (image, None) and the keyword teacher_image where the loader made a weak view; sb: the micro-batches of `source_batches`
@@ -563,7 +615,7 @@ def build_trainer(args, h, w, rank, dev, pg):
         # trainV1_warmup.py:177: keys of the pretrained checkpoint carry a 6-character prefix (`k[6:]`); shapes are filtered
         n = restore(state, args.restore_from, strip_prefix=6, required=required)
         tr = WarmupTrainer(state, Hyper(lambda_seg=args.lambda_seg, **hyper), args.batch_size, h, w, **kw, **feat_dist_kwargs(args, shapes, rank),
-                           **proto_contrast_kwargs(args))
+                           **proto_contrast_kwargs(args), **uncertainty_kwargs(args))
         return tr, f"restored {n} tensors", "loss_seg1 = {loss_seg1:.3f} loss_seg2 = {loss_seg2:.3f}", {}
     from simt_amd.step_single import WarmupSingleTrainer
     model, layers = ENGINE_MODEL[args.model], tuple(args.v3_layers)
@@ -577,7 +629,7 @@ def build_trainer(args, h, w, rank, dev, pg):
 def loss_tail(args, l, source):
     """What the flags add to the loss line behind the model's own losses, in this order; each term is "" without its flag."""
     return (labelled_text(args, l) + thresholds_text(args, l) + quality_text(args, l) + source_text(args, l) + rcs_text(source) +
-            feat_dist_text(args, l) + entropy_text(l) + proto_text(args, l) + proto_contrast_text(args, l))
+            feat_dist_text(args, l) + entropy_text(l) + uncertainty_text(l) + proto_text(args, l) + proto_contrast_text(args, l))
 
 
 def main(argv=None):
@@ -593,6 +645,7 @@ def main(argv=None):
         optimizer_line(args)
         online_label_line(args)
         entropy_line(args)
+        uncertainty_line(args)
         proto_line(args)
         proto_contrast_line(args)
         patch_mask_line(args, frozen=False)

@@ -752,7 +752,7 @@ class EmaSnapshots:
 RUN_DEFAULTS = {"scale_crop": False, "class_mix": False, "photometric": False, "weak_teacher": False, "patch_mask": False,
                 "online_labels": False, "online_labels_balanced": False, "online_mix": False, "online_labels_weighted": False,
                 "online_source": False, "rare_class_sampling": False, "fda": False, "entropy_min": False, "proto_denoise": False,
-                "proto_contrast": False}      # run_identity keys that are absent when their flag is off: what absence means
+                "proto_contrast": False, "uncertainty_rectify": False}      # run_identity keys that are absent when their flag is off: what absence means
 
 
 def run_identity(args, class_dist):
@@ -805,6 +805,8 @@ def run_identity(args, class_dist):
             from simt_amd.proto_contrast import DEFAULT_MIN_RATIO, DEFAULT_TEMP
             ident["proto_contrast"] = [float(args.proto_contrast), float(DEFAULT_TEMP if args.proto_contrast_temp is None else args.proto_contrast_temp),
                                        float(DEFAULT_MIN_RATIO if args.proto_contrast_min_ratio is None else args.proto_contrast_min_ratio)]
+    if getattr(args, "uncertainty_rectify", None) is not None:           # lambda_kl (trainV1_warmup --uncertainty-rectify; with or
+        ident["uncertainty_rectify"] = [float(args.uncertainty_rectify)]   # without --online-labels; a list, so that lambda_kl = 0 is not "off")
     if not args.synthetic and osp.isfile(args.data_list_target):
         ident["data_list_sha256"] = hashlib.sha256(open(args.data_list_target, "rb").read()).hexdigest()
     return ident

@@ -56,6 +56,9 @@ PROTO_FIELDS = ("proto_denoise", "proto_momentum")
 # and the prototype contrastive term on the student's layer-4 features (proto_contrast = lambda with its temperature and ratio: DESIGN 7.27),
 # written only when on; compared through value_mismatches(..., fields=PROTO_CONTRAST_FIELDS).  No accumulator: the term keeps no state of its own.
 PROTO_CONTRAST_FIELDS = ("proto_contrast", "proto_contrast_temp", "proto_contrast_min_ratio")
+# and the uncertainty rectification (uncertainty_rectify = lambda_kl: DESIGN 7.28), written only when on; compared through
+# value_mismatches(..., fields=UNCERTAINTY_FIELDS)
+UNCERTAINTY_FIELDS = ("uncertainty_rectify",)
 NTM_FIELDS = ("ntm", "ntm_m", "ntm_v", "wraw", "w_m", "w_v")
 
 
@@ -188,6 +191,8 @@ class TrainStateMixin:
             if getattr(self, "proto_contrast", None) is not None:
                 hy.update(proto_contrast=float(self.proto_contrast), proto_contrast_temp=float(self.proto_contrast_temp),
                           proto_contrast_min_ratio=float(self.proto_contrast_min_ratio))
+        if getattr(self, "uncertainty_rectify", None) is not None:      # (with or without online_labels; absent = off)
+            hy["uncertainty_rectify"] = float(self.uncertainty_rectify)
         if getattr(self, "feat_dist", None) is not None:      # (absent = off, like the keywords above)
             hy.update(feat_dist=float(self.feat_dist), feat_dist_classes=[int(c) for c in self.feat_dist_classes],
                       feat_dist_min_ratio=float(self.feat_dist_min_ratio), feat_dist_sha256=self.feat_dist_sha256)
@@ -225,6 +230,7 @@ class TrainStateMixin:
         ImageNet trunk, which is not stored -- and `accumulators` the three scalars of the last labelled pass (`feat_dist_out`).
         With `entropy_min` `hyper` also carries lambda, eta and the iteration that switches the term on; nothing else is kept (the
         term's two scalars ride in `hout`).
+        With `uncertainty_rectify` `hyper` also carries lambda_kl; nothing else is kept (the four scalars ride in `hout`).
         With `proto_denoise` `hyper` also carries temp and M and `accumulators` the prototypes, their update counts and the
         moved-cell counts of the last micro-batch (`proto_eta`, `proto_n`, `proto_changed_part`); without the keyword the dict is what it was.
         Synchronises the device.  Derived state (T, packed operands) and the frozen weights are not
@@ -283,6 +289,7 @@ class TrainStateMixin:
                value_mismatches(ts["hyper"], self._hyper_state(), fields=FEAT_DIST_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=OPTIMIZER_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=ENTROPY_FIELDS) +
+               value_mismatches(ts["hyper"], self._hyper_state(), fields=UNCERTAINTY_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_FIELDS) +
                value_mismatches(ts["hyper"], self._hyper_state(), fields=PROTO_CONTRAST_FIELDS))
         if bad:
